@@ -16,7 +16,8 @@ the only exchange is the RCCL all_gather of per-pair match counts at the end of 
 Rank 0 prints ONE JSON line.  After the timed region the step's own outputs are spot-checked (pairs of the batch
 re-run one at a time must reproduce them bit for bit): `"verified": true`, non-zero exit otherwise.  At N = 1 the
 default run also times a short strict-fp32 leg (`strict_f32`), BASELINE config 5's two encoders (`config5`) and the CPU
-oracle (`cpu_baseline`).
+oracle (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed step returned as .npy files (dump_outputs), so
+that two builds can be compared output for output on the same seeded inputs.
 
 `--workload linemod` (BASELINE config 4): one step = one pass over the 5 796 pair ids of the LINEMOD evaluation list
 (tests/golden/linemod_pairs.json; pixels synthetic, keyed by pair id), sharded contiguously over the ranks, walked
@@ -122,6 +123,42 @@ def cpu_baseline(n_pairs):
                       f"(all three listed: run-to-run spread on shared host cores), {int(len(out['i_ids']))} matches"}
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: data bytes written in all (under 64 MB with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_outputs(arrays, directory, budget=DUMP_BYTES):
+    """Write every tensor of `arrays` as `directory/<name>.npy`: floating point and booleans as float32 (float64 stays
+    float64), integers as float64 (exact).  Each array may take an equal share of `budget` bytes.  One that is larger
+    is replaced by a fixed seeded sample of its rows (rows = all dimensions but the last; elements of a 1-D array), in
+    ascending order, and the flat row numbers go to `<name>_rows.npy`.  The sample depends only on the array's own
+    shape and the number of arrays, so arrays of the same shape from two builds are sampled at the same rows.
+    Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: t for name, t in arrays.items() if isinstance(t, torch.Tensor)}
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        exact64 = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        dtype = torch.float64 if exact64 else torch.float32
+        lead = tuple(t.shape[:-1]) if t.dim() > 1 else tuple(t.shape)
+        row_bytes = (t.shape[-1] if t.dim() > 1 else 1) * (8 if exact64 else 4)
+        n_rows = int(np.prod(lead))
+        if n_rows * row_bytes <= share:
+            arr = t.detach().to(dtype).cpu().numpy()
+        else:
+            keep = max(1, share // (row_bytes + 8))   # + 8: the row number
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, keep, replace=False))
+            where = torch.as_tensor(np.stack(np.unravel_index(rows, lead)), device=t.device)
+            arr = t.detach()[tuple(where)].to(dtype).cpu().numpy()
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = rows.shape
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name] = arr.shape
+    return written
+
+
 def verify_step(model, img0, img1, out, picks):
     """The step's own outputs against the unbatched drop-in path: for each picked pair the two images are run
     through the model alone and matched alone; descriptors, match indices and confidences must be bit-identical to
@@ -205,7 +242,13 @@ def main():
     ap.add_argument("--launch-selftest", choices=["ok", "fail"], default=None,
                     help="dev: the ranks only rendezvous over gloo on the CPU and rank 0 prints a stub line (\"fail\": rank 1 "
                          "exits non-zero) — tests the launch / relay / exit-code path of `bench.py --gpus N` without a GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's share) as DIR/<name>.npy, "
+                         "float32 / float64, under 64 MB in all (a fixed seeded sample of rows of the largest arrays, "
+                         "their row numbers in DIR/<name>_rows.npy); the same arguments give the same inputs on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: start the N ranks ourselves.  This parent must never touch the
@@ -338,6 +381,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        # linemod: `out` is the step's last batch; the counts of the whole pair list go with it
+        shapes = dump_outputs(dict(out, list_counts=counts) if linemod else out, args.dump_outputs)
+        print(f"bench.py: wrote {len(shapes)} arrays to {args.dump_outputs}: {shapes}", file=sys.stderr)
 
     # ---- self-check of the timed step's own outputs (every rank; all must pass) --------------------------------
     if linemod:

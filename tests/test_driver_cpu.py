@@ -3,10 +3,13 @@ the reference's own DINOv2 + Matcher modules (oracle/gen_golden.py:gen_driver)."
 import os
 
 import numpy as np
+import pytest
 
 from oracle import driver_ref
 from pope_amd import synth
 from pope_amd.matcher import default_cfg
+
+pytestmark = pytest.mark.usefixtures("golden_threads")   # bit-exact against the fixtures (conftest.py)
 
 
 def test_oracle_driver_matches_reference_fixture(sd0, golden_dir):

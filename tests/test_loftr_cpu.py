@@ -13,6 +13,8 @@ from oracle import loftr_ref
 from pope_amd import loftr, synth
 from pope_amd.matcher import Matcher, default_cfg
 
+pytestmark = pytest.mark.usefixtures("golden_threads")   # bit-exact against the fixtures (conftest.py)
+
 CASES = ["loftr_256", "loftr_256_lowthr", "loftr_192x256_vs_256x192"]
 FLOAT_TOL = dict(rtol=2e-4, atol=2e-4)   # folded BN / regrouped sums vs the reference's op order, fp32
 

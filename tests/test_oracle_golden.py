@@ -10,6 +10,8 @@ from oracle import coarse_match_ref as cm
 from oracle import dinov2_ref
 from pope_amd import synth
 
+pytestmark = pytest.mark.usefixtures("golden_threads")   # bit-exact against the fixtures (conftest.py)
+
 
 def _digest(sd):
     return np.array([float(sd[k].double().sum()) for k in sorted(sd)], np.float64)

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+pytestmark = pytest.mark.usefixtures("golden_threads")   # bit-exact against the fixtures (conftest.py)
+
 
 @pytest.mark.parametrize("name", ["sam_hd80_256", "sam_hd64_224"])
 def test_oracle_reproduces_reference_fixture(golden_dir, name):
