@@ -220,6 +220,25 @@ int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float
                               float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
                               void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
                               void* stream);
+/* Padded batches and rescaling (coarse_matching.py:115-118,178-184,242-250): pope_dense_match_prec_f32 plus six optional
+ * inputs (NULL = absent; masks hold 0 / 1 as fp32):
+ *   fill_mask0[n,L], fill_mask1[n,S]: sim = -1e9 (finite, the reference's -INF) where fill_mask0[i] * fill_mask1[j] == 0,
+ *     before both softmaxes (a missing one counts as ones);
+ *   border_mask0[n,h0,w0], border_mask1[n,h1,w1]: when either is given, the bottom / right border of each pair lies at its
+ *     valid extent (h = max column sum, w = max row sum, per image) instead of the grid's (mask_border_with_padding);
+ *   scale0[n,2], scale1[n,2]: (x, y) factors, mkpts*_c = (idx % w, idx / w) * (scale * scale*[b]).
+ * With all six NULL this is exactly pope_dense_match_prec_f32 (which forwards here).
+ * Workspace: pope_dense_match_masked_workspace_bytes(..., has_border_masks). */
+size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks);
+int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
+                                int n, int L, int S, int C, int h0, int w0, int h1, int w1,
+                                float thr, int border_rm, float temperature, float scale,
+                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0,
+                                const float* border_mask1, const float* scale0, const float* scale1,
+                                float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids,
+                                float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
+                                void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
+                                void* stream);
 /* Shorthands: POPE_PREC_F32_MFMA, conf_matrix published, no range flag. */
 size_t pope_dense_match_workspace_bytes(int n, int L, int S);
 int pope_dense_match_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
@@ -248,6 +267,13 @@ size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead);
 int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
                                  int n, int L, int S, int C, int nhead, float ln_eps, int precision,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* The same layer with padding masks (linear_attention.py:35-41), each optional (NULL = no mask), 0 / 1 as fp32:
+ * x_mask[n,L] zeroes Q of padded query rows (their message is 0), source_mask[n,S] zeroes K and V of padded source rows
+ * (V / S keeps the full length S).  Same workspace; with both NULL this is pope_loftr_encoder_layer_f32. */
+int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
+                                        const float* x_mask, const float* source_mask,
+                                        int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
 /* ResNetFPN_8_2.forward — src/matcher/backbone/resnet_fpn.py:100-118 (BasicBlock :15-40), eval mode: the LoFTR
  * matcher's local-feature CNN.  gray[n,1,H,W] in [0,1], H and W multiples of 8.  Every convolution is an f16x3 planes
@@ -295,6 +321,11 @@ int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0_hos
  * (scale_px = hw0_i[0] / hw0_f[0]).  win0, win1: [M, Wn*Wn, C] fp32 (the fine transformer's outputs). */
 int pope_fine_match_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c,
                         float scale_px, float* expec_f, float* mkpts1_f, void* stream);
+/* The same with per-pair rescaling (fine_matching.py:68): scale1[n,2] (x, y) and b_ids int64[M] (the matches' pairs);
+ * mkpts1_f[m] = mkpts1_c[m] + expec_xy * (Wn/2) * (scale_px * scale1[b_ids[m]]).  scale1 = NULL: pope_fine_match_f32. */
+int pope_fine_match_scaled_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c,
+                               float scale_px, const float* scale1, const long long* b_ids, float* expec_f,
+                               float* mkpts1_f, void* stream);
 
 /* ---- SAM image encoder (BASELINE config 5) --------------------------------------------------- */
 

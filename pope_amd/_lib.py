@@ -97,9 +97,15 @@ PROTOTYPES = {
     "pope_dense_match_prec_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
                                   + [C.c_float, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 8
                                   + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_dense_match_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "pope_dense_match_masked_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
+                                    + [C.c_float, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.c_void_p] * 8
+                                    + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_loftr_layer_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "pope_loftr_encoder_layer_f32": (C.c_int, [C.POINTER(LoftrLayerWeights), C.c_void_p, C.c_void_p] + [C.c_int] * 5
                                      + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_loftr_encoder_layer_masked_f32": (C.c_int, [C.POINTER(LoftrLayerWeights)] + [C.c_void_p] * 4 + [C.c_int] * 5
+                                            + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_resnetfpn_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_resnetfpn_forward_f32": (C.c_int, [C.POINTER(ResnetFpnWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -109,6 +115,8 @@ PROTOTYPES = {
                                  + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_fine_match_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "pope_fine_match_scaled_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_sam_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(SamEncoderWeights), C.c_int]),
     "pope_sam_encoder_forward_f32": (C.c_int, [C.POINTER(SamEncoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_int_p,
                                                C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -238,6 +246,30 @@ def ptr(t):
     if not t.is_contiguous():
         raise ValueError("pope_amd expects contiguous tensors")
     return C.c_void_p(t.data_ptr())
+
+
+def padding_mask(m, shape, device, what):
+    """A padding mask (bool, or 0 / 1 in an integer or float dtype) of exactly `shape`, as the contiguous fp32 0 / 1 tensor on
+    `device` the kernels read; None stays None.  Anything else raises ValueError."""
+    if m is None:
+        return None
+    import torch
+    if not isinstance(m, torch.Tensor) or tuple(m.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected a padding mask of shape {tuple(shape)}, got {tuple(getattr(m, 'shape', ())) or type(m).__name__}")
+    m = m.to(device)
+    if m.dtype != torch.bool and (m.is_complex() or bool(((m != 0) & (m != 1)).any())):
+        raise ValueError(f"{what}: padding masks are binary (bool, or 0 / 1)")
+    return m.to(torch.float32).contiguous()
+
+
+def pair_scale(s, n, device, what):
+    """Per-pair (x, y) resize factors [n, 2] as a contiguous fp32 tensor on `device`; None stays None."""
+    if s is None:
+        return None
+    import torch
+    if not isinstance(s, torch.Tensor) or tuple(s.shape) != (n, 2) or s.is_complex():
+        raise ValueError(f"{what}: expected per-pair (x, y) factors of shape ({n}, 2), got {tuple(getattr(s, 'shape', ())) or type(s).__name__}")
+    return s.to(device=device, dtype=torch.float32).contiguous()
 
 
 def stream_of(device):

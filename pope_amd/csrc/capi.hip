@@ -516,14 +516,32 @@ int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float
                               long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0_c,
                               float* mkpts1_c, int* counts, void* workspace, size_t workspace_bytes, int precision,
                               unsigned* range_flag, void* stream) {
-    StreamDevice on_device(stream);
+    return pope_dense_match_masked_f32(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, temperature, scale,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, conf_matrix, b_ids, i_ids, j_ids, mconf,
+                                       mkpts0_c, mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream);
+}
+
+size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks) {
+    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
+    return MatchLayout(n, L, S, C, precision, publish_conf != 0).total + (has_border_masks ? align_up(size_t(n) * 4 * 4, 256) : 0);
+}
+
+int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
+                                int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
+                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
+                                const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
+                                long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
+                                size_t workspace_bytes, int precision, unsigned* range_flag, void* stream) {
     if (!feat0 || !feat1 || !b_ids || !i_ids || !j_ids || !mconf || !mkpts0_c || !mkpts1_c || !counts || !workspace)
         return POPE_ERR_ARG;
     if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return POPE_ERR_ARG;
     if (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
     const bool publish = conf_matrix != nullptr;
+    const bool padded = border_mask0 || border_mask1;
     const MatchLayout lay(n, L, S, C, precision, publish);
-    if (workspace_bytes < lay.total) return POPE_ERR_WORKSPACE;
+    const size_t ext_bytes = padded ? align_up(size_t(n) * 4 * 4, 256) : 0;
+    if (workspace_bytes < lay.total + ext_bytes) return POPE_ERR_WORKSPACE;
     char* ws = static_cast<char*>(workspace);
     auto take = [&](size_t bytes) { char* q = ws; ws += bytes; return q; };
     MatchParams p = {};
@@ -557,6 +575,10 @@ int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float
     p.range_flag = range_flag;
     p.b_ids = b_ids; p.i_ids = i_ids; p.j_ids = j_ids;
     p.mconf = mconf; p.mkpts0 = mkpts0_c; p.mkpts1 = mkpts1_c;
+    p.fill0 = fill_mask0; p.fill1 = fill_mask1;
+    p.border0 = border_mask0; p.border1 = border_mask1;
+    if (padded) p.extent = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.total);
+    p.scale0 = scale0; p.scale1 = scale1;
     return pope_launch_dense_match_f32(p, static_cast<hipStream_t>(stream));
 }
 
@@ -568,8 +590,15 @@ size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead) {
 int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
                                  int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
                                  unsigned* range_flag, void* stream) {
+    return pope_loftr_encoder_layer_masked_f32(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace,
+                                               workspace_bytes, range_flag, stream);
+}
+
+int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
+                                        const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    if (!w || !x || !source || !workspace || n <= 0 || L <= 0 || S <= 0) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
-    if (!w) return POPE_ERR_ARG;
     LoftrLayerParams p = {};
     p.x = x; p.source = source; p.n = n; p.L = L; p.S = S; p.C = C; p.H = nhead;
     p.precision = precision;
@@ -581,6 +610,7 @@ int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, co
     p.q_wp = w->q_wp; p.kv_wp = w->kv_wp; p.merge_wp = w->merge_wp; p.mlp0_wp = w->mlp0_wp; p.mlp1_wp = w->mlp1_wp;
     p.norm1_w = w->norm1_w; p.norm1_b = w->norm1_b; p.norm2_w = w->norm2_w; p.norm2_b = w->norm2_b;
     p.ln_eps = ln_eps; p.ws = workspace; p.ws_bytes = workspace_bytes; p.range_flag = range_flag;
+    p.x_mask = x_mask; p.source_mask = source_mask;
     return pope_launch_loftr_layer(p, static_cast<hipStream_t>(stream));
 }
 
@@ -630,6 +660,15 @@ int pope_fine_match_f32(const float* win0, const float* win1, int M, int Wn, int
                         float* expec_f, float* mkpts1_f, void* stream) {
     StreamDevice on_device(stream);
     return pope_launch_fine_match(win0, win1, M, Wn, C, mkpts1_c, scale_px, expec_f, mkpts1_f, static_cast<hipStream_t>(stream));
+}
+
+int pope_fine_match_scaled_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
+                               const float* scale1, const long long* b_ids, float* expec_f, float* mkpts1_f, void* stream) {
+    if (!win0 || !win1 || !mkpts1_c || !expec_f || !mkpts1_f || (scale1 && !b_ids) || M <= 0 || Wn <= 0 || Wn * Wn > 64 || C <= 0)
+        return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_fine_match_scaled(win0, win1, M, Wn, C, mkpts1_c, scale_px, scale1, b_ids, expec_f, mkpts1_f,
+                                         static_cast<hipStream_t>(stream));
 }
 
 static bool sam_params(const pope_sam_encoder_weights* w, int B, SamEncParams& q, SamBlockParams* blocks) {

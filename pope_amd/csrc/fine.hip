@@ -89,9 +89,12 @@ __global__ __launch_bounds__(256) void fine_gather_windows_kernel(FineMap f0, Fi
 
 // one wave per match: sim[k] = <win0[m, centre], win1[m, k]> / sqrt(C), softmax over the WW positions, expectation
 // of (x, y) on linspace(-1, 1, W)^2, spread = sum over the two axes of sqrt(max(E[g^2] - E[g]^2, 1e-10))
+// SCALED: the offset of match m is scaled per axis by scale_px * scale1[b_ids[m]] (fine_matching.py:68-69) instead of scale_px
+template <bool SCALED>
 __global__ __launch_bounds__(256) void fine_match_kernel(const float* __restrict__ win0, const float* __restrict__ win1, int M, int Wn,
                                                          int C, const float* __restrict__ mkpts1_c, float scale_px,
-                                                         float* __restrict__ expec, float* __restrict__ mkpts1_f) {
+                                                         float* __restrict__ expec, float* __restrict__ mkpts1_f,
+                                                         const float* __restrict__ scale1, const long long* __restrict__ b_ids) {
     const int WW = Wn * Wn;
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -117,8 +120,14 @@ __global__ __launch_bounds__(256) void fine_match_kernel(const float* __restrict
         expec[3 * m + 0] = ex;
         expec[3 * m + 1] = ey;
         expec[3 * m + 2] = sqrtf(fmaxf(vx, 1e-10f)) + sqrtf(fmaxf(vy, 1e-10f));
-        mkpts1_f[2 * m + 0] = mkpts1_c[2 * m + 0] + ex * float(Wn / 2) * scale_px;
-        mkpts1_f[2 * m + 1] = mkpts1_c[2 * m + 1] + ey * float(Wn / 2) * scale_px;
+        float sx = scale_px, sy = scale_px;
+        if constexpr (SCALED) {
+            const long long b = b_ids[m];
+            sx = scale_px * scale1[2 * b];
+            sy = scale_px * scale1[2 * b + 1];
+        }
+        mkpts1_f[2 * m + 0] = mkpts1_c[2 * m + 0] + ex * float(Wn / 2) * sx;
+        mkpts1_f[2 * m + 1] = mkpts1_c[2 * m + 1] + ey * float(Wn / 2) * sy;
     }
 }
 
@@ -178,6 +187,16 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
 int pope_launch_fine_match(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
                            float* expec, float* mkpts1_f, hipStream_t stream) {
     if (!win0 || !win1 || !mkpts1_c || !expec || !mkpts1_f || M <= 0 || Wn <= 0 || Wn * Wn > 64 || C <= 0) return POPE_ERR_ARG;
-    hipLaunchKernelGGL(fine_match_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, win0, win1, M, Wn, C, mkpts1_c, scale_px, expec, mkpts1_f);
+    hipLaunchKernelGGL(fine_match_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, stream, win0, win1, M, Wn, C, mkpts1_c, scale_px, expec,
+                       mkpts1_f, nullptr, nullptr);
+    return pope_check_launch();
+}
+
+int pope_launch_fine_match_scaled(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
+                                  const float* scale1, const long long* b_ids, float* expec, float* mkpts1_f, hipStream_t stream) {
+    if (!scale1) return pope_launch_fine_match(win0, win1, M, Wn, C, mkpts1_c, scale_px, expec, mkpts1_f, stream);
+    if (!win0 || !win1 || !mkpts1_c || !expec || !mkpts1_f || !b_ids || M <= 0 || Wn <= 0 || Wn * Wn > 64 || C <= 0) return POPE_ERR_ARG;
+    hipLaunchKernelGGL(fine_match_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, stream, win0, win1, M, Wn, C, mkpts1_c, scale_px, expec,
+                       mkpts1_f, scale1, b_ids);
     return pope_check_launch();
 }

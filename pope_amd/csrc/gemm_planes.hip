@@ -79,7 +79,8 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
     // consecutive lanes -> whole cache lines, and the same 128 contiguous bytes in LDS.  Thread -> rows prow + 32 i, piece pc.
     const int prow = tid >> 3, pc = tid & 7;
     const int nk = g.K / BK;  // >= 2 (launcher)
-    const unsigned nb = EPI == EPI_SIM ? unsigned(g.nbatch) : 1u;
+    constexpr bool SIM = EPI == EPI_SIM || EPI == EPI_SIM_MASK;
+    const unsigned nb = SIM ? unsigned(g.nbatch) : 1u;
     const unsigned a_rows = CONV ? unsigned(g.M) + 2u * unsigned(g.conv_wp) + 2u : nb * unsigned(g.M);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.a_pl), 0, a_rows * unsigned(g.lda) * 4u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.w_pl), 0, nb * unsigned(g.N) * unsigned(g.ldw) * 4u, 0x00020000);
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
         // past the end of the stream the last tile is re-loaded and never consumed
         const int lt = ld_tile < n_tiles ? ld_tile : n_tiles - 1;
         int m0, n0;
-        if constexpr (EPI == EPI_SIM) {  // batched: rows of batch b start at b * M (A) / b * N (W)
+        if constexpr (SIM) {  // batched: rows of batch b start at b * M (A) / b * N (W)
             const int b = lt / tiles_pb, rem = lt - b * tiles_pb;
             m0 = b * g.M + (rem / tiles_n) * BM;
             n0 = b * g.N + (rem % tiles_n) * BN;
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
     // Epilogue of one tile: branch-free, no loads between its stores (bias / gamma hoisted; rows >= M and columns >= N
     // dropped by the buffer range check; residual rows fetched eight at a time): finding 7 of DESIGN.md.
     auto epilogue = [&](int tile, float* epi) {
-        if constexpr (EPI == EPI_SIM) {
+        if constexpr (SIM) {
             // Similarity tile of batch b: sim = acc / divisor_eff (divisor_eff = T * 2^16: the operand scales are exact
             // powers of two), stored to C[b][row][col], plus this wave's partial softmax statistics of the tile — the
             // dual softmax of coarse_matching.py:119 needs max and sum(exp) of every row AND every column of sim, and
@@ -228,6 +229,31 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                         q = __builtin_fmaf(__builtin_fmaf(-dv, q, x), rdiv, q);
                         acc[mi][ni][j] = q;
                     }
+            if constexpr (EPI == EPI_SIM_MASK) {
+                // padding fill (coarse_matching.py:115-118): -1e9 (finite, as the reference's -INF = -1e9) where
+                // mask0[row] * mask1[col] == 0, after the division and before the statistics and the store; a fully padded
+                // row or column then has a uniform softmax.  Rows / columns past the edge read 1 and get -inf below.
+                float mr[4], mc[4][4];
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) {
+                    const int row = m0s + wm * 64 + mi * 16 + l15;
+                    mr[mi] = g.sim_mask0 && row < g.M ? g.sim_mask0[size_t(b) * g.M + row] : 1.f;
+                }
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int col = n0s + wn * 64 + ni * 16 + 4 * q4 + j;
+                        mc[ni][j] = g.sim_mask1 && col < g.N ? g.sim_mask1[size_t(b) * g.N + col] : 1.f;
+                    }
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (mr[mi] * mc[ni][j] == 0.f) acc[mi][ni][j] = -1e9f;
+            }
             if (edge) {
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) {
@@ -648,7 +674,9 @@ int pope_launch_planes16(const GemmParams& g, hipStream_t stream) {
         case EPI_BIAS_GELU: return out_planes ? launch16<EPI_BIAS_GELU, true>(g, stream) : launch16<EPI_BIAS_GELU, false>(g, stream);
         case EPI_BIAS_RELU: return out_planes ? launch16<EPI_BIAS_RELU, true>(g, stream) : launch16<EPI_BIAS_RELU, false>(g, stream);
         case EPI_BIAS_LS_RES: return launch16<EPI_BIAS_LS_RES, false>(g, stream);
-        case EPI_SIM: return launch16<EPI_SIM, false>(g, stream, g.nbatch);
+        case EPI_SIM:
+            if (g.sim_mask0 || g.sim_mask1) return launch16<EPI_SIM_MASK, false>(g, stream, g.nbatch);
+            return launch16<EPI_SIM, false>(g, stream, g.nbatch);
         case EPI_CONV:
             if (g.conv_cch > 0) {
                 if (g.K != 9 * 32 * g.conv_cch || g.lda != 32 * g.conv_cch || g.conv_wp < 3) return POPE_ERR_ARG;

@@ -11,6 +11,7 @@ enum GemmEpilogue {
     EPI_POSB = 3,         // patch embed: C = im2col(img).W^T + posb[token]   (A = image)
     EPI_BIAS_RELU = 5,    // C = max(A.W^T + bias, 0)                (LoFTR encoder MLP, transformer.py:24-28; gemm_planes.hip only)
     EPI_SIM = 4,          // batched similarity (planes kernel): C[b] = (A[b].W[b]^T * alpha) / divisor, no bias
+    EPI_SIM_MASK = 10,    // kernel-side instantiation of EPI_SIM with GemmParams::sim_mask0 / sim_mask1 (callers pass EPI_SIM)
     EPI_SAM_QKV = 7,      // SAM block's QKV projection written straight into the attention operand planes (sam.hip; gemm_planes.hip only)
     EPI_QKV_F16 = 8,      // plain f16 only (POPE_PREC_F16 ViT blocks): C = (A.W^T + bias) * (col < sam_dim ? sam_qscale : 1) -> f16 row-major
                           // [M, N] with NO activation scale: the operand of attention_f16.hip (q carries head_dim^-0.5 * log2 e before its ONE rounding)
@@ -103,6 +104,10 @@ struct GemmParams {
     // patch-embed gather (EPI_POSB)
     const float* posb;   // [ntok, N]: row 0 = cls_token + pos[0]; row n = conv bias + pos[n]
     int ntok, img_h, img_w, patch, grid_w;
+    // EPI_SIM padding masks (coarse_matching.py:115-118), 0 / 1 fp32, each optional: sim_mask0 [nbatch, M], sim_mask1 [nbatch, N];
+    // sim = -1e9 where sim_mask0[b][row] * sim_mask1[b][col] == 0 (a missing mask counts as ones)
+    const float* sim_mask0;
+    const float* sim_mask1;
 };
 
 int pope_launch_gemm_nt_f32(const GemmParams& g, hipStream_t stream);
@@ -202,6 +207,14 @@ struct MatchParams {
     // compacted outputs (capacity n * L)
     long long* b_ids; long long* i_ids; long long* j_ids;
     float* mconf; float* mkpts0; float* mkpts1;
+    // padding masks and rescaling (all optional, 0 / 1 fp32 masks): fill0 [n, L] / fill1 [n, S] set sim = -1e9 where
+    // fill0[i] * fill1[j] == 0 (coarse_matching.py:115-118); border0 [n, h0, w0] / border1 [n, h1, w1] move the bottom and
+    // right border to the valid extent of each pair (mask_border_with_padding, :28-43), extent [n, 4] ints of scratch
+    // (h0, w0, h1, w1 valid); scale0 / scale1 [n, 2] (x, y) factors of mkpts0_c / mkpts1_c (:242-250)
+    const float* fill0; const float* fill1;
+    const float* border0; const float* border1;
+    int* extent;
+    const float* scale0; const float* scale1;
 };
 int pope_match_nrb2(int L);
 int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream);
@@ -238,6 +251,10 @@ struct LoftrLayerParams {
     float ln_eps;
     void* ws; size_t ws_bytes;
     unsigned* range_flag;
+    // optional padding masks (linear_attention.py:35-41), 0 / 1 fp32: x_mask [n, L] zeroes padded query rows' Q,
+    // source_mask [n, S] padded source rows' K and V; null = no mask (the unmasked kernels)
+    const float* x_mask;
+    const float* source_mask;
 };
 // ResNet-FPN local-feature CNN of the LoFTR matcher (conv.hip; resnet_fpn.py:43-118)
 struct ResnetFpnParams {
@@ -276,6 +293,9 @@ size_t pope_fine_preprocess_workspace(int M, int WW, int Cc, int Cf);
 int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream);
 int pope_launch_fine_match(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
                            float* expec, float* mkpts1_f, hipStream_t stream);
+// per-pair rescaling (fine_matching.py:68): the offset of match m is scaled by scale_px * scale1[b_ids[m]] (x, y)
+int pope_launch_fine_match_scaled(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
+                                  const float* scale1, const long long* b_ids, float* expec, float* mkpts1_f, hipStream_t stream);
 size_t pope_loftr_layer_workspace(int n, int L, int S, int C, int H);
 int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream);
 

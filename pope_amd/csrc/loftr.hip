@@ -27,9 +27,11 @@ __device__ __forceinline__ float elu1(float x) { return (x > 0.f ? x : expf(x) -
 
 // Partial KV / Ksum of one (image, head) over one chunk of source rows.  kv: [n, S, 2C] fp32 (k | v).
 // part: [n * H, chunks, D * D + D].
-template <int D>
+// MASKED: kv_mask [n, S] (0 / 1) multiplies K and V before the reduction — K = (elu(k) + 1) * m, V = (v * m) / S with S
+// the full length (linear_attention.py:35-41): a padded source row adds nothing to KV and Ksum.
+template <int D, bool MASKED>
 __global__ __launch_bounds__(256) void linattn_reduce_kernel(const float* __restrict__ kv, int S, int C, int H, float inv_len_unused,
-                                                              float* __restrict__ part, int chunks) {
+                                                              float* __restrict__ part, int chunks, const float* __restrict__ kv_mask) {
     __shared__ float Kt[LA_CHUNK][D + 1];
     __shared__ float Vt[LA_CHUNK][D];
     constexpr int VPT = D * D / 256 > 0 ? D * D / 256 : 1;   // outputs per thread: 4 (D = 32) or 1 (D = 16)
@@ -41,8 +43,14 @@ __global__ __launch_bounds__(256) void linattn_reduce_kernel(const float* __rest
         const int s = i / D, d = i - s * D;
         float kk = 0.f, vv = 0.f;
         if (s < ns) {
-            kk = elu1(base[size_t(s) * 2 * C + d]);
-            vv = base[size_t(s) * 2 * C + C + d] / len;   // values / v_length (linear_attention.py:41)
+            if constexpr (MASKED) {
+                const float mk = kv_mask[size_t(n) * S + s0 + s];
+                kk = elu1(base[size_t(s) * 2 * C + d]) * mk;
+                vv = base[size_t(s) * 2 * C + C + d] * mk / len;
+            } else {
+                kk = elu1(base[size_t(s) * 2 * C + d]);
+                vv = base[size_t(s) * 2 * C + C + d] / len;   // values / v_length (linear_attention.py:41)
+            }
         }
         Kt[s][d] = kk;
         Vt[s][d] = vv;
@@ -81,10 +89,12 @@ __global__ __launch_bounds__(256) void linattn_finish_kernel(const float* __rest
 // Ksum in registers across the block's rows.
 // PLANES (round 4): the message leaves as activation planes — the merge GEMM's operand — instead of fp32 + a split_planes pass
 // (the same hi / lo arithmetic: bit-identical planes, one launch and two passes over the tensor less per layer)
-template <int D, bool PLANES>
+// MASKED: Q = (elu(q) + 1) * q_mask[n, l] (linear_attention.py:36-37): a padded query row gets the message 0 and still goes
+// through merge, LayerNorm and MLP like any other row.
+template <int D, bool PLANES, bool MASKED>
 __global__ __launch_bounds__(256) void linattn_apply_kernel(const float* __restrict__ q, const float* __restrict__ kvf, int L, int C, int H,
                                                              int S, float eps, float* __restrict__ msg, int rows_per_block,
-                                                             unsigned* range_flag) {
+                                                             unsigned* range_flag, const float* __restrict__ q_mask) {
     __shared__ float Qs[2][256];
     const int rpp = 256 / C;                          // rows per pass (C = 256: 1, C = 128: 2)
     const int sub = threadIdx.x / C, col = threadIdx.x - sub * C;
@@ -103,7 +113,8 @@ __global__ __launch_bounds__(256) void linattn_apply_kernel(const float* __restr
         const int l = l0 + r + sub;
         const bool ok = l < L && r + sub < rows_per_block;
         __syncthreads();
-        Qs[0][threadIdx.x] = ok ? elu1(q[(size_t(n) * L + l) * C + col]) : 0.f;
+        if constexpr (MASKED) Qs[0][threadIdx.x] = ok ? elu1(q[(size_t(n) * L + l) * C + col]) * q_mask[size_t(n) * L + l] : 0.f;
+        else Qs[0][threadIdx.x] = ok ? elu1(q[(size_t(n) * L + l) * C + col]) : 0.f;
         __syncthreads();
         const float* qh = &Qs[0][sub * C + h * D];
         float num = 0.f, den = 0.f;
@@ -283,19 +294,25 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     LT(gemm(xp, Wq, q, nullptr, int(rx), C, C, EPI_BIAS));
     LT(gemm(self ? xp : sp, Wkv, kv, nullptr, int(rs), 2 * C, C, EPI_BIAS));
     // 3. per-head state, 4. message
-    if (D == 32) hipLaunchKernelGGL(linattn_reduce_kernel<32>, dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, part, chunks);
-    else hipLaunchKernelGGL(linattn_reduce_kernel<16>, dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, part, chunks);
+    // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
+#define LA_REDUCE(DD, MK) hipLaunchKernelGGL((linattn_reduce_kernel<DD, MK>), dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, \
+                                             part, chunks, p.source_mask)
+    if (p.source_mask) { if (D == 32) LA_REDUCE(32, true); else LA_REDUCE(16, true); }
+    else { if (D == 32) LA_REDUCE(32, false); else LA_REDUCE(16, false); }
+#undef LA_REDUCE
     hipLaunchKernelGGL(linattn_finish_kernel, dim3(p.n * H, (per + 255) / 256), dim3(256), 0, stream, part, chunks, per, kvf);
     const int rpb = 16;
     // (f16x3: the message is written as planes straight away; fp32 mode: plain rows)
-#define LA_APPLY(DD, PL, DST) hipLaunchKernelGGL((linattn_apply_kernel<DD, PL>), dim3(p.n, (p.L + rpb - 1) / rpb), dim3(256), 0, stream, q, kvf, p.L, \
-                                                 C, H, p.S, 1e-6f, DST, rpb, p.range_flag)
+#define LA_APPLY(DD, PL, MK, DST) hipLaunchKernelGGL((linattn_apply_kernel<DD, PL, MK>), dim3(p.n, (p.L + rpb - 1) / rpb), dim3(256), 0, stream, q, \
+                                                     kvf, p.L, C, H, p.S, 1e-6f, DST, rpb, p.range_flag, p.x_mask)
+#define LA_APPLY_D(PL, MK, DST) do { if (D == 32) LA_APPLY(32, PL, MK, DST); else LA_APPLY(16, PL, MK, DST); } while (0)
     if (f32) {
-        if (D == 32) LA_APPLY(32, false, msg); else LA_APPLY(16, false, msg);
+        if (p.x_mask) LA_APPLY_D(false, true, msg); else LA_APPLY_D(false, false, msg);
         msgp = msg;
     } else {
-        if (D == 32) LA_APPLY(32, true, static_cast<float*>(msgp)); else LA_APPLY(16, true, static_cast<float*>(msgp));
+        if (p.x_mask) LA_APPLY_D(true, true, static_cast<float*>(msgp)); else LA_APPLY_D(true, false, static_cast<float*>(msgp));
     }
+#undef LA_APPLY_D
 #undef LA_APPLY
     // 5. merge (-> q buffer), 6. cat[x, LN1(merge)] as planes
     LT(gemm(msgp, Wm, q, nullptr, int(rx), C, C, EPI_BIAS));

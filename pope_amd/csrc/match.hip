@@ -31,6 +31,9 @@ using namespace gemm_core;
 
 constexpr float L2E = 1.44269504088896340736f;
 
+// MASKED: the padding fill of coarse_matching.py:115-118 (sim = -1e9 where fill0[row] * fill1[col] == 0) before the store, so
+// the statistics passes below see the filled matrix (the f16x3 route does the same in gemm_planes.hip's EPI_SIM epilogue)
+template <bool MASKED>
 __global__ __launch_bounds__(THREADS, 3) void sim_kernel(const MatchParams p, float inv_unused) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tiles_n = (p.S + BN - 1) / BN;
@@ -62,6 +65,14 @@ __global__ __launch_bounds__(THREADS, 3) void sim_kernel(const MatchParams p, fl
         if (row >= p.L || col >= p.S) return;
         float* o = sim + size_t(row) * p.S + col;
         v = v / temp;
+        if constexpr (MASKED) {
+            const float mr = p.fill0 ? p.fill0[size_t(pair) * p.L + row] : 1.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float mc = p.fill1 && col + e < p.S ? p.fill1[size_t(pair) * p.S + col + e] : 1.f;
+                if (mr * mc == 0.f) v[e] = -1e9f;
+            }
+        }
         if (even && col + 3 < p.S) {
             *reinterpret_cast<f32x2*>(o) = f32x2{v[0], v[1]};
             *reinterpret_cast<f32x2*>(o + 2) = f32x2{v[2], v[3]};
@@ -287,10 +298,61 @@ __global__ __launch_bounds__(256) void combine_colmax_kernel(const MatchParams p
     p.conf_colmax[size_t(pair) * p.S + col] = m;
 }
 
+// Valid extents of the padded grids (mask_border_with_padding, coarse_matching.py:36-37): per pair and image, h = max over
+// columns of the column sums, w = max over rows of the row sums, truncated to int.  Block (pair, image); extent [n, 4].
+__global__ __launch_bounds__(256) void border_extent_kernel(const MatchParams p) {
+    __shared__ int red[2][4];
+    const int pair = blockIdx.x, img = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = img ? p.h1 : p.h0, w = img ? p.w1 : p.w0;
+    const float* m = img ? p.border1 : p.border0;
+    int eh = h, ew = w;   // no mask: the whole grid
+    if (m) {
+        m += size_t(pair) * h * w;
+        eh = 0;
+        ew = 0;
+        for (int x = threadIdx.x; x < w; x += 256) {
+            float c = 0.f;
+            for (int y = 0; y < h; ++y) c += m[size_t(y) * w + x];
+            eh = max(eh, int(c));
+        }
+        for (int y = threadIdx.x; y < h; y += 256) {
+            float r = 0.f;
+            for (int x = 0; x < w; ++x) r += m[size_t(y) * w + x];
+            ew = max(ew, int(r));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            eh = max(eh, __shfl_xor(eh, o));
+            ew = max(ew, __shfl_xor(ew, o));
+        }
+        if (lane == 0) {
+            red[0][wave] = eh;
+            red[1][wave] = ew;
+        }
+        __syncthreads();
+        eh = max(max(red[0][0], red[0][1]), max(red[0][2], red[0][3]));
+        ew = max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3]));
+    }
+    if (threadIdx.x == 0) {
+        p.extent[4 * pair + 2 * img] = eh;
+        p.extent[4 * pair + 2 * img + 1] = ew;
+    }
+}
+
+// First index of the bottom / right border of a padded grid: the reference's `m[b, e - bd:] = v` with Python slice
+// semantics (a negative start counts from the end, then clamps at 0)
+__device__ __forceinline__ int padded_limit(int e, int b, int n) {
+    int s = e - b;
+    if (s < 0) s += n;
+    return s < 0 ? 0 : s;
+}
+
 // Per row (one wave): the first column passing threshold + border + mutual-NN equality tests.  Only a column that
 // attains the row maximum can pass; with a unique argmax (count == 1: practically always) that is one test, otherwise
 // the row is re-scanned for the first argmax column that passes all tests, as `mask.max(dim=2)` does.
-template <bool PUBLISHED>
+// PADDED: the bottom and right border lie at the pair's valid extents (border_extent_kernel) instead of the grid's
+// (coarse_matching.py:178-184 with 'mask0' in data); top and left keep the plain frame; border_rm <= 0 masks nothing.
+template <bool PUBLISHED, bool PADDED>
 __global__ __launch_bounds__(256) void select_kernel(const MatchParams p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), pair = blockIdx.y;
@@ -299,11 +361,21 @@ __global__ __launch_bounds__(256) void select_kernel(const MatchParams p) {
     const int y0 = row / p.w0, x0 = row - y0 * p.w0;
     const size_t o = size_t(pair) * p.L + row;
     const float rmax = p.conf_rowmax[o];
-    const bool row_ok = y0 >= b && y0 < p.h0 - b && x0 >= b && x0 < p.w0 - b && rmax > p.thr;
+    int ylim0 = p.h0 - b, xlim0 = p.w0 - b, ylim1 = p.h1 - b, xlim1 = p.w1 - b;
+    if constexpr (PADDED) {
+        if (b > 0) {
+            const int* e = p.extent + 4 * pair;
+            ylim0 = padded_limit(e[0], b, p.h0);
+            xlim0 = padded_limit(e[1], b, p.w0);
+            ylim1 = padded_limit(e[2], b, p.h1);
+            xlim1 = padded_limit(e[3], b, p.w1);
+        }
+    }
+    const bool row_ok = y0 >= b && y0 < ylim0 && x0 >= b && x0 < xlim0 && rmax > p.thr;
     const float* cmax = p.conf_colmax + size_t(pair) * p.S;
     auto col_ok = [&](int s) {
         const int y1 = s / p.w1, x1 = s - y1 * p.w1;
-        return y1 >= b && y1 < p.h1 - b && x1 >= b && x1 < p.w1 - b && rmax == cmax[s];
+        return y1 >= b && y1 < ylim1 && x1 >= b && x1 < xlim1 && rmax == cmax[s];
     };
     int first = -1;
     if (row_ok) {  // wave-uniform
@@ -347,6 +419,9 @@ __global__ __launch_bounds__(256) void count_kernel(const MatchParams p) {
 }
 
 // Ordered compaction: block per pair; rows ascending -> output ordered by (b, i) like torch.where.
+// SCALED: per-pair (x, y) factors scale * scale0[pair] / scale * scale1[pair] (coarse_matching.py:243-250; each side
+// separately, a missing one keeps `scale`).
+template <bool SCALED>
 __global__ __launch_bounds__(256) void scatter_kernel(const MatchParams p) {
     __shared__ int wcnt[4];
     __shared__ int base_s;
@@ -359,6 +434,17 @@ __global__ __launch_bounds__(256) void scatter_kernel(const MatchParams p) {
     }
     __syncthreads();
     int base = base_s;
+    float s0x = p.scale, s0y = p.scale, s1x = p.scale, s1y = p.scale;
+    if constexpr (SCALED) {
+        if (p.scale0) {
+            s0x = p.scale * p.scale0[2 * pair];
+            s0y = p.scale * p.scale0[2 * pair + 1];
+        }
+        if (p.scale1) {
+            s1x = p.scale * p.scale1[2 * pair];
+            s1y = p.scale * p.scale1[2 * pair + 1];
+        }
+    }
     const int* rj = p.row_j + size_t(pair) * p.L;
     const float* rc = p.row_conf + size_t(pair) * p.L;
     for (int l0 = 0; l0 < p.L; l0 += 256) {
@@ -377,10 +463,10 @@ __global__ __launch_bounds__(256) void scatter_kernel(const MatchParams p) {
             p.i_ids[o] = l;
             p.j_ids[o] = j;
             p.mconf[o] = rc[l];
-            p.mkpts0[2 * o] = float(l % p.w0) * p.scale;
-            p.mkpts0[2 * o + 1] = float(l / p.w0) * p.scale;
-            p.mkpts1[2 * o] = float(j % p.w1) * p.scale;
-            p.mkpts1[2 * o + 1] = float(j / p.w1) * p.scale;
+            p.mkpts0[2 * o] = float(l % p.w0) * s0x;
+            p.mkpts0[2 * o + 1] = float(l / p.w0) * s0y;
+            p.mkpts1[2 * o] = float(j % p.w1) * s1x;
+            p.mkpts1[2 * o + 1] = float(j / p.w1) * s1y;
         }
         base += total;
         __syncthreads();
@@ -509,7 +595,8 @@ template <bool PUBLISH>
 void launch_conf_and_select(const MatchParams& p, hipStream_t stream) {
     launch_conf_pass<PUBLISH>(p, stream);
     hipLaunchKernelGGL(combine_colmax_kernel, dim3((p.S + 255) / 256, p.n), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(select_kernel<PUBLISH>, dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
+    if (p.extent) hipLaunchKernelGGL((select_kernel<PUBLISH, true>), dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((select_kernel<PUBLISH, false>), dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
 }
 
 }  // namespace
@@ -522,6 +609,8 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
     if (p.bs0 < (long long)p.L * p.C || p.bs1 < (long long)p.S * p.C || (p.bs0 & 3) || (p.bs1 & 3)) return POPE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(p.feat0) & 15) || (reinterpret_cast<uintptr_t>(p.feat1) & 15)) return POPE_ERR_ARG;
     if (!p.sim || !p.colmax_part || p.nrb2 != pope_match_nrb2(p.L) || p.ldp < p.S || (p.ldp & 3)) return POPE_ERR_ARG;
+    if ((p.border0 || p.border1) && !p.extent) return POPE_ERR_ARG;
+    const bool fill = p.fill0 || p.fill1;
     bool sim_done = false;
     if (p.planes0 && p.planes1 && p.row_part && p.col_pmax && p.col_psum && (p.C & 31) == 0 && p.C >= 64) {
         // f16x3: (f0 / sqrt(C)) and (f1 / sqrt(C)) as hi/lo planes (x256), one batched planes GEMM whose epilogue
@@ -539,6 +628,7 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
         g.epilogue = EPI_SIM;
         g.row_part = p.row_part; g.col_pmax = p.col_pmax; g.col_psum = p.col_psum;
         g.ncb = p.ncb; g.nrb = p.nrb; g.ldp = p.ldp;
+        g.sim_mask0 = p.fill0; g.sim_mask1 = p.fill1;   // EPI_SIM_MASK when either is set
         rc = pope_launch_sim_f16x3_planes(g, stream);
         if (rc == 0) {
             sim_done = true;
@@ -550,13 +640,16 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
     }
     if (!sim_done) {
         const int tiles = ((p.L + BM - 1) / BM) * ((p.S + BN - 1) / BN);
-        hipLaunchKernelGGL(sim_kernel, dim3(tiles, p.n), dim3(THREADS), LDS_BYTES, stream, p, 0.f);
+        if (fill) hipLaunchKernelGGL(sim_kernel<true>, dim3(tiles, p.n), dim3(THREADS), LDS_BYTES, stream, p, 0.f);
+        else hipLaunchKernelGGL(sim_kernel<false>, dim3(tiles, p.n), dim3(THREADS), LDS_BYTES, stream, p, 0.f);
         hipLaunchKernelGGL(row_stats_kernel, dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
         hipLaunchKernelGGL(col_stats_kernel, dim3((p.S + 63) / 64, p.n), dim3(256), 0, stream, p);
     }
+    if (p.extent) hipLaunchKernelGGL(border_extent_kernel, dim3(p.n, 2), dim3(256), 0, stream, p);
     if (p.publish_conf) launch_conf_and_select<true>(p, stream);
     else launch_conf_and_select<false>(p, stream);
     hipLaunchKernelGGL(count_kernel, dim3(p.n), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(scatter_kernel, dim3(p.n), dim3(256), 0, stream, p);
+    if (p.scale0 || p.scale1) hipLaunchKernelGGL(scatter_kernel<true>, dim3(p.n), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(scatter_kernel<false>, dim3(p.n), dim3(256), 0, stream, p);
     return pope_check_launch();
 }

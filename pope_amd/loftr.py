@@ -301,13 +301,21 @@ class LoFTREncoderLayer(nn.Module):
                 ent[precision] = (_lib.LoftrLayerWeights(*[t.data_ptr() for t in keep + ent["norms"]]), keep)
         return None if ent[precision] is None else ent[precision][0]
 
-    def update_(self, x, source, workspace, precision="f16x3"):
+    def update_(self, x, source, workspace, precision="f16x3", x_mask=None, source_mask=None):
         """In-place layer update of `x` [n, L, C] (fp32, contiguous, CUDA) against `source` (may be `x`); returns the
-        call's range-flag word (device)."""
+        call's range-flag word (device).  x_mask [n, L] / source_mask [n, S]: optional fp32 0 / 1 padding masks
+        (`_lib.padding_mask`)."""
         w = self._weights(precision)
         n, L, Cd = x.shape
         S = source.shape[1]
         flag = torch.zeros(1, dtype=torch.int32, device=x.device)
+        if x_mask is not None or source_mask is not None:
+            with _lib.on_device_of(x):
+                _lib.check(_lib.lib().pope_loftr_encoder_layer_masked_f32(
+                    C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), _lib.ptr(x_mask), _lib.ptr(source_mask),
+                    n, L, S, Cd, self.nhead, float(self.norm1.eps), _lib.PRECISIONS[precision], C.c_void_p(workspace.data_ptr()),
+                    workspace.numel(), C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), "pope_loftr_encoder_layer_masked_f32")
+            return flag
         with _lib.on_device_of(x):
             _lib.check(_lib.lib().pope_loftr_encoder_layer_f32(
                 C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), n, L, S, Cd, self.nhead,
@@ -317,23 +325,25 @@ class LoFTREncoderLayer(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, source, x_mask=None, source_mask=None):
-        """The reference's single-layer call (transformer.py:35-58): returns the updated copy of `x`."""
-        if x_mask is not None or source_mask is not None:
-            raise NotImplementedError("pope_amd: padding masks are a training-time path (matcher.py:62-64)")
+        """The reference's single-layer call (transformer.py:35-58): returns the updated copy of `x`.  x_mask [n, L] and
+        source_mask [n, S] are the optional padding masks of the query and source rows (linear_attention.py:35-41; either
+        one alone is allowed)."""
         require_cuda(x, "LoFTREncoderLayer")
         require_cuda(source, "LoFTREncoderLayer")
         policy = ON_OVERFLOW
         n, L, Cd = x.shape
+        xm = _lib.padding_mask(x_mask, (n, L), x.device, "LoFTREncoderLayer x_mask")
+        sm = _lib.padding_mask(source_mask, (source.shape[0], source.shape[1]), x.device, "LoFTREncoderLayer source_mask")
         nbytes = _lib.lib().pope_loftr_layer_workspace_bytes(n, L, source.shape[1], Cd, self.nhead)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         src = source.float().contiguous()
         prec = "f16x3" if self._weights("f16x3") is not None else "f32"
         out = x.float().contiguous().clone()
-        bits = int(self.update_(out, out if source is x else src, ws, prec).item())
+        bits = int(self.update_(out, out if source is x else src, ws, prec, xm, sm).item())
         if bits:
             _overflow("LoFTR encoder layer", bits, policy)
             out = x.float().contiguous().clone()
-            self.update_(out, out if source is x else src, ws, "f32")
+            self.update_(out, out if source is x else src, ws, "f32", xm, sm)
         return out
 
 
@@ -358,15 +368,21 @@ class LocalFeatureTransformer(nn.Module):
                 nn.init.xavier_uniform_(p)
         self.on_overflow = None    # None: the module-level ON_OVERFLOW
 
-    def _run(self, feat0, feat1, precision):
+    def _run(self, feat0, feat1, precision, mask0=None, mask1=None):
+        """mask0 [n, L] / mask1 [n, S]: fp32 0 / 1 padding masks or None; 'self' layers pass (m0, m0) and (m1, m1), 'cross'
+        layers (m0, m1) then (m1, m0) (transformer.py:97-102)."""
         n, L, Cd = feat0.shape
         S = feat1.shape[1]
         lib = _lib.lib()
+        mboth = None
         if L == S:
             # both streams in ONE buffer: a 'self' layer treats them as a batch of 2n (same weights, independent
             # sequences: one call instead of two — the layers are launch-bound at the drivers' batch of three pairs)
             both = torch.cat([feat0.float(), feat1.float()], 0).contiguous()
             f0, f1 = both[:n], both[n:]
+            if mask0 is not None or mask1 is not None:   # the masks stacked the same way (a missing one: ones, i.e. no mask)
+                ones = torch.ones(n, L, dtype=torch.float32, device=both.device)
+                mboth = torch.cat([ones if mask0 is None else mask0, ones if mask1 is None else mask1], 0).contiguous()
         else:
             both = None
             f0, f1 = feat0.float().contiguous().clone(), feat1.float().contiguous().clone()
@@ -377,34 +393,36 @@ class LocalFeatureTransformer(nn.Module):
         for layer, name in zip(self.layers, self.layer_names):
             if name == "self":
                 if both is not None:
-                    flags.append(layer.update_(both, both, ws, precision))
+                    flags.append(layer.update_(both, both, ws, precision, mboth, mboth))
                 else:
-                    flags.append(layer.update_(f0, f0, ws, precision))
-                    flags.append(layer.update_(f1, f1, ws, precision))
+                    flags.append(layer.update_(f0, f0, ws, precision, mask0, mask0))
+                    flags.append(layer.update_(f1, f1, ws, precision, mask1, mask1))
             else:
-                flags.append(layer.update_(f0, f1, ws, precision))
-                flags.append(layer.update_(f1, f0, ws, precision))
+                flags.append(layer.update_(f0, f1, ws, precision, mask0, mask1))
+                flags.append(layer.update_(f1, f0, ws, precision, mask1, mask0))
         return (f0, f1), flags
 
     @torch.no_grad()
     def forward(self, feat0, feat1, mask0=None, mask1=None):
+        """mask0 [n, L], mask1 [n, S]: optional padding masks of the two streams (transformer.py:85-106; either alone is
+        allowed)."""
         assert self.d_model == feat0.size(2), "the feature number of src and transformer must be equal"
-        if mask0 is not None or mask1 is not None:
-            raise NotImplementedError("pope_amd: padding masks are a training-time path (matcher.py:62-64)")
         require_cuda(feat0, "LocalFeatureTransformer")
         require_cuda(feat1, "LocalFeatureTransformer")
+        m0 = _lib.padding_mask(mask0, feat0.shape[:2], feat0.device, "LocalFeatureTransformer mask0")
+        m1 = _lib.padding_mask(mask1, feat1.shape[:2], feat0.device, "LocalFeatureTransformer mask1")
         if feat0.shape[0] == 0:
             return feat0.float().clone(), feat1.float().clone()
         policy = self.on_overflow or ON_OVERFLOW
         if any(l._weights("f16x3") is None for l in self.layers):
             if policy == "raise":
                 raise PopeRangeError("pope_amd: a LoFTR transformer weight is outside the f16x3 weight range (|w| < 255.9)")
-            return self._run(feat0, feat1, "f32")[0]
-        out, flags = self._run(feat0, feat1, "f16x3")
+            return self._run(feat0, feat1, "f32", m0, m1)[0]
+        out, flags = self._run(feat0, feat1, "f16x3", m0, m1)
         bits = _read_flags(flags)   # one synchronisation per transformer
         if bits:
             _overflow("LoFTR transformer", bits, policy)
-            out = self._run(feat0, feat1, "f32")[0]
+            out = self._run(feat0, feat1, "f32", m0, m1)[0]
         return out
 
 
@@ -504,7 +522,7 @@ class FineMatching(nn.Module):
     """utils/fine_matching.py:9-74: correlate the centre of window 0 with window 1, softmax(1/sqrt(C)),
     expectation over the normalised [-1,1]^2 grid (x,y) (kornia dsnt.spatial_expectation2d / create_meshgrid
     in the reference; both are closed-form, see SURVEY.md §8c 'unpinned'): one kernel, fp32 throughout
-    (pope_fine_match_f32)."""
+    (pope_fine_match_f32; pope_fine_match_scaled_f32 with per-pair `scale1` rescaling)."""
 
     @torch.no_grad()
     def forward(self, feat_f0, feat_f1, data):
@@ -516,17 +534,29 @@ class FineMatching(nn.Module):
                          "mkpts0_f": data["mkpts0_c"], "mkpts1_f": data["mkpts1_c"]})
             return
         require_cuda(feat_f0, "FineMatching")
-        if "scale0" in data or WW > 64 or len(data["mconf"]) != M:
-            raise NotImplementedError("pope_amd: FineMatching covers the drivers' use (no per-image rescaling `scale0` / `scale1`, "
-                                      "windows up to 8 x 8, no training-time padding of the match list)")
+        if WW > 64 or len(data["mconf"]) != M:
+            raise NotImplementedError("pope_amd: FineMatching covers inference (windows up to 8 x 8, no training-time padding "
+                                      "of the match list)")
         w0, w1 = feat_f0.float().contiguous(), feat_f1.float().contiguous()
         mk1c = data["mkpts1_c"].float().contiguous()
         expec = torch.empty(M, 3, dtype=torch.float32, device=w0.device)
         mk1f = torch.empty(M, 2, dtype=torch.float32, device=w0.device)
+        # fine_matching.py:68: the offset is rescaled by data['scale1'] — keyed on 'scale0' being present, as in the reference
+        scale1 = None
+        if "scale0" in data:
+            n = int(data["bs"]) if "bs" in data else data["scale1"].shape[0]
+            scale1 = _lib.pair_scale(data["scale1"], n, w0.device, "FineMatching scale1")
         with _lib.on_device_of(w0):
-            _lib.check(_lib.lib().pope_fine_match_f32(
-                C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
-                float(scale), C.c_void_p(expec.data_ptr()), C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)),
-                "pope_fine_match_f32")
+            if scale1 is None:
+                _lib.check(_lib.lib().pope_fine_match_f32(
+                    C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
+                    float(scale), C.c_void_p(expec.data_ptr()), C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)),
+                    "pope_fine_match_f32")
+            else:
+                b_ids = data["b_ids"].contiguous()
+                _lib.check(_lib.lib().pope_fine_match_scaled_f32(
+                    C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
+                    float(scale), C.c_void_p(scale1.data_ptr()), C.c_void_p(b_ids.data_ptr()), C.c_void_p(expec.data_ptr()),
+                    C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)), "pope_fine_match_scaled_f32")
         # get_fine_match (:61-74): image 0 keeps its coarse cell centre, image 1 moves inside the window
         data.update({"expec_f": expec, "mkpts0_f": data["mkpts0_c"], "mkpts1_f": mk1f})

@@ -40,7 +40,8 @@ DEFAULT_PRECISION = "f16x3"   # arithmetic of the L x S x C contraction ("f32": 
 
 @torch.no_grad()
 def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, temperature=0.1, precision=None,
-                on_overflow="rerun_f32", want_conf=True):
+                on_overflow="rerun_f32", want_conf=True, mask0=None, mask1=None, border_mask0=None, border_mask1=None,
+                scale0=None, scale1=None):
     """All-pairs similarity -> dual softmax -> threshold/border/mutual-NN -> ordered matches.
 
     feat0 [n,L,C], feat1 [n,S,C] fp32 on the GPU.  Returns the dict CoarseMatching publishes
@@ -50,7 +51,12 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     One host synchronisation (to size the outputs), like torch.where in the reference.
     precision "f16x3" (default) keeps feat / sqrt(C) * 256 as f16 pairs: the kernel that converts them guards the
     f16 range with a device flag that travels with the match counts; on a breach the call is repeated with the
-    fp32-MFMA contraction (`on_overflow="rerun_f32"`) or raises PopeRangeError ("raise")."""
+    fp32-MFMA contraction (`on_overflow="rerun_f32"`) or raises PopeRangeError ("raise").
+
+    Padded batches and rescaling (coarse_matching.py:115-118,178-184,242-250), all optional and independent of each other:
+    mask0 [n, L] / mask1 [n, S] (or [n, h, w]) fill sim with -1e9 where mask0[i] * mask1[j] == 0 (a missing one counts as
+    ones); border_mask0 / border_mask1 [n, h, w] put the bottom / right border at each pair's valid extent; scale0 / scale1
+    [n, 2] (x, y) rescale mkpts0_c / mkpts1_c.  Masks are bool or 0 / 1; the kernels apply them, torch only converts."""
     require_cuda(feat0, "dense_match")
     require_cuda(feat1, "dense_match")
     if feat0.dtype != torch.float32 or feat1.dtype != torch.float32:
@@ -62,6 +68,18 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     h1, w1 = int(hw1_c[0]), int(hw1_c[1])
     assert feat1.shape[0] == n and feat1.shape[2] == Cc and L == h0 * w0 and S == h1 * w1
     dev = feat0.device
+    if mask0 is not None and mask0.dim() == 3:
+        mask0 = mask0.flatten(-2)
+    if mask1 is not None and mask1.dim() == 3:
+        mask1 = mask1.flatten(-2)
+    fill0 = _lib.padding_mask(mask0, (n, L), dev, "dense_match mask0")
+    fill1 = _lib.padding_mask(mask1, (n, S), dev, "dense_match mask1")
+    bord0 = _lib.padding_mask(border_mask0, (n, h0, w0), dev, "dense_match border_mask0")
+    bord1 = _lib.padding_mask(border_mask1, (n, h1, w1), dev, "dense_match border_mask1")
+    sc0 = _lib.pair_scale(scale0, n, dev, "dense_match scale0")
+    sc1 = _lib.pair_scale(scale1, n, dev, "dense_match scale1")
+    extra = (fill0, fill1, bord0, bord1, sc0, sc1)
+    masked = any(t is not None for t in extra)
     if n == 0:   # an empty batch: what torch.where gives the reference on a [0, L, S] mask
         el, ef = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
         out = {"b_ids": el, "i_ids": el.clone(), "j_ids": el.clone(), "gt_mask": torch.empty(0, dtype=torch.bool, device=dev),
@@ -74,7 +92,11 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     if Cc % 32 or Cc < 64:
         precision = "f32"   # the planes layout needs whole 32-column chunks
     prec = _lib.PRECISIONS[precision]
-    ws_bytes = lib.pope_dense_match_workspace_bytes_prec(n, L, S, Cc, prec, 1 if want_conf else 0)
+    if masked:
+        ws_bytes = lib.pope_dense_match_masked_workspace_bytes(n, L, S, Cc, prec, 1 if want_conf else 0,
+                                                               int(bord0 is not None or bord1 is not None))
+    else:
+        ws_bytes = lib.pope_dense_match_workspace_bytes_prec(n, L, S, Cc, prec, 1 if want_conf else 0)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     conf = torch.empty(n, L, S, dtype=torch.float32, device=dev) if want_conf else None
     cap = n * L
@@ -91,11 +113,19 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     bs0 = feat0.stride(0) if n > 1 else L * Cc
     bs1 = feat1.stride(0) if n > 1 else S * Cc
     with on_device_of(feat0):
-        check(lib.pope_dense_match_prec_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
-                                            bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
-                                            float(temperature), float(scale), ptr(conf), ptr(b_ids), ptr(i_ids), ptr(j_ids),
-                                            ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts), C.c_void_p(ws.data_ptr()), ws_bytes,
-                                            prec, flag_ptr, stream_of(dev)), "pope_dense_match_prec_f32")
+        if masked:
+            check(lib.pope_dense_match_masked_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
+                                                  bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
+                                                  float(temperature), float(scale), *[ptr(t) for t in extra], ptr(conf), ptr(b_ids),
+                                                  ptr(i_ids), ptr(j_ids), ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts),
+                                                  C.c_void_p(ws.data_ptr()), ws_bytes, prec, flag_ptr, stream_of(dev)),
+                  "pope_dense_match_masked_f32")
+        else:
+            check(lib.pope_dense_match_prec_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
+                                                bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
+                                                float(temperature), float(scale), ptr(conf), ptr(b_ids), ptr(i_ids), ptr(j_ids),
+                                                ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                                prec, flag_ptr, stream_of(dev)), "pope_dense_match_prec_f32")
     counts_h = counts.cpu()  # sync point
     if int(counts_h[n + 1]):   # features outside the f16x3 range: nothing of this call is valid
         msg = (f"pope_amd: f16x3 range contract breached in dense_match ({_lib.describe_range_bits(int(counts_h[n + 1]))}: "
@@ -104,7 +134,8 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
             raise PopeRangeError(msg)
         warnings.warn(msg + "; re-running with the fp32-MFMA contraction")
         del conf, ws, b_ids, i_ids, j_ids, mconf, mk0, mk1
-        return dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr, border_rm, temperature, "f32", on_overflow, want_conf)
+        return dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr, border_rm, temperature, "f32", on_overflow, want_conf,
+                           *extra)
     m = int(counts_h[n])
     b_ids, i_ids, j_ids, mconf = b_ids[:m], i_ids[:m], j_ids[:m], mconf[:m]
     return {
@@ -134,12 +165,19 @@ class CoarseMatching(nn.Module):
                                       "(default_cfg; sinkhorn needs the absent superglue.py in the reference too)")
 
     def forward(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None):
-        if mask_c0 is not None or "mask0" in data:
-            raise NotImplementedError("pope_amd: padding masks are a training-time path (matcher.py:62-64)")
+        """mask_c0 [n, L] / mask_c1 [n, S]: the similarity fill (coarse_matching.py:115-118, applied when mask_c0 is given);
+        data['mask0'] / data['mask1'] [n, h, w]: the padded border rule (:178-184, keyed on 'mask0' in data);
+        data['scale0'] / data['scale1'] [n, 2]: (x, y) factors of mkpts0_c / mkpts1_c (:243-250, each keyed on itself).
+        The three come from different places in the reference and are honoured independently."""
         if self.training:
             raise NotImplementedError("pope_amd: inference only (call .eval())")
+        if mask_c0 is not None and mask_c1 is None:
+            raise ValueError("CoarseMatching: mask_c0 needs mask_c1 (the fill is mask_c0[i] * mask_c1[j])")
+        fill0, fill1 = (mask_c0, mask_c1) if mask_c0 is not None else (None, None)
+        bord0, bord1 = (data["mask0"], data["mask1"]) if "mask0" in data else (None, None)
         out = dense_match(feat_c0, feat_c1, data["hw0_c"], data["hw1_c"], data["hw0_i"], self.thr, self.border_rm,
-                          self.temperature)
+                          self.temperature, mask0=fill0, mask1=fill1, border_mask0=bord0, border_mask1=bord1,
+                          scale0=data.get("scale0"), scale1=data.get("scale1"))
         out.pop("counts")
         data.update(out)
 
@@ -168,12 +206,14 @@ class Matcher(nn.Module):
         # the same input shapes on.  Same kernels, same order: bit-identical to the eager launches (tests/test_gpu_loftr.py).
         # Off by default because it buys nothing on this path: measured 4.23 -> 4.22 ms per 3-pair call, 17.32 -> 17.27 ms at
         # 24 pairs, driver step 7.34 -> 7.16 ms (scripts/loftr_time.py) — the C-side launch loops already keep the GPU fed,
-        # the time is the small-grid kernels themselves.
+        # the time is the small-grid kernels themselves.  A call with padding masks (data['mask0'/'mask1'])
+        # always runs eagerly: the masks are inputs the captured graph does not have.
         self.use_graph = False
         self._graphs, self._gsrc = {}, None
 
-    def _features(self, im0, im1):
-        """matcher.py:46-60: (feat_c0, feat_c1) after the coarse transformer [n, L, 256] and the fine maps (feat_f0, feat_f1)."""
+    def _features(self, im0, im1, mask_c0=None, mask_c1=None):
+        """matcher.py:46-60: (feat_c0, feat_c1) after the coarse transformer [n, L, 256] and the fine maps (feat_f0, feat_f1);
+        mask_c0 [n, L] / mask_c1 [n, S]: the coarse transformer's padding masks (:62-65)."""
         n = im0.size(0)
         if im0.shape[2:] == im1.shape[2:]:  # one CNN launch sequence for both images (matcher.py:46-48)
             feats_c, feats_f = self.backbone(torch.cat([im0, im1], 0))
@@ -183,7 +223,7 @@ class Matcher(nn.Module):
         hw_c = (feat_c0.shape[2:], feat_c1.shape[2:])
         feat_c0 = self.pos_encoding(feat_c0).flatten(2).transpose(1, 2)   # 'n c h w -> n (h w) c'
         feat_c1 = self.pos_encoding(feat_c1).flatten(2).transpose(1, 2)
-        feat_c0, feat_c1 = self.loftr_coarse(feat_c0, feat_c1)
+        feat_c0, feat_c1 = self.loftr_coarse(feat_c0, feat_c1, mask_c0, mask_c1)
         return feat_c0, feat_c1, feat_f0, feat_f1, hw_c
 
     def _features_graphed(self, im0, im1):
@@ -242,15 +282,24 @@ class Matcher(nn.Module):
         im0, im1 = data["image0"], data["image1"]
         require_cuda(im0, "Matcher")
         require_cuda(im1, "Matcher")
-        if "mask0" in data:
-            raise NotImplementedError("pope_amd: padding masks are a training-time path (matcher.py:62-64)")
         n = im0.size(0)
+        mask_c0 = mask_c1 = None
+        if "mask0" in data:   # matcher.py:62-65: coarse-grid padding masks [n, H/8, W/8]; mask0 without mask1 is a KeyError there too
+            hc0, hc1 = (n, im0.shape[2] // 8, im0.shape[3] // 8), (n, im1.shape[2] // 8, im1.shape[3] // 8)
+            mask_c0 = _lib.padding_mask(data["mask0"], hc0, im0.device, "Matcher mask0").flatten(-2)
+            mask_c1 = _lib.padding_mask(data["mask1"], hc1, im0.device, "Matcher mask1").flatten(-2)
+        for k in ("scale0", "scale1"):
+            if k in data:
+                _lib.pair_scale(data[k], n, im0.device, f"Matcher {k}")
         data.update({"bs": n, "hw0_i": im0.shape[2:], "hw1_i": im1.shape[2:]})
-        feat_c0, feat_c1, feat_f0, feat_f1, (hw0_c, hw1_c) = self._features_graphed(im0, im1)
+        if mask_c0 is not None:   # eager: the graphs are captured without masks
+            feat_c0, feat_c1, feat_f0, feat_f1, (hw0_c, hw1_c) = self._features(im0, im1, mask_c0, mask_c1)
+        else:
+            feat_c0, feat_c1, feat_f0, feat_f1, (hw0_c, hw1_c) = self._features_graphed(im0, im1)
         data.update({"hw0_c": hw0_c, "hw1_c": hw1_c, "hw0_f": feat_f0.shape[2:], "hw1_f": feat_f1.shape[2:]})
         if only_att_fea:   # the caller keeps these: never hand out a graph's static buffers
             return feat_c0.clone(), feat_c1.clone()
-        self.coarse_matching(feat_c0, feat_c1, data)
+        self.coarse_matching(feat_c0, feat_c1, data, mask_c0=mask_c0, mask_c1=mask_c1)
         win0, win1 = self.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data)
         if win0.size(0) != 0:
             win0, win1 = self.loftr_fine(win0, win1)

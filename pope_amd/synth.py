@@ -370,3 +370,88 @@ def synthetic_frame_case(n_proposals=8, seed=31, frame_hw=(480, 640)):
     K0 = np.array([[572.4114, 0, 128.0], [0, 573.57043, 128.0], [0, 0, 1.0]])
     K1 = np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1.0]])
     return to_u8(ref), to_u8(frame), boxes, K0, K1
+
+
+# ---- padded batches for the LoFTR matcher (mask0 / mask1, scale0 / scale1; tests/golden/*masked*.npz) ----------------------
+MASKED_LOFTR_CASES = ("loftr_masked_256", "loftr_masked_192x256_vs_256x192")
+
+
+def masked_loftr_case(name):
+    """Inputs of a padded Matcher batch: dict(image0, image1, mask0, mask1, scale0, scale1) on the CPU plus `thr`.
+    loftr_masked_256: the images of loftr_256_lowthr; pair 0 has image0 rows >= 192 and image1 columns >= 200 zeroed, with
+    coarse masks off from row 24 / column 25; pair 1 carries all-ones masks.  loftr_masked_192x256_vs_256x192: the images of
+    loftr_192x256_vs_256x192 (one pair, different shapes), image0 columns >= 224 and image1 rows >= 216 zeroed (masks off from
+    coarse column 28 / row 27)."""
+    if name == "loftr_masked_256":
+        i0, i1 = synthetic_gray_pairs(2, 256, 256, seed=21)
+        m0 = torch.ones(2, 32, 32, dtype=torch.bool)
+        m1 = torch.ones(2, 32, 32, dtype=torch.bool)
+        i0[0, :, 192:] = 0
+        m0[0, 24:] = False
+        i1[0, :, :, 200:] = 0
+        m1[0, :, 25:] = False
+        s0 = torch.tensor([[1.5, 1.25], [0.7, 2.0]])
+        s1 = torch.tensor([[1.0, 0.5], [2.0, 1.3]])
+    elif name == "loftr_masked_192x256_vs_256x192":
+        i0, _ = synthetic_gray_pairs(1, 192, 256, seed=21)
+        i1 = synthetic_gray_pairs(1, 256, 192, seed=22)[0]
+        i1[:, :, 32:224, :] = i0[:, :, :, 32:224]
+        m0 = torch.ones(1, 24, 32, dtype=torch.bool)
+        m1 = torch.ones(1, 32, 24, dtype=torch.bool)
+        i0[:, :, :, 224:] = 0
+        m0[:, :, 28:] = False
+        i1[:, :, 216:] = 0
+        m1[:, 27:] = False
+        s0 = torch.tensor([[1.25, 0.8]])
+        s1 = torch.tensor([[0.9, 1.1]])
+    else:
+        raise KeyError(name)
+    return {"image0": i0.contiguous(), "image1": i1.contiguous(), "mask0": m0, "mask1": m1, "scale0": s0, "scale1": s1}, 1e-3
+
+
+def masked_coarse_case():
+    """CoarseMatching inputs (3 pairs on a 12 x 12 grid, C = 256): feat1 = a fixed permutation of feat0 plus noise, so the
+    true pairs stand out; pair 0 padded on both sides (rows >= 9 of image 0, columns >= 10 of image 1), pair 1 with a valid
+    extent of 4 rows in image 0 (<= 2 * border: no matches), pair 2 with image 1 fully padded.  Returns (feat0, feat1,
+    mask0 [3,12,12], mask1 [3,12,12], scale0 [3,2], scale1 [3,2], thr)."""
+    g = torch.Generator().manual_seed(5)
+    n, h, w, c = 3, 12, 12, 256
+    f0 = torch.randn(n, h * w, c, generator=g)
+    perm = torch.randperm(h * w, generator=g)
+    f1 = f0[:, perm] + 0.3 * torch.randn(n, h * w, c, generator=g)
+    m0 = torch.ones(n, h, w, dtype=torch.bool)
+    m1 = torch.ones(n, h, w, dtype=torch.bool)
+    m0[0, 9:] = False
+    m1[0, :, 10:] = False
+    m0[1, 4:] = False
+    m1[2] = False
+    s0 = torch.tensor([[1.5, 0.75], [1.0, 1.0], [0.3, 2.5]])
+    s1 = torch.tensor([[0.6, 1.7], [2.0, 0.5], [1.0, 1.0]])
+    return f0.contiguous(), f1.contiguous(), m0, m1, s0, s1, 0.2
+
+
+def masked_coarse_case_large():
+    """CoarseMatching inputs at the LoFTR 256 x 256 grid (2 pairs, 32 x 32, C = 256), built like masked_coarse_case, with the
+    masks and scales of loftr_masked_256 (pair 0 padded from row 24 of image 0 and column 25 of image 1, pair 1 all ones).
+    Returns (feat0, feat1, mask0 [2,32,32], mask1 [2,32,32], scale0 [2,2], scale1 [2,2], thr)."""
+    g = torch.Generator().manual_seed(6)
+    n, h, w, c = 2, 32, 32, 256
+    f0 = torch.randn(n, h * w, c, generator=g)
+    perm = torch.randperm(h * w, generator=g)
+    f1 = f0[:, perm] + 0.3 * torch.randn(n, h * w, c, generator=g)
+    inp, _ = masked_loftr_case("loftr_masked_256")
+    return f0.contiguous(), f1.contiguous(), inp["mask0"], inp["mask1"], inp["scale0"], inp["scale1"], 0.2
+
+
+def masked_xfmr_case():
+    """LocalFeatureTransformer inputs with L != S: feat0 [2, 1024, 256] (32 x 32 grid), feat1 [2, 768, 256] (24 x 32) and
+    two-sided masks mask0 [2, 1024], mask1 [2, 768] (pair 0 padded in both, pair 1 in image 0 only)."""
+    g = torch.Generator().manual_seed(9)
+    f0 = torch.randn(2, 1024, 256, generator=g)
+    f1 = torch.randn(2, 768, 256, generator=g)
+    m0 = torch.ones(2, 32, 32, dtype=torch.bool)
+    m1 = torch.ones(2, 24, 32, dtype=torch.bool)
+    m0[0, 24:] = False
+    m0[1, :, 20:] = False
+    m1[0, :, 28:] = False
+    return f0, f1, m0.flatten(1), m1.flatten(1)
