@@ -139,7 +139,7 @@ int pope_linear_planes_f32(const void* a_planes, const void* w_planes, const flo
     g.M = M; g.N = N; g.K = K;
     g.epilogue = epilogue;
     g.gamma = gamma; g.res = res; g.ldres = N;
-    return pope_launch_gemm_nt_f16x3_planes(g, static_cast<hipStream_t>(stream));
+    return pope_launch_gemm_planes(g, static_cast<hipStream_t>(stream));
 }
 
 int pope_layernorm_planes_f32(const float* x, const float* weight, const float* bias, void* y_planes, int rows, int dim,
@@ -184,7 +184,7 @@ int pope_patch_embed_planes_f32(const float* img, const void* proj_w_planes, con
     g.M = B * ntok; g.N = dim; g.K = kp;
     g.epilogue = EPI_BIAS_LS_RES;
     g.res = posb; g.ldres = dim; g.res_mod = ntok;
-    return pope_launch_gemm_nt_f16x3_planes(g, stream);
+    return pope_launch_gemm_planes(g, stream);
 }
 
 int pope_attention_planes_f32(const void* qkv_planes, void* out_planes, int B, int N, int heads, void* stream) {
@@ -308,7 +308,7 @@ static int vit_forward_impl(const pope_vit_weights* w, const float* img, int B, 
         g.M = rows; g.N = N; g.epilogue = epi; g.gamma = gamma; g.res = res; g.ldres = N;
         g.plain = 1;
         if (epi == EPI_QKV_F16) { g.sam_dim = N / 3; g.sam_qscale = 0.125f * 1.44269504088896340736f; }   // heads of 64: head_dim^-0.5 * log2 e
-        return pope_launch_gemm_nt_f16x3_planes(g, stream);
+        return pope_launch_gemm_planes(g, stream);
     };
     // residual GEMM + following LayerNorm: x = res + gamma * (a . W^T + bias); LN(x; ln_w, ln_b) -> planes or fp32
     auto rowln = [&](const void* a_pl, const void* w_pl, int K, const float* bias, const float* gamma, const float* res, int res_mod,

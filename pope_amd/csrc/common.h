@@ -157,3 +157,58 @@ static inline int pope_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? POPE_OK : POPE_ERR_LAUNCH;
 }
+
+// Launch of a kernel with more than 64 KB of dynamic LDS: the one-time opt-in (per kernel and device), the launch, its check.
+template <auto KERNEL, typename... Args>
+static inline int pope_launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args) {
+    static pope_dev_mask lds_ok{0};
+    if (!pope_opt_in_lds(KERNEL, lds_bytes, lds_ok)) return POPE_ERR_LAUNCH;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, stream, args...);
+    return pope_check_launch();
+}
+
+// ---- exact-erf GELU -------------------------------------------------------------------------------------------------
+// nn.GELU() default = exact erf form, 0.5 x (1 + erf(x / sqrt 2)), evaluated branch-free (ocml erff: ~35 VALU
+// per element with divergent range branches = ~20 % of an FC1 tile).  erfc via Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7):
+// with z = |x|/sqrt2, t = 1/(1 + p z), q = 0.5 t P(t) exp(-z^2):
+//   gelu(x) = x (1 - q) for x >= 0,  x q for x < 0   ==   relu(x) (1 - 2q) + x q.
+// Max abs error vs the exact form over [-12, 12] in fp32: 4.7e-7 (one ulp at |x| ~ 4).  Every GEMM epilogue uses these two
+// definitions, so the routes of one GEMM give the same bits.
+namespace pope_gelu {
+constexpr float P = 0.3275911f * 0.70710678118654752440f;
+constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f, A4 = 0.5f * -1.453152027f,
+                A5 = 0.5f * 1.061405429f;
+constexpr float NHL2E = -0.5f * 1.44269504088896340736f;  // exp(-x^2/2) = exp2(x * x * NHL2E)
+}  // namespace pope_gelu
+
+// on element PAIRS with packed f32 math (v_pk_fma_f32 / v_pk_mul_f32 for the polynomial)
+__device__ __forceinline__ f32x2 pope_gelu_erf_pair(f32x2 x) {
+    using namespace pope_gelu;
+    f32x2 t, e, relu;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
+        relu[i] = __builtin_fmaxf(x[i], 0.0f);
+    }
+    const f32x2 arg = (x * NHL2E) * x;
+    e[0] = __builtin_amdgcn_exp2f(arg[0]);
+    e[1] = __builtin_amdgcn_exp2f(arg[1]);
+    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
+    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
+    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
+    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
+    const f32x2 q = (poly * t) * e;
+    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
+}
+// the same formula on one element
+__device__ __forceinline__ float pope_gelu_erf(float x) {
+    using namespace pope_gelu;
+    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x), P, 1.0f));
+    const float e = __builtin_amdgcn_exp2f((x * NHL2E) * x);
+    float poly = __builtin_fmaf(t, A5, A4);
+    poly = __builtin_fmaf(poly, t, A3);
+    poly = __builtin_fmaf(poly, t, A2);
+    poly = __builtin_fmaf(poly, t, A1);
+    const float q = (poly * t) * e;
+    return __builtin_fmaf(__builtin_fmaxf(x, 0.0f), __builtin_fmaf(q, -2.f, 1.f), x * q);
+}

@@ -263,7 +263,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
         }
         g.range_flag = q.range_flag; g.range_bit = POPE_RANGE_INPUT;
         g.nbatch = 1;
-        return pope_launch_planes16(g, stream);
+        return pope_launch_gemm_planes(g, stream);
     };
     auto zero_border = [&](void* b, int level, int pitch) -> int {
         const long long total = (long long)q.n * (2 * p.Wp[level] + 2 * (p.Hp[level] - 2)) * (pitch / 4);
@@ -305,8 +305,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
         g.conv_s2_in_rows = int(p.rows[level_in]);
         g.range_flag = q.range_flag; g.range_bit = POPE_RANGE_INPUT; g.nbatch = 1;
         if (!pope_wide_conv_s2_supported(g)) return 1;
-        const int r = pope_launch_wide_conv_s2(g, stream);
-        return r ? r : 0;
+        return pope_launch_gemm_planes(g, stream);
     };
     auto block_s2 = [&](Buf x, int level_in, Buf g9, Buf g1, Buf t, Buf s, Buf y, int w0, int N) -> int {
         const int lo = level_in + 1;

@@ -168,7 +168,7 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
     g.A = reinterpret_cast<const float*>(cpl); g.W = q.down_w;
     g.M = 2 * q.M; g.N = q.Cf; g.K = q.Cc; g.lda = q.Cc; g.ldw = q.Cc; g.ldc = q.Cf;
     g.epilogue = EPI_BIAS; g.nbatch = 1;
-    if ((rc = f32 ? pope_launch_gemm_nt_f32(g, stream) : pope_launch_gemm_nt_f16x3_planes(g, stream))) return rc;
+    if ((rc = f32 ? pope_launch_gemm_nt_f32(g, stream) : pope_launch_gemm_planes(g, stream))) return rc;
     FineMap m0 = {q.f0, q.s0[0], q.s0[1], q.s0[2], q.s0[3], q.H0, q.W0, q.wc0};
     FineMap m1 = {q.f1, q.s1[0], q.s1[1], q.s1[2], q.s1[3], q.H1, q.W1, q.wc1};
     if (f32) hipLaunchKernelGGL(fine_gather_windows_kernel<false>, dim3(grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
@@ -181,7 +181,7 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
     h.A = reinterpret_cast<const float*>(mpl); h.W = q.merge_w;
     h.M = 2 * q.M * WW; h.N = q.Cf; h.K = 2 * q.Cf; h.lda = 2 * q.Cf; h.ldw = 2 * q.Cf; h.ldc = q.Cf;
     h.epilogue = EPI_BIAS; h.nbatch = 1;
-    return f32 ? pope_launch_gemm_nt_f32(h, stream) : pope_launch_gemm_nt_f16x3_planes(h, stream);
+    return f32 ? pope_launch_gemm_nt_f32(h, stream) : pope_launch_gemm_planes(h, stream);
 }
 
 int pope_launch_fine_match(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,

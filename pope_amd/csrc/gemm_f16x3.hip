@@ -33,6 +33,7 @@ constexpr size_t X3_LDS_BYTES = size_t(2) * STAGE * sizeof(_Float16);
 static_assert(X3_LDS_BYTES >= size_t(4) * 32 * EPI_ST * sizeof(float), "epilogue staging must fit");
 
 constexpr float A_SCALE = 8.0f, W_SCALE = 256.0f;  // powers of two: exact
+static_assert(A_SCALE == K_PLANES_ACT_SCALE && W_SCALE == K_PLANES_W_SCALE, "plane scales");
 
 __device__ __forceinline__ void split(f32x4 v, float scale, f16x4& hi, f16x4& lo) {
     pope_split4(v * scale, hi, lo);   // common.h: v_cvt_pk_f16_f32 x2 + v_fma_mixlo/mixhi_f16 x2
@@ -40,30 +41,6 @@ __device__ __forceinline__ void split(f32x4 v, float scale, f16x4& hi, f16x4& lo
 
 __device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float gelu_erf_scalar(float x);  // defined below (shared formula with gemm_f32.hip)
-// the same formula on a pair (v_pk_fma_f32 / v_pk_mul_f32 for the polynomial): gemm_f32.hip:gelu_erf2
-__device__ __forceinline__ f32x2 gelu_erf_pair(f32x2 x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;
-    f32x2 t, e, relu;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
-        relu[i] = __builtin_fmaxf(x[i], 0.0f);
-    }
-    const f32x2 arg = (x * NHL2E) * x;
-    e[0] = __builtin_amdgcn_exp2f(arg[0]);
-    e[1] = __builtin_amdgcn_exp2f(arg[1]);
-    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
-    const f32x2 q = (poly * t) * e;
-    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
 }
 
 template <int EPI>
@@ -191,7 +168,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_nt_f16x3_kernel(const GemmPar
         } else if constexpr (EPI == EPI_BIAS_GELU) {
             v = v + bias;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf_scalar(v[e]);
+            for (int e = 0; e < 4; ++e) v[e] = pope_gelu_erf(v[e]);
         } else {
             const f32x4 gamma = *reinterpret_cast<const f32x4*>(g.gamma + col);
             const f32x4 res = *reinterpret_cast<const f32x4*>(g.res + size_t(row) * g.ldres + col);
@@ -201,71 +178,13 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_nt_f16x3_kernel(const GemmPar
     });
 }
 
-// exact-erf GELU, Abramowitz-Stegun 7.1.26 form (see gemm_f32.hip:gelu_erf2 for the derivation)
-__device__ __forceinline__ float gelu_erf_scalar(float x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x), P, 1.0f));
-    const float e = __builtin_amdgcn_exp2f((x * NHL2E) * x);
-    float poly = __builtin_fmaf(t, A5, A4);
-    poly = __builtin_fmaf(poly, t, A3);
-    poly = __builtin_fmaf(poly, t, A2);
-    poly = __builtin_fmaf(poly, t, A1);
-    const float q = (poly * t) * e;
-    return __builtin_fmaf(__builtin_fmaxf(x, 0.0f), __builtin_fmaf(q, -2.f, 1.f), x * q);
-}
-
 template <int EPI>
 int launch(const GemmParams& g, hipStream_t stream) {
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_nt_f16x3_kernel<EPI>, X3_LDS_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_nt_f16x3_kernel<EPI>), dim3(tiles), dim3(THREADS), X3_LDS_BYTES, stream, g);
-    return pope_check_launch();
+    return pope_launch_lds<gemm_nt_f16x3_kernel<EPI>>(dim3(tiles), dim3(THREADS), X3_LDS_BYTES, stream, g);
 }
 
 }  // namespace
-
-// Batched similarity for the dense matcher: C[b] = (A[b] . W[b]^T * alpha) / divisor on planes operands.
-int pope_launch_sim_f16x3_planes(const GemmParams& g, hipStream_t stream) {
-    if (g.epilogue != EPI_SIM || !g.a_pl || !g.w_pl || !g.C || g.nbatch <= 0 || g.M <= 0 || g.N <= 0) return POPE_ERR_ARG;
-    if (g.K < 2 * BK || (g.K % BK) || (g.lda & 31) || (g.ldw & 31) || g.ldc != g.N || g.divisor_eff == 0.f) return POPE_ERR_ARG;
-    if ((g.row_part || g.col_pmax) &&
-        (!g.row_part || !g.col_pmax || !g.col_psum || g.ncb != 2 * ((g.N + BN - 1) / BN) || g.nrb != 4 * ((g.M + BM - 1) / BM) ||
-         g.ldp < g.N || (g.ldp & 3)))
-        return POPE_ERR_ARG;
-    if ((size_t(g.nbatch) * g.M + BM) * g.lda * 4 >= (size_t(1) << 32) || (size_t(g.nbatch) * g.N + BN) * g.ldw * 4 >= (size_t(1) << 32) ||
-        (size_t(g.nbatch) * g.M + BM) * g.ldc * 4 >= (size_t(1) << 32) - 512)
-        return POPE_ERR_ARG;
-    if (static_cast<long long>(g.nbatch) * ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) > 0x7fffffffLL) return POPE_ERR_ARG;
-    return pope_launch_planes16(g, stream);
-}
-
-int pope_launch_gemm_nt_f16x3_planes(const GemmParams& g, hipStream_t stream) {
-    static_assert(A_SCALE == K_PLANES_ACT_SCALE && W_SCALE == K_PLANES_W_SCALE, "plane scales");
-    if (g.M <= 0 || g.N <= 0 || g.K < 2 * BK || (g.K % BK) || (g.N & 3) || (g.ldc & 3) || (g.lda & 7) || (g.ldw & 7)) return POPE_ERR_ARG;
-    if (!g.a_pl || !g.w_pl || (g.lda & 31) || (g.ldw & 31)) return POPE_ERR_ARG;
-    if (size_t(g.M + 256) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + BN) * g.ldw * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
-    const bool out_planes = g.c_pl != nullptr;
-    if (out_planes ? (g.ldc & 31) != 0 : !g.C) return POPE_ERR_ARG;
-    // the epilogue addresses C (and res) through 32-bit buffer offsets
-    if (size_t(g.M + 256) * g.ldc * 4 >= (size_t(1) << 32) - 512) return POPE_ERR_ARG;
-    if (g.epilogue == EPI_BIAS_LS_RES && size_t(g.M + 256) * g.ldres * 4 >= (size_t(1) << 32) - 512) return POPE_ERR_ARG;
-    switch (g.epilogue) {
-        case EPI_BIAS:
-        case EPI_BIAS_GELU:
-        case EPI_BIAS_RELU: return pope_launch_planes16(g, stream);
-        case EPI_QKV_F16:
-            if (!g.plain || !out_planes || g.sam_dim <= 0 || (g.sam_dim & 63)) return POPE_ERR_ARG;
-            return pope_launch_planes16(g, stream);
-        case EPI_BIAS_LS_RES:
-            if (!g.res || out_planes || (!g.gamma && g.res_mod <= 0)) return POPE_ERR_ARG;
-            return pope_launch_planes16(g, stream);
-    }
-    return POPE_ERR_ARG;
-}
 
 bool pope_gemm_f16x3_supported(const GemmParams& g) {
     return g.epilogue != EPI_POSB && (g.K % BK) == 0 && size_t(g.M + BM) * g.lda * 4 < (size_t(1) << 32) &&

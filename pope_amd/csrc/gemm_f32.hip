@@ -19,35 +19,6 @@ namespace {
 
 using namespace gemm_core;
 
-// nn.GELU() default = exact erf form, 0.5 x (1 + erf(x / sqrt 2)), evaluated
-// branch-free on element PAIRS with packed f32 math: the f32 MFMA shares the SIMD's VALU lanes, so
-// the epilogue's instruction count is paid in full against the matrix stream (ocml erff: ~35 VALU
-// per element with divergent range branches = ~20 % of an FC1 tile).  erfc via Abramowitz-Stegun
-// 7.1.26 (|err| <= 1.5e-7): with z = |x|/sqrt2, t = 1/(1 + p z), q = 0.5 t P(t) exp(-z^2):
-//   gelu(x) = x (1 - q) for x >= 0,  x q for x < 0   ==   relu(x) (1 - 2q) + x q.
-// Max abs error vs the exact form over [-12, 12] in fp32: 4.7e-7 (one ulp at |x| ~ 4).
-__device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;  // exp(-x^2/2) = exp2(x * x * NHL2E)
-    f32x2 t, e, relu;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
-        relu[i] = __builtin_fmaxf(x[i], 0.0f);
-    }
-    const f32x2 arg = (x * NHL2E) * x;
-    e[0] = __builtin_amdgcn_exp2f(arg[0]);
-    e[1] = __builtin_amdgcn_exp2f(arg[1]);
-    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
-    const f32x2 q = (poly * t) * e;
-    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
-}
-
 enum { LOAD_GENERIC = 0, LOAD_BUFFER = 1, LOAD_PATCH = 2, LOAD_CONV = 3 };
 
 template <int LOADER>
@@ -149,7 +120,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& g, int m0, int n
                     v = v + bias;
                 } else if constexpr (EPI == EPI_BIAS_GELU) {
                     v = v + bias;
-                    const f32x2 lo = gelu_erf2(f32x2{v[0], v[1]}), hi = gelu_erf2(f32x2{v[2], v[3]});
+                    const f32x2 lo = pope_gelu_erf_pair(f32x2{v[0], v[1]}), hi = pope_gelu_erf_pair(f32x2{v[2], v[3]});
                     v = f32x4{lo[0], lo[1], hi[0], hi[1]};
                 } else if constexpr (EPI == EPI_BIAS_LS_RES) {
                     v = extra[i] + (v + bias) * gamma;

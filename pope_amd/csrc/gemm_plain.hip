@@ -18,7 +18,7 @@
 // Served: EPI_BIAS -> fp32, EPI_BIAS_GELU -> f16, EPI_BIAS_LS_RES -> fp32 (in place), EPI_SAM_QKV, EPI_QKV_F16; M >= 2 048, K % 64 == 0.
 // Everything else (and the implicit 3 x 3 convolution of the neck) stays on gemm_planes16_kernel.
 #include "gemm_core.h"
-#include "kernels.h"
+#include "gemm_routes.h"
 
 namespace {
 
@@ -39,29 +39,6 @@ static_assert(size_t(8) * 32 * EPI_ST * sizeof(float) <= pl_lds_bytes(128), "epi
 #define PL_FENCE() __builtin_amdgcn_sched_barrier(0x76)   // VALU | SALU | VMEM may cross; MFMA and DS may not
 
 __device__ __forceinline__ f32x4 pl_mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
-// exact-erf GELU on a pair: the arithmetic of gemm_planes.hip:gelu_erf_pair, instruction for instruction (bit-identical)
-__device__ __forceinline__ f32x2 pl_gelu_pair(f32x2 x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;
-    f32x2 t, e, relu;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
-        relu[i] = __builtin_fmaxf(x[i], 0.0f);
-    }
-    const f32x2 arg = (x * NHL2E) * x;
-    e[0] = __builtin_amdgcn_exp2f(arg[0]);
-    e[1] = __builtin_amdgcn_exp2f(arg[1]);
-    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
-    const f32x2 q = (poly * t) * e;
-    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
-}
 
 // NWN: waves along N (4: 256-column tiles, a wave owns 128 x 64; 2: 128-column tiles, a wave owns 64 x 64)
 // X3: the operands are f16x3 PLANES (a row's K-step = [32 hi | 32 lo] halves — the same 128 bytes per row and K-step as 64
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                                                           col_ok ? off + unsigned(col) * 2u : DROP, 0, 0);
                 } else if constexpr (EPI == EPI_BIAS_GELU) {
                     v = v * inv + bias;
-                    const f32x2 g01 = pl_gelu_pair(f32x2{v[0], v[1]}), g23 = pl_gelu_pair(f32x2{v[2], v[3]});
+                    const f32x2 g01 = pope_gelu_erf_pair(f32x2{v[0], v[1]}), g23 = pope_gelu_erf_pair(f32x2{v[2], v[3]});
                     v = f32x4{g01[0], g01[1], g23[0], g23[1]};
                     if constexpr (X3 && OUT_F16) {
                         store_planes(v);
@@ -396,14 +373,12 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
         pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) * PL_A_SCALE < POPE_F16_OVERFLOW));
 }
 
-template <int EPI, bool OUT_F16, int NWN>
-int launch_plain(const GemmParams& g, hipStream_t stream) {
+// one workgroup per 256-row x (64 NWN)-column tile
+template <int EPI, bool OUT_F16, int NWN, bool X3 = false, int CONV = 0>
+int launch(const GemmParams& g, hipStream_t stream) {
     constexpr int BN = 64 * NWN;
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_plain256_kernel<EPI, OUT_F16, NWN>, pl_lds_bytes(BN), lds_ok)) return POPE_ERR_LAUNCH;
     const int tiles = ((g.M + PL_BM - 1) / PL_BM) * ((g.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_plain256_kernel<EPI, OUT_F16, NWN>), dim3(tiles), dim3(PL_THREADS), pl_lds_bytes(BN), stream, g);
-    return pope_check_launch();
+    return pope_launch_lds<gemm_plain256_kernel<EPI, OUT_F16, NWN, X3, CONV>>(dim3(tiles), dim3(PL_THREADS), pl_lds_bytes(BN), stream, g);
 }
 
 template <int EPI, bool OUT_F16>
@@ -411,26 +386,7 @@ int launch_plain_n(const GemmParams& g, hipStream_t stream) {
     // 256-column tiles wherever the output is at least two of them wide: even at 1.25 rounds of the chip (SAM ViT-H proj / FC2
     // at 4 images: 64 x 5 tiles on 256 CUs) their half-as-many operand bytes per MFMA beat the 128-column tiles' better
     // quantisation (FC2 0.345 -> 0.27 ms, same-box A/B; profiles/r04/config5_f16_gemm_ab.txt)
-    return g.N >= 512 ? launch_plain<EPI, OUT_F16, 4>(g, stream) : launch_plain<EPI, OUT_F16, 2>(g, stream);
-}
-
-template <int EPI>
-int launch_x3(const GemmParams& g, hipStream_t stream) {
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_plain256_kernel<EPI, true, 4, true>, pl_lds_bytes(256), lds_ok)) return POPE_ERR_LAUNCH;
-    const int tiles = ((g.M + PL_BM - 1) / PL_BM) * ((g.N + 255) / 256);
-    hipLaunchKernelGGL((gemm_plain256_kernel<EPI, true, 4, true>), dim3(tiles), dim3(PL_THREADS), pl_lds_bytes(256), stream, g);
-    return pope_check_launch();
-}
-
-template <bool OUT_PL, int NWN, int CONV = 1>
-int launch_conv(const GemmParams& g, hipStream_t stream) {
-    constexpr int BN = 64 * NWN;
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_plain256_kernel<EPI_CONV, OUT_PL, NWN, true, CONV>, pl_lds_bytes(BN), lds_ok)) return POPE_ERR_LAUNCH;
-    const int tiles = ((g.M + PL_BM - 1) / PL_BM) * ((g.N + BN - 1) / BN);
-    hipLaunchKernelGGL((gemm_plain256_kernel<EPI_CONV, OUT_PL, NWN, true, CONV>), dim3(tiles), dim3(PL_THREADS), pl_lds_bytes(BN), stream, g);
-    return pope_check_launch();
+    return g.N >= 512 ? launch<EPI, OUT_F16, 4>(g, stream) : launch<EPI, OUT_F16, 2>(g, stream);
 }
 
 }  // namespace
@@ -448,8 +404,7 @@ bool pope_wide_conv_s2_supported(const GemmParams& g) {
 }
 
 int pope_launch_wide_conv_s2(const GemmParams& g, hipStream_t stream) {
-    if (!pope_wide_conv_s2_supported(g)) return POPE_ERR_ARG;
-    return g.N <= 128 ? launch_conv<true, 2, 2>(g, stream) : launch_conv<true, 4, 2>(g, stream);
+    return g.N <= 128 ? launch<EPI_CONV, true, 2, true, 2>(g, stream) : launch<EPI_CONV, true, 4, true, 2>(g, stream);
 }
 
 // the implicit 3 x 3 convolutions of the LoFTR CNN (conv.hip) at batch size: 256-row tiles, 128 (N <= 128) or 256 columns
@@ -464,12 +419,11 @@ bool pope_wide_conv_supported(const GemmParams& g) {
 }
 
 int pope_launch_wide_conv(const GemmParams& g, hipStream_t stream) {
-    if (!pope_wide_conv_supported(g)) return POPE_ERR_ARG;
     if (size_t(g.M + PL_BM + 2 * g.conv_wp + 2) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + 256) * g.ldw * 4 >= (size_t(1) << 32) ||
         size_t(g.M + PL_BM) * g.ldc * 4 >= (size_t(1) << 32) - 512 || (g.res_pl && size_t(g.M + PL_BM) * g.ldres_pl * 4 >= (size_t(1) << 32) - 512))
         return POPE_ERR_ARG;
-    if (g.c_pl) return g.N <= 128 ? launch_conv<true, 2>(g, stream) : launch_conv<true, 4>(g, stream);
-    return g.N <= 128 ? launch_conv<false, 2>(g, stream) : launch_conv<false, 4>(g, stream);
+    if (g.c_pl) return g.N <= 128 ? launch<EPI_CONV, true, 2, true, 1>(g, stream) : launch<EPI_CONV, true, 4, true, 1>(g, stream);
+    return g.N <= 128 ? launch<EPI_CONV, false, 2, true, 1>(g, stream) : launch<EPI_CONV, false, 4, true, 1>(g, stream);
 }
 
 // f16x3 planes -> planes (QKV, FC1 of the ViT blocks) on the 256 x 256 LDS-direct mainloop: the shapes it serves
@@ -482,11 +436,10 @@ bool pope_wide_x3_supported(const GemmParams& g) {
 }
 
 int pope_launch_wide_x3(const GemmParams& g, hipStream_t stream) {
-    if (!pope_wide_x3_supported(g)) return POPE_ERR_ARG;
     if (size_t(g.M + PL_BM) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + 256) * g.ldw * 4 >= (size_t(1) << 32) ||
         size_t(g.M + PL_BM) * g.ldc * 4 >= (size_t(1) << 32) - 512)
         return POPE_ERR_ARG;
-    return g.epilogue == EPI_BIAS_GELU ? launch_x3<EPI_BIAS_GELU>(g, stream) : launch_x3<EPI_BIAS>(g, stream);
+    return g.epilogue == EPI_BIAS_GELU ? launch<EPI_BIAS_GELU, true, 4, true>(g, stream) : launch<EPI_BIAS, true, 4, true>(g, stream);
 }
 
 bool pope_plain256_supported(const GemmParams& g) {
@@ -504,7 +457,6 @@ bool pope_plain256_supported(const GemmParams& g) {
 }
 
 int pope_launch_plain256(const GemmParams& g, hipStream_t stream) {
-    if (!pope_plain256_supported(g)) return POPE_ERR_ARG;
     if (size_t(g.M + PL_BM) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + 256) * g.ldw * 4 >= (size_t(1) << 32) ||
         size_t(g.M + PL_BM) * g.ldc * 4 >= (size_t(1) << 32) - 512 || size_t(g.K) * 4 >= (size_t(1) << 31))
         return POPE_ERR_ARG;

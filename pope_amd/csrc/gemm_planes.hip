@@ -13,7 +13,7 @@
 // LDS rows are 160 bytes ([32 hi | 32 lo] halves + 32 B pad): conflict-free for the 16-row x 4-chunk fragment
 // reads; two stages x 256 rows = 80 KB per workgroup, two workgroups per CU = all 160 KB.
 #include "gemm_core.h"
-#include "kernels.h"
+#include "gemm_routes.h"
 
 namespace {
 
@@ -34,29 +34,6 @@ constexpr float L2E = 1.44269504088896340736f;
 
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// exact-erf GELU on a pair, Abramowitz-Stegun 7.1.26 form (derivation: gemm_f32.hip:gelu_erf2)
-__device__ __forceinline__ f32x2 gelu_erf_pair(f32x2 x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;
-    f32x2 t, e, relu;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
-        relu[i] = __builtin_fmaxf(x[i], 0.0f);
-    }
-    const f32x2 arg = (x * NHL2E) * x;
-    e[0] = __builtin_amdgcn_exp2f(arg[0]);
-    e[1] = __builtin_amdgcn_exp2f(arg[1]);
-    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
-    const f32x2 q = (poly * t) * e;
-    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
 }
 
 // PLAIN (GemmParams::plain): single-product f16 arithmetic on the same loader, LDS layout and epilogues.  An f16
@@ -496,7 +473,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                     continue;
                 } else if constexpr (EPI == EPI_BIAS_GELU) {
                     v = v * inv + bias;
-                    const f32x2 g01 = gelu_erf_pair(f32x2{v[0], v[1]}), g23 = gelu_erf_pair(f32x2{v[2], v[3]});
+                    const f32x2 g01 = pope_gelu_erf_pair(f32x2{v[0], v[1]}), g23 = pope_gelu_erf_pair(f32x2{v[2], v[3]});
                     v = f32x4{g01[0], g01[1], g23[0], g23[1]};
                 } else if constexpr (EPI == EPI_BIAS_RELU) {
                     v = v * inv + bias;
@@ -631,42 +608,73 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
 
 template <int EPI, bool OUT_PLANES, bool CONV = false, bool PLAIN = false>
 int launch16(const GemmParams& g, hipStream_t stream, int nbatch = 1) {
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_planes16_kernel<EPI, OUT_PLANES, CONV, PLAIN>, P16_LDS_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
     const int tiles = nbatch * ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     const int slots = 2 * pope_cu_count();   // two resident workgroups per CU (2 x 80 KB LDS)
-    hipLaunchKernelGGL((gemm_planes16_kernel<EPI, OUT_PLANES, CONV, PLAIN>), dim3(tiles < slots ? tiles : slots), dim3(THREADS), P16_LDS_BYTES,
-                       stream, g, tiles);
-    return pope_check_launch();
+    return pope_launch_lds<gemm_planes16_kernel<EPI, OUT_PLANES, CONV, PLAIN>>(dim3(tiles < slots ? tiles : slots), dim3(THREADS),
+                                                                               P16_LDS_BYTES, stream, g, tiles);
+}
+
+// The operand contract of the tile kernel, for every call that is not a stride-2 convolution: 32-bit buffer offsets, K-steps
+// of 32 (at least two), 16-byte rows, and the fields each epilogue reads.  The LDS-direct routes check their own shapes on top.
+bool args_ok(const GemmParams& g) {
+    if (g.epilogue == EPI_SIM) {   // batched similarity (dense matcher): C[b] = (A[b] . W[b]^T * alpha) / divisor
+        if (!g.a_pl || !g.w_pl || !g.C || g.nbatch <= 0 || g.M <= 0 || g.N <= 0) return false;
+        if (g.K < 2 * BK || (g.K % BK) || (g.lda & 31) || (g.ldw & 31) || g.ldc != g.N || g.divisor_eff == 0.f) return false;
+        if ((g.row_part || g.col_pmax) &&
+            (!g.row_part || !g.col_pmax || !g.col_psum || g.ncb != 2 * ((g.N + BN - 1) / BN) || g.nrb != 4 * ((g.M + BM - 1) / BM) ||
+             g.ldp < g.N || (g.ldp & 3)))
+            return false;
+        if ((size_t(g.nbatch) * g.M + BM) * g.lda * 4 >= (size_t(1) << 32) || (size_t(g.nbatch) * g.N + BN) * g.ldw * 4 >= (size_t(1) << 32) ||
+            (size_t(g.nbatch) * g.M + BM) * g.ldc * 4 >= (size_t(1) << 32) - 512)
+            return false;
+        return static_cast<long long>(g.nbatch) * ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) <= 0x7fffffffLL;
+    }
+    if (g.M <= 0 || g.N <= 0 || g.K < 2 * BK || (g.K % BK) || (g.N & 3) || (g.ldc & 3) || (g.lda & 7) || (g.ldw & 7)) return false;
+    if (!g.a_pl || !g.w_pl || (g.lda & 31) || (g.ldw & 31)) return false;
+    if (size_t(g.M + 256) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + BN) * g.ldw * 4 >= (size_t(1) << 32)) return false;
+    const bool out_planes = g.c_pl != nullptr;
+    if (out_planes ? (g.ldc & 31) != 0 : !g.C) return false;
+    // the epilogue addresses C (and res) through 32-bit buffer offsets
+    if (size_t(g.M + 256) * g.ldc * 4 >= (size_t(1) << 32) - 512) return false;
+    if (g.epilogue == EPI_BIAS_LS_RES && size_t(g.M + 256) * g.ldres * 4 >= (size_t(1) << 32) - 512) return false;
+    switch (g.epilogue) {
+        case EPI_BIAS:
+        case EPI_BIAS_GELU:
+        case EPI_BIAS_RELU: return true;
+        case EPI_QKV_F16: return g.plain && out_planes && g.sam_dim > 0 && !(g.sam_dim & 63);
+        case EPI_BIAS_LS_RES: return g.res && !out_planes && (g.gamma || g.res_mod > 0);
+        case EPI_SAM_QKV:
+            return g.sam_q && g.sam_k && g.sam_v && g.sam_rowmap && g.sam_hd > 0 && !(g.sam_hd & 3) && !(g.sam_dim & 63) &&
+                   g.N == 3 * g.sam_dim;
+        case EPI_CONV:
+            if (g.conv_cch > 0) return g.K == 9 * 32 * g.conv_cch && g.lda == 32 * g.conv_cch && g.conv_wp >= 3;
+            return !g.up_src || (out_planes && !g.res_pl);
+    }
+    return false;
 }
 
 }  // namespace
 
-// argument checks are the callers' (gemm_f16x3.hip: pope_launch_gemm_nt_f16x3_planes / pope_launch_sim_f16x3_planes)
-int pope_launch_planes16(const GemmParams& g, hipStream_t stream) {
+int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream) {
+    if (g.conv_s2_taps) return pope_wide_conv_s2_supported(g) ? pope_launch_wide_conv_s2(g, stream) : POPE_ERR_ARG;
+    if (!args_ok(g)) return POPE_ERR_ARG;
     const bool out_planes = g.c_pl != nullptr;
-    if (g.epilogue == EPI_SAM_QKV) {
-        if (!g.sam_q || !g.sam_k || !g.sam_v || !g.sam_rowmap || g.sam_hd <= 0 || (g.sam_hd & 3) || (g.sam_dim & 63) || g.N != 3 * g.sam_dim)
-            return POPE_ERR_ARG;
-        if (g.plain && pope_plain256_supported(g)) return pope_launch_plain256(g, stream);
-        return g.plain ? launch16<EPI_SAM_QKV, true, false, true>(g, stream) : launch16<EPI_SAM_QKV, true, false, false>(g, stream);
-    }
     if (g.plain && pope_plain256_supported(g)) return pope_launch_plain256(g, stream);   // long-K shapes at large M: gemm_plain.hip
-    if (g.plain) {   // single-product f16 (SAM encoder, precision "f16"): the four forms that path uses
+    if (g.epilogue == EPI_SAM_QKV)
+        return g.plain ? launch16<EPI_SAM_QKV, true, false, true>(g, stream) : launch16<EPI_SAM_QKV, true, false, false>(g, stream);
+    if (g.plain) {   // single-product f16 (SAM encoder, precision "f16"): the five forms that path uses
         if (g.epilogue == EPI_BIAS && !out_planes) return launch16<EPI_BIAS, false, false, true>(g, stream);
         if (g.epilogue == EPI_BIAS_GELU && out_planes) return launch16<EPI_BIAS_GELU, true, false, true>(g, stream);
         if (g.epilogue == EPI_QKV_F16 && out_planes) return launch16<EPI_QKV_F16, true, false, true>(g, stream);
         if (g.epilogue == EPI_BIAS_LS_RES && !out_planes) return launch16<EPI_BIAS_LS_RES, false, false, true>(g, stream);
-        if (g.epilogue == EPI_CONV && !out_planes && g.conv_cch > 0 && g.K == 9 * 32 * g.conv_cch && g.lda == 32 * g.conv_cch &&
-            g.conv_wp >= 3)
-            return launch16<EPI_CONV, false, true, true>(g, stream);
+        if (g.epilogue == EPI_CONV && !out_planes && g.conv_cch > 0) return launch16<EPI_CONV, false, true, true>(g, stream);
         return POPE_ERR_ARG;
     }
-    // planes -> planes at large M (QKV, FC1 of the ViT blocks): the 256 x 256 LDS-direct mainloop of gemm_plain.hip, same bits
-    // (round 4, same-box A/B inside bench.py: QKV 0.285 -> 0.273 ms, FC1 0.427 -> 0.351 ms, step 92.9 -> 89.0 ms)
     // large planes -> planes Linears on the LDS-direct mainloops (bit-identical to the tile kernel below): widths that leave a
     // partial 256-column tile but are multiples of 384 (QKV 1 152: 4.5 tiles of 256) on the 192 x 384 stream of gemm_rowln.hip
-    // (0.294 -> 0.266 ms; FC1's 1 536 = 6 x 256 is 2 % faster on the 256 x 256 tiles: profiles/r04/stream384_ab.txt)
+    // (0.294 -> 0.266 ms; FC1's 1 536 = 6 x 256 is 2 % faster on the 256 x 256 tiles: profiles/r04/stream384_ab.txt), the rest
+    // on the 256 x 256 mainloop of gemm_plain.hip (round 4, same-box A/B inside bench.py: QKV 0.285 -> 0.273 ms, FC1 0.427 ->
+    // 0.351 ms, step 92.9 -> 89.0 ms)
     if ((g.N & 255) && pope_stream384_supported(g)) return pope_launch_stream384(g, stream);
     if (pope_wide_x3_supported(g)) return pope_launch_wide_x3(g, stream);
     switch (g.epilogue) {
@@ -679,11 +687,10 @@ int pope_launch_planes16(const GemmParams& g, hipStream_t stream) {
             return launch16<EPI_SIM, false>(g, stream, g.nbatch);
         case EPI_CONV:
             if (g.conv_cch > 0) {
-                if (g.K != 9 * 32 * g.conv_cch || g.lda != 32 * g.conv_cch || g.conv_wp < 3) return POPE_ERR_ARG;
                 if (pope_wide_conv_supported(g)) return pope_launch_wide_conv(g, stream);   // 256-row LDS-direct tiles, same bits
                 return out_planes ? launch16<EPI_CONV, true, true>(g, stream) : launch16<EPI_CONV, false, true>(g, stream);
             }
-            if (g.up_src) return out_planes && !g.res_pl ? launch16<EPI_CONV_UP, true>(g, stream) : POPE_ERR_ARG;
+            if (g.up_src) return launch16<EPI_CONV_UP, true>(g, stream);
             return out_planes ? launch16<EPI_CONV, true>(g, stream) : launch16<EPI_CONV, false>(g, stream);
     }
     return POPE_ERR_ARG;

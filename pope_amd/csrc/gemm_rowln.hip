@@ -25,7 +25,7 @@
 // the stand-alone kernel: no E[x^2] - mean^2 cancellation); x and xn are stored with no load between the stores.
 // Reduction orders depend on the column only: batch invariance and run-to-run determinism are kept.
 #include "gemm_core.h"
-#include "kernels.h"
+#include "gemm_routes.h"
 
 namespace {
 
@@ -101,29 +101,6 @@ __device__ __forceinline__ void rl_barrier() {
 // of 384-column tiles (QKV: 3, FC1: 4 — the ViT-S/14 widths are multiples of 384, so the 192 x 384 stream has no partial
 // column tile, where 256 x 256 tiles compute 1 280 columns for QKV's 1 152), in gemm_plain.hip's epilogue arithmetic.
 enum { RL_LN_PLANES = 0, RL_LN_F32 = 1, RL_BIAS_PLANES = 2, RL_GELU_PLANES = 3 };
-
-// exact-erf GELU on a pair: the arithmetic of gemm_planes.hip:gelu_erf_pair, instruction for instruction (bit-identical)
-__device__ __forceinline__ f32x2 rl_gelu_pair(f32x2 x) {
-    constexpr float P = 0.3275911f * 0.70710678118654752440f;
-    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f,
-                    A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
-    constexpr float NHL2E = -0.5f * 1.44269504088896340736f;
-    f32x2 t, e, relu;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        t[i] = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x[i]), P, 1.0f));
-        relu[i] = __builtin_fmaxf(x[i], 0.0f);
-    }
-    const f32x2 arg = (x * NHL2E) * x;
-    e[0] = __builtin_amdgcn_exp2f(arg[0]);
-    e[1] = __builtin_amdgcn_exp2f(arg[1]);
-    f32x2 poly = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A3, A3});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A2, A2});
-    poly = __builtin_elementwise_fma(poly, t, f32x2{A1, A1});
-    const f32x2 q = (poly * t) * e;
-    return __builtin_elementwise_fma(relu, __builtin_elementwise_fma(q, f32x2{-2.f, -2.f}, f32x2{1.f, 1.f}), x * q);
-}
 
 // RES_TABLE (LayerNorm modes): the residual row is row % res_mod of a [res_mod, 384] table (patch embed: cls / conv bias + pos)
 template <class G, int MODE, bool RES_TABLE>
@@ -411,7 +388,7 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
                     for (int ni = 0; ni < 6; ++ni) {
                         f32x4 v = acc[mi][ni] * inv + bias[ni];
                         if constexpr (MODE == RL_GELU_PLANES) {
-                            const f32x2 g01 = rl_gelu_pair(f32x2{v[0], v[1]}), g23 = rl_gelu_pair(f32x2{v[2], v[3]});
+                            const f32x2 g01 = pope_gelu_erf_pair(f32x2{v[0], v[1]}), g23 = pope_gelu_erf_pair(f32x2{v[2], v[3]});
                             v = f32x4{g01[0], g01[1], g23[0], g23[1]};
                         }
                         pope_amax4x2(amax, v);
@@ -514,13 +491,10 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
 
 template <class G, int MODE, bool RES_TABLE>
 int launch_rowln_geo(const GemmParams& g, hipStream_t stream) {
-    static pope_dev_mask lds_ok{0};   // per kernel instantiation, per device
-    if (!pope_opt_in_lds(gemm_rowln16_kernel<G, MODE, RES_TABLE>, G::LDS_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
     const int ncol = (g.N + RN - 1) / RN;
     const int tiles = ((g.M + G::RM - 1) / G::RM) * ncol, cus = pope_cu_count();
-    hipLaunchKernelGGL((gemm_rowln16_kernel<G, MODE, RES_TABLE>), dim3(tiles < cus ? tiles : cus), dim3(G::RTH), G::LDS_BYTES, stream,
-                       g, tiles, ncol);
-    return pope_check_launch();
+    return pope_launch_lds<gemm_rowln16_kernel<G, MODE, RES_TABLE>>(dim3(tiles < cus ? tiles : cus), dim3(G::RTH), G::LDS_BYTES, stream,
+                                                                    g, tiles, ncol);
 }
 
 // Two tile geometries, the same arithmetic (bit-identical results): 192 rows (2 x 4 waves of 96 x 96: 1.0 staged byte per output
@@ -573,7 +547,6 @@ bool pope_stream384_supported(const GemmParams& g) {
 }
 
 int pope_launch_stream384(const GemmParams& g, hipStream_t stream) {
-    if (!pope_stream384_supported(g)) return POPE_ERR_ARG;
     return g.epilogue == EPI_BIAS_GELU ? launch_rowln_geo<RlGeo<192, 2>, RL_GELU_PLANES, false>(g, stream)
                                        : launch_rowln_geo<RlGeo<192, 2>, RL_BIAS_PLANES, false>(g, stream);
 }

@@ -76,7 +76,7 @@ struct GemmParams {
     int ldres_pl;
     float act_slope;
     int conv_cch, conv_wp;
-    // gemm_plain.hip CONV = 2 (pope_launch_wide_conv_s2): stride-2 convolution read straight from the zero-bordered INPUT tensor
+    // gemm_plain.hip CONV = 2 (conv_s2_taps > 0): stride-2 convolution read straight from the zero-bordered INPUT tensor
     // [n, conv_s2_hpi, conv_wp, 32 * conv_cch] (conv_s2_in_rows pixel rows) for the output grid [n, conv_s2_hpo, conv_s2_wpo];
     // conv_s2_taps = 9 (3 x 3, pad 1) or 1 (the 1 x 1 shortcut)
     int conv_s2_taps, conv_s2_hpi, conv_s2_hpo, conv_s2_wpo, conv_s2_in_rows;
@@ -114,27 +114,15 @@ int pope_launch_gemm_nt_f32(const GemmParams& g, hipStream_t stream);
 
 // Same contract on the f16 matrix cores with error-compensated operands (gemm_f16x3.hip).
 bool pope_gemm_f16x3_supported(const GemmParams& g);
-// Planes variant: W (and optionally A / C) as pre-split f16 planes, no splitting in the K loop.
-int pope_launch_gemm_nt_f16x3_planes(const GemmParams& g, hipStream_t stream);
-int pope_launch_sim_f16x3_planes(const GemmParams& g, hipStream_t stream);  // EPI_SIM, batched
+// Every GEMM on pre-split f16x3 planes or (GemmParams::plain) plain f16 operands: Linears (BIAS, BIAS_GELU, BIAS_RELU,
+// BIAS_LS_RES, QKV_F16, SAM_QKV), the batched similarity (SIM) and the convolutions (CONV: implicit 3 x 3, up_src, and —
+// conv_s2_taps > 0 — the stride-2 implicit form).  Checks the arguments and picks the mainloop (gemm_planes.hip).
+int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream);
+// whether pope_launch_gemm_planes takes a stride-2 convolution without the gathered tap tensor (conv.hip gathers otherwise)
+bool pope_wide_conv_s2_supported(const GemmParams& g);
 // residual GEMM + the following LayerNorm in one kernel (gemm_rowln.hip; N = 384 only: `supported` says)
 bool pope_gemm_rowln_supported(const GemmParams& g);
 int pope_launch_gemm_rowln(const GemmParams& g, hipStream_t stream);
-// the same 192 x 384 LDS-direct tile stream for planes -> planes Linears whose width is a multiple of 384 (gemm_rowln.hip)
-bool pope_stream384_supported(const GemmParams& g);
-int pope_launch_stream384(const GemmParams& g, hipStream_t stream);
-// plain-f16 long-K mainloop (gemm_plain.hip: 256-row tiles, LDS-direct staging) for the GemmParams::plain shapes it serves;
-// same results as pope_launch_planes16 on them
-bool pope_wide_x3_supported(const GemmParams& g);   // the same mainloop on f16x3 planes -> planes (BIAS, BIAS_GELU) at large M
-int pope_launch_wide_x3(const GemmParams& g, hipStream_t stream);
-bool pope_wide_conv_s2_supported(const GemmParams& g);   // stride-2 convolutions without the gathered tap tensor (large M)
-int pope_launch_wide_conv_s2(const GemmParams& g, hipStream_t stream);
-bool pope_wide_conv_supported(const GemmParams& g);  // the implicit 3 x 3 convolutions (EPI_CONV, conv_cch > 0) at large M
-int pope_launch_wide_conv(const GemmParams& g, hipStream_t stream);
-bool pope_plain256_supported(const GemmParams& g);
-int pope_launch_plain256(const GemmParams& g, hipStream_t stream);
-// the v_mfma_f32_16x16x32_f16 mainloop (gemm_planes.hip) behind both of the above; arguments already validated
-int pope_launch_planes16(const GemmParams& g, hipStream_t stream);
 constexpr float K_PLANES_ACT_SCALE = 8.0f, K_PLANES_W_SCALE = 256.0f;  // == POPE_PLANES_*_SCALE of pope_hip.h
 
 // y = LayerNorm(x) written as f16 planes (scale POPE_PLANES_ACT_SCALE), [rows, dim] halves each.

@@ -275,7 +275,7 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
         g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
         g.epilogue = epi;
         g.range_flag = p.range_flag; g.range_bit = POPE_RANGE_GELU;
-        return pope_launch_gemm_nt_f16x3_planes(g, stream);
+        return pope_launch_gemm_planes(g, stream);
     };
     // 1. operands of the projections
     if (f32) {

@@ -629,7 +629,7 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
         g.row_part = p.row_part; g.col_pmax = p.col_pmax; g.col_psum = p.col_psum;
         g.ncb = p.ncb; g.nrb = p.nrb; g.ldp = p.ldp;
         g.sim_mask0 = p.fill0; g.sim_mask1 = p.fill1;   // EPI_SIM_MASK when either is set
-        rc = pope_launch_sim_f16x3_planes(g, stream);
+        rc = pope_launch_gemm_planes(g, stream);
         if (rc == 0) {
             sim_done = true;
             hipLaunchKernelGGL(combine_row_stats_kernel, dim3(unsigned((size_t(p.n) * p.L + 255) / 256)), dim3(256), 0, stream, p);

@@ -935,7 +935,7 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
         gp_.lda = Kc; gp_.ldw = Kc; gp_.ldc = plain && c_pl ? N / 2 : N; gp_.M = rows; gp_.N = N; gp_.K = Kc;
         gp_.epilogue = epi; gp_.gamma = gamma; gp_.res = res; gp_.ldres = N; gp_.res_mod = res_mod;
         gp_.plain = plain;
-        return pope_launch_gemm_nt_f16x3_planes(gp_, stream);
+        return pope_launch_gemm_planes(gp_, stream);
     };
     auto layernorm = [&](const float* w, const float* b) -> int {   // LN(x) -> xn_pl as this precision's GEMM operand
         if (!plain) return pope_launch_layernorm_planes(x, dim, w, b, xn_pl, rows, dim, eps, flag, stream);
@@ -1004,7 +1004,7 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
             gq.sam_bytes[0] = unsigned(p.qp); gq.sam_bytes[1] = unsigned(p.kp); gq.sam_bytes[2] = unsigned(p.vp);
             gq.sam_hd = hd; gq.sam_dim = dim; gq.sam_npad = a.Npad; gq.sam_dq = a.DQ; gq.sam_dv = a.DV;
             gq.sam_qscale = 1.0f / sqrtf(float(hd)) * L2E;
-            POPE_TRY(pope_launch_planes16(gq, stream));
+            POPE_TRY(pope_launch_gemm_planes(gq, stream));
             if (a.nw * a.ws > a.g) {   // ... the rows of the edge windows' zero-padded tokens from the bias ...
                 const long long total = (long long)a.B * (a.nw * a.ws * a.nw * a.ws - a.g * a.g) * a.heads * 3 * (hd / 8);
                 if (plain)
@@ -1095,7 +1095,7 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
         c.conv_cch = occ / 32; c.conv_wp = Wp;
         c.range_flag = flag; c.range_bit = POPE_RANGE_INPUT;
         c.nbatch = 1;
-        POPE_TRY(pope_launch_planes16(c, stream));
+        POPE_TRY(pope_launch_gemm_planes(c, stream));
     }
     hipLaunchKernelGGL((sam_ln2d_kernel<false, false>), dim3(grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out,
                        q.B, g, oc, neck_eps, nullptr);
