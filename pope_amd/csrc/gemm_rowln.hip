@@ -427,10 +427,12 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
     RL_STAMP(0);
 
     for (int s = 0; tile < n_tiles; ++s) {
-        // This wave's pieces of stage s have landed.  After a tile seam nothing is waited for: the step's loads were issued
-        // before the epilogue, whose residual loads — younger, and returning in order — have been consumed since; waiting here
-        // would wait for the acknowledgement of the epilogue's last stores.
-        if (kt != 0 || ord == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
+        // This wave's pieces of stage s have landed.  After a tile seam of the LayerNorm modes nothing is waited for: the step's
+        // loads were issued before the epilogue, whose residual loads — issued by every lane of every wave, younger, and
+        // returning in order — have been consumed since; waiting here would wait for the acknowledgement of the epilogue's last
+        // stores.  The planes modes (RL_BIAS_PLANES / RL_GELU_PLANES) load nothing in their epilogue unless there is a bias, so
+        // they wait at every K-step.
+        if (!LN || kt != 0 || ord == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
         rl_barrier();   // ... and everyone's; every wave has left the other stage (K-step s - 1, or the epilogue's buffers)
         const bool seam = kt + 1 == nk;
         dma((s + 1) & 1, seam ? next_tile : tile, seam ? 0 : kt + 1);
