@@ -378,6 +378,60 @@ int pope_sam_encoder_forward_f32(const pope_sam_encoder_weights* w_host, const f
                                  int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
+/* ---- SAM mask decoder (point and box prompts) ------------------------------------------------------------------ */
+
+/* MaskDecoder.forward with TwoWayTransformer — segment_anything/segment_anything/modeling/{mask_decoder,transformer}.py as
+ * build_sam.py configures them (dim 256, 8 heads, attention_downsample_rate 2, mlp_dim 2048, depth 2, a 64 x 64 embedding,
+ * 4 mask tokens, IoU head depth 3 / hidden 256).  image[256, 64, 64] and image_pe[256, 64, 64] fp32 (one image);
+ * sparse[P, n_sparse, 256] (0 <= n_sparse <= 11; NULL when 0); dense[P, 256, 64, 64] with dense_stride floats between
+ * prompts: 0 (a broadcast, what PromptEncoder returns without a mask: layer 0's image-only projections then run once per
+ * call) or 256 * 4096.  multimask != 0: masks[P, 3, 256, 256] = mask tokens 1..3 and iou[P, 3]; else masks[P, 1, 256, 256]
+ * = mask token 0 and iou[P, 1] (predict_masks' slices).  Optional hs_out[P, 5 + n_sparse, 256] (final tokens) and
+ * keys_out[P, 4096, 256] (final image tokens).  The prompts run in chunks: the workspace is bounded by 16 prompts, and a
+ * prompt's outputs are bit-identical whatever P and wherever it falls.
+ * precision POPE_PREC_F16X3: the image-side Linears (`*_wp`) on weight planes (scale 256), their activations as planes
+ * (range-guarded: POPE_RANGE_LAYERNORM, POPE_RANGE_QKV); POPE_PREC_F32_MFMA: every `*_wp` a plain fp32 matrix on the fp32
+ * GEMM.  Token-side Linears, attention, LayerNorms and the upscaling tail are fp32 in both.
+ * Layouts (torch [out, in] unless stated): sa_qkv_w[768, 256] = q | k | v of self_attn; img_qk_wp[256, 256] =
+ * cross_attn_token_to_image.k_proj | cross_attn_image_to_token.q_proj (both read keys + pe); img_v_wp[128, 256] =
+ * cross_attn_token_to_image.v_proj; i2t_kv_w[256, 256] = cross_attn_image_to_token.k_proj | v_proj; tokens[5, 256] = iou
+ * token, mask tokens; up1_wp[256, 256]: row tap * 64 + co (tap = 2 dy + dx) = output_upscaling[0].weight[:, co, dy, dx],
+ * up1_b[256] its bias per row; up2_w[128, 64]: row tap * 32 + c = output_upscaling[3].weight[:, c, dy, dx] (fp32);
+ * hyper_w / hyper_b[3 i + j] = output_hypernetworks_mlps[i].layers[j]; iou_w / iou_b[j] = iou_prediction_head.layers[j]. */
+typedef struct pope_sam_decoder_layer_weights {
+    const float *sa_qkv_w, *sa_qkv_b, *sa_o_w, *sa_o_b, *norm1_w, *norm1_b;
+    const float *t2i_q_w, *t2i_q_b, *t2i_o_w, *t2i_o_b, *norm2_w, *norm2_b;
+    const float *mlp1_w, *mlp1_b, *mlp2_w, *mlp2_b, *norm3_w, *norm3_b;
+    const float *i2t_kv_w, *i2t_kv_b;
+    const void* img_qk_wp; const float* img_qk_b;
+    const void* img_v_wp; const float* img_v_b;
+    const void* i2t_o_wp; const float* i2t_o_b;
+    const float *norm4_w, *norm4_b;
+} pope_sam_decoder_layer_weights;
+typedef struct pope_sam_decoder_weights {
+    int dim, heads, mlp_dim, depth, grid, num_mask_tokens, iou_hidden, iou_depth;
+    int precision;                /* POPE_PREC_F16X3 or POPE_PREC_F32_MFMA */
+    float token_eps, up_eps;      /* nn.LayerNorm of the tokens / image tokens (1e-5); LayerNorm2d of the upscaling (1e-6) */
+    const float* tokens;
+    const pope_sam_decoder_layer_weights* layers_host;   /* HOST array [depth] */
+    const float *fin_q_w, *fin_q_b;
+    const void* fin_k_wp; const float* fin_k_b;
+    const void* fin_v_wp; const float* fin_v_b;
+    const float *fin_o_w, *fin_o_b, *norm_final_w, *norm_final_b;
+    const void* up1_wp; const float* up1_b;
+    const float *up_ln_w, *up_ln_b, *up2_w, *up2_b;
+    const float* hyper_w[12];
+    const float* hyper_b[12];
+    const float* iou_w[3];
+    const float* iou_b[3];
+} pope_sam_decoder_weights;
+/* 0 for an unsupported geometry or argument; shared != 0: the dense embedding is a broadcast (dense_stride 0). */
+size_t pope_sam_decoder_workspace_bytes(const pope_sam_decoder_weights* w_host, int P, int n_sparse, int shared);
+int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w_host, const float* image, const float* image_pe,
+                                 const float* sparse, int P, int n_sparse, const float* dense, long long dense_stride,
+                                 int multimask, float* masks, float* iou, float* hs_out, float* keys_out,
+                                 void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+
 /* ---- caller-side preprocessing, batched ------------------------------------------------- */
 
 /* set_torch_image for P crops at once — segment_anything/segment_anything/dinov2_utils.py:55-78: Resize (Pillow's

@@ -50,6 +50,22 @@ class SamEncoderWeights(C.Structure):
         ("neck2_wp", C.c_void_p), ("neck3_w", C.c_void_p), ("neck3_b", C.c_void_p), ("block_eps", C.c_float), ("neck_eps", C.c_float)]
 
 
+class SamDecoderLayerWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "sa_qkv_w", "sa_qkv_b", "sa_o_w", "sa_o_b", "norm1_w", "norm1_b", "t2i_q_w", "t2i_q_b", "t2i_o_w", "t2i_o_b", "norm2_w",
+        "norm2_b", "mlp1_w", "mlp1_b", "mlp2_w", "mlp2_b", "norm3_w", "norm3_b", "i2t_kv_w", "i2t_kv_b", "img_qk_wp", "img_qk_b",
+        "img_v_wp", "img_v_b", "i2t_o_wp", "i2t_o_b", "norm4_w", "norm4_b")]
+
+
+class SamDecoderWeights(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dim", "heads", "mlp_dim", "depth", "grid", "num_mask_tokens", "iou_hidden", "iou_depth",
+                                       "precision")] + [
+        ("token_eps", C.c_float), ("up_eps", C.c_float), ("tokens", C.c_void_p), ("layers_host", C.POINTER(SamDecoderLayerWeights))] + [
+        (n, C.c_void_p) for n in ("fin_q_w", "fin_q_b", "fin_k_wp", "fin_k_b", "fin_v_wp", "fin_v_b", "fin_o_w", "fin_o_b",
+                                  "norm_final_w", "norm_final_b", "up1_wp", "up1_b", "up_ln_w", "up_ln_b", "up2_w", "up2_b")] + [
+        ("hyper_w", C.c_void_p * 12), ("hyper_b", C.c_void_p * 12), ("iou_w", C.c_void_p * 3), ("iou_b", C.c_void_p * 3)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pope_hip.h
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
@@ -120,6 +136,10 @@ PROTOTYPES = {
     "pope_sam_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(SamEncoderWeights), C.c_int]),
     "pope_sam_encoder_forward_f32": (C.c_int, [C.POINTER(SamEncoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_int_p,
                                                C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_sam_decoder_workspace_bytes": (C.c_size_t, [C.POINTER(SamDecoderWeights), C.c_int, C.c_int, C.c_int]),
+    "pope_sam_decoder_forward_f32": (C.c_int, [C.POINTER(SamDecoderWeights)] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p,
+                                                                                                  C.c_longlong, C.c_int]
+                                     + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_preprocess_u8_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
                                + [C.c_int] * 7 + [c_float_p, c_float_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pope_crop_normalize_u8_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [c_float_p, c_float_p, C.c_void_p, C.c_void_p]),

@@ -711,6 +711,24 @@ int pope_sam_encoder_forward_f32(const pope_sam_encoder_weights* w, const float*
     return pope_launch_sam_encoder(q, static_cast<hipStream_t>(stream));
 }
 
+size_t pope_sam_decoder_workspace_bytes(const pope_sam_decoder_weights* w, int P, int n_sparse, int shared) {
+    return pope_sam_decoder_workspace(w, P, n_sparse, shared);
+}
+
+int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w, const float* image, const float* image_pe, const float* sparse,
+                                 int P, int n_sparse, const float* dense, long long dense_stride, int multimask, float* masks,
+                                 float* iou, float* hs_out, float* keys_out, void* workspace, size_t workspace_bytes,
+                                 unsigned* range_flag, void* stream) {
+    SamDecArgs a{};
+    a.w = w; a.image = image; a.image_pe = image_pe; a.sparse = sparse; a.dense = dense;
+    a.P = P; a.n_sparse = n_sparse; a.multimask = multimask; a.dense_stride = dense_stride;
+    a.masks = masks; a.iou = iou; a.hs_out = hs_out; a.keys_out = keys_out;
+    a.ws = workspace; a.ws_bytes = workspace_bytes; a.range_flag = range_flag;
+    if (pope_sam_decoder_workspace(w, P, n_sparse, dense_stride == 0) == 0) return POPE_ERR_ARG;   // before any HIP call
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
+}
+
 int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount,
                            const int* hk, int kh, const int* vstart, const int* vcount, const int* vk, int kv, int top, int left,
                            int ch, int cw, int row0, int nrows, const float* mean_host, const float* std_host, float* out,

@@ -343,3 +343,17 @@ struct PoseParams {
 size_t pope_pose_workspace(int B, long long M);
 int pope_launch_estimate_pose(PoseParams q, void* ws, size_t ws_bytes, hipStream_t stream);
 int pope_launch_five_point(const double* x0, const double* x1, int S, double* E_out, int* n_out, hipStream_t stream);
+
+// SAM mask decoder (sam_decoder.hip): the arguments of pope_sam_decoder_forward_f32
+struct SamDecArgs {
+    const pope_sam_decoder_weights* w;
+    const float *image, *image_pe, *sparse, *dense;
+    int P, n_sparse, multimask;
+    long long dense_stride;
+    float *masks, *iou, *hs_out, *keys_out;
+    void* ws;
+    size_t ws_bytes;
+    unsigned* range_flag;
+};
+size_t pope_sam_decoder_workspace(const pope_sam_decoder_weights* w, int P, int n_sparse, int shared);
+int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream);

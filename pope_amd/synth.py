@@ -455,3 +455,74 @@ def masked_xfmr_case():
     m0[1, :, 20:] = False
     m1[0, :, 28:] = False
     return f0, f1, m0.flatten(1), m1.flatten(1)
+
+
+# ---- SAM prompt encoder + mask decoder ---------------------------------------------------------------------------------
+def synthetic_sam_decoder_state_dict(seed=0):
+    """Seeded synthetic weights in the layout of a `Sam` checkpoint's `prompt_encoder.*` and `mask_decoder.*` keys
+    (segment_anything/modeling/{prompt_encoder,mask_decoder,transformer}.py as build_sam.py builds them).  Linear and
+    (transposed) convolution weights have std 1 / sqrt(fan_in), so every branch and the mask logits stay O(1)."""
+    from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer
+    g = torch.Generator().manual_seed(seed)
+    pe = PromptEncoder(embed_dim=256, image_embedding_size=(64, 64), input_image_size=(1024, 1024), mask_in_chans=16)
+    md = MaskDecoder(transformer_dim=256, transformer=TwoWayTransformer(depth=2, embedding_dim=256, num_heads=8, mlp_dim=2048),
+                     num_multimask_outputs=3, iou_head_depth=3, iou_head_hidden_dim=256)
+    sd = {}
+    for prefix, model in (("prompt_encoder.", pe), ("mask_decoder.", md)):
+        for mname, m in model.named_modules():
+            for pname, t in list(m.named_parameters(recurse=False)) + list(m.named_buffers(recurse=False)):
+                key = prefix + (mname + "." if mname else "") + pname
+                shape = tuple(t.shape)
+                if isinstance(m, (torch.nn.LayerNorm,)) or type(m).__name__ == "LayerNorm2d":
+                    v = (1.0 + 0.1 * torch.randn(shape, generator=g)) if pname == "weight" else 0.05 * torch.randn(shape, generator=g)
+                elif pname == "bias":
+                    v = 0.1 * torch.randn(shape, generator=g)
+                elif isinstance(m, torch.nn.Linear):
+                    v = torch.randn(shape, generator=g) / math.sqrt(shape[1])
+                elif isinstance(m, torch.nn.ConvTranspose2d):
+                    v = torch.randn(shape, generator=g) / math.sqrt(shape[0])
+                elif isinstance(m, torch.nn.Conv2d):
+                    v = torch.randn(shape, generator=g) / math.sqrt(shape[1] * shape[2] * shape[3])
+                else:   # embeddings, the Gaussian frequency matrix
+                    v = torch.randn(shape, generator=g)
+                sd[key] = v.float().contiguous()
+    return sd
+
+
+def synthetic_sam_image_embedding(seed=0):
+    """A seeded unit-scale image embedding [1, 256, 64, 64] (what the SAM image encoder hands the decoder)."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(1, 256, 64, 64, generator=g, dtype=torch.float32)
+
+
+SAM_DECODER_CASES = ("grid", "box")
+
+
+def sam_decoder_case(name):
+    """Prompts of the decoder fixtures: (points (coords, labels) or None, boxes or None, multimask_output).
+    "grid": SamAutomaticMaskGenerator's 16 x 16 point grid of a 480 x 640 frame, mapped into the 1024 frame as
+    ResizeLongestSide.apply_coords maps it (float64, as the generator hands them to predict_torch), label 1, one point per
+    prompt (the prompt encoder adds the padding point).  "box": 6 prompts of two points (labels 1 / 0) and a box."""
+    import numpy as np
+    if name == "grid":
+        n, h, w = 16, 480, 640
+        off = 1 / (2 * n)
+        side = np.linspace(off, 1 - off, n)
+        xs, ys = np.tile(side[None, :], (n, 1)), np.tile(side[:, None], (1, n))
+        pts = np.stack([xs, ys], axis=-1).reshape(-1, 2) * np.array([w, h])[None, :]
+        scale = 1024 * 1.0 / max(h, w)
+        nh, nw = int(h * scale + 0.5), int(w * scale + 0.5)
+        pts = pts.astype(float)
+        pts[..., 0] = pts[..., 0] * (nw / w)
+        pts[..., 1] = pts[..., 1] * (nh / h)
+        coords = torch.as_tensor(pts)[:, None, :]
+        labels = torch.ones(coords.shape[0], dtype=torch.int)[:, None]
+        return (coords, labels), None, True
+    if name == "box":
+        g = torch.Generator().manual_seed(17)
+        coords = torch.rand(6, 2, 2, generator=g) * torch.tensor([1024.0, 768.0])
+        labels = torch.tensor([[1, 0]] * 6, dtype=torch.int)
+        lo = torch.rand(6, 2, generator=g) * torch.tensor([600.0, 400.0])
+        boxes = torch.cat([lo, lo + 100 + torch.rand(6, 2, generator=g) * 300], dim=1)
+        return (coords, labels), boxes, False
+    raise KeyError(name)
