@@ -95,6 +95,24 @@ int pope_linear_planes_f32(const void* a_planes, const void* w_planes, const flo
 int pope_layernorm_planes_f32(const float* x, const float* weight, const float* bias, void* y_planes,
                               int rows, int dim, float eps, unsigned* range_flag, void* stream);
 
+/* Test entry of the ViT's LayerNorm-fused residual GEMM (dim 384; the patch embed, proj and fc2 launches of
+ * pope_vit_forward_f32 past its small-batch switch):
+ *     x  = res + gamma * (A.W^T + bias)            A planes [M,K], W planes [384,K]; x [M,384] fp32, may alias res
+ *     xn = LayerNorm(x) * ln_w + ln_b              eps inside the sqrt; exactly one of ln_planes (activation planes
+ *                                                  [M,384], range-guarded: POPE_RANGE_LAYERNORM) and ln_out (fp32 [M,384])
+ * res_mod == 0: res [M,384], gamma required; res_mod > 0: residual row = res[row % res_mod] of a [res_mod,384] table.
+ * bias and gamma may be NULL (zero, one).  K % 32 == 0, K >= 64, M >= 1, (M + 192) * 1536 < 2^32 - 512; a call outside
+ * this returns POPE_ERR_ARG before any HIP call. */
+int pope_linear_rowln_f32(const void* a_planes, const void* w_planes, int M, int K, const float* bias, const float* gamma,
+                          const float* res, int res_mod, float* x, const float* ln_w, const float* ln_b, float eps,
+                          void* ln_planes, float* ln_out, unsigned* range_flag, void* stream);
+/* Test entry of its small-batch twin, the stand-alone LayerNorm that pope_vit_forward_f32 runs after a
+ * pope_linear_planes_f32(..., POPE_EPI_BIAS_LS_RES) below the switch: the fused epilogue's reduction order, bit for bit.
+ * x [rows,384] -> exactly one of y_planes (activation planes, POPE_RANGE_LAYERNORM) and y_f32 (fp32; range_flag
+ * untouched).  rows >= 1; a call outside this returns POPE_ERR_ARG before any HIP call. */
+int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const float* bias, void* y_planes, float* y_f32,
+                                   int rows, float eps, unsigned* range_flag, void* stream);
+
 /* PatchEmbed.forward + prepare_tokens_with_masks — patch_embed.py:69-82,
  * vision_transformer.py:191-200.  img[B,3,H,W]; proj_w[dim, 3*patch*patch];
  * posb[ntok, dim] = {cls_token + pos[0]; conv_bias + pos[n]} with pos already interpolated to

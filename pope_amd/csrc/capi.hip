@@ -149,6 +149,28 @@ int pope_layernorm_planes_f32(const float* x, const float* weight, const float* 
     return pope_launch_layernorm_planes(x, dim, weight, bias, y_planes, rows, dim, eps, range_flag, static_cast<hipStream_t>(stream));
 }
 
+// the `rowln` launch of vit_forward_impl with every operand from the caller; checked before the stream's device is touched
+int pope_linear_rowln_f32(const void* a_planes, const void* w_planes, int M, int K, const float* bias, const float* gamma,
+                          const float* res, int res_mod, float* x, const float* ln_w, const float* ln_b, float eps,
+                          void* ln_planes, float* ln_out, unsigned* range_flag, void* stream) {
+    GemmParams g = {};
+    g.a_pl = a_planes; g.w_pl = w_planes; g.bias = bias; g.gamma = gamma; g.res = res; g.res_mod = res_mod;
+    g.C = x; g.M = M; g.N = 384; g.K = K; g.lda = K; g.ldw = K; g.ldc = 384; g.ldres = 384;
+    g.epilogue = EPI_BIAS_LS_RES;
+    g.ln_w = ln_w; g.ln_b = ln_b; g.ln_eps = eps; g.ln_planes = ln_planes; g.ln_f32 = ln_out;
+    g.range_flag = range_flag;
+    if (!pope_gemm_rowln_args_ok(g)) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_gemm_rowln(g, static_cast<hipStream_t>(stream));
+}
+
+int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const float* bias, void* y_planes, float* y_f32,
+                                   int rows, float eps, unsigned* range_flag, void* stream) {
+    if (!x || !weight || !bias || (!y_planes) == (!y_f32) || rows <= 0) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_layernorm_rowln_order(x, weight, bias, y_planes, y_f32, rows, eps, range_flag, static_cast<hipStream_t>(stream));
+}
+
 int pope_patch_embed_f32(const float* img, const float* proj_w, const float* posb, float* tokens, int B, int H,
                          int W, int patch, int dim, void* stream) {
     StreamDevice on_device(stream);

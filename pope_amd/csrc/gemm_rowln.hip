@@ -316,9 +316,13 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
         }
         __builtin_amdgcn_sched_barrier(0);
         RL_STAMP(4);
+        // Rows past M (the ragged last tile: zero A rows, a zero or table residual row) are normalised but never stored, and
+        // they raise nothing: the range flag depends on the real rows only, as in layernorm_rowln_order.  Row 16 mi of this
+        // lane is real when 16 mi < live.
+        const int live = g.M - (m0 + rl);
         float finite_probe = 0.f;   // a non-finite row (poisoned x) has a non-finite mean or rstd
 #pragma unroll
-        for (int mi = 0; mi < NMI; ++mi) finite_probe += __builtin_fabsf(mean[mi]) + rstd[mi];
+        for (int mi = 0; mi < NMI; ++mi) finite_probe += 16 * mi < live ? __builtin_fabsf(mean[mi]) + rstd[mi] : 0.f;
         // ---- 4. xn = (x - mean) * rstd * w + b -> planes (or fp32) ---------------------------------------------------
         f32x2 amax = {0.f, 0.f};
 #pragma unroll
@@ -333,7 +337,7 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
                         const f32x4 y = acc[mi][ni] * rstd[mi] * lw + lb;
                         if constexpr (LN_PLANES) {
                             const f32x4 ys = y * A_SCALE;
-                            pope_amax4x2(amax, ys);
+                            pope_amax4x2(amax, 16 * mi < live ? ys : f32x4{0.f, 0.f, 0.f, 0.f});
                             f16x4 hi, lo;
                             pope_split4(ys, hi, lo);
                             const int c = ni * 16 + 4 * q4;   // column within the wave's 96 = three planes chunks of 128 bytes
@@ -524,13 +528,17 @@ bool pope_gemm_rowln_supported(const GemmParams& g) {
            size_t(g.M + 192) * g.lda * 4 < (size_t(1) << 32) && size_t(g.M + 192) * RN * 4 < (size_t(1) << 32) - 512;
 }
 
+bool pope_gemm_rowln_args_ok(const GemmParams& g) {
+    if (!g.a_pl || !g.w_pl || !g.C || !g.res || !g.ln_w || !g.ln_b || (!g.ln_planes) == (!g.ln_f32) || g.M <= 0) return false;
+    if (!pope_gemm_rowln_supported(g)) return false;
+    return g.res_mod >= 0 && (g.res_mod > 0 || g.gamma);
+}
+
 // x = res + gamma * (A.W^T + bias) -> g.C (fp32, may alias res), LayerNorm(x; ln_w, ln_b, ln_eps) -> g.ln_planes or g.ln_f32
 int pope_launch_gemm_rowln(const GemmParams& g_in, hipStream_t stream) {
     GemmParams g = g_in;
     g.rl_prefetch = 1;   // touch the tile's residual lines during its K loop (finding 21: proj -3 %)
-    if (!g.a_pl || !g.w_pl || !g.C || !g.res || !g.ln_w || !g.ln_b || (!g.ln_planes) == (!g.ln_f32) || g.M <= 0) return POPE_ERR_ARG;
-    if (!pope_gemm_rowln_supported(g)) return POPE_ERR_ARG;
-    if (g.res_mod < 0 || (g.res_mod == 0 && !g.gamma)) return POPE_ERR_ARG;
+    if (!pope_gemm_rowln_args_ok(g)) return POPE_ERR_ARG;
     if (g.res_mod > 0) return g.ln_planes ? launch_rowln<RL_LN_PLANES, true>(g, stream) : launch_rowln<RL_LN_F32, true>(g, stream);
     return g.ln_planes ? launch_rowln<RL_LN_PLANES, false>(g, stream) : launch_rowln<RL_LN_F32, false>(g, stream);
 }

@@ -122,6 +122,8 @@ int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream);
 bool pope_wide_conv_s2_supported(const GemmParams& g);
 // residual GEMM + the following LayerNorm in one kernel (gemm_rowln.hip; N = 384 only: `supported` says)
 bool pope_gemm_rowln_supported(const GemmParams& g);
+// the whole argument contract of pope_launch_gemm_rowln (host only: no HIP call)
+bool pope_gemm_rowln_args_ok(const GemmParams& g);
 int pope_launch_gemm_rowln(const GemmParams& g, hipStream_t stream);
 constexpr float K_PLANES_ACT_SCALE = 8.0f, K_PLANES_W_SCALE = 256.0f;  // == POPE_PLANES_*_SCALE of pope_hip.h
 
