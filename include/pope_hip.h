@@ -450,6 +450,32 @@ int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w_host, const f
                                  int multimask, float* masks, float* iou, float* hs_out, float* keys_out,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
+/* ---- SAM automatic mask generator: post-processing of one decoder call ------------------------------------------ */
+
+/* Sam.postprocess_masks (modeling/sam.py) and the tail of SamAutomaticMaskGenerator._process_batch in one pass over the
+ * low-res logits.  low_res[M, h, w] fp32 (the decoder's masks, flattened over prompts x masks); selection[n_sel] = DEVICE
+ * int32 indices into M in the order the results are wanted (NULL: the first n_sel masks; an index outside [0, M) yields an
+ * empty mask); the frame: img_size (the 1024 square), (ih, iw) = the resized frame inside it, (H, W) = the original frame.
+ * Per selected mask the logit of every frame pixel is the reference's two bilinear resamplings (low-res -> img_size x
+ * img_size, crop to [:ih, :iw], -> H x W; align_corners=False), bit-equal to torch's CPU kernels: per axis
+ * scale = (float)n_in / n_out, src = max(fmaf(scale, dst + 0.5f, -0.5f), 0), i0 = (int)src, i1 = min(i0 + 1, n_in - 1),
+ * l1 = src - i0, value = fmaf(1 - l1, in[i0], l1 * in[i1]), x axis first.  Outputs:
+ *   stats[n_sel, 8] int32: #(logit > thr + offset), #(logit > thr - offset), #(logit > thr), the box x0, y0, x1, y1 of
+ *     logit > thr (inclusive maxima, 0 0 0 0 for an empty mask: amg.py batched_mask_to_box) and the fp32 bits of the
+ *     stability score (float)n_hi / (float)n_lo; the thresholds are (float)(mask_threshold +- stability_offset);
+ *   packed[n_sel, H, ceil(W / 32)] uint32 (optional): logit > thr, bit (x & 31) of word (x >> 5), pad bits zero;
+ *   logits[n_sel, H, W] fp32 (optional): the dense logits (what postprocess_masks returns).
+ * A mask's results do not depend on M, n_sel or the other masks of the call.  workspace: 4-byte aligned. */
+size_t pope_sam_postprocess_workspace_bytes(int img_size, int H, int W);   /* 0 for an unsupported geometry */
+int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const int* selection, int n_sel, int img_size,
+                             int ih, int iw, int H, int W, double mask_threshold, double stability_offset, int* stats,
+                             unsigned* packed, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+/* Greedy box NMS for one category as torchvision.ops.nms defines it: boxes[n, 4] fp32 XYXY, scores[n] fp32, n <= 2048;
+ * order by score descending, stable; a box is dropped when its IoU with a kept box is > iou_threshold
+ * (area = (x1 - x0) * (y1 - y0), iou = inter / (area_i + area_j - inter), fp32).  keep[n] int32 receives the kept indices
+ * in score order, count[1] their number (both DEVICE). */
+int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_threshold, int* keep, int* count, void* stream);
+
 /* ---- caller-side preprocessing, batched ------------------------------------------------- */
 
 /* set_torch_image for P crops at once — segment_anything/segment_anything/dinov2_utils.py:55-78: Resize (Pillow's

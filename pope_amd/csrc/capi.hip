@@ -751,6 +751,25 @@ int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w, const float*
     return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
 }
 
+size_t pope_sam_postprocess_workspace_bytes(int img_size, int H, int W) { return pope_sam_postprocess_workspace(img_size, H, W); }
+
+int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const int* selection, int n_sel, int img_size, int ih, int iw,
+                             int H, int W, double mask_threshold, double stability_offset, int* stats, unsigned* packed,
+                             float* logits, void* workspace, size_t workspace_bytes, void* stream) {
+    SamPostArgs a{};
+    a.low = low_res; a.M = M; a.h = h; a.w = w; a.sel = selection; a.n_sel = n_sel;
+    a.img = img_size; a.ih = ih; a.iw = iw; a.H = H; a.W = W;
+    a.mask_threshold = mask_threshold; a.stability_offset = stability_offset;
+    a.stats = stats; a.packed = packed; a.logits = logits; a.ws = workspace; a.ws_bytes = workspace_bytes;
+    StreamDevice on_device(stream);
+    return pope_launch_sam_postprocess(a, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_threshold, int* keep, int* count, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_nms(boxes, scores, n, iou_threshold, keep, count, static_cast<hipStream_t>(stream));
+}
+
 int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount,
                            const int* hk, int kh, const int* vstart, const int* vcount, const int* vk, int kv, int top, int left,
                            int ch, int cw, int row0, int nrows, const float* mean_host, const float* std_host, float* out,

@@ -359,3 +359,20 @@ struct SamDecArgs {
 };
 size_t pope_sam_decoder_workspace(const pope_sam_decoder_weights* w, int P, int n_sparse, int shared);
 int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream);
+
+// SAM generator post-processing (sam_postprocess.hip): the arguments of pope_sam_postprocess_f32
+struct SamPostArgs {
+    const float* low;
+    int M, h, w;
+    const int* sel;
+    int n_sel, img, ih, iw, H, W;
+    double mask_threshold, stability_offset;
+    int* stats;
+    unsigned* packed;
+    float* logits;
+    void* ws;
+    size_t ws_bytes;
+};
+size_t pope_sam_postprocess_workspace(int img, int H, int W);
+int pope_launch_sam_postprocess(const SamPostArgs& a, hipStream_t stream);
+int pope_launch_sam_nms(const float* boxes, const float* scores, int n, float thresh, int* keep, int* count, hipStream_t stream);

@@ -1,0 +1,422 @@
+"""SAM container, predictor and automatic mask generator on the HIP library.
+
+Drop-ins for `segment_anything.{modeling.sam.Sam, predictor.SamPredictor, automatic_mask_generator.SamAutomaticMaskGenerator}`
+and `build_sam.py`, for a single crop and point / box prompts.  The generator's post-processing is one fused HIP pass per decoder
+call (`pope_sam_postprocess_f32`, pope_amd/csrc/sam_postprocess.hip): from the 256 x 256 low-res logits of the masks that pass
+the IoU filter straight to per-mask counts, boxes, stability scores and bit-packed masks, without the 1024 x 1024 or the
+frame-sized fp32 tensors of `Sam.postprocess_masks`; the logits are bit-equal to torch's CPU `F.interpolate` (pope_amd/sam_amg.py
+restates the arithmetic), so counts, boxes and masks are exact.  Box NMS is `pope_sam_nms_f32`.  There is no torch fallback.
+
+Not supported: crop layers (`crop_n_layers > 0`), mask prompts, `output_mode="coco_rle"`.
+"""
+import ctypes as C
+from functools import partial
+from typing import Any, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, sam_amg
+from ._lib import check, on_device_of, ptr, require_cuda, stream_of
+from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer
+from .sam_encoder import ImageEncoderViT
+
+NMS_MAX = 2048   # boxes per pope_sam_nms_f32 call
+
+
+# ---- device ops ----------------------------------------------------------------------------------------------------------
+def postprocess_batch(low_res, selection, input_size, original_size, mask_threshold=0.0, stability_score_offset=1.0,
+                      img_size=sam_amg.IMG_SIZE, packed=True, logits=False):
+    """One fused pass over low_res [M, h, w] (fp32, CUDA) for the masks listed in `selection` (int32 CUDA tensor, or None for
+    all M, in order).  Returns (stats int32 [n, 8], packed int32 [n, H, ceil(W / 32)] or None, logits fp32 [n, H, W] or None);
+    stats columns: n_hi, n_lo, area, x0, y0, x1, y1, stability score as fp32 bits (`stats[:, 7].view(torch.float32)`)."""
+    require_cuda(low_res, "postprocess_batch")
+    if low_res.dtype != torch.float32 or low_res.dim() != 3:
+        raise TypeError(f"postprocess_batch: low_res must be float32 [M, h, w], got {low_res.dtype} {tuple(low_res.shape)}")
+    low_res = low_res.contiguous()
+    M, h, w = low_res.shape
+    dev = low_res.device
+    if selection is not None:
+        require_cuda(selection, "postprocess_batch")
+        if selection.dtype != torch.int32 or selection.dim() != 1:
+            raise TypeError("postprocess_batch: selection must be an int32 vector")
+        selection = selection.contiguous()
+    n = M if selection is None else selection.numel()
+    (ih, iw), (H, W) = (int(v) for v in input_size), (int(v) for v in original_size)
+    need = int(_lib.lib().pope_sam_postprocess_workspace_bytes(img_size, H, W))
+    if need <= 0 or not (0 < ih <= img_size and 0 < iw <= img_size):
+        raise ValueError(f"postprocess_batch: unsupported geometry (input {ih} x {iw} in {img_size}, frame {H} x {W})")
+    stats = torch.empty(n, 8, dtype=torch.int32, device=dev)
+    bits = torch.empty(n, H, sam_amg.row_words(W), dtype=torch.int32, device=dev) if packed else None
+    dense = torch.empty(n, H, W, dtype=torch.float32, device=dev) if logits else None
+    if n == 0 or M == 0:
+        return stats, bits, dense
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with on_device_of(low_res):
+        check(_lib.lib().pope_sam_postprocess_f32(
+            ptr(low_res), M, h, w, ptr(selection), n, img_size, ih, iw, H, W, float(mask_threshold), float(stability_score_offset),
+            ptr(stats), ptr(bits), ptr(dense), ptr(ws), ws.numel(), stream_of(dev)), "pope_sam_postprocess_f32")
+    return stats, bits, dense
+
+
+def box_nms(boxes, scores, iou_threshold):
+    """Greedy box NMS on the device (`pope_sam_nms_f32`): `torchvision.ops.batched_nms` with one category restated from its
+    definition (torchvision is not a dependency, so it is not pinned against the library itself; `sam_amg.nms` is the same
+    definition on the CPU).  boxes [n, 4] XYXY, scores [n]; returns the kept indices in score order (int64, on the device)."""
+    require_cuda(boxes, "box_nms")
+    n = boxes.shape[0]
+    if n > NMS_MAX:
+        raise ValueError(f"box_nms: at most {NMS_MAX} boxes per call, got {n}")
+    dev = boxes.device
+    boxes = boxes.to(torch.float32).contiguous()
+    scores = scores.to(device=dev, dtype=torch.float32).contiguous()
+    keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    with on_device_of(boxes):
+        check(_lib.lib().pope_sam_nms_f32(ptr(boxes), ptr(scores), n, float(iou_threshold), ptr(keep), ptr(count), stream_of(dev)),
+              "pope_sam_nms_f32")
+    return keep[:int(count.item())].to(torch.int64)
+
+
+# ---- Sam -----------------------------------------------------------------------------------------------------------------
+class Sam(nn.Module):
+    """modeling/sam.py: the container a `Sam` checkpoint loads into with strict=True (`pixel_mean` / `pixel_std` are
+    non-persistent buffers, as in the reference)."""
+    mask_threshold: float = 0.0
+    image_format: str = "RGB"
+
+    def __init__(self, image_encoder: ImageEncoderViT, prompt_encoder: PromptEncoder, mask_decoder: MaskDecoder,
+                 pixel_mean: List[float] = [123.675, 116.28, 103.53], pixel_std: List[float] = [58.395, 57.12, 57.375]) -> None:
+        super().__init__()
+        self.image_encoder = image_encoder
+        self.prompt_encoder = prompt_encoder
+        self.mask_decoder = mask_decoder
+        self.register_buffer("pixel_mean", torch.Tensor(pixel_mean).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.Tensor(pixel_std).view(-1, 1, 1), False)
+
+    @property
+    def device(self) -> Any:
+        return self.pixel_mean.device
+
+    def preprocess(self, x: torch.Tensor) -> torch.Tensor:
+        """Normalize pixel values and pad to the square input."""
+        x = (x - self.pixel_mean) / self.pixel_std
+        h, w = x.shape[-2:]
+        return F.pad(x, (0, self.image_encoder.img_size - w, 0, self.image_encoder.img_size - h))
+
+    @torch.no_grad()
+    def postprocess_masks(self, masks: torch.Tensor, input_size: Tuple[int, ...], original_size: Tuple[int, ...]) -> torch.Tensor:
+        """[B, C, h, w] low-res logits -> [B, C, H, W] fp32 logits at the original size: the fused kernel's logit path with a
+        dense store, bit-equal to the reference's two `F.interpolate` calls on the CPU."""
+        B, Cm = masks.shape[:2]
+        _, _, dense = postprocess_batch(masks.reshape(B * Cm, *masks.shape[2:]).float(), None, input_size, original_size,
+                                        self.mask_threshold, 1.0, self.image_encoder.img_size, packed=False, logits=True)
+        return dense.view(B, Cm, int(original_size[0]), int(original_size[1]))
+
+
+def _build_sam(encoder_embed_dim, encoder_depth, encoder_num_heads, encoder_global_attn_indexes, checkpoint=None):
+    prompt_embed_dim, image_size, vit_patch_size = 256, 1024, 16
+    grid = image_size // vit_patch_size
+    sam = Sam(
+        image_encoder=ImageEncoderViT(depth=encoder_depth, embed_dim=encoder_embed_dim, img_size=image_size, mlp_ratio=4,
+                                      norm_layer=partial(torch.nn.LayerNorm, eps=1e-6), num_heads=encoder_num_heads,
+                                      patch_size=vit_patch_size, qkv_bias=True, use_rel_pos=True,
+                                      global_attn_indexes=encoder_global_attn_indexes, window_size=14, out_chans=prompt_embed_dim),
+        prompt_encoder=PromptEncoder(embed_dim=prompt_embed_dim, image_embedding_size=(grid, grid),
+                                     input_image_size=(image_size, image_size), mask_in_chans=16),
+        mask_decoder=MaskDecoder(num_multimask_outputs=3,
+                                 transformer=TwoWayTransformer(depth=2, embedding_dim=prompt_embed_dim, mlp_dim=2048, num_heads=8),
+                                 transformer_dim=prompt_embed_dim, iou_head_depth=3, iou_head_hidden_dim=256),
+        pixel_mean=[123.675, 116.28, 103.53], pixel_std=[58.395, 57.12, 57.375])
+    sam.eval()
+    if checkpoint is not None:
+        with open(checkpoint, "rb") as f:
+            sam.load_state_dict(torch.load(f))
+    return sam
+
+
+def build_sam_vit_h(checkpoint=None):
+    return _build_sam(1280, 32, 16, [7, 15, 23, 31], checkpoint)
+
+
+def build_sam_vit_l(checkpoint=None):
+    return _build_sam(1024, 24, 16, [5, 11, 17, 23], checkpoint)
+
+
+def build_sam_vit_b(checkpoint=None):
+    return _build_sam(768, 12, 12, [2, 5, 8, 11], checkpoint)
+
+
+build_sam = build_sam_vit_h
+sam_model_registry = {"default": build_sam_vit_h, "vit_h": build_sam_vit_h, "vit_l": build_sam_vit_l, "vit_b": build_sam_vit_b}
+
+
+# ---- predictor -----------------------------------------------------------------------------------------------------------
+class ResizeLongestSide:
+    """utils/transforms.py: `apply_image` is torchvision's `resize(to_pil_image(image), size)`, i.e. Pillow's 8-bit bilinear
+    resample, run on the host once per frame."""
+
+    def __init__(self, target_length: int) -> None:
+        self.target_length = target_length
+
+    @staticmethod
+    def get_preprocess_shape(oldh: int, oldw: int, long_side_length: int) -> Tuple[int, int]:
+        return sam_amg.preprocess_shape(oldh, oldw, long_side_length)
+
+    def apply_image(self, image: np.ndarray) -> np.ndarray:
+        from PIL import Image
+        h, w = self.get_preprocess_shape(image.shape[0], image.shape[1], self.target_length)
+        return np.array(Image.fromarray(np.ascontiguousarray(image)).resize((w, h), Image.BILINEAR))
+
+    def apply_coords(self, coords: np.ndarray, original_size: Tuple[int, ...]) -> np.ndarray:
+        old_h, old_w = original_size
+        new_h, new_w = self.get_preprocess_shape(old_h, old_w, self.target_length)
+        coords = np.array(coords, copy=True).astype(float)
+        coords[..., 0] = coords[..., 0] * (new_w / old_w)
+        coords[..., 1] = coords[..., 1] * (new_h / old_h)
+        return coords
+
+    def apply_boxes(self, boxes: np.ndarray, original_size: Tuple[int, ...]) -> np.ndarray:
+        return self.apply_coords(np.asarray(boxes).reshape(-1, 2, 2), original_size).reshape(-1, 4)
+
+
+class SamPredictor:
+    """predictor.py: `set_image` / `set_torch_image` run the image encoder once, `predict_torch` the prompt encoder, the mask
+    decoder and `Sam.postprocess_masks`."""
+
+    def __init__(self, sam_model: Sam) -> None:
+        self.model = sam_model
+        self.transform = ResizeLongestSide(sam_model.image_encoder.img_size)
+        self.reset_image()
+
+    @property
+    def device(self) -> torch.device:
+        return self.model.device
+
+    def set_image(self, image: np.ndarray, image_format: str = "RGB") -> None:
+        assert image_format in ["RGB", "BGR"], f"image_format must be in ['RGB', 'BGR'], is {image_format}."
+        if image_format != self.model.image_format:
+            image = image[..., ::-1]
+        input_image = self.transform.apply_image(image)
+        t = torch.as_tensor(input_image, device=self.device).permute(2, 0, 1).contiguous()[None, :, :, :]
+        self.set_torch_image(t, image.shape[:2])
+
+    @torch.no_grad()
+    def set_torch_image(self, transformed_image: torch.Tensor, original_image_size: Tuple[int, ...]) -> None:
+        size = self.model.image_encoder.img_size
+        assert (len(transformed_image.shape) == 4 and transformed_image.shape[1] == 3
+                and max(*transformed_image.shape[2:]) == size), f"set_torch_image input must be BCHW with long side {size}."
+        self.reset_image()
+        self.original_size = tuple(int(v) for v in original_image_size)
+        self.input_size = tuple(transformed_image.shape[-2:])
+        self.features = self.model.image_encoder(self.model.preprocess(transformed_image).contiguous())
+        self.is_image_set = True
+
+    @torch.no_grad()
+    def predict_low_res(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True):
+        """The prompt encoder and the mask decoder of `predict_torch`: (low_res_masks [B, C, 256, 256], iou_predictions [B, C])."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        points = (point_coords, point_labels) if point_coords is not None else None
+        sparse, dense = self.model.prompt_encoder(points=points, boxes=boxes, masks=mask_input)
+        return self.model.mask_decoder(image_embeddings=self.features, image_pe=self.model.prompt_encoder.get_dense_pe(),
+                                       sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense,
+                                       multimask_output=multimask_output)
+
+    @torch.no_grad()
+    def predict_torch(self, point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor],
+                      boxes: Optional[torch.Tensor] = None, mask_input: Optional[torch.Tensor] = None,
+                      multimask_output: bool = True, return_logits: bool = False):
+        low_res_masks, iou_predictions = self.predict_low_res(point_coords, point_labels, boxes, mask_input, multimask_output)
+        masks = self.model.postprocess_masks(low_res_masks, self.input_size, self.original_size)
+        if not return_logits:
+            masks = masks > self.model.mask_threshold
+        return masks, iou_predictions, low_res_masks
+
+    def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output=True, return_logits=False):
+        """numpy wrapper of `predict_torch` for one prompt (predictor.py:91-165)."""
+        if mask_input is not None:
+            raise NotImplementedError("pope_amd SamPredictor: mask prompts are not supported")
+        coords = labels = box_t = None
+        if point_coords is not None:
+            assert point_labels is not None, "point_labels must be supplied if point_coords is supplied."
+            pc = self.transform.apply_coords(point_coords, self.original_size)
+            coords = torch.as_tensor(pc, dtype=torch.float, device=self.device)[None, :, :]
+            labels = torch.as_tensor(point_labels, dtype=torch.int, device=self.device)[None, :]
+        if box is not None:
+            box_t = torch.as_tensor(self.transform.apply_boxes(box, self.original_size), dtype=torch.float, device=self.device)[None, :]
+        masks, iou, low = self.predict_torch(coords, labels, box_t, None, multimask_output, return_logits=return_logits)
+        return masks[0].cpu().numpy(), iou[0].cpu().numpy(), low[0].cpu().numpy()
+
+    def get_image_embedding(self) -> torch.Tensor:
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) to generate an embedding.")
+        return self.features
+
+    def reset_image(self) -> None:
+        self.is_image_set = False
+        self.features = None
+        self.original_size = None
+        self.input_size = None
+
+
+# ---- the generator -------------------------------------------------------------------------------------------------------
+def process_low_res(low_res, iou_preds, input_size, original_size, pred_iou_thresh, stability_score_thresh, mask_threshold=0.0,
+                    stability_score_offset=1.0, img_size=sam_amg.IMG_SIZE):
+    """`_process_batch` after the decoder, on the device: low_res [M, h, w], iou_preds [M] -> dict of the masks that pass the
+    IoU and the stability filter, in index order: `index` (into M, int64), `iou_preds`, `stability_score`, `boxes` (int32 XYXY),
+    `area`, `packed` (int32 words [n, H, ceil(W / 32)]), plus `index_iou` (after the IoU filter only) and its `stats`."""
+    iou_preds = iou_preds.reshape(-1)
+    if pred_iou_thresh > 0.0:
+        sel = torch.nonzero(iou_preds > pred_iou_thresh).reshape(-1).to(torch.int32)   # index order; its length is the one sync
+    else:
+        sel = torch.arange(iou_preds.numel(), device=iou_preds.device, dtype=torch.int32)
+    stats, packed, _ = postprocess_batch(low_res, sel, input_size, original_size, mask_threshold, stability_score_offset, img_size)
+    stability = stats[:, 7].view(torch.float32)
+    idx = sel.to(torch.int64)
+    out = {"index_iou": idx, "stats": stats}
+    if stability_score_thresh > 0.0:
+        keep = torch.nonzero(stability >= stability_score_thresh).reshape(-1)
+        idx, stats, packed, stability = idx[keep], stats[keep], packed[keep], stability[keep]
+    out.update(index=idx, iou_preds=iou_preds[idx], stability_score=stability, boxes=stats[:, 3:7], area=stats[:, 2], packed=packed)
+    return out
+
+
+def unpack_on_device(packed, W):
+    """int32 words [n, H, ceil(W / 32)] -> bool [n, H, W] (torch, on the words' device)."""
+    shifts = torch.arange(32, device=packed.device, dtype=torch.int32)
+    bits = (packed.unsqueeze(-1) >> shifts) & 1
+    return bits.reshape(*packed.shape[:-1], packed.shape[-1] * 32)[..., :W].to(torch.bool)
+
+
+class SamAutomaticMaskGenerator:
+    """automatic_mask_generator.py with the constructor and defaults of the POPE fork (16 x 16 points, 2048 points per batch,
+    IoU 0.9, stability 0.95, box NMS 0.35, min_mask_region_area 250), for a single crop."""
+
+    def __init__(self, model: Sam, points_per_side: Optional[int] = 16, points_per_batch: int = 2048, pred_iou_thresh: float = 0.9,
+                 stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.35,
+                 crop_n_layers: int = 0, crop_nms_thresh: float = 0.35, crop_overlap_ratio: float = 512 / 1500,
+                 crop_n_points_downscale_factor: int = 1, point_grids: Optional[List[np.ndarray]] = None,
+                 min_mask_region_area: int = 250, output_mode: str = "binary_mask") -> None:
+        assert (points_per_side is None) != (point_grids is None), "Exactly one of points_per_side or point_grid must be provided."
+        if crop_n_layers > 0:
+            raise NotImplementedError("pope_amd SamAutomaticMaskGenerator: crop layers are not supported (crop_n_layers must be 0)")
+        assert output_mode in ["binary_mask", "uncompressed_rle", "coco_rle"], f"Unknown output_mode {output_mode}."
+        if output_mode == "coco_rle":
+            raise NotImplementedError("pope_amd SamAutomaticMaskGenerator: output_mode='coco_rle' needs pycocotools, which is not a dependency")
+        self.point_grids = [sam_amg.build_point_grid(points_per_side)] if points_per_side is not None else point_grids
+        self.predictor = SamPredictor(model)
+        self.points_per_batch = points_per_batch
+        self.pred_iou_thresh = pred_iou_thresh
+        self.stability_score_thresh = stability_score_thresh
+        self.stability_score_offset = stability_score_offset
+        self.box_nms_thresh = box_nms_thresh
+        self.crop_n_layers = crop_n_layers
+        self.crop_nms_thresh = crop_nms_thresh
+        self.crop_overlap_ratio = crop_overlap_ratio
+        self.crop_n_points_downscale_factor = crop_n_points_downscale_factor
+        self.min_mask_region_area = min_mask_region_area
+        self.output_mode = output_mode
+        self.last_low_res = None   # (low_res [M, 256, 256], iou_preds [M]) of the last generate(keep_low_res=True) call
+
+    # the decoder call of one point batch: (low_res [P * 3, 256, 256], iou [P * 3])
+    def _decode(self, points, im_size):
+        pr = self.predictor
+        tp = pr.transform.apply_coords(points, im_size)
+        in_points = torch.as_tensor(tp, device=pr.device)
+        in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=in_points.device)
+        low, iou = pr.predict_low_res(in_points[:, None, :], in_labels[:, None], multimask_output=True)
+        return low.flatten(0, 1), iou.flatten(0, 1)
+
+    @torch.no_grad()
+    def generate(self, image: np.ndarray, keep_low_res: bool = False) -> List[Dict[str, Any]]:
+        """HWC uint8 image -> list of records (`segmentation`, `area`, `bbox` XYWH, `predicted_iou`, `point_coords`,
+        `stability_score`, `crop_box`), in the reference's order."""
+        H, W = image.shape[:2]
+        pr = self.predictor
+        pr.set_image(image)
+        points_all = self.point_grids[0] * np.array([[W, H]])
+        lows, ious, parts, pts, base = [], [], [], [], 0
+        for b in range(0, len(points_all), self.points_per_batch):
+            points = points_all[b:b + self.points_per_batch]
+            low, iou = self._decode(points, (H, W))
+            if keep_low_res:
+                lows.append(low)
+                ious.append(iou)
+            d = process_low_res(low, iou, pr.input_size, (H, W), self.pred_iou_thresh, self.stability_score_thresh,
+                                pr.model.mask_threshold, self.stability_score_offset, pr.model.image_encoder.img_size)
+            d["index"] = d["index"] + base
+            base += low.shape[0]
+            parts.append(d)
+            pts.append(np.repeat(points, 3, axis=0))
+        pr.reset_image()
+        if keep_low_res:
+            self.last_low_res = (torch.cat(lows), torch.cat(ious))
+        data = {k: torch.cat([p[k] for p in parts]) for k in ("index", "iou_preds", "stability_score", "boxes", "area", "packed")}
+        return self._finish(data, np.concatenate(pts), (H, W))
+
+    def _finish(self, data, points, hw):
+        """NMS, small regions, encoding and the records, from the filtered per-mask results of `process_low_res`."""
+        H, W = hw
+        keep = box_nms(data["boxes"], data["iou_preds"], self.box_nms_thresh)
+        data = {k: v[keep] for k, v in data.items()}
+        masks = None
+        if self.min_mask_region_area > 0 and data["index"].numel() > 0:
+            data, masks = postprocess_small_regions(data, W, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
+        if masks is None:
+            masks = unpack_on_device(data["packed"], W)
+        masks = masks.cpu().numpy()
+        host = {k: data[k].cpu().numpy() for k in ("index", "iou_preds", "stability_score", "boxes")}
+        anns = []
+        for i in range(len(masks)):
+            rle = sam_amg.mask_to_rle(masks[i])
+            anns.append({
+                "segmentation": masks[i] if self.output_mode == "binary_mask" else rle,
+                "area": sam_amg.area_from_rle(rle),
+                "bbox": sam_amg.box_xyxy_to_xywh(host["boxes"][i]),
+                "predicted_iou": float(host["iou_preds"][i]),
+                "point_coords": [points[int(host["index"][i])].tolist()],
+                "stability_score": float(host["stability_score"][i]),
+                "crop_box": [0, 0, W, H],
+            })
+        return anns
+
+
+def clean_masks(masks, min_area):
+    """Holes, then islands, below `min_area` removed from bool [n, H, W] (device): (masks, unchanged bool [n])."""
+    out, same = [], []
+    for m in masks:
+        m, c0 = sam_amg.remove_small_regions(m, min_area, "holes")
+        m, c1 = sam_amg.remove_small_regions(m, min_area, "islands")
+        out.append(m)
+        same.append(not (c0 or c1))
+    return torch.stack(out), torch.tensor(same, device=masks.device)
+
+
+def mask_boxes(masks):
+    """`batched_mask_to_box` of bool [n, H, W] on its device: int32 [n, 4]."""
+    n, H, W = masks.shape
+    rows, cols = masks.any(2), masks.any(1)
+    ar_h, ar_w = torch.arange(H, device=masks.device), torch.arange(W, device=masks.device)
+    y1 = (rows * ar_h).max(1).values
+    y0 = (rows * ar_h + H * (~rows)).min(1).values
+    x1 = (cols * ar_w).max(1).values
+    x0 = (cols * ar_w + W * (~cols)).min(1).values
+    empty = (x1 < x0) | (y1 < y0)
+    return (torch.stack([x0, y0, x1, y1], 1) * (~empty)[:, None]).to(torch.int32)
+
+
+def postprocess_small_regions(data, W, min_area, nms_thresh):
+    """automatic_mask_generator.py:325-375 on the device: small holes and islands removed (8-connectivity), changed masks score
+    0 and unchanged ones 1 in a second NMS, boxes (and masks) of the changed survivors recomputed.  Returns (data, masks)."""
+    masks = unpack_on_device(data["packed"], W)
+    masks, unchanged = clean_masks(masks, min_area)
+    boxes = mask_boxes(masks)
+    keep = box_nms(boxes, unchanged.to(torch.float32), nms_thresh)
+    changed = ~unchanged
+    new_boxes = torch.where(changed[:, None], boxes, data["boxes"])
+    data = dict(data, boxes=new_boxes)
+    data = {k: v[keep] for k, v in data.items() if k != "packed"}
+    return data, masks[keep]

@@ -526,3 +526,56 @@ def sam_decoder_case(name):
         boxes = torch.cat([lo, lo + 100 + torch.rand(6, 2, generator=g) * 300], dim=1)
         return (coords, labels), boxes, False
     raise KeyError(name)
+
+
+# ---- SAM automatic mask generator: post-processing ---------------------------------------------------------------------
+# name -> (M masks, frame (H, W)); the resized frame inside the 1024 square follows from ResizeLongestSide
+SAM_GENERATOR_CASES = {"frame": (128, (480, 640)), "portrait": (48, (333, 332))}
+
+
+def sam_generator_case(name, M=None):
+    """Seeded inputs of the generator's post-processing fixtures: (low_res [M, 256, 256] fp32, iou_preds [M] fp32,
+    input_size (ih, iw), original_size (H, W)).  A mask's logits are a negative floor with one to three flat-topped blobs of
+    +-12 (the steepness of their rims varies, so stability scores spread around 0.95), small satellite blobs and pin holes
+    (islands and holes on either side of 250 pixels) and low-amplitude noise.  Blob centres come from a small pool so
+    that near-duplicate masks exist for NMS; some masks have no blob (empty after thresholding) and some sit on the frame
+    border.  `iou_preds` are drawn around 0.9, all distinct."""
+    M0, (H, W) = SAM_GENERATOR_CASES[name]
+    M = M or M0          # a larger M (timing runs) extends the same seeded sequence
+    g = torch.Generator().manual_seed({"frame": 101, "portrait": 202}[name])
+    scale = 1024.0 / max(H, W)
+    ih, iw = int(H * scale + 0.5), int(W * scale + 0.5)
+    n = 256
+    fy, fx = ih / 1024.0, iw / 1024.0          # the part of the low-res square the frame covers
+    yy, xx = torch.meshgrid(torch.arange(n, dtype=torch.float32) / n, torch.arange(n, dtype=torch.float32) / n, indexing="ij")
+    u = lambda *s: torch.rand(*s, generator=g)
+    pool = torch.stack([u(24) * fy, u(24) * fx], 1)
+    pool[:4, 0] = torch.tensor([0.0, fy, 0.5 * fy, fy])     # four centres on the frame border (fy / fx: its far edges)
+    pool[:4, 1] = torch.tensor([0.5 * fx, 0.4 * fx, fx, fx])
+    low = torch.empty(M, n, n)
+
+    def disc(cy, cx, ry, rx, gain):
+        """A flat-topped blob: `gain` logits per radius across its rim, clamped to +-12."""
+        d = torch.sqrt(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2)
+        return (gain * (1.0 - d)).clamp_(-12.0, 12.0)
+
+    for i in range(M):
+        z = torch.full((n, n), -12.0)
+        if i % 16 != 7:                          # every sixteenth mask stays empty
+            c = pool[int(torch.randint(0, 24, (1,), generator=g))]
+            k = 1 + int(torch.randint(0, 3, (1,), generator=g))
+            gain = 30.0 * 8.0 ** u(1).item()     # 30 .. 240: stability roughly 1 - 4 / gain
+            for b in range(k):
+                cy = c[0] + (0.0 if b == 0 else (u(1).item() - 0.5) * 0.2)
+                cx = c[1] + (0.0 if b == 0 else (u(1).item() - 0.5) * 0.2)
+                z = torch.maximum(z, disc(cy, cx, 0.05 + 0.15 * u(1).item(), 0.05 + 0.15 * u(1).item(), gain))
+            for _ in range(int(torch.randint(0, 4, (1,), generator=g))):   # satellites: islands, or holes in the blobs
+                r = (2.0 + 4.0 * u(1).item()) / n
+                if u(1).item() < 0.5:
+                    z = torch.maximum(z, disc(u(1).item() * fy, u(1).item() * fx, r, r, 24.0))
+                else:
+                    z = torch.minimum(z, -disc(c[0] + (u(1).item() - 0.5) * 0.08, c[1] + (u(1).item() - 0.5) * 0.08, r, r, 24.0))
+        low[i] = z + 0.25 * torch.randn(n, n, generator=g)
+    iou = (0.9 + 0.05 * torch.randn(M, generator=g)).float()
+    assert iou.unique().numel() == M
+    return low.contiguous(), iou.contiguous(), (ih, iw), (H, W)

@@ -1,0 +1,114 @@
+"""Times the SAM generator's post-processing on one GPU, in one process, with events after a warm-up:
+ (1) the fused HIP pass + filters + NMS for the generator's call (M = 768 masks at 480 x 640, IoU filter off: all 768 processed);
+ (2) a torch restatement of the reference's path on the same card and inputs (`Sam.postprocess_masks`, then
+     `_process_batch`'s tail: stability score, binarisation, boxes, the transposed diff + nonzero of `mask_to_rle_pytorch`;
+     the per-mask Python loop that turns change indices into count lists is host work and is left out of both);
+ (3) `generate()` of one frame split into encoder / decoder / post-processing (synthetic ViT-B weights, filters off, so the
+     whole batch reaches NMS; min_mask_region_area=0).
+Prints medians, minima and the bytes/s of (1) against its floor: the low-res logits read once plus the packed masks written.
+usage: python scripts/sam_generator_time.py [--reps 20] [--skip-generate]"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pope_amd import sam_amg, synth  # noqa: E402
+from pope_amd import sam_generator as sg  # noqa: E402
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out), min(out), max(out)
+
+
+def reference_tail(low, input_size, hw, thr=0.0, off=1.0):
+    masks = F.interpolate(low[:, None], (1024, 1024), mode="bilinear", align_corners=False)
+    masks = masks[..., :input_size[0], :input_size[1]]
+    masks = F.interpolate(masks, hw, mode="bilinear", align_corners=False)[:, 0]
+    inter = (masks > (thr + off)).sum(-1, dtype=torch.int16).sum(-1, dtype=torch.int32)
+    union = (masks > (thr - off)).sum(-1, dtype=torch.int16).sum(-1, dtype=torch.int32)
+    stability = inter / union
+    m = masks > thr
+    boxes = sg.mask_boxes(m)
+    t = m.permute(0, 2, 1).flatten(1)
+    change = (t[:, 1:] ^ t[:, :-1]).nonzero()
+    return stability, boxes, change
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--skip-generate", action="store_true")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    dev = "cuda:0"
+    M, (H, W) = 768, (480, 640)
+    low, iou, input_size, hw = synth.sam_generator_case("frame", M=M)
+    low, iou = low.to(dev), iou.to(dev)
+    floor = M * 256 * 256 * 4 + M * H * sam_amg.row_words(W) * 4
+
+    def fused_kernel():
+        return sg.postprocess_batch(low, None, input_size, hw, 0.0, 1.0)
+
+    def fused_stage():
+        d = sg.process_low_res(low, iou, input_size, hw, 0.0, 0.95, 0.0, 1.0)
+        return sg.box_nms(d["boxes"], d["iou_preds"], 0.35)
+
+    stats, _, _ = fused_kernel()
+    st_ref, boxes_ref, _ = reference_tail(low, input_size, hw)
+    same = bool(torch.equal(stats[:, 3:7], boxes_ref)) and bool(torch.equal(torch.nan_to_num(stats[:, 7].view(torch.float32), -1),
+                                                                            torch.nan_to_num(st_ref, -1)))
+    print(f"boxes and stability scores of the fused pass equal the torch path on this GPU: {same}")
+    k_med, k_min, k_max = timed(fused_kernel, a.reps)
+    s_med, s_min, s_max = timed(fused_stage, a.reps)
+    r_med, r_min, r_max = timed(lambda: reference_tail(low, input_size, hw), max(5, a.reps // 2))
+    print(f"(1) fused kernels only      median {k_med:.3f} ms  min {k_min:.3f}  max {k_max:.3f}   "
+          f"{floor / k_med / 1e6:.1f} GB/s of the {floor / 1e6:.1f} MB floor (min: {floor / k_min / 1e6:.1f} GB/s)")
+    print(f"(1) fused + filters + NMS   median {s_med:.3f} ms  min {s_min:.3f}  max {s_max:.3f}")
+    print(f"(2) torch reference path    median {r_med:.3f} ms  min {r_min:.3f}  max {r_max:.3f}   ratio (2)/(1) = {r_med / s_med:.1f}")
+    if a.skip_generate:
+        return
+    sam = sg.build_sam_vit_b()
+    sd = {"image_encoder." + k: v for k, v in synth.synthetic_sam_encoder_state_dict(seed=0, dim=768, depth=12, heads=12,
+                                                                                      global_idx=(2, 5, 8, 11)).items()}
+    sd.update(synth.synthetic_sam_decoder_state_dict(seed=0))
+    sam.load_state_dict(sd, strict=True)
+    sam = sam.to(dev)
+    gen = sg.SamAutomaticMaskGenerator(sam, pred_iou_thresh=0.0, stability_score_thresh=0.0, min_mask_region_area=0)
+    frame = (torch.rand(H, W, 3, generator=torch.Generator().manual_seed(5)) * 255).to(torch.uint8).numpy()
+    pr = gen.predictor
+    points = gen.point_grids[0] * np.array([[W, H]])
+    pr.set_image(frame)
+    lo, io = gen._decode(points, (H, W))
+    q = torch.quantile(io, torch.tensor([0.0, 0.25, 0.5, 0.75, 1.0], device=dev)).cpu().numpy().round(3)
+    d = sg.process_low_res(lo, io, pr.input_size, hw, 0.0, 0.0)
+    sq = np.nanquantile(d["stability_score"].cpu().numpy(), [0, 0.25, 0.5, 0.75, 1]).round(3)
+    print(f"synthetic ViT-B: iou_preds quantiles {q.tolist()}, stability quantiles {sq.tolist()}")
+    e = timed(lambda: pr.set_image(frame), 5, 1)
+    c = timed(lambda: gen._decode(points, (H, W)), 5, 1)
+
+    def post():
+        d = sg.process_low_res(lo, io, pr.input_size, hw, 0.0, 0.0)
+        return sg.box_nms(d["boxes"], d["iou_preds"], 0.35)
+    p = timed(post, 5, 1)
+    for name, t in (("encoder (set_image, host resize included)", e), ("decoder (256 prompts x 3)", c), ("post-processing", p)):
+        print(f"(3) {name:44s} median {t[0]:.3f} ms  min {t[1]:.3f}")
+
+
+if __name__ == "__main__":
+    main()
