@@ -40,7 +40,15 @@ extern "C" {
 enum {
     POPE_EPI_BIAS = 0,        /* C = A.W^T + bias                         nn.Linear                     */
     POPE_EPI_BIAS_GELU = 1,   /* C = gelu_erf(A.W^T + bias)               mlp.py:35-41 (fc1 + nn.GELU)  */
-    POPE_EPI_BIAS_LS_RES = 2  /* C = res + gamma*(A.W^T + bias)           block.py:105-106 + layer_scale.py:28 */
+    POPE_EPI_BIAS_LS_RES = 2, /* C = res + gamma*(A.W^T + bias)           block.py:105-106 + layer_scale.py:28 */
+    /* The w12 GEMM of the SwiGLU FFN with its activation (swiglu_ffn.py:29-33): A[M,K], W[N,K] with N = 2*hidden,
+     * C[M, hidden] = silu(gate) * value — the [M, 2*hidden] product never reaches memory.  A 64 x 64 accumulator block has to
+     * hold a hidden column's gate AND value, so the ROWS of W and bias are expected permuted: for every block t of 32 hidden
+     * columns, rows 64t .. 64t+31 are w12 rows 32t .. 32t+31 (gates), rows 64t+32 .. 64t+63 are w12 rows
+     * hidden+32t .. hidden+32t+31 (values).  N % 64 == 0.  silu(x) = x / (1 + exp(-x)) in fp32 (exp as exp2 of the pre-scaled
+     * argument), finite for every finite gate.  pope_linear_planes_f32 (planes or fp32 out, range bit POPE_RANGE_GELU: it marks the
+     * FC1 producer) and pope_linear_prec_f32 with POPE_PREC_F32_MFMA take it; gamma and res are ignored. */
+    POPE_EPI_BIAS_SWIGLU = 11
 };
 
 /* Arithmetic of the contractions.  Both take and return fp32 and accumulate in fp32:
@@ -86,7 +94,8 @@ int pope_linear_prec_f32(const float* A, const float* W, const float* bias, floa
 int pope_split_planes_f32(const float* src, void* planes, int rows, int cols, float scale,
                           unsigned* range_flag, void* stream);
 /* nn.Linear on planes: A planes [M,K], W planes [N,K]; output either fp32 C[M,N] (c_planes == NULL) or
- * activation planes [M,N] (C == NULL; not for POPE_EPI_BIAS_LS_RES).  K % 32 == 0, K >= 64. */
+ * activation planes [M,N] (C == NULL; not for POPE_EPI_BIAS_LS_RES).  K % 32 == 0, K >= 64.  POPE_EPI_BIAS_SWIGLU: the output
+ * is [M, N/2]. */
 int pope_linear_planes_f32(const void* a_planes, const void* w_planes, const float* bias, float* C,
                            void* c_planes, int M, int N, int K, int epilogue, const float* gamma,
                            const float* res, unsigned* range_flag, void* stream);
@@ -185,6 +194,12 @@ typedef struct pope_vit_weights {
 
 size_t pope_vit_workspace_bytes(int B, int ntok, int dim, int hidden);
 
+/* Feed-forward kind of the blocks.  POPE_FFN_MLP: fc2(gelu(fc1(x))), mlp.py:35-44.  POPE_FFN_SWIGLU: w3(silu(x1) * x2) with
+ * x1, x2 = w12(x).chunk(2), swiglu_ffn.py:13-63 (ViT-g/14): fc1_w / fc1_b / fc1_wp hold w12 [2*hidden, dim] with its rows
+ * permuted as POPE_EPI_BIAS_SWIGLU describes, fc2_* hold w3 [dim, hidden], pope_vit_weights::hidden = w3's in_features
+ * (a multiple of 32); not with POPE_PREC_F16. */
+enum { POPE_FFN_MLP = 0, POPE_FFN_SWIGLU = 1 };
+
 /* DinoVisionTransformer.forward_features — vision_transformer.py:221-236.
  * Outputs: x_prenorm[B,ntok,dim] (also the residual stream, required) and x_norm[B,ntok,dim]
  * (final LayerNorm; row 0 = x_norm_clstoken, rows 1.. = x_norm_patchtokens; may be NULL).
@@ -194,6 +209,13 @@ int pope_vit_forward_f32(const pope_vit_weights* w_host, const float* img, int B
                          const float* posb, float* x_prenorm, float* x_norm,
                          int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
                          void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+
+/* Same with an explicit POPE_FFN_* (pope_vit_forward_f32 == POPE_FFN_MLP).  An unknown kind, POPE_FFN_SWIGLU with
+ * POPE_PREC_F16, with hidden % 32 != 0 or with a NULL fc1_w / fc1_b / fc2_w return POPE_ERR_ARG before any HIP call. */
+int pope_vit_forward_ffn_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
+                             const float* posb, float* x_prenorm, float* x_norm,
+                             int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
+                             void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
 /* In-situ kernel timing of the product path (bench.py's roofline leg): identical launches, plus
  * events_host[i] (hipEvent_t made by pope_event_create) recorded on `stream` immediately before
@@ -211,6 +233,12 @@ int pope_vit_forward_profiled_mask_f32(const pope_vit_weights* w_host, const flo
                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream,
                                        void* const* events_host, int n_events, int* kinds_host,
                                        int* n_launches_host, unsigned kind_mask);
+/* Same with an explicit POPE_FFN_* (see pope_vit_forward_ffn_f32). */
+int pope_vit_forward_ffn_profiled_mask_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
+                                           const float* posb, float* x_prenorm, float* x_norm,
+                                           void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream,
+                                           void* const* events_host, int n_events, int* kinds_host,
+                                           int* n_launches_host, unsigned kind_mask);
 int pope_event_create(void** event_host);
 int pope_event_destroy(void* event);
 int pope_event_elapsed_ms(void* start, void* stop, float* ms_host);  /* both events must have completed */

@@ -70,10 +70,12 @@ class SamDecoderWeights(C.Structure):
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
 PRECISIONS = {"f32": PREC_F32_MFMA, "f16x3": PREC_F16X3, "f16": PREC_F16}
+FFN_KINDS = {"mlp": 0, "swiglu": 1}    # POPE_FFN_*
+EPI_BIAS_SWIGLU = 11                   # POPE_EPI_BIAS_SWIGLU
 c_uint_p = C.POINTER(C.c_uint)
 F16_MAX = 65504.0
 # bits of an f16x3 range-guard word (pope_hip.h POPE_RANGE_*)
-RANGE_BITS = {1: "patch embed input", 2: "LayerNorm output", 4: "q/k/v", 8: "MLP hidden (GELU output)",
+RANGE_BITS = {1: "patch embed input", 2: "LayerNorm output", 4: "q/k/v", 8: "MLP hidden (GELU / SwiGLU output)",
               16: "matcher features", 32: "op-level operand"}
 
 PROTOTYPES = {
@@ -100,6 +102,13 @@ PROTOTYPES = {
     "pope_vit_forward_f32": (C.c_int, [C.POINTER(VitWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_void_p),
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_vit_forward_ffn_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_void_p),
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_vit_forward_ffn_profiled_mask_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_int_p,
+                                                         c_int_p, C.c_uint]),
     "pope_vit_launch_count": (C.c_int, [C.c_int]),
     "pope_vit_forward_profiled_mask_f32": (C.c_int, [C.POINTER(VitWeights), C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

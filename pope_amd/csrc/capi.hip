@@ -104,12 +104,15 @@ int pope_linear_f32(const float* A, const float* W, const float* bias, float* C,
 int pope_linear_prec_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
                          int epilogue, const float* gamma, const float* res, int precision, unsigned* range_flag,
                          void* stream) {
-    StreamDevice on_device(stream);
-    if (!A || !W || !C || epilogue < 0 || epilogue > POPE_EPI_BIAS_LS_RES) return POPE_ERR_ARG;
+    const bool swiglu = epilogue == POPE_EPI_BIAS_SWIGLU;
+    if (!A || !W || !C || epilogue < 0 || (epilogue > POPE_EPI_BIAS_LS_RES && !swiglu)) return POPE_ERR_ARG;
     if (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
+    // SwiGLU: fp32 MFMA only here (the f16x3 form is the planes entry below); N = 2 hidden columns in, [M, N / 2] out
+    if (swiglu && (precision != POPE_PREC_F32_MFMA || N <= 0 || (N & 63))) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
     GemmParams g = {};
     g.A = A; g.W = W; g.bias = bias; g.C = C;
-    g.lda = K; g.ldw = K; g.ldc = N;
+    g.lda = K; g.ldw = K; g.ldc = swiglu ? N / 2 : N;
     g.M = M; g.N = N; g.K = K;
     g.epilogue = epilogue;
     g.gamma = gamma; g.res = res; g.ldres = N;
@@ -128,14 +131,16 @@ int pope_split_planes_f32(const float* src, void* planes, int rows, int cols, fl
 int pope_linear_planes_f32(const void* a_planes, const void* w_planes, const float* bias, float* C, void* c_planes,
                            int M, int N, int K, int epilogue, const float* gamma, const float* res, unsigned* range_flag,
                            void* stream) {
+    const bool swiglu = epilogue == POPE_EPI_BIAS_SWIGLU;
+    if (epilogue < 0 || (epilogue > POPE_EPI_BIAS_LS_RES && !swiglu)) return POPE_ERR_ARG;
+    if (swiglu && (!a_planes || !w_planes || (!C) == (!c_planes) || N <= 0 || (N & 63))) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
-    if (epilogue < 0 || epilogue > POPE_EPI_BIAS_LS_RES) return POPE_ERR_ARG;
     GemmParams g = {};
     g.range_flag = range_flag;
-    g.range_bit = epilogue == POPE_EPI_BIAS_GELU ? POPE_RANGE_GELU : POPE_RANGE_QKV;
+    g.range_bit = epilogue == POPE_EPI_BIAS_GELU || swiglu ? POPE_RANGE_GELU : POPE_RANGE_QKV;   // the FC1 producer's bit
     g.a_pl = a_planes; g.w_pl = w_planes;
     g.bias = bias; g.C = C; g.c_pl = c_planes;
-    g.lda = K; g.ldw = K; g.ldc = N;
+    g.lda = K; g.ldw = K; g.ldc = swiglu ? N / 2 : N;
     g.M = M; g.N = N; g.K = K;
     g.epilogue = epilogue;
     g.gamma = gamma; g.res = res; g.ldres = N;
@@ -261,17 +266,25 @@ size_t pope_vit_workspace_bytes(int B, int ntok, int dim, int hidden) {
     return align_up(rows * dim * sizeof(float), 256) + align_up(rows * big * sizeof(float), 256);
 }
 
-static int vit_forward_impl(const pope_vit_weights* w, const float* img, int B, int H, int W, const float* posb,
+static int vit_forward_impl(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
                             float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
                             float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
                             void* stream_, Recorder& rec) {
-    StreamDevice on_device(stream_);
     if (!w || !img || !posb || !x_prenorm || !workspace || !w->blocks_host) return POPE_ERR_ARG;
     if (w->dim != w->heads * 64 || w->patch <= 0 || H % w->patch || W % w->patch || B <= 0) return POPE_ERR_ARG;
     if (n_taps < 0 || (n_taps > 0 && (!tap_blocks_host || !tap_out_host))) return POPE_ERR_ARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int dim = w->dim, hidden = w->hidden, prec = w->precision;
     if (prec != POPE_PREC_F32_MFMA && prec != POPE_PREC_F16X3 && prec != POPE_PREC_F16) return POPE_ERR_ARG;
+    // SwiGLU FFN (pope_hip.h POPE_FFN_SWIGLU): fc1 = the permuted w12 [2 hidden, dim], fc2 = w3 [dim, hidden]; the w12 GEMM's
+    // 64-column blocks need hidden % 32 == 0; no plain-f16 form
+    if (ffn != POPE_FFN_MLP && ffn != POPE_FFN_SWIGLU) return POPE_ERR_ARG;
+    const bool swiglu = ffn == POPE_FFN_SWIGLU;
+    if (swiglu && (prec == POPE_PREC_F16 || hidden <= 0 || (hidden & 31))) return POPE_ERR_ARG;
+    for (int i = 0; swiglu && i < w->depth; ++i)
+        if (!w->blocks_host[i].fc1_w || !w->blocks_host[i].fc1_b || !w->blocks_host[i].fc2_w) return POPE_ERR_ARG;
+    StreamDevice on_device(stream_);
+    const int fc1_n = swiglu ? 2 * hidden : hidden, fc1_epi = swiglu ? int(EPI_BIAS_SWIGLU) : int(EPI_BIAS_GELU);
     const int ntok = 1 + (H / w->patch) * (W / w->patch);
     const int rows = B * ntok;
     if (workspace_bytes < pope_vit_workspace_bytes(B, ntok, dim, hidden)) return POPE_ERR_WORKSPACE;
@@ -414,9 +427,9 @@ static int vit_forward_impl(const pope_vit_weights* w, const float* img, int B, 
         }
         POPE_MARK(POPE_K_GEMM_FC1);
         if (planes)
-            POPE_TRY(pope_linear_planes_f32(xn_pl, k.fc1_wp, k.fc1_b, nullptr, hid_pl, rows, hidden, dim, EPI_BIAS_GELU, nullptr,
-                                            nullptr, range_flag, stream));
-        else POPE_TRY(pope_linear_prec_f32(xn, k.fc1_w, k.fc1_b, hid, rows, hidden, dim, EPI_BIAS_GELU, nullptr, nullptr, f32, nullptr, stream));
+            POPE_TRY(pope_linear_planes_f32(xn_pl, k.fc1_wp, k.fc1_b, nullptr, hid_pl, rows, fc1_n, dim, fc1_epi, nullptr,
+                                            nullptr, range_flag, stream));   // -> hid [rows, hidden] either way
+        else POPE_TRY(pope_linear_prec_f32(xn, k.fc1_w, k.fc1_b, hid, rows, fc1_n, dim, fc1_epi, nullptr, nullptr, f32, nullptr, stream));
         POPE_MARK(POPE_K_GEMM_FC2);
         if (fused && !last) {
             const pope_vit_block_weights& kn = w->blocks_host[i + 1];
@@ -453,8 +466,16 @@ int pope_vit_forward_f32(const pope_vit_weights* w, const float* img, int B, int
                          float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
                          float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
                          void* stream) {
+    return pope_vit_forward_ffn_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host,
+                                    workspace, workspace_bytes, range_flag, stream);
+}
+
+int pope_vit_forward_ffn_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
+                             float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
+                             float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
+                             void* stream) {
     Recorder rec{nullptr, 0, nullptr, 0};
-    return vit_forward_impl(w, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host, workspace,
+    return vit_forward_impl(w, ffn, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host, workspace,
                             workspace_bytes, range_flag, stream, rec);
 }
 
@@ -463,10 +484,19 @@ int pope_vit_forward_profiled_mask_f32(const pope_vit_weights* w, const float* i
                                        size_t workspace_bytes, unsigned* range_flag, void* stream,
                                        void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
                                        unsigned kind_mask) {
+    return pope_vit_forward_ffn_profiled_mask_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, workspace, workspace_bytes,
+                                                  range_flag, stream, events_host, n_events, kinds_host, n_launches_host, kind_mask);
+}
+
+int pope_vit_forward_ffn_profiled_mask_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W,
+                                           const float* posb, float* x_prenorm, float* x_norm, void* workspace,
+                                           size_t workspace_bytes, unsigned* range_flag, void* stream,
+                                           void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
+                                           unsigned kind_mask) {
     if (!events_host || n_events < 2 || !kinds_host || !n_launches_host) return POPE_ERR_ARG;
     Recorder rec{events_host, n_events, kinds_host, 0};
     rec.mask = kind_mask;
-    const int rc = vit_forward_impl(w, img, B, H, W, posb, x_prenorm, x_norm, 0, nullptr, nullptr, workspace,
+    const int rc = vit_forward_impl(w, ffn, img, B, H, W, posb, x_prenorm, x_norm, 0, nullptr, nullptr, workspace,
                                     workspace_bytes, range_flag, stream, rec);
     *n_launches_host = rec.n > 0 ? rec.n - 1 : 0;
     return rc;

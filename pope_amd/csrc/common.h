@@ -212,3 +212,25 @@ __device__ __forceinline__ float pope_gelu_erf(float x) {
     const float q = (poly * t) * e;
     return __builtin_fmaf(__builtin_fmaxf(x, 0.0f), __builtin_fmaf(q, -2.f, 1.f), x * q);
 }
+
+// ---- SwiGLU ---------------------------------------------------------------------------------------------------------
+// dinov2/layers/swiglu_ffn.py:29-33: hidden = silu(gate) * value, silu(x) = x / (1 + exp(-x)), in fp32 with exp(-x) as
+// exp2(-x log2 e) (the softmax kernels' stated deviation) and the quotient as x * rcp(.) (1 ulp, as the GELU's).  Finite for
+// every finite gate: exp2 saturates to +inf (x * rcp(inf) = -0) or to 0 (x * rcp(1) = x), never inf / inf.  Every GEMM
+// epilogue uses this one definition, so the routes of one GEMM give the same bits.  `inv` un-scales the f16x3 accumulators
+// (1 on the fp32 MFMA), the biases are the gate's and the value's.
+__device__ __forceinline__ f32x4 pope_swiglu4(f32x4 acc_gate, f32x4 acc_value, f32x4 bias_gate, f32x4 bias_value, float inv) {
+    constexpr float NL2E = -1.44269504088896340736f;
+    f32x4 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float gt = __builtin_fmaf(acc_gate[e], inv, bias_gate[e]), vl = __builtin_fmaf(acc_value[e], inv, bias_value[e]);
+        const float silu = gt * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gt * NL2E));
+        h[e] = silu * vl;
+    }
+    return h;
+}
+// The SwiGLU epilogues re-map the lanes over a wave's staged 32 x 64 block ([32 gate | 32 value] columns, kernels.h
+// EPI_BIAS_SWIGLU): lane -> row (lane >> 3) + 8 i, hidden columns 4 (lane & 7) .. + 3, so that the eight lanes of a row write
+// one whole 32-column chunk (64 B of hi + 64 B of lo halves, or 128 B of fp32).
+

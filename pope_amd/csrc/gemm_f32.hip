@@ -97,6 +97,29 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& g, int m0, int n
             }
         const int row0 = m0 + wm * 64 + mi * 32 + lr;
         __builtin_amdgcn_wave_barrier();
+        if constexpr (EPI == EPI_BIAS_SWIGLU) {
+            // this wave's 64 columns are [32 gate | 32 value] of 32 hidden columns (kernels.h; N % 64 == 0): the planes kernels'
+            // lane map (common.h) and the same pope_swiglu4, fp32 rows of pitch ldc out
+            const int sg_r = lane >> 3, sg_c4 = (lane & 7) * 4, blk = n0 + wn * 64, hc = blk / 2 + sg_c4;
+            const bool ok = blk < g.N;
+            f32x4 bg = {0.f, 0.f, 0.f, 0.f}, bv = {0.f, 0.f, 0.f, 0.f};
+            if (g.bias) {
+                bg = *reinterpret_cast<const f32x4*>(g.bias + (ok ? blk : 0) + sg_c4);
+                bv = *reinterpret_cast<const f32x4*>(g.bias + (ok ? blk : 0) + sg_c4 + 32);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = m0 + wm * 64 + mi * 32 + sg_r + 8 * i;
+                const float* er = &E[(sg_r + 8 * i) * EPI_ST + sg_c4];
+                const f32x4 hv = pope_swiglu4(*reinterpret_cast<const f32x4*>(er), *reinterpret_cast<const f32x4*>(er + 32), bg, bv, 1.0f);
+                if (wide) {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4e, hv), rc,
+                                                           ok ? unsigned(row) * unsigned(g.ldc) * 4u + unsigned(hc) * 4u : DROP, 0, 0);
+                } else if (row < g.M && ok) {
+                    *reinterpret_cast<f32x4*>(g.C + size_t(row) * g.ldc + hc) = hv;
+                }
+            }
+        } else {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             f32x4 extra[4];  // residual / table rows of this half pass (four at a time: the fp32 kernels run at 168 VGPRs)
@@ -138,6 +161,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& g, int m0, int n
                     *reinterpret_cast<f32x4*>(g.C + size_t(row) * g.ldc + col) = v;
                 }
             }
+        }
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -226,6 +250,9 @@ int pope_launch_gemm_nt_f32(const GemmParams& g, hipStream_t stream) {
     switch (g.epilogue) {
         case EPI_BIAS: return launch_linear<EPI_BIAS>(g, stream);
         case EPI_BIAS_GELU: return launch_linear<EPI_BIAS_GELU>(g, stream);
+        case EPI_BIAS_SWIGLU:   // C is [M, N / 2] with pitch ldc
+            if ((g.N & 63) || g.ldc < g.N / 2) return POPE_ERR_ARG;
+            return launch_linear<EPI_BIAS_SWIGLU>(g, stream);
         case EPI_BIAS_LS_RES:
             if (!g.gamma || !g.res) return POPE_ERR_ARG;
             return launch_linear<EPI_BIAS_LS_RES>(g, stream);

@@ -267,6 +267,17 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
     [[maybe_unused]] const bool col_pad = EPI == EPI_CONV && OUT_F16 && !col_ok && col < g.ldc;
     [[maybe_unused]] float qkv_scale = 1.0f;
     if constexpr (EPI == EPI_QKV_F16) qkv_scale = colc < g.sam_dim ? g.sam_qscale : 1.0f;   // a lane's four columns lie in one of q / k / v
+    // EPI_BIAS_SWIGLU (X3, planes out): gemm_planes.hip's lane map over this wave's [32 gate | 32 value] columns
+    [[maybe_unused]] const int sg_r = lane >> 3, sg_c4 = (lane & 7) * 4, sg_hc = (n0 + wn * 64) / 2 + sg_c4;
+    [[maybe_unused]] const bool sg_ok = n0 + wn * 64 < g.N;
+    [[maybe_unused]] f32x4 sg_bg = {0.f, 0.f, 0.f, 0.f}, sg_bv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EPI == EPI_BIAS_SWIGLU) {
+        if (g.bias) {
+            const float* bp = g.bias + (sg_ok ? n0 + wn * 64 : 0) + sg_c4;
+            sg_bg = *reinterpret_cast<const f32x4*>(bp);
+            sg_bv = *reinterpret_cast<const f32x4*>(bp + 32);
+        }
+    }
     __syncthreads();   // all waves have finished reading the last stage: the LDS is the epilogue's now
     float* E = smem + wave * 32 * EPI_ST;
     f32x2 amax = {0.f, 0.f};
@@ -305,6 +316,20 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                 }
             }
             __builtin_amdgcn_wave_barrier();
+            if constexpr (EPI == EPI_BIAS_SWIGLU) {
+                static_assert(EPI != EPI_BIAS_SWIGLU || (X3 && OUT_F16), "the SwiGLU epilogue of this kernel writes planes");
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float* er = &E[(sg_r + 8 * i) * EPI_ST + sg_c4];
+                    const f32x4 h = pope_swiglu4(*reinterpret_cast<const f32x4*>(er), *reinterpret_cast<const f32x4*>(er + 32), sg_bg, sg_bv, inv);
+                    const unsigned o = sg_ok ? unsigned(m_base + mh * 32 + sg_r + 8 * i) * c_row_bytes + unsigned((sg_hc >> 5) * 128 + (sg_hc & 31) * 2) : DROP;
+                    f16x4 hi, lo;
+                    pope_amax4x2(amax, h);
+                    pope_split4(h * PL_A_SCALE, hi, lo);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), rc, o, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), rc, o + 64u, 0, 2);
+                }
+            } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 f32x4 v = *reinterpret_cast<const f32x4*>(&E[(elr + 4 * i) * EPI_ST + ec4]);
@@ -363,6 +388,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                     v = res[i] + v * gamma + bias;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rc, col_ok ? off + unsigned(col) * 4u : DROP, 0, 0);
                 }
+            }
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -426,10 +452,10 @@ int pope_launch_wide_conv(const GemmParams& g, hipStream_t stream) {
     return g.N <= 128 ? launch<EPI_CONV, false, 2, true, 1>(g, stream) : launch<EPI_CONV, false, 4, true, 1>(g, stream);
 }
 
-// f16x3 planes -> planes (QKV, FC1 of the ViT blocks) on the 256 x 256 LDS-direct mainloop: the shapes it serves
+// f16x3 planes -> planes (QKV, FC1 / the SwiGLU w12 of the ViT blocks) on the 256 x 256 LDS-direct mainloop: the shapes it serves
 bool pope_wide_x3_supported(const GemmParams& g) {
     if (g.plain || !g.a_pl || !g.w_pl || !g.c_pl || g.conv_cch > 0 || g.nbatch > 1) return false;
-    if (g.epilogue != EPI_BIAS && g.epilogue != EPI_BIAS_GELU) return false;
+    if (g.epilogue != EPI_BIAS && g.epilogue != EPI_BIAS_GELU && g.epilogue != EPI_BIAS_SWIGLU) return false;
     if (g.N < 512 || (g.N & 63) || g.K < 64 || (g.K & 31) || (g.lda & 31) || (g.ldw & 31) || (g.ldc & 31)) return false;
     // 256-row tiles must fill the chip for several rounds: one workgroup per CU, nothing runs under a tile's epilogue
     return size_t((g.M + PL_BM - 1) / PL_BM) * ((g.N + 255) / 256) >= size_t(4) * pope_cu_count();
@@ -439,6 +465,7 @@ int pope_launch_wide_x3(const GemmParams& g, hipStream_t stream) {
     if (size_t(g.M + PL_BM) * g.lda * 4 >= (size_t(1) << 32) || size_t(g.N + 256) * g.ldw * 4 >= (size_t(1) << 32) ||
         size_t(g.M + PL_BM) * g.ldc * 4 >= (size_t(1) << 32) - 512)
         return POPE_ERR_ARG;
+    if (g.epilogue == EPI_BIAS_SWIGLU) return launch<EPI_BIAS_SWIGLU, true, 4, true>(g, stream);   // N = the GEMM's 2 x hidden columns
     return g.epilogue == EPI_BIAS_GELU ? launch<EPI_BIAS_GELU, true, 4, true>(g, stream) : launch<EPI_BIAS, true, 4, true>(g, stream);
 }
 

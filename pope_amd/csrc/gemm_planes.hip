@@ -371,6 +371,18 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
         }
         [[maybe_unused]] float qkv_scale = 1.0f;
         if constexpr (EPI == EPI_QKV_F16) qkv_scale = colc < g.sam_dim ? g.sam_qscale : 1.0f;   // a lane's four columns lie in one of q / k / v
+        // EPI_BIAS_SWIGLU: this wave's 64 columns are [32 gate | 32 value] of the hidden columns hc0 .. hc0 + 31 (common.h has the
+        // lane map); N % 64 == 0, so the block lies inside N or outside as a whole
+        [[maybe_unused]] const int sg_r = lane >> 3, sg_c4 = (lane & 7) * 4, sg_hc = (n0 + wn * 64) / 2 + sg_c4;
+        [[maybe_unused]] const bool sg_ok = n0 + wn * 64 < g.N;
+        [[maybe_unused]] f32x4 sg_bg = {0.f, 0.f, 0.f, 0.f}, sg_bv = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EPI == EPI_BIAS_SWIGLU) {
+            if (g.bias) {
+                const float* bp = g.bias + (sg_ok ? n0 + wn * 64 : 0) + sg_c4;
+                sg_bg = *reinterpret_cast<const f32x4*>(bp);
+                sg_bv = *reinterpret_cast<const f32x4*>(bp + 32);
+            }
+        }
         __syncthreads();  // all waves have finished reading the last K-step stage
         float* E = epi + wave * 32 * EPI_ST;
         f32x2 amax = {0.f, 0.f};  // OUT_PLANES: largest magnitude written as planes (range guard; rows >= M hold finite
@@ -510,7 +522,24 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 }
             }
             };
-            if constexpr (EPI == EPI_CONV_UP) {   // four rows at a time: the persistent mainloop keeps two K-steps of staging registers
+            if constexpr (EPI == EPI_BIAS_SWIGLU) {   // 32 rows x 32 hidden columns: four rows of eight lanes at a time
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float* er = &E[(sg_r + 8 * i) * EPI_ST + sg_c4];
+                    const f32x4 h = pope_swiglu4(*reinterpret_cast<const f32x4*>(er), *reinterpret_cast<const f32x4*>(er + 32), sg_bg, sg_bv, inv);
+                    const unsigned off = unsigned(m0 + wm * 64 + mh * 32 + sg_r + 8 * i) * c_row_bytes;
+                    if constexpr (OUT_PLANES) {
+                        f16x4 hi, lo;
+                        pope_amax4x2(amax, h);
+                        pope_split4(h * A_SCALE, hi, lo);
+                        const unsigned o = sg_ok ? off + unsigned((sg_hc >> 5) * 128 + (sg_hc & 31) * 2) : DROP;
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), rc, o, 0, 2);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), rc, o + 64u, 0, 2);
+                    } else {
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, h), rc, sg_ok ? off + unsigned(sg_hc) * 4u : DROP, 0, 2);
+                    }
+                }
+            } else if constexpr (EPI == EPI_CONV_UP) {   // four rows at a time: the persistent mainloop keeps two K-steps of staging registers
                 up_rows(0, 4);                    // alive across the epilogue, and 8 rows of neighbours on top of them spill those
                 store_rows(0, 4);
                 up_rows(4, 8);
@@ -641,6 +670,7 @@ bool args_ok(const GemmParams& g) {
         case EPI_BIAS:
         case EPI_BIAS_GELU:
         case EPI_BIAS_RELU: return true;
+        case EPI_BIAS_SWIGLU: return !g.plain && !(g.N & 63) && g.ldc >= g.N / 2;   // ldc: the pitch of the [M, N / 2] hidden rows
         case EPI_QKV_F16: return g.plain && out_planes && g.sam_dim > 0 && !(g.sam_dim & 63);
         case EPI_BIAS_LS_RES: return g.res && !out_planes && (g.gamma || g.res_mod > 0);
         case EPI_SAM_QKV:
@@ -681,6 +711,7 @@ int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream) {
         case EPI_BIAS: return out_planes ? launch16<EPI_BIAS, true>(g, stream) : launch16<EPI_BIAS, false>(g, stream);
         case EPI_BIAS_GELU: return out_planes ? launch16<EPI_BIAS_GELU, true>(g, stream) : launch16<EPI_BIAS_GELU, false>(g, stream);
         case EPI_BIAS_RELU: return out_planes ? launch16<EPI_BIAS_RELU, true>(g, stream) : launch16<EPI_BIAS_RELU, false>(g, stream);
+        case EPI_BIAS_SWIGLU: return out_planes ? launch16<EPI_BIAS_SWIGLU, true>(g, stream) : launch16<EPI_BIAS_SWIGLU, false>(g, stream);
         case EPI_BIAS_LS_RES: return launch16<EPI_BIAS_LS_RES, false>(g, stream);
         case EPI_SIM:
             if (g.sim_mask0 || g.sim_mask1) return launch16<EPI_SIM_MASK, false>(g, stream, g.nbatch);

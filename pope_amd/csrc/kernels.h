@@ -16,6 +16,10 @@ enum GemmEpilogue {
     EPI_QKV_F16 = 8,      // plain f16 only (POPE_PREC_F16 ViT blocks): C = (A.W^T + bias) * (col < sam_dim ? sam_qscale : 1) -> f16 row-major
                           // [M, N] with NO activation scale: the operand of attention_f16.hip (q carries head_dim^-0.5 * log2 e before its ONE rounding)
     EPI_CONV_UP = 9,      // kernel-side instantiation of EPI_CONV with GemmParams::up_src (callers pass EPI_CONV)
+    EPI_BIAS_SWIGLU = 11, // C[M, N / 2] = silu(gate + b_gate) * (value + b_value), the w12 GEMM of the SwiGLU FFN (swiglu_ffn.py:29-33) with
+                          // the rows of W / bias PERMUTED (pope_hip.h POPE_EPI_BIAS_SWIGLU): output columns 64 t .. 64 t + 31 are the
+                          // gates of hidden columns 32 t .. 32 t + 31, columns 64 t + 32 .. 64 t + 63 their values; N = 2 hidden is a
+                          // multiple of 64, ldc is the pitch of the HIDDEN rows; planes -> planes / fp32 and the fp32 GEMM
     EPI_CONV = 6,         // C = act(A.W^T + bias [+ res_pl]), act(v) = max(v, 0) + act_slope * min(v, 0): ReLU (0), LeakyReLU
                           // (0.01) or identity (1); the ResNet-FPN convolutions (conv.hip; gemm_planes.hip only)
 };
@@ -115,7 +119,7 @@ int pope_launch_gemm_nt_f32(const GemmParams& g, hipStream_t stream);
 // Same contract on the f16 matrix cores with error-compensated operands (gemm_f16x3.hip).
 bool pope_gemm_f16x3_supported(const GemmParams& g);
 // Every GEMM on pre-split f16x3 planes or (GemmParams::plain) plain f16 operands: Linears (BIAS, BIAS_GELU, BIAS_RELU,
-// BIAS_LS_RES, QKV_F16, SAM_QKV), the batched similarity (SIM) and the convolutions (CONV: implicit 3 x 3, up_src, and —
+// BIAS_SWIGLU, BIAS_LS_RES, QKV_F16, SAM_QKV), the batched similarity (SIM) and the convolutions (CONV: implicit 3 x 3, up_src, and —
 // conv_s2_taps > 0 — the stride-2 implicit form).  Checks the arguments and picks the mainloop (gemm_planes.hip).
 int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream);
 // whether pope_launch_gemm_planes takes a stride-2 convolution without the gathered tap tensor (conv.hip gathers otherwise)

@@ -5,8 +5,8 @@ Same constructor arguments, attribute names, state-dict keys (175 for ViT-S/14, 
 ``dinov2/dinov2/models/vision_transformer.py:45-295`` — ``model(x)``, ``model(x, is_training=True)``,
 ``forward_features``, ``get_intermediate_layers`` — but the forward pass is ONE call into the HIP
 library (``pope_vit_forward_f32``): patch-embed GEMM (+cls +pos), depth x [LN, QKV GEMM, flash
-attention, proj GEMM + LayerScale + residual, LN, FC1 GEMM + GELU, FC2 GEMM + LayerScale +
-residual], final LN — all hand-written gfx950 kernels.  fp32 in HBM, fp32 accumulation; the contractions
+attention, proj GEMM + LayerScale + residual, LN, FC1 GEMM + GELU (or, ``ffn_layer="swiglufused"``: the w12 GEMM
++ SwiGLU of ViT-g/14), FC2 GEMM + LayerScale + residual], final LN — all hand-written gfx950 kernels.  fp32 in HBM, fp32 accumulation; the contractions
 run in ``model.precision``: "f16x3" (default: operands as f16 hi+lo pairs on the f16 matrix cores, three
 MFMAs per product) or "f32" (fp32-in MFMA).
 
@@ -62,6 +62,28 @@ class _Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden, dim, bias=bias)
 
 
+def swiglu_hidden(dim, mlp_ratio):
+    """Hidden width of the reference's fused SwiGLU FFN (block.py:69 -> swiglu_ffn.py:57): 2/3 of the MLP's, rounded up to 8."""
+    return (int(int(dim * mlp_ratio) * 2 / 3) + 7) // 8 * 8
+
+
+def swiglu_permutation(hidden):
+    """Row order in which the w12 GEMM wants `w12.weight` / `w12.bias` (pope_hip.h POPE_EPI_BIAS_SWIGLU): per block of 32
+    hidden columns its 32 gate rows, then its 32 value rows — so that one 64-column accumulator block holds both halves of
+    `silu(x1) * x2` and the [rows, 2 hidden] product never leaves the kernel.  A bijection of range(2 * hidden)."""
+    t = torch.arange(hidden).view(hidden // 32, 1, 32)
+    return torch.cat([t, t + hidden], dim=1).reshape(-1)
+
+
+class _SwiGLUFFN(nn.Module):
+    """Parameter container of `SwiGLUFFNFused` (swiglu_ffn.py:45-63): w12 = Linear(dim, 2 h), w3 = Linear(h, dim)."""
+
+    def __init__(self, dim, hidden, bias):
+        super().__init__()
+        self.w12 = nn.Linear(dim, 2 * hidden, bias=bias)
+        self.w3 = nn.Linear(hidden, dim, bias=bias)
+
+
 class _LayerScale(nn.Module):
     def __init__(self, dim, init_values):
         super().__init__()
@@ -69,13 +91,13 @@ class _LayerScale(nn.Module):
 
 
 class _Block(nn.Module):
-    def __init__(self, dim, num_heads, mlp_ratio, qkv_bias, proj_bias, ffn_bias, init_values):
+    def __init__(self, dim, num_heads, mlp_ratio, qkv_bias, proj_bias, ffn_bias, init_values, swiglu=False):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = _Attention(dim, num_heads, qkv_bias, proj_bias)
         self.ls1 = _LayerScale(dim, init_values)
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio), ffn_bias)
+        self.mlp = _SwiGLUFFN(dim, swiglu_hidden(dim, mlp_ratio), ffn_bias) if swiglu else _Mlp(dim, int(dim * mlp_ratio), ffn_bias)
         self.ls2 = _LayerScale(dim, init_values)
 
 
@@ -90,8 +112,12 @@ class DinoVisionTransformer(nn.Module):
             raise NotImplementedError("pope_amd: the patch-embed kernel is built for 3-channel images")
         if embed_dim != num_heads * 64:
             raise NotImplementedError("pope_amd: attention kernel is built for head_dim 64 (all DINOv2 archs)")
-        if ffn_layer != "mlp":
-            raise NotImplementedError("pope_amd: only the 'mlp' FFN (ViT-S/B/L) is on the hot path")
+        if ffn_layer not in ("mlp", "swiglu", "swiglufused"):   # vision_transformer.py:109-114 ("identity" is a test stub there)
+            raise NotImplementedError("pope_amd: the 'mlp' (ViT-S/B/L) and 'swiglu' / 'swiglufused' (ViT-g) FFNs are on the hot path")
+        self.ffn = "swiglu" if ffn_layer != "mlp" else "mlp"
+        if self.ffn == "swiglu" and swiglu_hidden(embed_dim, mlp_ratio) % 64:
+            raise NotImplementedError(f"pope_amd: the SwiGLU GEMM needs a hidden size that is a multiple of 64; embed_dim {embed_dim} "
+                                      f"with mlp_ratio {mlp_ratio} gives {swiglu_hidden(embed_dim, mlp_ratio)}")
         if not (qkv_bias and ffn_bias and proj_bias):
             raise NotImplementedError("pope_amd: reference configs enable all biases (ssl_default_config.yaml:71-82)")
         if block_chunks not in (0, None):
@@ -107,7 +133,8 @@ class DinoVisionTransformer(nn.Module):
         # LayerScale is mandatory on this path (init_values=1e-5 in the eval config); None -> identity scale
         gamma0 = init_values if init_values else 1.0
         self.blocks = nn.ModuleList(
-            [_Block(embed_dim, num_heads, mlp_ratio, qkv_bias, proj_bias, ffn_bias, gamma0) for _ in range(depth)])
+            [_Block(embed_dim, num_heads, mlp_ratio, qkv_bias, proj_bias, ffn_bias, gamma0, self.ffn == "swiglu")
+             for _ in range(depth)])
         self.chunked_blocks = False
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
         self.head = nn.Identity()
@@ -147,11 +174,32 @@ class DinoVisionTransformer(nn.Module):
         self._wcache, self._posb_cache = {}, {}
         return out
 
+    # ---- the two FFN kinds ---------------------------------------------------------------
+    def _ffn_linears(self, b):
+        """(first, second) Linear of a block's FFN as the state dict holds them: (fc1, fc2) or (w12, w3)."""
+        return (b.mlp.w12, b.mlp.w3) if self.ffn == "swiglu" else (b.mlp.fc1, b.mlp.fc2)
+
+    @property
+    def ffn_hidden(self):
+        """Width of the FFN's hidden activation = in_features of its second Linear."""
+        return int(self._ffn_linears(self.blocks[0])[1].weight.shape[1])
+
+    def _ffn_first(self, b):
+        """Weight and bias of the first FFN GEMM as the kernels read them: fc1's, or w12's with the rows permuted
+        (`swiglu_permutation`; derived tensors, kept alive by the slot-keyed weight cache)."""
+        lin = self._ffn_linears(b)[0]
+        if self.ffn != "swiglu":
+            return lin.weight, lin.bias
+        perm = swiglu_permutation(self.ffn_hidden).to(lin.weight.device)
+        return lin.weight.detach()[perm].contiguous(), lin.bias.detach()[perm].contiguous()
+
     def _weights(self, precision=None):
         """ctypes weight struct of one arithmetic mode (cached per mode: the fp32 re-run of the range guard does not
         evict the f16x3 planes).  f16x3: the Linear / patch-embed weights as hi/lo planes, after a range check —
         |w| * 256 must be finite in f16; a checkpoint that breaches it runs on the fp32 MFMA (or raises)."""
         precision = precision or self.precision
+        if precision == "f16" and self.ffn == "swiglu":
+            raise NotImplementedError("pope_amd: precision='f16' with the SwiGLU FFN is not built (use 'f16x3' or 'f32')")
         if self._src is None:
             self._src = _lib.param_slots(self)
         dev_ptr = _lib.slots_key(self._src)   # addresses + in-place versions of the tensors NOW in every parameter slot
@@ -160,7 +208,7 @@ class DinoVisionTransformer(nn.Module):
             return hit[1]
         if precision in ("f16x3", "f16"):
             lin = [self.patch_embed.proj.weight] + [t for b in self.blocks for t in
-                                                    (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight)]
+                                                    (b.attn.qkv.weight, b.attn.proj.weight) + tuple(l.weight for l in self._ffn_linears(b))]
             amax = float(torch.stack([t.detach().abs().max() for t in lin]).max())
             if not amax * _lib.PLANES_W_SCALE < _lib.F16_MAX:   # also catches NaN
                 self.overflow_events += 1
@@ -196,11 +244,13 @@ class DinoVisionTransformer(nn.Module):
 
         blocks = (_lib.VitBlockWeights * self.n_blocks)()
         for i, b in enumerate(self.blocks):
+            w1, b1 = self._ffn_first(b)
+            fc2 = self._ffn_linears(b)[1]
             blocks[i] = _lib.VitBlockWeights(
                 P(b.norm1.weight), P(b.norm1.bias), P(b.attn.qkv.weight), P(b.attn.qkv.bias),
                 P(b.attn.proj.weight), P(b.attn.proj.bias), P(b.ls1.gamma), P(b.norm2.weight), P(b.norm2.bias),
-                P(b.mlp.fc1.weight), P(b.mlp.fc1.bias), P(b.mlp.fc2.weight), P(b.mlp.fc2.bias), P(b.ls2.gamma),
-                planes(b.attn.qkv.weight), planes(b.mlp.fc1.weight), planes(b.mlp.fc2.weight),
+                P(w1), P(b1), P(fc2.weight), P(fc2.bias), P(b.ls2.gamma),
+                planes(b.attn.qkv.weight), planes(w1), planes(fc2.weight),
                 planes(b.attn.proj.weight))
         pw = self.patch_embed.proj.weight.detach().reshape(self.embed_dim, -1)
         patch_wp = None
@@ -208,7 +258,7 @@ class DinoVisionTransformer(nn.Module):
             kp = (pw.shape[1] + 31) // 32 * 32                 # (the patch embed is f16x3 in both modes)
             patch_wp = planes(torch.nn.functional.pad(pw.float(), (0, kp - pw.shape[1])), plain=False)
         w = _lib.VitWeights(self.embed_dim, self.n_blocks, self.num_heads, self.patch_size,
-                            self.blocks[0].mlp.fc1.weight.shape[0], P(pw),
+                            self.ffn_hidden, P(pw),
                             P(self.norm.weight), P(self.norm.bias), blocks, _lib.PRECISIONS[precision], patch_wp)
         self._wcache[precision] = (dev_ptr, w, blocks, tensors)
         return w
@@ -281,7 +331,7 @@ class DinoVisionTransformer(nn.Module):
             return e, (out_norm if out_norm is not None else e.clone()), [e.clone() for _ in taps]
         # The kernels address a launch sequence's activations through 32-bit byte offsets: larger batches are run as
         # several sequences writing into slices of the same outputs (identical results: images are independent).
-        widest = max(4 * dim, int(self.blocks[0].mlp.fc1.weight.shape[0]))
+        widest = max(4 * dim, self.ffn_hidden)
         max_b = max(1, ((1 << 32) - (1 << 20)) // ((ntok * widest + 256 * widest) * 4))
         max_b = min(max_b, getattr(self, "_max_batch", None) or max_b)   # test hook
         if B > max_b:
@@ -317,20 +367,21 @@ class DinoVisionTransformer(nn.Module):
             tap_out = [torch.empty(B, ntok, dim, device=x.device, dtype=torch.float32) for _ in taps]
             tap_blocks = (C.c_int * max(1, len(taps)))(*taps)
             tap_ptrs = (C.c_void_p * max(1, len(taps)))(*[t.data_ptr() for t in tap_out])
+            ffn = _lib.FFN_KINDS[self.ffn]
             slot = self.profiler.next_slot() if (self.profiler is not None and not taps) else None
             if slot is not None:
                 off, ev, cap, kinds = slot
                 n_launch = C.c_int()
-                check(L.pope_vit_forward_profiled_mask_f32(C.byref(w), ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
-                                                           C.c_void_p(ws.data_ptr()), ws.numel(), flag_ptr,
-                                                           stream_of(x.device), ev, cap, kinds, C.byref(n_launch),
-                                                           self.profiler.mask),
-                      "pope_vit_forward_profiled_mask_f32")
+                check(L.pope_vit_forward_ffn_profiled_mask_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
+                                                               C.c_void_p(ws.data_ptr()), ws.numel(), flag_ptr,
+                                                               stream_of(x.device), ev, cap, kinds, C.byref(n_launch),
+                                                               self.profiler.mask),
+                      "pope_vit_forward_ffn_profiled_mask_f32")
                 self.profiler.commit(off, n_launch.value)
             else:
-                check(L.pope_vit_forward_f32(C.byref(w), ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
-                                             len(taps), tap_blocks, tap_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                             flag_ptr, stream_of(x.device)), "pope_vit_forward_f32")
+                check(L.pope_vit_forward_ffn_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
+                                                 len(taps), tap_blocks, tap_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                 flag_ptr, stream_of(x.device)), "pope_vit_forward_ffn_f32")
         if own_flag is not None:
             bits = int(own_flag.item())  # the direct call's synchronisation point
             if bits:
@@ -416,5 +467,13 @@ def vit_large(patch_size=16, **kw):
     return DinoVisionTransformer(patch_size=patch_size, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4, **kw)
 
 
+def vit_giant2(patch_size=16, **kw):
+    """vision_transformer.py:345-358: 1536-d, 40 blocks, 24 heads of 64; its checkpoints use ffn_layer="swiglufused"
+    (hubconf.py:79), which the caller passes."""
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=1536, depth=40, num_heads=24, mlp_ratio=4, **kw)
+
+
 # the eval config of the reference (configs/eval/vits14_pretrain.yaml + ssl_default_config.yaml:71-82)
 build_vits14 = partial(vit_small, patch_size=14, img_size=518, init_values=1e-5, ffn_layer="mlp", block_chunks=0)
+# ... and of ViT-g/14 (configs/eval/vitg14_pretrain.yaml: the giant is always built with the fused SwiGLU FFN)
+build_vitg14 = partial(vit_giant2, patch_size=14, img_size=518, init_values=1e-5, ffn_layer="swiglufused", block_chunks=0)

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .dinov2 import build_vits14
+from .dinov2 import build_vitg14, build_vits14
 from .synth import IMAGENET_MEAN, IMAGENET_STD
 
 DEFAULT_WEIGHTS = "weights/dinov2_vits14.pth"  # dinov2_utils.py:45
@@ -25,12 +25,16 @@ def load_dinov2_weights(model, pretrained_weights, checkpoint_key="student"):
     return model.load_state_dict(state_dict, strict=True)
 
 
-def load_dinov2_model(weights=DEFAULT_WEIGHTS, state_dict=None):
+ARCHS = {"vits14": build_vits14, "vitg14": build_vitg14}   # eval configs of the reference (dinov2.py)
+
+
+def load_dinov2_model(weights=DEFAULT_WEIGHTS, state_dict=None, arch="vits14"):
     """dinov2_utils.py:38-47: ViT-S/14 (img_size 518, LayerScale 1e-5, mlp FFN), weights loaded
     strictly, eval mode, returned on CPU (the caller moves it to 'cuda:0',
     eval_linemod_json.py:11-12).  `state_dict` lets callers without the checkpoint file (offline
-    benchmarks) supply weights in the same layout."""
-    model = build_vits14()
+    benchmarks) supply weights in the same layout.  Extension: `arch="vitg14"` builds ViT-g/14 with its fused SwiGLU FFN
+    (configs/eval/vitg14_pretrain.yaml) for a checkpoint in that layout (`blocks.{i}.mlp.w12.*` / `mlp.w3.*`)."""
+    model = ARCHS[arch]()
     if state_dict is not None:
         model.load_state_dict(state_dict, strict=True)
     else:

@@ -14,7 +14,7 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 def synthetic_state_dict(seed=0, dim=384, depth=12, patch=14, grid=37, gamma=1.0,
-                         wscale=None):
+                         wscale=None, ffn="mlp"):
     """Seeded synthetic weights in the reference checkpoint layout (175 keys for
     ViT-S/14).  Unlike the reference initialisers (gamma=1e-5,
     trunc_normal(0.02)), branch outputs here are O(1) so that attention / MLP
@@ -43,10 +43,17 @@ def synthetic_state_dict(seed=0, dim=384, depth=12, patch=14, grid=37, gamma=1.0
         sd[p + "ls1.gamma"] = gamma * (0.3 + 0.1 * rn(dim))
         sd[p + "norm2.weight"] = 1.0 + rn(dim, std=0.1)
         sd[p + "norm2.bias"] = rn(dim, std=0.05)
-        sd[p + "mlp.fc1.weight"] = rn(4 * dim, dim, std=ws / math.sqrt(dim))
-        sd[p + "mlp.fc1.bias"] = rn(4 * dim, std=0.1)
-        sd[p + "mlp.fc2.weight"] = rn(dim, 4 * dim, std=ws / math.sqrt(4 * dim))
-        sd[p + "mlp.fc2.bias"] = rn(dim, std=0.05)
+        if ffn == "swiglu":   # SwiGLUFFNFused (swiglu_ffn.py:45-63): w12 [2 h, dim], w3 [dim, h], same O(1) recipe
+            h = (int(4 * dim * 2 / 3) + 7) // 8 * 8
+            sd[p + "mlp.w12.weight"] = rn(2 * h, dim, std=ws / math.sqrt(dim))
+            sd[p + "mlp.w12.bias"] = rn(2 * h, std=0.1)
+            sd[p + "mlp.w3.weight"] = rn(dim, h, std=ws / math.sqrt(h))
+            sd[p + "mlp.w3.bias"] = rn(dim, std=0.05)
+        else:
+            sd[p + "mlp.fc1.weight"] = rn(4 * dim, dim, std=ws / math.sqrt(dim))
+            sd[p + "mlp.fc1.bias"] = rn(4 * dim, std=0.1)
+            sd[p + "mlp.fc2.weight"] = rn(dim, 4 * dim, std=ws / math.sqrt(4 * dim))
+            sd[p + "mlp.fc2.bias"] = rn(dim, std=0.05)
         sd[p + "ls2.gamma"] = gamma * (0.3 + 0.1 * rn(dim))
     sd["norm.weight"] = 1.0 + rn(dim, std=0.1)
     sd["norm.bias"] = rn(dim, std=0.05)
