@@ -571,6 +571,31 @@ int pope_estimate_pose_f64(const float* kpts0, const float* kpts1, const int* co
  * x0 / x1 [S, 5, 2] fp64 -> E_out [S, 10, 9] (unit Frobenius norm, ascending root order, zero filled), n_out [S]. */
 int pope_five_point_f64(const double* x0, const double* x1, int S, double* E_out, int* n_out, void* stream);
 
+/* ---- batched driver step: device-side vote and slot tally (vote.hip) ------------------------------------------------ */
+
+/* CLS cosine + streaming top-3 vote for Q queries in one launch (one workgroup per query, any P; eval_linemod_json.py:93-101).
+ * cls_ref [Q, D], cls_prop [N, D] fp32; seg [Q + 1] int32 (DEVICE): query q owns proposal rows seg[q] .. seg[q + 1] (P_q = 0
+ * allowed; rows are clamped to [0, N]).  scores [N]: the arithmetic of pope_cls_cosine_f32, bit-equal to it called per query.
+ * slot_scores [Q, 3] fp32 / slot_index [Q, 3] int64 (local to the query, -1 = slot never filled): exactly
+ * pope_streaming_top3_host over the query's scores in proposal order.  pair_row [3 Q] int32: global proposal row of slot s of
+ * query q (0 for a dead slot); pair_live [3 Q] bytes: 1 when the slot was filled.  Q = 0: POPE_OK, nothing launched. */
+int pope_vote_top3_batch_f32(const float* cls_ref, const float* cls_prop, const int* seg, int Q, int N, int D, float eps,
+                             float* scores, float* slot_scores, long long* slot_index, int* pair_row, unsigned char* pair_live,
+                             void* stream);
+
+/* The published matches of a Matcher call over 3 Q pairs (pair 3 q + s = slot s of query q) -> the pose solver's inputs.
+ * m_bids [M] int64 sorted (matches pair-contiguous, pairs in order), mconf [M], mkpts0_f / mkpts1_f [M, 2] fp32, pair_live
+ * [3 Q] bytes.  pair_begin / pair_count [3 Q] int32: each pair's rows in the match list; matching_score [Q, 3] int64 =
+ * #(mconf > conf_thr) per slot (fp32, strict; eval_linemod_json.py:121-122), 0 for a dead slot; best_slot [Q] int32 = first
+ * maximum of the three (np.argmax, :150); best_count [Q] int32 = matches of the best slot (0 when it is dead); best_kpts0 /
+ * best_kpts1 [M, 2]: each query's best-slot matches, in order, at the exclusive scan of best_count — the layout
+ * pope_estimate_pose_f64 takes with counts = best_count (rows past sum(best_count) are not written).
+ * Two launches, integer arithmetic only, no atomics.  M = 0 or Q = 0: POPE_OK, nothing launched, nothing written. */
+int pope_slot_tally_f32(const long long* m_bids, const float* mconf, const float* mkpts0_f, const float* mkpts1_f,
+                        const unsigned char* pair_live, int Q, long long M, float conf_thr, int* pair_begin, int* pair_count,
+                        long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,
+                        void* stream);
+
 /* ---- host-side helper ------------------------------------------------------------------------ */
 
 /* Streaming top-3 proposal vote — eval_linemod_json.py:71,95-101 (HOST pointers): slots start at

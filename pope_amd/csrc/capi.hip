@@ -851,6 +851,23 @@ int pope_streaming_top3_host(const float* scores, int P, float* slot_scores, lon
     return POPE_OK;
 }
 
+int pope_vote_top3_batch_f32(const float* cls_ref, const float* cls_prop, const int* seg, int Q, int N, int D, float eps,
+                             float* scores, float* slot_scores, long long* slot_index, int* pair_row, unsigned char* pair_live,
+                             void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_vote_top3_batch(cls_ref, cls_prop, seg, Q, N, D, eps, scores, slot_scores, slot_index, pair_row, pair_live,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int pope_slot_tally_f32(const long long* m_bids, const float* mconf, const float* mkpts0_f, const float* mkpts1_f,
+                        const unsigned char* pair_live, int Q, long long M, float conf_thr, int* pair_begin, int* pair_count,
+                        long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,
+                        void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_slot_tally(m_bids, mconf, mkpts0_f, mkpts1_f, pair_live, Q, M, conf_thr, pair_begin, pair_count,
+                                  matching_score, best_slot, best_count, best_kpts0, best_kpts1, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 size_t pope_estimate_pose_workspace_bytes(int B, long long M) { return pope_pose_workspace(B, M); }

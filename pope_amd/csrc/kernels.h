@@ -350,6 +350,15 @@ size_t pope_pose_workspace(int B, long long M);
 int pope_launch_estimate_pose(PoseParams q, void* ws, size_t ws_bytes, hipStream_t stream);
 int pope_launch_five_point(const double* x0, const double* x1, int S, double* E_out, int* n_out, hipStream_t stream);
 
+// Device-side glue of the batched driver step (vote.hip): the arguments of pope_vote_top3_batch_f32 / pope_slot_tally_f32
+int pope_launch_vote_top3_batch(const float* cls_ref, const float* cls_prop, const int* seg, int Q, int N, int D, float eps,
+                                float* scores, float* slot_scores, long long* slot_index, int* pair_row, unsigned char* pair_live,
+                                hipStream_t stream);
+int pope_launch_slot_tally(const long long* m_bids, const float* mconf, const float* mkpts0, const float* mkpts1,
+                           const unsigned char* pair_live, int Q, long long M, float conf_thr, int* pair_begin, int* pair_count,
+                           long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,
+                           hipStream_t stream);
+
 // SAM mask decoder (sam_decoder.hip): the arguments of pope_sam_decoder_forward_f32
 struct SamDecArgs {
     const pope_sam_decoder_weights* w;

@@ -8,6 +8,10 @@ vote (order-dependent by definition) and ONE Matcher call over the occupied slot
 `locate_match_pose_u8` is the whole per-pair body of the loop after SAM: frame + proposal boxes in, pose out — proposal
 crops and their intrinsics (crops.py), preprocessing (preprocess.py), DINOv2 vote, LoFTR matches and the essential-matrix
 RANSAC (pose.py) all on the card.  SAM proposal generation itself is upstream of the path (SURVEY.md §8 'OUT').
+
+The `*_batch` functions take Q independent queries per call: one DINOv2 forward, the vote on the device (ops.vote_top3_batch),
+ONE Matcher call over 3 Q pairs, the per-slot tally and best-slot choice on the device (ops.slot_tally), one pose launch and a
+single download; each query's result is what the single-query function returns for it alone.
 """
 import numpy as np
 import torch
@@ -102,3 +106,175 @@ def locate_match_pose_u8(dinov2_model, matcher, ref_bgr, frame_bgr, bboxes_xywh,
     s = out["best_slot"]
     out["pose"] = estimate_pose(out["mkpts0"][s], out["mkpts1"][s], K0, out["pre_K"], ransac_thr, ransac_conf, device=dev)
     return out
+
+
+# ---- Q queries per call: the same step with the vote, the slot tally and the best-slot choice on the device ------------------
+def _counts(proposals_per_query, Q, N, what):
+    """The Q per-query proposal counts as ints; ValueError unless there are Q of them, none negative, summing to N."""
+    counts = [int(p) for p in proposals_per_query]
+    if len(counts) != Q:
+        raise ValueError(f"{what}: {len(counts)} proposal counts for {Q} queries")
+    if any(c < 0 for c in counts) or sum(counts) != N:
+        raise ValueError(f"{what}: proposals_per_query must be non-negative and sum to the {N} proposal rows (got {sum(counts)})")
+    return counts
+
+
+def _batch_on_device(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs, select_gray, counts, conf_thr):
+    """Launch sequence of the batched step, nothing read back: one DINOv2 forward over the Q references and the N proposals
+    -> `vote_top3_batch` -> ONE Matcher call over 3 Q pairs (pair 3 q + s: reference q against the crop in slot s of query q;
+    a dead slot keeps its place with an all-zero image1, so the batch is sized without a host read) -> `slot_tally`.
+    `select_gray(pair_row)` -> [3 Q, 1, H1, W1] gray crops of the voted rows.  Returns the device tensors of both ops."""
+    from .ops import slot_tally, vote_top3_batch
+    Q = len(counts)
+    if ref_tensors.shape[1:] == crop_tensors.shape[1:]:
+        both = get_cls_token_torch(dinov2_model, torch.cat([ref_tensors, crop_tensors], 0))
+        ref, fea = both[:Q], both[Q:]
+    else:
+        ref = get_cls_token_torch(dinov2_model, ref_tensors)
+        fea = get_cls_token_torch(dinov2_model, crop_tensors)
+    dv = vote_top3_batch(ref, fea, counts, eps=1e-8)
+    live = dv["pair_live"].bool()[:, None, None, None]
+    sel = select_gray(dv["pair_row"])
+    batch = {"image0": gray_refs.repeat_interleave(3, dim=0), "image1": torch.where(live, sel, torch.zeros_like(sel[:1, :1, :1, :1]))}
+    matcher(batch)
+    dv.update(slot_tally(batch["m_bids"], batch["mconf"], batch["mkpts0_f"], batch["mkpts1_f"], dv["pair_live"], conf_thr))
+    dv.update(mkpts0=batch["mkpts0_f"], mkpts1=batch["mkpts1_f"], mconf=batch["mconf"])
+    # the best proposal's global row (a dead best slot points at row 0: any valid row, its result is dropped on the host)
+    dv["best_row"] = dv["pair_row"].view(Q, 3).gather(1, dv["best_slot"].long()[:, None])[:, 0]
+    return dv
+
+
+def _empty_result(device):
+    return {"scores": torch.empty(0, dtype=torch.float32, device=device), "slot_scores": np.zeros(3, np.float32),
+            "slot_index": np.full(3, -1, np.int64), "mkpts0": [np.zeros((0, 2), np.float32)] * 3,
+            "mkpts1": [np.zeros((0, 2), np.float32)] * 3, "mconf": [np.zeros((0,), np.float32)] * 3,
+            "matching_score": np.zeros(3, np.int64), "best_slot": 0, "best_proposal": -1}
+
+
+def _download(dv, counts):
+    """The one download of the batched step: Q dicts with the keys and types of `locate_and_match`."""
+    Q = len(counts)
+    keys = ("slot_scores", "slot_index", "pair_live", "pair_begin", "pair_count", "matching_score", "best_slot", "mkpts0", "mkpts1", "mconf")
+    h = {k: dv[k].cpu().numpy() for k in keys}
+    seg = np.concatenate([[0], np.cumsum(counts)])
+    outs = []
+    for q in range(Q):
+        out = _empty_result(dv["scores"].device)
+        out["scores"] = dv["scores"][seg[q]:seg[q + 1]]
+        out["slot_scores"], out["slot_index"] = h["slot_scores"][q].copy(), h["slot_index"][q].copy()
+        out["matching_score"] = h["matching_score"][q].copy()
+        out["mkpts0"], out["mkpts1"], out["mconf"] = list(out["mkpts0"]), list(out["mkpts1"]), list(out["mconf"])
+        for s in range(3):
+            b = 3 * q + s
+            if h["pair_live"][b]:
+                rows = slice(int(h["pair_begin"][b]), int(h["pair_begin"][b]) + int(h["pair_count"][b]))
+                out["mkpts0"][s], out["mkpts1"][s], out["mconf"][s] = h["mkpts0"][rows], h["mkpts1"][rows], h["mconf"][rows]
+        out["best_slot"] = int(h["best_slot"][q])
+        out["best_proposal"] = int(out["slot_index"][out["best_slot"]])
+        outs.append(out)
+    return outs
+
+
+@torch.no_grad()
+def locate_and_match_batch(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs, gray_crops, proposals_per_query, conf_thr=0.9):
+    """`locate_and_match` for Q independent queries in one call.
+
+    ref_tensors [Q,3,h,w], gray_refs [Q,1,H0,W0]: one reference per query; crop_tensors [N,3,h,w], gray_crops [N,1,H1,W1]: the
+    proposals of all queries, query q owning the next `proposals_per_query[q]` rows (0 is allowed: the empty result, every
+    slot -1, best_proposal -1).  Returns a list of Q dicts, each what `locate_and_match` returns for that query alone.
+    Nothing is read back between the DINOv2 forward and the Matcher launch, nor between the Matcher and the final download:
+    the vote and the slot tally run on the device (ops.vote_top3_batch, ops.slot_tally)."""
+    Q, N = int(ref_tensors.shape[0]), int(crop_tensors.shape[0])
+    counts = _counts(proposals_per_query, Q, N, "locate_and_match_batch")
+    if int(gray_refs.shape[0]) != Q or int(gray_crops.shape[0]) != N:
+        raise ValueError(f"locate_and_match_batch: {Q} references / {N} proposals, but {int(gray_refs.shape[0])} / "
+                         f"{int(gray_crops.shape[0])} gray images")
+    if Q == 0 or N == 0:
+        return [_empty_result(ref_tensors.device) for _ in range(Q)]
+    dv = _batch_on_device(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs,
+                          lambda rows: gray_crops.index_select(0, rows), counts, conf_thr)
+    return _download(dv, counts)
+
+
+def _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr):
+    from .preprocess import gray_batch, set_torch_images
+    # gray conversion of the 3 Q voted crops only (a per-pixel op: bit-equal to converting all N and selecting)
+    return _batch_on_device(dinov2_model, matcher, set_torch_images(refs, center_crop=True), set_torch_images(crops, center_crop=True),
+                            gray_batch(refs), lambda rows: gray_batch(crops.index_select(0, rows)), counts, conf_thr)
+
+
+@torch.no_grad()
+def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, proposals_per_query, conf_thr=0.9):
+    """`locate_and_match_u8` for Q queries: `refs_bgr` [Q, H0, W0, 3] and `crops_bgr` [N, 256, 256, 3] uint8 BGR (numpy or
+    tensors), query q owning the next `proposals_per_query[q]` crops.  Preprocessing as there, except that only the 3 Q crops
+    the vote selected are converted to gray."""
+    refs, crops = torch.as_tensor(refs_bgr), torch.as_tensor(crops_bgr)
+    Q, N = int(refs.shape[0]), int(crops.shape[0])
+    counts = _counts(proposals_per_query, Q, N, "locate_and_match_batch_u8")
+    dev = next(dinov2_model.parameters()).device
+    if Q == 0 or N == 0:
+        return [_empty_result(dev) for _ in range(Q)]
+    return _download(_batch_u8_on_device(dinov2_model, matcher, refs.to(dev), crops.to(dev), counts, conf_thr), counts)
+
+
+@torch.no_grad()
+def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bboxes_xywh, K0, K1, conf_thr=0.9, ransac_thr=0.5,
+                               ransac_conf=0.99, out_size=256):
+    """`locate_match_pose_u8` for Q queries in one call: `refs_bgr` [Q, H0, W0, 3] uint8, `frames_bgr` [Q, H, W, 3] uint8 (an
+    array, a tensor or Q frames of one size), `bboxes_xywh` a list of Q arrays [P_q, 4] (P_q = 0 allowed), `K0` / `K1` [3, 3]
+    for all queries or [Q, 3, 3].  Returns a list of Q dicts, each what `locate_match_pose_u8` returns for that query alone.
+
+    crop_proposals per frame (asynchronous launches) -> the batched vote + ONE Matcher call over 3 Q pairs + slot tally
+    (`locate_and_match_batch_u8`) -> ONE `estimate_pose_batch` over the Q best slots, fed by the tally's compacted matches
+    and the crop intrinsics gathered on the device by best proposal row -> one download.  `pose` is None under
+    `estimate_pose`'s conditions (fewer than five matches, no inliers) and when no slot was filled."""
+    from .crops import crop_proposals
+    from .pose import estimate_pose_batch
+    refs = torch.as_tensor(refs_bgr)
+    Q = int(refs.shape[0])
+    if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
+        frames_bgr = [torch.as_tensor(f) for f in frames_bgr]
+        if len({tuple(f.shape) for f in frames_bgr}) > 1:
+            raise ValueError("locate_match_pose_batch_u8: the frames of one call have one size")
+        frames_bgr = torch.stack(frames_bgr) if frames_bgr else torch.zeros(0, 1, 1, 3, dtype=torch.uint8)
+    frames = torch.as_tensor(frames_bgr)
+    if frames.dim() != 4:
+        raise ValueError("locate_match_pose_batch_u8: frames_bgr is [Q, H, W, 3] (frames of one size)")
+    boxes_in = [np.asarray(b).reshape(-1, 4) for b in bboxes_xywh]
+
+    def per_query(K, name):
+        K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
+        if K.shape not in ((3, 3), (Q, 3, 3)):
+            raise ValueError(f"locate_match_pose_batch_u8: {name} is [3, 3] or [{Q}, 3, 3]")
+        return np.ascontiguousarray(np.broadcast_to(K, (Q, 3, 3)))
+
+    if int(frames.shape[0]) != Q or len(boxes_in) != Q:
+        raise ValueError(f"locate_match_pose_batch_u8: {Q} references, {int(frames.shape[0])} frames, {len(boxes_in)} box lists")
+    K0q, K1q = per_query(K0, "K0"), per_query(K1, "K1")
+    counts = [len(b) for b in boxes_in]
+    dev = next(dinov2_model.parameters()).device
+    frames = frames.to(dev)
+    props = [crop_proposals(frames[q], boxes_in[q], K1q[q], out_size=out_size) for q in range(Q)]
+    N = sum(counts)
+    if Q == 0 or N == 0:
+        outs = [_empty_result(dev) for _ in range(Q)]
+        pose = None
+    else:
+        crops = torch.cat([p["crops"] for p in props], 0)
+        K_crops = torch.from_numpy(np.ascontiguousarray(np.concatenate([p["K"] for p in props], 0))).to(dev)
+        dv = _batch_u8_on_device(dinov2_model, matcher, refs.to(dev), crops, counts, conf_thr)
+        pose = estimate_pose_batch(dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], K0q, K_crops.index_select(0, dv["best_row"]),
+                                   ransac_thr, ransac_conf)
+        outs = _download(dv, counts)
+        R, t, inl, n_inl = (pose[k].cpu().numpy() for k in ("R", "t", "inliers", "n_inliers"))
+        off = np.concatenate([[0], np.cumsum(dv["best_count"].cpu().numpy())])
+    for q, out in enumerate(outs):
+        out["boxes"], out["K_crops"] = props[q]["boxes"], props[q]["K"]
+        best = out["best_proposal"]
+        if best < 0:
+            out["pre_bbox"], out["pre_K"], out["pose"] = None, None, None
+            continue
+        out["pre_bbox"], out["pre_K"] = props[q]["boxes"][best], props[q]["K"][best]
+        n = int(off[q + 1] - off[q])
+        out["pose"] = (R[q], t[q], inl[off[q]:off[q + 1]]) if n >= 5 and int(n_inl[q]) > 0 else None
+    return outs

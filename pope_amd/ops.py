@@ -119,3 +119,61 @@ def streaming_top3(scores):
                                               slots.ctypes.data_as(_lib.c_float_p),
                                               idx.ctypes.data_as(_lib.c_ll_p)), "pope_streaming_top3_host")
     return slots, idx
+
+
+def vote_top3_batch(cls_ref, cls_prop, proposals_per_query, eps=1e-8):
+    """`cls_cosine` + `streaming_top3` for Q queries in one launch, results on the device (pope_vote_top3_batch_f32).
+    cls_ref [Q, D], cls_prop [N, D]; `proposals_per_query`: Q counts summing to N (query q owns the next P_q rows), or the
+    int32 [Q + 1] row offsets themselves as a tensor.  Returns a dict of device tensors: scores [N], slot_scores [Q, 3],
+    slot_index [Q, 3] int64 (-1 = empty slot), pair_row [3 Q] int32 (global row of each slot, 0 when dead), pair_live [3 Q] uint8,
+    and `seg`."""
+    cls_ref = _f32c(cls_ref, "vote_top3_batch")
+    cls_prop = _f32c(cls_prop, "vote_top3_batch")
+    dev = cls_ref.device
+    q, d = cls_ref.shape
+    n = int(cls_prop.shape[0])
+    if torch.is_tensor(proposals_per_query):
+        seg = proposals_per_query.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        counts = [int(p) for p in proposals_per_query]
+        if min(counts, default=0) < 0 or sum(counts) != n:
+            raise ValueError("vote_top3_batch: proposals_per_query must be non-negative and sum to the number of proposal rows")
+        seg = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+    if seg.numel() != q + 1 or (n and cls_prop.shape[1] != d):
+        raise ValueError("vote_top3_batch: one segment per reference row, and one feature width")
+    out = {"scores": torch.empty(n, device=dev, dtype=torch.float32), "slot_scores": torch.empty(q, 3, device=dev, dtype=torch.float32),
+           "slot_index": torch.empty(q, 3, device=dev, dtype=torch.int64), "pair_row": torch.empty(3 * q, device=dev, dtype=torch.int32),
+           "pair_live": torch.empty(3 * q, device=dev, dtype=torch.uint8), "seg": seg}
+    with on_device_of(cls_ref):
+        check(_lib.lib().pope_vote_top3_batch_f32(ptr(cls_ref), ptr(cls_prop), ptr(seg), q, n, d, float(eps), ptr(out["scores"]),
+                                                  ptr(out["slot_scores"]), ptr(out["slot_index"]), ptr(out["pair_row"]),
+                                                  ptr(out["pair_live"]), stream_of(dev)), "pope_vote_top3_batch_f32")
+    return out
+
+
+def slot_tally(m_bids, mconf, mkpts0_f, mkpts1_f, pair_live, conf_thr=0.9):
+    """The matches a `Matcher` call over 3 Q pairs published (pair 3 q + s = slot s of query q) -> per-slot counts, the best
+    slot of every query and its matches compacted for `estimate_pose_batch` (pope_slot_tally_f32), all on the device.
+    Returns pair_begin / pair_count [3 Q] int32, matching_score [Q, 3] int64, best_slot / best_count [Q] int32 and
+    best_kpts0 / best_kpts1 [M, 2] (each query's best-slot matches at the exclusive scan of best_count)."""
+    require_cuda(m_bids, "slot_tally")
+    if m_bids.dtype != torch.int64 or pair_live.dtype != torch.uint8:
+        raise TypeError("slot_tally: m_bids is int64 (as the Matcher publishes it), pair_live uint8")
+    dev = m_bids.device
+    m_bids, pair_live = m_bids.contiguous(), pair_live.to(dev).contiguous()
+    mconf, mk0, mk1 = _f32c(mconf, "slot_tally"), _f32c(mkpts0_f, "slot_tally"), _f32c(mkpts1_f, "slot_tally")
+    m = int(m_bids.numel())
+    if pair_live.numel() % 3 or mconf.numel() != m or mk0.shape != (m, 2) or mk1.shape != (m, 2):
+        raise ValueError("slot_tally: m_bids / mconf [M], mkpts0_f / mkpts1_f [M, 2], pair_live [3 Q]")
+    q = pair_live.numel() // 3
+    new = torch.zeros if m == 0 else torch.empty      # without matches nothing is launched: the empty tally is all zeros
+    out = {"pair_begin": new(3 * q, device=dev, dtype=torch.int32), "pair_count": new(3 * q, device=dev, dtype=torch.int32),
+           "matching_score": new(q, 3, device=dev, dtype=torch.int64), "best_slot": new(q, device=dev, dtype=torch.int32),
+           "best_count": new(q, device=dev, dtype=torch.int32), "best_kpts0": torch.empty(m, 2, device=dev, dtype=torch.float32),
+           "best_kpts1": torch.empty(m, 2, device=dev, dtype=torch.float32)}
+    with on_device_of(m_bids):
+        check(_lib.lib().pope_slot_tally_f32(ptr(m_bids), ptr(mconf), ptr(mk0), ptr(mk1), ptr(pair_live), q, m, float(conf_thr),
+                                             *[ptr(out[k]) for k in ("pair_begin", "pair_count", "matching_score", "best_slot",
+                                                                     "best_count", "best_kpts0", "best_kpts1")], stream_of(dev)),
+              "pope_slot_tally_f32")
+    return out
