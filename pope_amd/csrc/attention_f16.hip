@@ -23,18 +23,15 @@
 // maximum / rescale 0.03): with ONE MFMA per product a wave reads the whole K and V tile (16 KB) for 16 MFMAs — 128 KB per tile
 // and CU, ~1 500 LDS cycles against 1 024 MFMA cycles per SIMD — and the eight waves run their phases in lock step behind the
 // per-tile barrier.  The way out is 64 queries per wave (NQ = 2), which does not fit 256 registers next to two score buffers.
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 #include <type_traits>
 
 namespace {
+using namespace pope_attn;
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
-constexpr int HD = 64, KT = 64;
 constexpr int WAVES = 8, NQ = 1;                        // waves per workgroup, 32-query blocks per wave
 // NQ = 2 with four waves (one per SIMD, 512 registers: every K / V fragment feeds two MFMAs, half the LDS reads) was built and
 // measured: 0.39 ms against 0.32 at the ViT-L/14 shape — and wrong: at that register pressure the allocator moves the outputs of
@@ -42,19 +39,15 @@ constexpr int WAVES = 8, NQ = 1;                        // waves per workgroup, 
 // their destinations stay put, i.e. well below the register limit.
 static_assert(NQ == 1 && WAVES == 8, "see above");
 constexpr int QB = 32 * NQ * WAVES, NT = 64 * WAVES;    // 256 queries per workgroup
-constexpr int KST = 72, VST = 96;                       // halves per LDS row: 144 B (9 pieces), 192 B (12 pieces)
+static_assert(KST == 9 * 8 && VST == 12 * 8, "LDS rows of 9 (K) and 12 (V) 16-byte pieces: the staging below");
 constexpr int K_BYTES = KT * KST * 2, V_BYTES = KT * VST * 2, STAGE_BYTES = K_BYTES + V_BYTES;   // 9 216 + 12 288
 constexpr int NST = 4;
-constexpr int OST = 68;                                 // epilogue staging row (floats)
 constexpr size_t F16_ATTN_LDS = size_t(NST) * STAGE_BYTES;   // 86 016 B
 static_assert(size_t(32) * WAVES * OST * sizeof(float) <= F16_ATTN_LDS, "epilogue staging fits the stages");
 static_assert(K_BYTES % 1024 == 0 && V_BYTES % 1024 == 0, "whole 1 KB staging instructions per plane");
 constexpr int KBLK = K_BYTES / 1024, VBLK = V_BYTES / 1024;   // 9 + 12 = 21 wave-instructions per tile
 constexpr int NDMA = (KBLK + VBLK + WAVES - 1) / WAVES;       // six per wave (the three slots past the end repeat blocks 0..2)
 
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f16x8 cat(f16x4 a, f16x4 b) { return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-__device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 // workgroup barrier that leaves LDS-direct loads in flight (the waits are explicit at the call sites); the empty asm statements
 // keep the compiler from moving LDS accesses across it
 __device__ __forceinline__ void raw_barrier() {
@@ -70,9 +63,8 @@ __global__ __launch_bounds__(NT, 2) void attn_f16_dma_kernel(const _Float16* __r
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int n_qb = (N + QB - 1) / QB;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);   // query blocks of one (image, head) share an XCD's L2
-    const int bh = logical / n_qb, head = bh % heads, b = bh / heads, q0 = (logical - bh * n_qb) * QB;
+    const Block blk = decode_block(N, heads, QB);
+    const int head = blk.head, b = blk.b, q0 = blk.q0;
     const int D = heads * HD, rs = 3 * D;                    // row of the qkv tensor, in halves
     const _Float16* base = qkv + size_t(b) * N * rs;
 
@@ -119,8 +111,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f16_dma_kernel(const _Float16* __r
     // under the score MFMAs of tile t + 1, the K fragments of tile t + 2 under the P.V MFMAs of tile t.
     const unsigned lds_base = unsigned(size_t((lds_void_ptr)lds));
     const unsigned k_addr = lds_base + unsigned(r * KST + 8 * h) * 2u;
-    // ds_read_b64_tr_b16 (attention_f16x3.hip): within a 16-lane group, lane 4q + p supplies row q, columns 4p..4p+3 of a 4-key x
-    // 16-d block and lane i receives column i (its d) of the 4 keys
+    // = tr_off(lane, h) of attention_common.h in bytes, written out (through the helper the compiler schedules this kernel differently)
     const unsigned tr_addr = lds_base + unsigned((4 * h + ((lane & 15) >> 2)) * VST + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2u;
     f16x8 kreg[4][2];                 // K fragments of the tile whose scores are formed next: [kg][key half]
     struct VFrag { s16x4 a, c; };
@@ -170,6 +161,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f16_dma_kernel(const _Float16* __r
     using P1 = std::integral_constant<int, 1>;
     const int nkt = (N + KT - 1) / KT;
 
+    // pope_attn::mask_tail written out, as tr_addr above
     auto mask_tail = [&](int kt, f32x16& d0, f32x16& d1) {   // padded keys of the last tile
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -365,13 +357,10 @@ static_assert(K_PLANES_ACT_SCALE == 8.0f, "attention f16 epilogue scale");
 
 // qkv: f16 [B * N, 3 * heads * 64] with q pre-scaled (EPI_QKV_F16); out: f16 [B * N, heads * 64], value * 8
 int pope_launch_attention_f16_dma(const void* qkv_f16, void* out_f16, int B, int N, int heads, hipStream_t stream) {
-    if (!qkv_f16 || !out_f16 || B <= 0 || N <= 0 || heads <= 0 || size_t(B) * heads * ((N + QB - 1) / QB) > 0x7fffffffull) return POPE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(qkv_f16) & 15) || (reinterpret_cast<uintptr_t>(out_f16) & 15)) return POPE_ERR_ARG;
-    if (size_t(N + KT) * 3 * heads * HD * 2 >= (size_t(1) << 32) - 512) return POPE_ERR_ARG;
-    const dim3 grid(unsigned((N + QB - 1) / QB) * heads * B);
-    static pope_dev_mask lds_ok{0};
-    if (!pope_opt_in_lds(attn_f16_dma_kernel, F16_ATTN_LDS, lds_ok)) return POPE_ERR_LAUNCH;
-    hipLaunchKernelGGL(attn_f16_dma_kernel, grid, dim3(NT), F16_ATTN_LDS, stream, static_cast<const _Float16*>(qkv_f16),
-                       static_cast<_Float16*>(out_f16), N, heads);
-    return pope_check_launch();
+    // the stricter extent bound, N + KT rows and 512 bytes of margin: the padding pieces of the LDS-direct loads fetch from
+    // offset 0xFFFFFF00, which has to stay beyond the extent of every tile
+    unsigned grid;
+    if (!args_ok(B, N, heads, QB, 2, KT, 512, qkv_f16, out_f16, &grid)) return POPE_ERR_ARG;
+    return pope_launch_lds<attn_f16_dma_kernel>(dim3(grid), dim3(NT), F16_ATTN_LDS, stream, static_cast<const _Float16*>(qkv_f16),
+                                                static_cast<_Float16*>(out_f16), N, heads);
 }

@@ -2,272 +2,16 @@
 // ("f16x3": x = hi + lo, three v_mfma_f32_32x32x16_f16 per product block, fp32 accumulate).
 // Same contract as attention_f32.hip (attention.py:49-62: qkv[B,N,3,H,64] fp32 -> out[B,N,H*64]
 // fp32), same orientation: S^T = K.Q^T (16 keys of one query per lane), O^T += V^T.P^T with the
-// score registers converted in place into the B operand of the second product.
+// score registers converted in place into the B operand of the second product; also with qkv and / or out as f16 hi/lo
+// planes (the whole-model f16x3 dataflow).
 //
 // Why: on gfx950 the f32 MFMA runs on the VALU lanes (157 TF/s, softmax VALU work is paid in full
-// on top); the f16 MFMA has 16x the rate on a separate pipe, so 3 MFMAs per product are 5.3x faster
-// and the softmax overlaps.  Accuracy: hi+lo carries 22 significand bits; Q is pre-scaled to the
-// log2 domain, P is computed as 2^(s - m + 10) (the 2^10 cancels in O / l) so that every probability
-// down to 1e-4 keeps a normal-range lo half; measured error of the output is at the level of the
-// fp32 chain (tests/test_gpu_ops.py).  Range contract: |q|,|k|,|v| < 65504.
-#include "common.h"
-#include "kernels.h"
-#include <cstdlib>
-#include <type_traits>
-
-namespace {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-constexpr int HD = 64, KT = 64;
-constexpr int WAVES = 8;          // 8 waves x 32 queries share each K/V tile: half the L2 -> LDS traffic and half the
-constexpr int QB = 32 * WAVES;    // per-wave K/V split work of a 4-wave block (the kernel is L2-bandwidth sensitive)
-constexpr int NT = 64 * WAVES;
-constexpr int KST = 72;   // K plane row stride (halves): 144 B = 9 x 16 B (odd) -> ds_read_b128 rows conflict-free
-constexpr int VST = 96;   // V plane row stride (halves): 192 B -> the 4 rows of a ds_read_b64_tr_b16 block hit disjoint banks
-// + 32 halves: the lo plane starts 16 banks after the hi plane, so the eight lanes that copy one 128-byte planes chunk
-// (4 hi pieces + 4 lo pieces) into LDS hit 32 different store banks (without it: a 2-way conflict on every ds_write_b128)
-constexpr int K_PLANE = KT * KST + 32, V_PLANE = KT * VST + 32;
-constexpr size_t X3_ATTN_STAGE_BYTES = size_t(2) * (K_PLANE + V_PLANE) * sizeof(_Float16);  // 43 008 B
-constexpr int OST = 68;   // epilogue staging row (floats)
-constexpr size_t X3_ATTN_EPI_BYTES = size_t(32) * 8 * OST * sizeof(float);  // O^T transpose staging, 32 rows per wave
-
-
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void split4(f32x4 v, f16x4& hi, f16x4& lo) { pope_split4(v, hi, lo); }  // common.h
-__device__ __forceinline__ f16x8 cat(f16x4 a, f16x4 b) { return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-// OUT_PLANES: write the output as f16 hi/lo activation planes (pope_hip.h layout, scale 8) for the
-// f16x3 proj GEMM instead of fp32.
-// (POPE_PREC_F16's single-product attention lives in attention_f16.hip since round 4.)
-template <bool OUT_PLANES>
-__global__ __launch_bounds__(NT, 2) void attn_f16x3_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                             int N, int heads) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    _Float16* Kh = reinterpret_cast<_Float16*>(smem);
-    _Float16* Kl = Kh + K_PLANE;
-    _Float16* Vh = Kl + K_PLANE;
-    _Float16* Vl = Vh + V_PLANE;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int n_qb = (N + QB - 1) / QB;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);  // query blocks of one (image, head) share an XCD's L2
-    const int bh = logical / n_qb, head = bh % heads, b = bh / heads, q0 = (logical - bh * n_qb) * QB;
-    const int D = heads * HD, rs = 3 * D;
-    const float* base = qkv + size_t(b) * N * rs;
-    const int koff = D + head * HD;
-
-    // Q^T fragments (B operand of S^T = K.Q^T): lane (r,h) holds Q[q = r][d = 16kg + 8h + j], scaled by
-    // head_dim^-0.5 * log2(e) so that the scores leave the MFMA in the log2 domain.
-    constexpr float QSCALE = 0.125f * 1.44269504088896340736f;
-    f16x8 qh[4], ql[4];
-    {
-        const int qrow = q0 + wave * 32 + r;
-#pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-            f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
-            if (qrow < N) {
-                const float* p = base + size_t(qrow) * rs + head * HD + 16 * kg + 8 * h;
-                v0 = *reinterpret_cast<const f32x4*>(p);
-                v1 = *reinterpret_cast<const f32x4*>(p + 4);
-            }
-            f16x4 h0, l0, h1, l1;
-            split4(v0 * QSCALE, h0, l0);
-            split4(v1 * QSCALE, h1, l1);
-            qh[kg] = cat(h0, h1);
-            ql[kg] = cat(l0, l1);
-        }
-    }
-
-    // K/V staging: bounds-checked buffer loads (keys >= N read as zeros), split into hi/lo planes on
-    // the way into LDS (row-major [key][d]; V is consumed through the transposing LDS read).
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, unsigned(N) * unsigned(rs) * 4u, 0x00020000);
-    constexpr int RPP = NT / 16, NP = KT / RPP;  // staging rows per pass, passes per 64-key tile
-    const int srow = tid >> 4, scol = (tid & 15) * 4;
-    unsigned kvoff[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) kvoff[i] = (unsigned(srow + RPP * i) * unsigned(rs) + scol + koff) * 4u;
-    const unsigned tile_bytes = unsigned(KT) * unsigned(rs) * 4u, v_delta = unsigned(D) * 4u;
-    f32x4 rk[NP], rv[NP];
-    auto load_kv = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            rk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, kvoff[i], kt * tile_bytes, 0));
-            rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, kvoff[i] + v_delta, kt * tile_bytes, 0));
-        }
-    };
-    auto store_kv = [&]() {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            f16x4 hi, lo;
-            split4(rk[i], hi, lo);
-            *reinterpret_cast<f16x4*>(Kh + (srow + RPP * i) * KST + scol) = hi;
-            *reinterpret_cast<f16x4*>(Kl + (srow + RPP * i) * KST + scol) = lo;
-            split4(rv[i], hi, lo);
-            *reinterpret_cast<f16x4*>(Vh + (srow + RPP * i) * VST + scol) = hi;
-            *reinterpret_cast<f16x4*>(Vl + (srow + RPP * i) * VST + scol) = lo;
-        }
-    };
-
-    // ds_read_b64_tr_b16 addressing for the V^T fragments (A operand of O^T += V^T.P^T): within a
-    // 16-lane group, lane 4q+p supplies row q, columns 4p..4p+3 of a 4-key x 16-d block and lane i
-    // receives column i (its d) of the 4 keys.  Block of lane l: keys 4*(l>>5) + q (+16s +8 +32u),
-    // d columns 16*((l>>4)&1) + 4p (+32dt).
-    const int tr_off = (4 * h + ((lane & 15) >> 2)) * VST + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    auto vfrag = [&](const _Float16* plane, int u, int s, int dt) {
-        const _Float16* p = plane + tr_off + (32 * u + 16 * s) * VST + 32 * dt;
-        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-        const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 8 * VST));
-        return cat(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, c));
-    };
-
-    f32x16 o0, o1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { o0[i] = 0.f; o1[i] = 0.f; }
-    float m_run = -INFINITY;   // running max (log2 domain)
-    f32x2 l_run = {0.f, 0.f};  // running sum of 2^10-scaled probabilities, two partial lanes
-
-    auto tile = [&](int kt, auto last_tag) {
-        constexpr bool LAST = decltype(last_tag)::value;
-        if (kt) __syncthreads();  // every wave is done with the previous K/V stage
-        store_kv();
-        __syncthreads();
-        if constexpr (!LAST) load_kv(kt + 1);
-
-        // ---- S^T = K . Q^T, two 32-key sub-tiles, 3 MFMAs per 16-wide d step --------------------
-        f32x16 s0, s1;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s0[i] = 0.f; s1[i] = 0.f; }
-        const _Float16* kb_h = Kh + r * KST + 8 * h;
-        const _Float16* kb_l = Kl + r * KST + 8 * h;
-#pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-            const f16x8 k0h = *reinterpret_cast<const f16x8*>(kb_h + 16 * kg);
-            const f16x8 k1h = *reinterpret_cast<const f16x8*>(kb_h + 32 * KST + 16 * kg);
-            const f16x8 k0l = *reinterpret_cast<const f16x8*>(kb_l + 16 * kg);
-            const f16x8 k1l = *reinterpret_cast<const f16x8*>(kb_l + 32 * KST + 16 * kg);
-            s0 = mfma_f16(k0l, qh[kg], s0);
-            s1 = mfma_f16(k1l, qh[kg], s1);
-            s0 = mfma_f16(k0h, ql[kg], s0);
-            s1 = mfma_f16(k1h, ql[kg], s1);
-            s0 = mfma_f16(k0h, qh[kg], s0);
-            s1 = mfma_f16(k1h, qh[kg], s1);
-        }
-        if constexpr (LAST) {  // mask the padded keys of the last tile
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = kt * KT + mfma32_row(i, h);
-                if (key >= N) s0[i] = -INFINITY;
-                if (key + 32 >= N) s1[i] = -INFINITY;
-            }
-        }
-        // ---- online softmax in registers (log2 domain; p' = 2^(s - m + 10)) ------------------------
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(s0), "+v"(s1));  // XDL write -> asm VALU read wait states
-        float mt = vmax3(s0[0], s1[0], s0[1]);
-#pragma unroll
-        for (int i = 1; i < 15; ++i) mt = vmax3(mt, s1[i], s0[i + 1]);
-        mt = vmax3(mt, s1[15], s1[15]);
-        mt = __builtin_fmaxf(mt, __shfl_xor(mt, 32));
-        const float m_new = __builtin_fmaxf(m_run, mt);
-        if (__any(m_new > m_run)) {  // rescale only when some row's max moved (exact: alpha == 1 otherwise)
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run = l_run * alpha;
-            o0 *= alpha;
-            o1 *= alpha;
-        }
-        m_run = m_new;
-        const float mshift = m_new - 10.0f;
-        f32x2 ls = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            s0[i] = __builtin_amdgcn_exp2f(s0[i] - mshift);
-            s0[i + 1] = __builtin_amdgcn_exp2f(s0[i + 1] - mshift);
-            s1[i] = __builtin_amdgcn_exp2f(s1[i] - mshift);
-            s1[i + 1] = __builtin_amdgcn_exp2f(s1[i + 1] - mshift);
-            ls += f32x2{s0[i], s0[i + 1]} + f32x2{s1[i], s1[i + 1]};
-        }
-        l_run += ls;
-
-        // ---- O^T += V^T . P^T: score registers 8s..8s+7 of sub-tile u are the B fragment of k-step (u,s)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f32x4 p0, p1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    p0[e] = (u ? s1 : s0)[8 * s + e];
-                    p1[e] = (u ? s1 : s0)[8 * s + 4 + e];
-                }
-                f16x4 h0, l0, h1, l1;
-                split4(p0, h0, l0);
-                split4(p1, h1, l1);
-                const f16x8 ph = cat(h0, h1), pl = cat(l0, l1);
-                const f16x8 v0h = vfrag(Vh, u, s, 0), v0l = vfrag(Vl, u, s, 0);
-                const f16x8 v1h = vfrag(Vh, u, s, 1), v1l = vfrag(Vl, u, s, 1);
-                o0 = mfma_f16(v0l, ph, o0);
-                o1 = mfma_f16(v1l, ph, o1);
-                o0 = mfma_f16(v0h, pl, o0);
-                o1 = mfma_f16(v1h, pl, o1);
-                o0 = mfma_f16(v0h, ph, o0);
-                o1 = mfma_f16(v1h, ph, o1);
-            }
-    };
-
-    const int nkt = (N + KT - 1) / KT;
-    load_kv(0);
-    for (int kt = 0; kt + 1 < nkt; ++kt) tile(kt, std::false_type{});
-    tile(nkt - 1, std::true_type{});
-    __syncthreads();  // the stage is free: reuse it for the O^T transpose
-
-    // Normalise (the 2^10 of p' cancels), transpose O^T through LDS, store whole 256-B head rows.
-    const float l_half = l_run[0] + l_run[1];
-    const float inv = 1.0f / (l_half + __shfl_xor(l_half, 32));
-    float* Os = smem + (wave * 32) * OST;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-        f32x4 a, c;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { a[e] = o0[4 * g4 + e] * inv; c[e] = o1[4 * g4 + e] * inv; }
-        *reinterpret_cast<f32x4*>(&Os[r * OST + 8 * g4 + 4 * h]) = a;
-        *reinterpret_cast<f32x4*>(&Os[r * OST + 32 + 8 * g4 + 4 * h]) = c;
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int lr = (lane >> 4) + 4 * i, c4 = (lane & 15) * 4;
-        const int qrow = q0 + wave * 32 + lr;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(&Os[lr * OST + c4]);
-        if (qrow < N) {
-            if constexpr (OUT_PLANES) {
-                f16x4 hi, lo;
-                split4(v * 8.0f, hi, lo);  // K_PLANES_ACT_SCALE
-                const int col = head * HD + c4;
-                _Float16* o = reinterpret_cast<_Float16*>(out) + (size_t(b) * N + qrow) * 2 * D + (col >> 5) * 64 + (col & 31);
-                *reinterpret_cast<f16x4*>(o) = hi;
-                *reinterpret_cast<f16x4*>(o + 32) = lo;
-            } else {
-                *reinterpret_cast<f32x4*>(out + (size_t(b) * N + qrow) * D + head * HD + c4) = v;
-            }
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------
-// Software-pipelined variant.  Measured on gfx950 (scripts/overlap16_lab.hip): an f16 MFMA phase of one wave
+// on top); the f16 MFMA has 16x the rate on a separate pipe, so 3 MFMAs per product are 5.3x faster.
+// Accuracy: hi+lo carries 22 significand bits; Q is pre-scaled to the log2 domain, P is computed as 2^(s - ref) against a
+// lazy reference (below) that keeps every probability's lo half in the normal range; measured error of the output is at the
+// level of the fp32 chain (tests/test_gpu_ops.py).  Range contract: |q|,|k|,|v| < 65504.
+//
+// Software pipeline.  Measured on gfx950 (scripts/overlap16_lab.hip): an f16 MFMA phase of one wave
 // does NOT overlap a VALU phase of another wave on the same SIMD (2 or 4 waves per SIMD, any priorities or start
 // skews: the phases add up), but VALU instructions placed BETWEEN the MFMAs of the same wave cost about 2 cycles
 // each instead of 4+ (t ~ 32 + 2 n cycles per MFMA with n VALU ops behind it).  So the only way to hide the
@@ -277,6 +21,25 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_kernel(const float* __restri
 // tile t+2 is written (under the P.V MFMAs) into the stage nobody reads during iteration t, so an iteration has
 // ONE workgroup barrier and no store-only bubble (with two stages: barrier, store, barrier = 17 % of an iteration
 // with the matrix pipe idle).  One workgroup of 8 waves per CU (256 registers per wave at 2 waves per SIMD).
+#include "attention_common.h"
+#include "kernels.h"
+#include <type_traits>
+
+namespace {
+using namespace pope_attn;
+
+typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
+
+constexpr int WAVES = 8;          // 8 waves x 32 queries share each K/V tile: half the L2 -> LDS traffic and half the
+constexpr int QB = 32 * WAVES;    // per-wave K/V split work of a 4-wave block (the kernel is L2-bandwidth sensitive)
+constexpr int NT = 64 * WAVES;
+// + 32 halves: the lo plane starts 16 banks after the hi plane, so the eight lanes that copy one 128-byte planes chunk
+// (4 hi pieces + 4 lo pieces) into LDS hit 32 different store banks (without it: a 2-way conflict on every ds_write_b128)
+constexpr int K_PLANE = KT * KST + 32, V_PLANE = KT * VST + 32;
+constexpr size_t X3_ATTN_EPI_BYTES = size_t(32) * WAVES * OST * sizeof(float);  // O^T transpose staging, 32 rows per wave
+
+__device__ __forceinline__ void split4(f32x4 v, f16x4& hi, f16x4& lo) { pope_split4(v, hi, lo); }  // common.h
+
 #ifdef ATTN_STAMPS  // dev: per-iteration cycle stamps of block 300, wave 0 (scripts/attn_stamps.py)
 __device__ unsigned long long g_attn_dbg[32 * 8];
 #define ATTN_STAMP(t, slot)                                                                                     \
@@ -291,7 +54,7 @@ __device__ unsigned long long g_attn_dbg[32 * 8];
 // spilled registers and 6 % (0.644 -> 0.685 ms, measured) — the loop sits at 256 VGPRs with zero slack.
 __device__ unsigned long long g_attn_exact_passes;
 constexpr int STAGE_H = 2 * (K_PLANE + V_PLANE);  // halves per K/V stage (Kh | Kl | Vh | Vl)
-constexpr size_t X3_ATTN_PIPE_BYTES = size_t(3) * STAGE_H * sizeof(_Float16);  // 129 024 B: three stages, see below
+constexpr size_t X3_ATTN_PIPE_BYTES = size_t(3) * STAGE_H * sizeof(_Float16);  // 129 024 B: three stages, see above
 static_assert(X3_ATTN_PIPE_BYTES >= X3_ATTN_EPI_BYTES, "epilogue staging fits the stages");
 
 // IN_PLANES: qkv is the planes tensor the QKV GEMM's epilogue writes (pope_hip.h layout, scale 8): K/V rows go to
@@ -305,9 +68,8 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
-    const int n_qb = (N + QB - 1) / QB;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = logical / n_qb, head = bh % heads, b = bh / heads, q0 = (logical - bh * n_qb) * QB;
+    const Block blk = decode_block(N, heads, QB);
+    const int head = blk.head, b = blk.b, q0 = blk.q0;
     const int D = heads * HD, rs = 3 * D;
     const float* base = qkv + size_t(b) * N * rs;
     const int koff = D + head * HD;
@@ -411,9 +173,9 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
         *reinterpret_cast<u32x4*>(S) = regs[c];
     };
 
-    const int tr_off = (4 * h + ((lane & 15) >> 2)) * VST + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const int v_off = tr_off(lane, h);
     auto vfrag = [&](const _Float16* plane, int u, int s, int dt) {
-        const _Float16* p = plane + tr_off + (32 * u + 16 * s) * VST + 32 * dt;
+        const _Float16* p = plane + v_off + (32 * u + 16 * s) * VST + 32 * dt;
         const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
         const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 8 * VST));
         return cat(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, c));
@@ -451,14 +213,6 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
         if (j == 3) d1 = mfma_f16(f.k1h, ql[kg], d1);
         if (j == 4) d0 = mfma_f16(f.k0h, qh[kg], d0);
         if (j == 5) d1 = mfma_f16(f.k1h, qh[kg], d1);
-    };
-    auto mask_tail = [&](int kt, f32x16& d0, f32x16& d1) {  // padded keys of the last tile
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = kt * KT + mfma32_row(i, h);
-            if (key >= N) d0[i] = -INFINITY;
-            if (key + 32 >= N) d1[i] = -INFINITY;
-        }
     };
     // Online softmax of (c0, c1) with a LAZY reference (log2 domain): p' = 2^(s - ref), where ref = (the row maximum
     // as of the last advance) - 8, not this tile's.  On gfx950 every VALU instruction issued between the MFMAs takes
@@ -659,7 +413,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
             for (int j = 0; j < 6; ++j) qk_step(kg, j, kf, sb[0][0], sb[0][1], std::false_type{});
         }
     }
-    if (nkt == 1) mask_tail(0, sb[0][0], sb[0][1]);
+    if (nkt == 1) mask_tail(0, h, N, sb[0][0], sb[0][1]);
     if constexpr (IN_PLANES) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) write_chunk(1, c, pb);
@@ -706,7 +460,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
         using Q = std::integral_constant<int, P ^ 1>;
         if (t + 1 < nkt) {  // second-to-last tile: S^T of the last tile needs the key mask
             phase1(st_next, ptag);
-            mask_tail(t + 1, sb[P ^ 1][0], sb[P ^ 1][1]);
+            mask_tail(t + 1, h, N, sb[P ^ 1][0], sb[P ^ 1][1]);
             asm volatile("" : "+v"(sb[P ^ 1][0]), "+v"(sb[P ^ 1][1]));
             settle();
             phase2(st_cur, st_write, std::false_type{}, pa, ptag, std::true_type{});   // look-ahead over the masked scores
@@ -769,18 +523,6 @@ __global__ __launch_bounds__(NT, 2) void attn_f16x3_pipe_kernel(const float* __r
 
 static_assert(K_PLANES_ACT_SCALE == 8.0f, "attention planes epilogue scale");
 
-template <bool OUT_PLANES>
-static int launch_attn_x3(const float* qkv, float* out, int B, int N, int heads, hipStream_t stream) {
-    if (B <= 0 || N <= 0 || heads <= 0 || size_t(B) * heads * ((N + QB - 1) / QB) > 0x7fffffffull) return POPE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return POPE_ERR_ARG;
-    if (size_t(N) * 3 * heads * HD * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
-    const dim3 grid(unsigned((N + QB - 1) / QB) * heads * B);
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(attn_f16x3_pipe_kernel<OUT_PLANES, false>, X3_ATTN_PIPE_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
-    hipLaunchKernelGGL((attn_f16x3_pipe_kernel<OUT_PLANES, false>), grid, dim3(NT), X3_ATTN_PIPE_BYTES, stream, qkv, out, N, heads);
-    return pope_check_launch();
-}
-
 #ifdef ATTN_STAMPS
 extern "C" int pope_lab_attn_stamps(unsigned long long* host256) {
     return hipMemcpyFromSymbol(host256, HIP_SYMBOL(g_attn_dbg), sizeof(unsigned long long) * 256) == hipSuccess ? 0 : -1;
@@ -788,40 +530,34 @@ extern "C" int pope_lab_attn_stamps(unsigned long long* host256) {
 #endif
 
 int pope_launch_attention_f16x3(const float* qkv, float* out, int B, int N, int heads, hipStream_t stream) {
-    return launch_attn_x3<false>(qkv, out, B, N, heads, stream);
+    unsigned grid;
+    if (!args_ok(B, N, heads, QB, 4, 0, 0, qkv, out, &grid)) return POPE_ERR_ARG;
+    return pope_launch_lds<attn_f16x3_pipe_kernel<false, false>>(dim3(grid), dim3(NT), X3_ATTN_PIPE_BYTES, stream, qkv, out, N, heads);
 }
-// the diagnostic twin of pope_launch_attention_f16x3_planes_io: same results, counts exact passes (slower: see above)
-int pope_launch_attention_f16x3_planes_io_diag(const void* qkv_planes, void* out_planes, int B, int N, int heads, long long* exact_passes_host,
-                                               hipStream_t stream) {
-    if (B <= 0 || N <= 0 || heads <= 0 || ((heads * HD) & 31) || size_t(B) * heads * ((N + QB - 1) / QB) > 0x7fffffffull) return POPE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(qkv_planes) & 15) || (reinterpret_cast<uintptr_t>(out_planes) & 15) || !exact_passes_host) return POPE_ERR_ARG;
-    if (size_t(N) * 3 * heads * HD * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
-    const dim3 grid(unsigned((N + QB - 1) / QB) * heads * B);
-    static pope_dev_mask lds_ok{0};
-    if (!pope_opt_in_lds(attn_f16x3_pipe_kernel<true, true, true>, X3_ATTN_PIPE_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
+
+// planes in, planes out (a planes row takes the bytes of its fp32 row).  exact_passes_host: null = the product kernel;
+// otherwise its diagnostic twin: same results, counts exact passes into *exact_passes_host and synchronises (slower: see above)
+static int launch_attn_x3_planes(const void* qkv_planes, void* out_planes, int B, int N, int heads, long long* exact_passes_host,
+                                 hipStream_t stream) {
+    unsigned grid;
+    if (!args_ok(B, N, heads, QB, 4, 0, 0, qkv_planes, out_planes, &grid)) return POPE_ERR_ARG;
+    const float* qkv = static_cast<const float*>(qkv_planes);
+    float* out = static_cast<float*>(out_planes);
+    if (!exact_passes_host)
+        return pope_launch_lds<attn_f16x3_pipe_kernel<true, true>>(dim3(grid), dim3(NT), X3_ATTN_PIPE_BYTES, stream, qkv, out, N, heads);
     unsigned long long v = 0;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_exact_passes), &v, sizeof(v)) != hipSuccess) return POPE_ERR_LAUNCH;
-    hipLaunchKernelGGL((attn_f16x3_pipe_kernel<true, true, true>), grid, dim3(NT), X3_ATTN_PIPE_BYTES, stream,
-                       static_cast<const float*>(qkv_planes), static_cast<float*>(out_planes), N, heads);
-    if (pope_check_launch() || hipStreamSynchronize(stream) != hipSuccess) return POPE_ERR_LAUNCH;
+    if (pope_launch_lds<attn_f16x3_pipe_kernel<true, true, true>>(dim3(grid), dim3(NT), X3_ATTN_PIPE_BYTES, stream, qkv, out, N, heads) ||
+        hipStreamSynchronize(stream) != hipSuccess)
+        return POPE_ERR_LAUNCH;
     if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_attn_exact_passes), sizeof(v)) != hipSuccess) return POPE_ERR_LAUNCH;
     *exact_passes_host = (long long)v;
     return POPE_OK;
 }
 int pope_launch_attention_f16x3_planes_io(const void* qkv_planes, void* out_planes, int B, int N, int heads, hipStream_t stream) {
-    if (B <= 0 || N <= 0 || heads <= 0 || ((heads * HD) & 31) || size_t(B) * heads * ((N + QB - 1) / QB) > 0x7fffffffull) return POPE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(qkv_planes) & 15) || (reinterpret_cast<uintptr_t>(out_planes) & 15)) return POPE_ERR_ARG;
-    if (size_t(N) * 3 * heads * HD * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
-    const dim3 grid(unsigned((N + QB - 1) / QB) * heads * B);
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(attn_f16x3_pipe_kernel<true, true>, X3_ATTN_PIPE_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
-    hipLaunchKernelGGL((attn_f16x3_pipe_kernel<true, true>), grid, dim3(NT), X3_ATTN_PIPE_BYTES, stream,
-                       static_cast<const float*>(qkv_planes), static_cast<float*>(out_planes), N, heads);
-    return pope_check_launch();
+    return launch_attn_x3_planes(qkv_planes, out_planes, B, N, heads, nullptr, stream);
 }
-
-
-int pope_launch_attention_f16x3_planes(const float* qkv, void* out_planes, int B, int N, int heads, hipStream_t stream) {
-    if ((heads * HD) & 31) return POPE_ERR_ARG;
-    return launch_attn_x3<true>(qkv, static_cast<float*>(out_planes), B, N, heads, stream);
+int pope_launch_attention_f16x3_planes_io_diag(const void* qkv_planes, void* out_planes, int B, int N, int heads, long long* exact_passes_host,
+                                               hipStream_t stream) {
+    return exact_passes_host ? launch_attn_x3_planes(qkv_planes, out_planes, B, N, heads, exact_passes_host, stream) : POPE_ERR_ARG;
 }

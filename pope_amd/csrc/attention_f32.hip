@@ -11,27 +11,20 @@
 //   O^T += V^T . P^T -> the S^T accumulator registers ARE the B operand (key index = the
 //                      k of the MFMA, one key per lane half per step); V rows are read from
 //                      LDS with the matching key order; alpha/normaliser are per-lane scalars.
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 #include <type_traits>
 
 namespace {
+using namespace pope_attn;
 
-constexpr int HD = 64;    // head dim (all DINOv2 archs)
-constexpr int KT = 64;    // keys per LDS tile
 constexpr int QB = 128;   // queries per block (4 waves x 32)
-constexpr int ST = 68;    // padded LDS row (floats): 17 x 16 B -> ds_read_b128 conflict-free
+constexpr int ST = OST;   // K/V stage row (floats) = the epilogue's staging row
 // ONE K and ONE V stage (34.8 KB): three workgroups per CU, so every SIMD hosts three waves of
 // independent workgroups whose softmax (VALU) and barrier phases fall under each other's MFMAs.
 constexpr size_t ATTN_LDS_BYTES = size_t(2) * KT * ST * sizeof(float);
 
-// Single-instruction VALU helpers: hipcc would otherwise canonicalise MFMA outputs before fmaxf
-// (one extra v_max per element) and leave most of the packed-f32 forms unused.
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
+// Single-instruction VALU helpers (with vmax3): hipcc leaves most of the packed-f32 forms unused.
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
     f32x2 d;
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
@@ -54,12 +47,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const float* __restric
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
-    // 1-D grid, XCD-aware: the query blocks of one (image, head) get consecutive logical ids, i.e.
-    // run on ONE XCD, so its private L2 serves their K/V re-reads (12 query blocks re-read the
-    // same 784 KB; spread round-robin over the 8 XCDs the fabric saw 4.6x the algorithmic bytes).
-    const int n_qb = (N + QB - 1) / QB;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = logical / n_qb, head = bh % heads, b = bh / heads, q0 = (logical - bh * n_qb) * QB;
+    const Block blk = decode_block(N, heads, QB);   // 12 query blocks of one (image, head) re-read the same 784 KB
+    const int head = blk.head, b = blk.b, q0 = blk.q0;
     const int D = heads * HD, rs = 3 * D;
     const float* base = qkv + size_t(b) * N * rs;
     const int koff = D + head * HD;
@@ -145,14 +134,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const float* __restric
                 s1 = mfma_32x32x2(k1[s], q[j][s], s1);
             }
         }
-        if constexpr (LAST) {  // mask the padded keys of the last tile
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = kt * KT + mfma32_row(i, h);
-                if (key >= N) s0[i] = -INFINITY;
-                if (key + 32 >= N) s1[i] = -INFINITY;
-            }
-        }
+        if constexpr (LAST) mask_tail(kt, h, N, s0, s1);
         if constexpr (!(ABLATE & 1)) {
             // the MFMA results feed inline-asm VALU ops next: cover the XDL-write -> VALU-read wait
             // states ourselves (hipcc pads nothing it cannot see inside an asm statement)
@@ -236,11 +218,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const float* __restric
 }  // namespace
 
 int pope_launch_attention_f32(const float* qkv, float* out, int B, int N, int heads, hipStream_t stream) {
-    if (B <= 0 || N <= 0 || heads <= 0 || size_t(B) * heads * ((N + QB - 1) / QB) > 0x7fffffffull) return POPE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return POPE_ERR_ARG;
-    static pope_dev_mask lds_ok{0};  // per kernel instantiation, per device
-    if (!pope_opt_in_lds(attn_f32_kernel<0>, ATTN_LDS_BYTES, lds_ok)) return POPE_ERR_LAUNCH;
-    const dim3 grid(unsigned((N + QB - 1) / QB) * heads * B);
-    hipLaunchKernelGGL(attn_f32_kernel<0>, grid, dim3(256), ATTN_LDS_BYTES, stream, qkv, out, N, heads);
-    return pope_check_launch();
+    unsigned grid;
+    if (!args_ok(B, N, heads, QB, 4, 0, 0, qkv, out, &grid)) return POPE_ERR_ARG;
+    return pope_launch_lds<attn_f32_kernel<0>>(dim3(grid), dim3(256), ATTN_LDS_BYTES, stream, qkv, out, N, heads);
 }

@@ -165,8 +165,6 @@ int pope_launch_attention_f16_dma(const void* qkv_f16, void* out_f16, int B, int
 // Multi-head softmax attention over qkv[B, N, 3, heads, 64] -> out[B, N, heads*64].
 int pope_launch_attention_f32(const float* qkv, float* out, int B, int N, int heads, hipStream_t stream);
 int pope_launch_attention_f16x3(const float* qkv, float* out, int B, int N, int heads, hipStream_t stream);
-// same, output as activation planes [B*N, heads*64] for the f16x3 proj GEMM
-int pope_launch_attention_f16x3_planes(const float* qkv, void* out_planes, int B, int N, int heads, hipStream_t stream);
 // qkv given as planes (the QKV GEMM epilogue's output), output planes: the whole-model f16x3 dataflow
 int pope_launch_attention_f16x3_planes_io_diag(const void* qkv_planes, void* out_planes, int B, int N, int heads, long long* exact_passes_host,
                                                hipStream_t stream);   // diagnostic twin: counts exact passes, synchronises

@@ -57,6 +57,30 @@ def test_argument_validation_without_gpu(hip_lib):
     assert hip_lib.pope_layernorm_f32(None, None, None, None, 4, 384, 1e-6, None) == -1
     assert hip_lib.pope_linear_f32(None, None, None, None, 1, 1, 4, 0, None, None, None) == -1
     assert hip_lib.pope_attention_f32(None, None, 1, 1, 6, None) == -1
+    # every attention entry shares one argument check; nothing below gets as far as a launch (a null range flag: no scan).
+    # The accepting side of a bound cannot be shown here: a call that passes the check launches.
+    import ctypes
+    buf = ctypes.create_string_buffer(64)
+    ok = (ctypes.addressof(buf) + 15) & ~15          # 16-byte aligned, never dereferenced
+    count = ctypes.c_longlong(0)
+    entries = {
+        "f32": lambda q, o, B, N, H: hip_lib.pope_attention_f32(q, o, B, N, H, None),
+        "prec f32": lambda q, o, B, N, H: hip_lib.pope_attention_prec_f32(q, o, B, N, H, _lib.PREC_F32_MFMA, None, None),
+        "prec f16x3": lambda q, o, B, N, H: hip_lib.pope_attention_prec_f32(q, o, B, N, H, _lib.PREC_F16X3, None, None),
+        "planes": lambda q, o, B, N, H: hip_lib.pope_attention_planes_f32(q, o, B, N, H, None),
+        "planes diag": lambda q, o, B, N, H: hip_lib.pope_attention_planes_diag_f32(q, o, B, N, H, ctypes.byref(count), None),
+        "f16": lambda q, o, B, N, H: hip_lib.pope_attention_f16(q, o, B, N, H, None),
+    }
+    for name, call in entries.items():
+        for q, o in ((None, ok), (ok, None), (ok + 8, ok), (ok, ok + 8)):      # null, not 16-byte aligned
+            assert call(q, o, 1, 64, 6) == -1, (name, q, o)
+        for B, N, H in ((0, 64, 6), (-1, 64, 6), (1, 0, 6), (1, -5, 6), (1, 64, 0), (1, 64, -2)):
+            assert call(ok, ok, B, N, H) == -1, (name, B, N, H)
+        # the qkv image reaches the 32-bit extent of the kernels' buffer descriptor: fp32 and planes rows of 3 * heads * 64 * 4
+        # bytes, N * 12288 >= 2^32 from N = 349526 at 16 heads; f16 rows of half that, N + 64 of them, 512 bytes of margin:
+        # (N + 64) * 6144 >= 2^32 - 512 from N = 698987
+        assert call(ok, ok, 1, 698987 if name == "f16" else 349526, 16) == -1, name
+    assert hip_lib.pope_attention_planes_diag_f32(ok, ok, 1, 64, 6, None, None) == -1    # the diagnostic entry needs its counter
 
 
 def test_streaming_top3_host_matches_oracle(golden_dir):
