@@ -319,7 +319,7 @@ def on_device_of(t):
     """Context manager: make `t`'s GPU the current HIP device around a C-ABI call.  torch hands out the NULL handle
     for every device's default stream, so the stream alone does not name the device (the reference keeps its matcher
     on cuda:1 while cuda:0 is current, pope_model_api.py:181-184); non-default streams are additionally resolved on
-    the C side (capi.hip:StreamDevice)."""
+    the C side (stream_device.h:StreamDevice)."""
     import torch
     return torch.cuda.device(t.device)
 

@@ -1,57 +1,13 @@
-// C ABI (include/pope_hip.h) over the kernel launchers: argument checks, workspace carving and the
-// launch sequence of one DinoVisionTransformer forward.  No allocation, no synchronisation.
+// C ABI (include/pope_hip.h) over the kernel launchers: the device scope of the stream, argument checks and the translation
+// of the public structs into the launchers' parameters.  No allocation, no synchronisation.  (The ViT forward: vit_forward.hip.)
 #include "../../include/pope_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "linear.h"
+#include "stream_device.h"
 #include <cstdlib>
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Every launching entry point runs on the device that owns `stream` (the reference keeps the matcher on cuda:1 while
-// cuda:0 is current, pope_model_api.py:181-184): the launchers' per-device state (LDS opt-in, CU count) and the
-// launches themselves then belong to the right GPU whatever the caller's current device is.  NULL = the current
-// device's default stream.  The previous device is restored on return.
-struct StreamDevice {
-    int prev = -1;
-    bool switched = false;
-    explicit StreamDevice(void* stream) {
-        int dev = -1;
-        if (!stream || hipGetDevice(&prev) != hipSuccess) return;
-        if (hipStreamGetDevice(static_cast<hipStream_t>(stream), &dev) == hipSuccess && dev != prev)
-            switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~StreamDevice() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    StreamDevice(const StreamDevice&) = delete;
-    StreamDevice& operator=(const StreamDevice&) = delete;
-};
-
-// Optional in-situ timing: events[i] is recorded on the stream right before launch i and one more
-// after the last launch, so events[i]..events[i+1] bracket exactly one kernel of the product path.
-// With a kind mask only the selected launches are bracketed: an event is recorded when the coming launch is
-// selected (it starts a bracket) or the previous one was (it closes one); kinds[i] = -1 marks close-only events.
-struct Recorder {
-    void* const* events;
-    int capacity;
-    int* kinds;
-    int n;
-    unsigned mask = ~0u;
-    bool open = false;
-    bool mark(int kind, hipStream_t stream) {
-        if (!events) return true;
-        const bool sel = kind >= 0 && ((mask >> kind) & 1u);
-        if (!sel && !open) return true;
-        if (n >= capacity) return false;
-        if (hipEventRecord(static_cast<hipEvent_t>(events[n]), stream) != hipSuccess) return false;
-        if (kinds) kinds[n] = sel ? kind : -1;
-        open = sel;
-        ++n;
-        return true;
-    }
-};
 
 __global__ __launch_bounds__(256) void cls_cosine_kernel(const float* __restrict__ ref, const float* __restrict__ fea,
                                                           int P, int D, float eps, float* __restrict__ scores) {
@@ -110,13 +66,7 @@ int pope_linear_prec_f32(const float* A, const float* W, const float* bias, floa
     // SwiGLU: fp32 MFMA only here (the f16x3 form is the planes entry below); N = 2 hidden columns in, [M, N / 2] out
     if (swiglu && (precision != POPE_PREC_F32_MFMA || N <= 0 || (N & 63))) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
-    GemmParams g = {};
-    g.A = A; g.W = W; g.bias = bias; g.C = C;
-    g.lda = K; g.ldw = K; g.ldc = swiglu ? N / 2 : N;
-    g.M = M; g.N = N; g.K = K;
-    g.epilogue = epilogue;
-    g.gamma = gamma; g.res = res; g.ldres = N;
-    g.range_flag = range_flag;
+    const GemmParams g = pope_linear_params(LINEAR_F32, A, W, bias, C, nullptr, M, N, K, epilogue, gamma, res, 0, range_flag);
     // shapes the f16x3 kernel does not take (K % 32 != 0) run on the fp32 MFMA: same contract, same results
     if (precision == POPE_PREC_F16X3 && pope_gemm_f16x3_supported(g))
         return pope_launch_gemm_nt_f16x3(g, static_cast<hipStream_t>(stream));
@@ -135,16 +85,8 @@ int pope_linear_planes_f32(const void* a_planes, const void* w_planes, const flo
     if (epilogue < 0 || (epilogue > POPE_EPI_BIAS_LS_RES && !swiglu)) return POPE_ERR_ARG;
     if (swiglu && (!a_planes || !w_planes || (!C) == (!c_planes) || N <= 0 || (N & 63))) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
-    GemmParams g = {};
-    g.range_flag = range_flag;
-    g.range_bit = epilogue == POPE_EPI_BIAS_GELU || swiglu ? POPE_RANGE_GELU : POPE_RANGE_QKV;   // the FC1 producer's bit
-    g.a_pl = a_planes; g.w_pl = w_planes;
-    g.bias = bias; g.C = C; g.c_pl = c_planes;
-    g.lda = K; g.ldw = K; g.ldc = swiglu ? N / 2 : N;
-    g.M = M; g.N = N; g.K = K;
-    g.epilogue = epilogue;
-    g.gamma = gamma; g.res = res; g.ldres = N;
-    return pope_launch_gemm_planes(g, static_cast<hipStream_t>(stream));
+    return pope_launch_gemm_planes(pope_linear_params(LINEAR_PLANES, a_planes, w_planes, bias, C, c_planes, M, N, K, epilogue, gamma, res,
+                                                      0, range_flag), static_cast<hipStream_t>(stream));
 }
 
 int pope_layernorm_planes_f32(const float* x, const float* weight, const float* bias, void* y_planes, int rows, int dim,
@@ -154,16 +96,12 @@ int pope_layernorm_planes_f32(const float* x, const float* weight, const float* 
     return pope_launch_layernorm_planes(x, dim, weight, bias, y_planes, rows, dim, eps, range_flag, static_cast<hipStream_t>(stream));
 }
 
-// the `rowln` launch of vit_forward_impl with every operand from the caller; checked before the stream's device is touched
+// the `rowln` launch of vit_forward.hip with every operand from the caller; checked before the stream's device is touched
 int pope_linear_rowln_f32(const void* a_planes, const void* w_planes, int M, int K, const float* bias, const float* gamma,
                           const float* res, int res_mod, float* x, const float* ln_w, const float* ln_b, float eps,
                           void* ln_planes, float* ln_out, unsigned* range_flag, void* stream) {
-    GemmParams g = {};
-    g.a_pl = a_planes; g.w_pl = w_planes; g.bias = bias; g.gamma = gamma; g.res = res; g.res_mod = res_mod;
-    g.C = x; g.M = M; g.N = 384; g.K = K; g.lda = K; g.ldw = K; g.ldc = 384; g.ldres = 384;
-    g.epilogue = EPI_BIAS_LS_RES;
-    g.ln_w = ln_w; g.ln_b = ln_b; g.ln_eps = eps; g.ln_planes = ln_planes; g.ln_f32 = ln_out;
-    g.range_flag = range_flag;
+    const GemmParams g = pope_linear_rowln_params(a_planes, w_planes, M, 384, K, bias, gamma, res, res_mod, x, ln_w, ln_b, eps, ln_planes,
+                                                  ln_out, range_flag);
     if (!pope_gemm_rowln_args_ok(g)) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
     return pope_launch_gemm_rowln(g, static_cast<hipStream_t>(stream));
@@ -179,39 +117,15 @@ int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const fl
 int pope_patch_embed_f32(const float* img, const float* proj_w, const float* posb, float* tokens, int B, int H,
                          int W, int patch, int dim, void* stream) {
     StreamDevice on_device(stream);
-    if (!img || !proj_w || !posb || !tokens || B <= 0 || patch <= 0 || H % patch || W % patch) return POPE_ERR_ARG;
-    GemmParams g = {};
-    g.A = img; g.W = proj_w; g.C = tokens;
-    g.K = 3 * patch * patch;
-    g.ldw = g.K; g.ldc = dim;
-    g.ntok = 1 + (H / patch) * (W / patch);
-    g.M = B * g.ntok; g.N = dim;
-    g.epilogue = EPI_POSB;
-    g.posb = posb;
-    g.img_h = H; g.img_w = W; g.patch = patch; g.grid_w = W / patch;
-    return pope_launch_gemm_nt_f32(g, static_cast<hipStream_t>(stream));
+    return pope_launch_patch_embed_f32(img, proj_w, posb, tokens, B, H, W, patch, dim, static_cast<hipStream_t>(stream));
 }
 
 int pope_patch_embed_planes_f32(const float* img, const void* proj_w_planes, const float* posb, float* tokens, int B, int H,
                                 int W, int patch, int dim, void* a_planes_scratch, size_t scratch_bytes, unsigned* range_flag,
-                                void* stream_) {
-    StreamDevice on_device(stream_);
-    if (!img || !proj_w_planes || !posb || !tokens || !a_planes_scratch || B <= 0 || patch <= 0 || H % patch || W % patch)
-        return POPE_ERR_ARG;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int kp = (3 * patch * patch + 31) & ~31, ntok = 1 + (H / patch) * (W / patch);
-    if (scratch_bytes < size_t(B) * ntok * kp * 4) return POPE_ERR_WORKSPACE;
-    int rc = pope_launch_im2col_planes(img, a_planes_scratch, B, H, W, patch, kp, range_flag, stream);
-    if (rc) return rc;
-    // tokens[b, n] = posb[n] + 1 * (A[b, n] . W^T): rows n = 0 are all-zero A rows (cls_token + pos_embed[0] from the table)
-    GemmParams g = {};
-    g.a_pl = a_planes_scratch; g.w_pl = proj_w_planes;
-    g.C = tokens;
-    g.lda = kp; g.ldw = kp; g.ldc = dim;
-    g.M = B * ntok; g.N = dim; g.K = kp;
-    g.epilogue = EPI_BIAS_LS_RES;
-    g.res = posb; g.ldres = dim; g.res_mod = ntok;
-    return pope_launch_gemm_planes(g, stream);
+                                void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_patch_embed_planes(img, proj_w_planes, posb, tokens, B, H, W, patch, dim, a_planes_scratch, scratch_bytes,
+                                          range_flag, static_cast<hipStream_t>(stream));
 }
 
 int pope_attention_planes_f32(const void* qkv_planes, void* out_planes, int B, int N, int heads, void* stream) {
@@ -259,251 +173,6 @@ int pope_cls_cosine_f32(const float* ref, const float* fea, int P, int D, float 
     return pope_check_launch();
 }
 
-size_t pope_vit_workspace_bytes(int B, int ntok, int dim, int hidden) {
-    if (B <= 0 || ntok <= 0 || dim <= 0 || hidden <= 0) return 0;
-    const size_t rows = size_t(B) * ntok;
-    const size_t big = size_t(hidden) > size_t(4) * dim ? size_t(hidden) : size_t(4) * dim;
-    return align_up(rows * dim * sizeof(float), 256) + align_up(rows * big * sizeof(float), 256);
-}
-
-static int vit_forward_impl(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
-                            float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
-                            float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
-                            void* stream_, Recorder& rec) {
-    if (!w || !img || !posb || !x_prenorm || !workspace || !w->blocks_host) return POPE_ERR_ARG;
-    if (w->dim != w->heads * 64 || w->patch <= 0 || H % w->patch || W % w->patch || B <= 0) return POPE_ERR_ARG;
-    if (n_taps < 0 || (n_taps > 0 && (!tap_blocks_host || !tap_out_host))) return POPE_ERR_ARG;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int dim = w->dim, hidden = w->hidden, prec = w->precision;
-    if (prec != POPE_PREC_F32_MFMA && prec != POPE_PREC_F16X3 && prec != POPE_PREC_F16) return POPE_ERR_ARG;
-    // SwiGLU FFN (pope_hip.h POPE_FFN_SWIGLU): fc1 = the permuted w12 [2 hidden, dim], fc2 = w3 [dim, hidden]; the w12 GEMM's
-    // 64-column blocks need hidden % 32 == 0; no plain-f16 form
-    if (ffn != POPE_FFN_MLP && ffn != POPE_FFN_SWIGLU) return POPE_ERR_ARG;
-    const bool swiglu = ffn == POPE_FFN_SWIGLU;
-    if (swiglu && (prec == POPE_PREC_F16 || hidden <= 0 || (hidden & 31))) return POPE_ERR_ARG;
-    for (int i = 0; swiglu && i < w->depth; ++i)
-        if (!w->blocks_host[i].fc1_w || !w->blocks_host[i].fc1_b || !w->blocks_host[i].fc2_w) return POPE_ERR_ARG;
-    StreamDevice on_device(stream_);
-    const int fc1_n = swiglu ? 2 * hidden : hidden, fc1_epi = swiglu ? int(EPI_BIAS_SWIGLU) : int(EPI_BIAS_GELU);
-    const int ntok = 1 + (H / w->patch) * (W / w->patch);
-    const int rows = B * ntok;
-    if (workspace_bytes < pope_vit_workspace_bytes(B, ntok, dim, hidden)) return POPE_ERR_WORKSPACE;
-
-    // workspace: xn [rows,dim] | big [rows, max(4dim, hidden)] = {qkv [rows,3dim], attn [rows,dim]} or fc1 out
-    char* ws = static_cast<char*>(workspace);
-    float* xn = reinterpret_cast<float*>(ws);
-    float* big = reinterpret_cast<float*>(ws + align_up(size_t(rows) * dim * sizeof(float), 256));
-    float* qkv = big;
-    float* att = big + size_t(rows) * 3 * dim;
-    float* hid = big;
-    float* x = x_prenorm;
-    const float eps = 1e-6f;  // vision_transformer.py:90
-
-    // f16x3 = the planes dataflow end to end (every operand is split ONCE by its producer, which also guards the f16
-    // range: range_flag).  It needs the weight planes of all four Linear layers of every block; without them (or with
-    // a width the planes layout does not take) the model runs on the fp32 MFMA, which has no range contract.
-    bool planes = (prec == POPE_PREC_F16X3 || prec == POPE_PREC_F16) && dim % 32 == 0 && dim >= 64 && hidden % 32 == 0;
-    for (int i = 0; planes && i < w->depth; ++i) {
-        const pope_vit_block_weights& k = w->blocks_host[i];
-        planes = k.qkv_wp && k.proj_wp && k.fc1_wp && k.fc2_wp;
-    }
-    // POPE_PREC_F16: the blocks' Linear layers and attention in plain f16 (one MFMA per product; `*_wp` of the blocks
-    // are f16 row-major matrices, value * 256); the patch embed stays f16x3 (`patch_wp` = planes) and the residual
-    // stream, LayerNorm statistics, softmax and GELU fp32.  Needs the weights and widths the plain GEMM takes.
-    const bool plain = prec == POPE_PREC_F16;
-    if (plain && (!planes || !w->patch_wp || (dim & 63) || (hidden & 63))) return POPE_ERR_ARG;
-    const int f32 = POPE_PREC_F32_MFMA;
-
-#define POPE_MARK(kind) do { if (!rec.mark(kind, stream)) return POPE_ERR_ARG; } while (0)
-#define POPE_TRY(call) do { if ((rc = (call))) return rc; } while (0)
-    int rc;
-    void* xn_pl = xn;    // planes alias the xn / fc1 buffers: 2 x f16 per element = the fp32 footprint
-    void* hid_pl = hid;
-    // Fused form (dim 384): every residual GEMM (patch embed, proj, fc2) also emits the LayerNorm that follows it —
-    // as planes for the next GEMM, or as fp32 x_norm after the last block — so no stand-alone LayerNorm launch is left
-    // (gemm_rowln.hip).
-    GemmParams probe = {};
-    probe.M = rows; probe.N = dim; probe.K = dim; probe.lda = dim; probe.ldw = dim; probe.ldc = dim; probe.ldres = dim;
-    const bool fusable = planes && !plain && w->patch_wp && pope_gemm_rowln_supported(probe);
-    // Small batches: the full-row-tile kernel has one tile per 128 rows, each a serial chain of K / 32 K-steps + a 23 us
-    // epilogue; while the 128 x 128 residual GEMM still fits ONE round of its 2 x CUs workgroup slots (3 column tiles per row
-    // tile) it finishes sooner, and `layernorm_rowln_order` reproduces the fused epilogue's LayerNorm bit for bit — an image
-    // gives the same tokens alone (this path) and inside a 64-image chunk (fused path).  Driver step (9 images of 196 x
-    // 196): proj 38 -> ~25 us, FC2 105 -> ~70 us per launch.
-    const bool small = fusable && 3 * ((rows + 127) / 128) <= 2 * pope_cu_count();
-    const bool fused = fusable && !small;
-    // plain GEMM over the token rows: C (fp32) or c_f16 (f16 row-major) = epi(a_f16 . w_f16^T + bias [...])
-    auto plain_gemm = [&](const void* a_f16, const void* w_f16, const float* bias, float* Cf, void* c_f16, int N, int K, int epi,
-                          const float* gamma, const float* res) {
-        GemmParams g = {};
-        g.range_flag = range_flag;
-        g.range_bit = epi == EPI_BIAS_GELU ? POPE_RANGE_GELU : POPE_RANGE_QKV;
-        g.a_pl = a_f16; g.w_pl = w_f16; g.bias = bias; g.C = Cf; g.c_pl = c_f16;
-        g.lda = K / 2; g.ldw = K / 2; g.K = K / 2; g.ldc = c_f16 ? N / 2 : N;   // column pairs (GemmParams::plain)
-        g.M = rows; g.N = N; g.epilogue = epi; g.gamma = gamma; g.res = res; g.ldres = N;
-        g.plain = 1;
-        if (epi == EPI_QKV_F16) { g.sam_dim = N / 3; g.sam_qscale = 0.125f * 1.44269504088896340736f; }   // heads of 64: head_dim^-0.5 * log2 e
-        return pope_launch_gemm_planes(g, stream);
-    };
-    // residual GEMM + following LayerNorm: x = res + gamma * (a . W^T + bias); LN(x; ln_w, ln_b) -> planes or fp32
-    auto rowln = [&](const void* a_pl, const void* w_pl, int K, const float* bias, const float* gamma, const float* res, int res_mod,
-                     const float* ln_w, const float* ln_b, void* ln_planes, float* ln_f32) {
-        GemmParams g = {};
-        g.a_pl = a_pl; g.w_pl = w_pl; g.bias = bias; g.gamma = gamma; g.res = res; g.res_mod = res_mod;
-        g.C = x; g.M = rows; g.N = dim; g.K = K; g.lda = K; g.ldw = K; g.ldc = dim; g.ldres = dim;
-        g.epilogue = EPI_BIAS_LS_RES;
-        g.ln_w = ln_w; g.ln_b = ln_b; g.ln_eps = eps; g.ln_planes = ln_planes; g.ln_f32 = ln_f32;
-        g.range_flag = range_flag;
-        return pope_launch_gemm_rowln(g, stream);
-    };
-    POPE_MARK(POPE_K_PATCH_EMBED);
-    if (fused) {   // `big` is free here: it holds the im2col planes
-        const int kp = (3 * w->patch * w->patch + 31) & ~31;
-        if (workspace_bytes - size_t(reinterpret_cast<char*>(big) - ws) < size_t(rows) * kp * 4) return POPE_ERR_WORKSPACE;
-        POPE_TRY(pope_launch_im2col_planes(img, big, B, H, W, w->patch, kp, range_flag, stream));
-        const pope_vit_block_weights& k0 = w->blocks_host[0];
-        POPE_TRY(rowln(big, w->patch_wp, kp, nullptr, nullptr, posb, ntok, k0.norm1_w, k0.norm1_b, xn_pl, nullptr));
-    } else if (planes && w->patch_wp) {
-        POPE_TRY(pope_patch_embed_planes_f32(img, w->patch_wp, posb, x, B, H, W, w->patch, dim, big,
-                                             workspace_bytes - size_t(reinterpret_cast<char*>(big) - ws), range_flag, stream));
-    } else {
-        POPE_TRY(pope_patch_embed_f32(img, w->patch_w, posb, x, B, H, W, w->patch, dim, stream));
-    }
-    for (int i = 0; i < w->depth; ++i) {
-        const pope_vit_block_weights& k = w->blocks_host[i];
-        const bool last = i + 1 == w->depth;
-        // x = x + ls1(attn(norm1(x)))                                      block.py:105
-        if (plain) {   // the same seven launches per block in single-product f16 arithmetic
-            POPE_MARK(POPE_K_LAYERNORM);
-            POPE_TRY(pope_launch_layernorm_f16(x, k.norm1_w, k.norm1_b, xn_pl, rows, dim, eps, range_flag, stream));
-            POPE_MARK(POPE_K_GEMM_QKV);
-            // q (pre-scaled by head_dim^-0.5 log2 e), k, v leave the QKV epilogue as f16 rows: the attention kernel stages K / V
-            // memory -> LDS directly (attention_f16.hip)
-            POPE_TRY(plain_gemm(xn_pl, k.qkv_wp, k.qkv_b, nullptr, qkv, 3 * dim, dim, EPI_QKV_F16, nullptr, nullptr));
-            POPE_MARK(POPE_K_ATTENTION);
-            POPE_TRY(pope_launch_attention_f16_dma(qkv, att, B, ntok, w->heads, stream));
-            POPE_MARK(POPE_K_GEMM_PROJ);
-            POPE_TRY(plain_gemm(att, k.proj_wp, k.proj_b, x, nullptr, dim, dim, EPI_BIAS_LS_RES, k.ls1, x));
-            POPE_MARK(POPE_K_LAYERNORM);
-            POPE_TRY(pope_launch_layernorm_f16(x, k.norm2_w, k.norm2_b, xn_pl, rows, dim, eps, range_flag, stream));
-            POPE_MARK(POPE_K_GEMM_FC1);
-            POPE_TRY(plain_gemm(xn_pl, k.fc1_wp, k.fc1_b, nullptr, hid_pl, hidden, dim, EPI_BIAS_GELU, nullptr, nullptr));
-            POPE_MARK(POPE_K_GEMM_FC2);
-            POPE_TRY(plain_gemm(hid_pl, k.fc2_wp, k.fc2_b, x, nullptr, dim, hidden, EPI_BIAS_LS_RES, k.ls2, x));
-            for (int t = 0; t < n_taps; ++t)
-                if (tap_blocks_host[t] == i && tap_out_host[t]) {
-                    POPE_MARK(POPE_K_TAP_COPY);
-                    if (hipMemcpyAsync(tap_out_host[t], x, size_t(rows) * dim * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
-                        return POPE_ERR_LAUNCH;
-                }
-            continue;
-        }
-        if (!fused) {
-            POPE_MARK(POPE_K_LAYERNORM);
-            if (small) POPE_TRY(pope_launch_layernorm_rowln_order(x, k.norm1_w, k.norm1_b, xn_pl, nullptr, rows, eps, range_flag, stream));
-            else if (planes) POPE_TRY(pope_launch_layernorm_planes(x, dim, k.norm1_w, k.norm1_b, xn_pl, rows, dim, eps, range_flag, stream));
-            else POPE_TRY(pope_launch_layernorm_f32(x, dim, k.norm1_w, k.norm1_b, xn, dim, rows, dim, eps, stream));
-        }
-        POPE_MARK(POPE_K_GEMM_QKV);
-        if (planes)  // q, k, v stay planes from the QKV epilogue to the attention kernel's LDS
-            POPE_TRY(pope_linear_planes_f32(xn_pl, k.qkv_wp, k.qkv_b, nullptr, qkv, rows, 3 * dim, dim, EPI_BIAS, nullptr, nullptr,
-                                            range_flag, stream));
-        else POPE_TRY(pope_linear_prec_f32(xn, k.qkv_w, k.qkv_b, qkv, rows, 3 * dim, dim, EPI_BIAS, nullptr, nullptr, f32, nullptr, stream));
-        POPE_MARK(POPE_K_ATTENTION);
-        if (planes) POPE_TRY(pope_launch_attention_f16x3_planes_io(qkv, att, B, ntok, w->heads, stream));
-        else POPE_TRY(pope_attention_prec_f32(qkv, att, B, ntok, w->heads, f32, nullptr, stream));
-        POPE_MARK(POPE_K_GEMM_PROJ);
-        if (fused)
-            POPE_TRY(rowln(att, k.proj_wp, dim, k.proj_b, k.ls1, x, 0, k.norm2_w, k.norm2_b, xn_pl, nullptr));
-        else if (planes)
-            POPE_TRY(pope_linear_planes_f32(att, k.proj_wp, k.proj_b, x, nullptr, rows, dim, dim, EPI_BIAS_LS_RES, k.ls1, x, nullptr, stream));
-        else POPE_TRY(pope_linear_prec_f32(att, k.proj_w, k.proj_b, x, rows, dim, dim, EPI_BIAS_LS_RES, k.ls1, x, f32, nullptr, stream));
-        // x = x + ls2(mlp(norm2(x)))                                       block.py:106
-        if (!fused) {
-            POPE_MARK(POPE_K_LAYERNORM);
-            if (small) POPE_TRY(pope_launch_layernorm_rowln_order(x, k.norm2_w, k.norm2_b, xn_pl, nullptr, rows, eps, range_flag, stream));
-            else if (planes) POPE_TRY(pope_launch_layernorm_planes(x, dim, k.norm2_w, k.norm2_b, xn_pl, rows, dim, eps, range_flag, stream));
-            else POPE_TRY(pope_launch_layernorm_f32(x, dim, k.norm2_w, k.norm2_b, xn, dim, rows, dim, eps, stream));
-        }
-        POPE_MARK(POPE_K_GEMM_FC1);
-        if (planes)
-            POPE_TRY(pope_linear_planes_f32(xn_pl, k.fc1_wp, k.fc1_b, nullptr, hid_pl, rows, fc1_n, dim, fc1_epi, nullptr,
-                                            nullptr, range_flag, stream));   // -> hid [rows, hidden] either way
-        else POPE_TRY(pope_linear_prec_f32(xn, k.fc1_w, k.fc1_b, hid, rows, fc1_n, dim, fc1_epi, nullptr, nullptr, f32, nullptr, stream));
-        POPE_MARK(POPE_K_GEMM_FC2);
-        if (fused && !last) {
-            const pope_vit_block_weights& kn = w->blocks_host[i + 1];
-            POPE_TRY(rowln(hid_pl, k.fc2_wp, hidden, k.fc2_b, k.ls2, x, 0, kn.norm1_w, kn.norm1_b, xn_pl, nullptr));
-        } else if (fused && x_norm) {   // last block: the final norm (vision_transformer.py:230) as fp32
-            POPE_TRY(rowln(hid_pl, k.fc2_wp, hidden, k.fc2_b, k.ls2, x, 0, w->norm_w, w->norm_b, nullptr, x_norm));
-        } else if (planes) {
-            POPE_TRY(pope_linear_planes_f32(hid_pl, k.fc2_wp, k.fc2_b, x, nullptr, rows, dim, hidden, EPI_BIAS_LS_RES, k.ls2, x,
-                                            nullptr, stream));
-        } else {
-            POPE_TRY(pope_linear_prec_f32(hid, k.fc2_w, k.fc2_b, x, rows, dim, hidden, EPI_BIAS_LS_RES, k.ls2, x, f32, nullptr, stream));
-        }
-        for (int t = 0; t < n_taps; ++t)
-            if (tap_blocks_host[t] == i && tap_out_host[t]) {
-                POPE_MARK(POPE_K_TAP_COPY);
-                if (hipMemcpyAsync(tap_out_host[t], x, size_t(rows) * dim * sizeof(float), hipMemcpyDeviceToDevice,
-                                   stream) != hipSuccess)
-                    return POPE_ERR_LAUNCH;
-            }
-    }
-    if (x_norm && !fused) {
-        POPE_MARK(POPE_K_LAYERNORM);
-        if (small) POPE_TRY(pope_launch_layernorm_rowln_order(x, w->norm_w, w->norm_b, nullptr, x_norm, rows, eps, nullptr, stream));
-        else POPE_TRY(pope_launch_layernorm_f32(x, dim, w->norm_w, w->norm_b, x_norm, dim, rows, dim, eps, stream));
-    }
-    POPE_MARK(-1);  // closing event
-#undef POPE_TRY
-#undef POPE_MARK
-    return POPE_OK;
-}
-
-
-int pope_vit_forward_f32(const pope_vit_weights* w, const float* img, int B, int H, int W, const float* posb,
-                         float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
-                         float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
-                         void* stream) {
-    return pope_vit_forward_ffn_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host,
-                                    workspace, workspace_bytes, range_flag, stream);
-}
-
-int pope_vit_forward_ffn_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
-                             float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
-                             float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
-                             void* stream) {
-    Recorder rec{nullptr, 0, nullptr, 0};
-    return vit_forward_impl(w, ffn, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host, workspace,
-                            workspace_bytes, range_flag, stream, rec);
-}
-
-int pope_vit_forward_profiled_mask_f32(const pope_vit_weights* w, const float* img, int B, int H, int W,
-                                       const float* posb, float* x_prenorm, float* x_norm, void* workspace,
-                                       size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                       void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
-                                       unsigned kind_mask) {
-    return pope_vit_forward_ffn_profiled_mask_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, workspace, workspace_bytes,
-                                                  range_flag, stream, events_host, n_events, kinds_host, n_launches_host, kind_mask);
-}
-
-int pope_vit_forward_ffn_profiled_mask_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W,
-                                           const float* posb, float* x_prenorm, float* x_norm, void* workspace,
-                                           size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                           void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
-                                           unsigned kind_mask) {
-    if (!events_host || n_events < 2 || !kinds_host || !n_launches_host) return POPE_ERR_ARG;
-    Recorder rec{events_host, n_events, kinds_host, 0};
-    rec.mask = kind_mask;
-    const int rc = vit_forward_impl(w, ffn, img, B, H, W, posb, x_prenorm, x_norm, 0, nullptr, nullptr, workspace,
-                                    workspace_bytes, range_flag, stream, rec);
-    *n_launches_host = rec.n > 0 ? rec.n - 1 : 0;
-    return rc;
-}
-
-int pope_vit_launch_count(int depth) { return depth > 0 ? 7 * depth + 2 : 0; }
-
 int pope_event_create(void** event_host) {
     if (!event_host) return POPE_ERR_ARG;
     hipEvent_t e;
@@ -526,19 +195,19 @@ struct MatchLayout {
     size_t nl, ns, part, rowp, colp, pl0, pl1, simb, total;
     int ncb, nrb, nrb2, ldp;
     MatchLayout(int n, int L, int S, int C, int precision, bool publish_conf) {
-        nl = align_up(size_t(n) * L * 4, 256);
-        ns = align_up(size_t(n) * S * 4, 256);
+        nl = pope_align256(size_t(n) * L * 4);
+        ns = pope_align256(size_t(n) * S * 4);
         ncb = 2 * ((S + 127) / 128);
         nrb = 4 * ((L + 127) / 128);
         nrb2 = pope_match_nrb2(L);
         ldp = (S + 3) & ~3;
-        part = align_up(size_t(n) * nrb2 * ldp * 4, 256);
+        part = pope_align256(size_t(n) * nrb2 * ldp * 4);
         const bool x3 = precision == POPE_PREC_F16X3;
-        rowp = x3 ? align_up(size_t(n) * L * ncb * 8, 256) : 0;
-        colp = x3 ? align_up(size_t(n) * nrb * ldp * 4, 256) : 0;
-        pl0 = x3 ? align_up(size_t(n) * L * C * 4, 256) : 0;
-        pl1 = x3 ? align_up(size_t(n) * S * C * 4, 256) : 0;
-        simb = publish_conf ? 0 : align_up(size_t(n) * L * S * 4, 256);
+        rowp = x3 ? pope_align256(size_t(n) * L * ncb * 8) : 0;
+        colp = x3 ? pope_align256(size_t(n) * nrb * ldp * 4) : 0;
+        pl0 = x3 ? pope_align256(size_t(n) * L * C * 4) : 0;
+        pl1 = x3 ? pope_align256(size_t(n) * S * C * 4) : 0;
+        simb = publish_conf ? 0 : pope_align256(size_t(n) * L * S * 4);
         total = 7 * nl + 3 * ns + part + rowp + 2 * colp + pl0 + pl1 + simb;
     }
 };
@@ -575,7 +244,7 @@ int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float
 
 size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks) {
     if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
-    return MatchLayout(n, L, S, C, precision, publish_conf != 0).total + (has_border_masks ? align_up(size_t(n) * 4 * 4, 256) : 0);
+    return MatchLayout(n, L, S, C, precision, publish_conf != 0).total + (has_border_masks ? pope_align256(size_t(n) * 4 * 4) : 0);
 }
 
 int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
@@ -592,10 +261,9 @@ int pope_dense_match_masked_f32(const float* feat0, long long stride0, const flo
     const bool publish = conf_matrix != nullptr;
     const bool padded = border_mask0 || border_mask1;
     const MatchLayout lay(n, L, S, C, precision, publish);
-    const size_t ext_bytes = padded ? align_up(size_t(n) * 4 * 4, 256) : 0;
+    const size_t ext_bytes = padded ? pope_align256(size_t(n) * 4 * 4) : 0;
     if (workspace_bytes < lay.total + ext_bytes) return POPE_ERR_WORKSPACE;
-    char* ws = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* q = ws; ws += bytes; return q; };
+    pope_carver ws{static_cast<char*>(workspace)};   // (every piece of the layout is a multiple of 256 bytes)
     MatchParams p = {};
     p.feat0 = feat0; p.feat1 = feat1;
     p.n = n; p.L = L; p.S = S; p.C = C;
@@ -604,25 +272,25 @@ int pope_dense_match_masked_f32(const float* feat0, long long stride0, const flo
     p.thr = thr; p.temperature = temperature; p.border = border_rm; p.scale = scale;
     p.publish_conf = publish;
     p.ncb = lay.ncb; p.nrb = lay.nrb; p.nrb2 = lay.nrb2; p.ldp = lay.ldp;
-    p.row_max = reinterpret_cast<float*>(take(lay.nl));
-    p.row_sum = reinterpret_cast<float*>(take(lay.nl));
-    p.conf_rowmax = reinterpret_cast<float*>(take(lay.nl));
-    p.row_j = reinterpret_cast<int*>(take(lay.nl));
-    p.row_conf = reinterpret_cast<float*>(take(lay.nl));
-    p.row_arg = reinterpret_cast<int*>(take(lay.nl));
-    p.row_cnt = reinterpret_cast<int*>(take(lay.nl));
-    p.col_max = reinterpret_cast<float*>(take(lay.ns));
-    p.col_sum = reinterpret_cast<float*>(take(lay.ns));
-    p.conf_colmax = reinterpret_cast<float*>(take(lay.ns));
-    p.colmax_part = reinterpret_cast<float*>(take(lay.part));
+    p.row_max = ws.take<float>(lay.nl);
+    p.row_sum = ws.take<float>(lay.nl);
+    p.conf_rowmax = ws.take<float>(lay.nl);
+    p.row_j = ws.take<int>(lay.nl);
+    p.row_conf = ws.take<float>(lay.nl);
+    p.row_arg = ws.take<int>(lay.nl);
+    p.row_cnt = ws.take<int>(lay.nl);
+    p.col_max = ws.take<float>(lay.ns);
+    p.col_sum = ws.take<float>(lay.ns);
+    p.conf_colmax = ws.take<float>(lay.ns);
+    p.colmax_part = ws.take<float>(lay.part);
     if (precision == POPE_PREC_F16X3) {
-        p.row_part = reinterpret_cast<float*>(take(lay.rowp));
-        p.col_pmax = reinterpret_cast<float*>(take(lay.colp));
-        p.col_psum = reinterpret_cast<float*>(take(lay.colp));
-        p.planes0 = take(lay.pl0);
-        p.planes1 = take(lay.pl1);
+        p.row_part = ws.take<float>(lay.rowp);
+        p.col_pmax = ws.take<float>(lay.colp);
+        p.col_psum = ws.take<float>(lay.colp);
+        p.planes0 = ws.take(lay.pl0);
+        p.planes1 = ws.take(lay.pl1);
     }
-    p.sim = publish ? conf_matrix : reinterpret_cast<float*>(take(lay.simb));
+    p.sim = publish ? conf_matrix : ws.take<float>(lay.simb);
     p.counts = counts;
     p.range_flag = range_flag;
     p.b_ids = b_ids; p.i_ids = i_ids; p.j_ids = j_ids;

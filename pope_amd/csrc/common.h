@@ -157,6 +157,21 @@ static inline int pope_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? POPE_OK : POPE_ERR_LAUNCH;
 }
+// return the first non-zero POPE_* code of a launch sequence
+#define POPE_TRY(call) do { if (const int pope_rc_ = (call)) return pope_rc_; } while (0)
+
+// Grid of a grid-stride kernel over `total` items: one block per `per_block` of them, at least one, at most 64 per CU.
+static inline int pope_grid_for(long long total, int per_block = 256) {
+    const long long b = (total + per_block - 1) / per_block, cap = 64ll * pope_cu_count();
+    return int(b < 1 ? 1 : (b < cap ? b : cap));
+}
+
+// Workspaces are carved into 256-byte aligned pieces, by the size queries and the launchers alike.
+static inline size_t pope_align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+struct pope_carver {
+    char* at;
+    template <typename T = void> T* take(size_t bytes) { char* r = at; at += pope_align256(bytes); return reinterpret_cast<T*>(r); }
+};
 
 // Launch of a kernel with more than 64 KB of dynamic LDS: the one-time opt-in (per kernel and device), the launch, its check.
 template <auto KERNEL, typename... Args>

@@ -162,12 +162,6 @@ __global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* _
     if constexpr (PLANES) pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
 }
 
-inline int grid_for(long long total) {
-    const long long b = (total + 255) / 256;
-    const long long cap = 64ll * pope_cu_count();
-    return int(b < 1 ? 1 : (b < cap ? b : cap));
-}
-
 struct Plan {
     int n, H, W;
     int Hp[4], Wp[4];           // zero-bordered grids at 1/2, 1/4, 1/8 (index 1..3)
@@ -183,7 +177,6 @@ inline Plan make_plan(int n, int H, int W) {
     }
     return p;
 }
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // workspace buffers, in floats-per-row (= bytes / 4 of a planes row or an fp32 row)
 enum Buf { G0, P1A, P1B, P1C, F1, T1A, T1B, G2, D2, P2A, P2B, P2C, F2, T2A, T2B, X2O, G3, D3, P3A, P3B, P3C, NBUF };
@@ -198,7 +191,7 @@ constexpr BufSpec kBufs[NBUF] = {
 size_t pope_resnetfpn_workspace(int n, int H, int W) {
     const Plan p = make_plan(n, H, W);
     size_t total = 0;
-    for (int b = 0; b < NBUF; ++b) total += align256(p.rows[kBufs[b].level] * kBufs[b].pitch * 4);
+    for (int b = 0; b < NBUF; ++b) total += pope_align256(p.rows[kBufs[b].level] * kBufs[b].pitch * 4);
     return total;
 }
 
@@ -216,7 +209,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     char* buf[NBUF];
     for (int b = 0; b < NBUF; ++b) {
         buf[b] = base;
-        base += align256(p.rows[kBufs[b].level] * kBufs[b].pitch * 4);
+        base += pope_align256(p.rows[kBufs[b].level] * kBufs[b].pitch * 4);
     }
     // Borders and the channel padding (196 -> 224) must read as zeros.  Nothing is cleared wholesale: every planes
     // buffer is written in full by its producer — the GEMM epilogue zero-fills the padding columns, the gathers and
@@ -267,7 +260,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     };
     auto zero_border = [&](void* b, int level, int pitch) -> int {
         const long long total = (long long)q.n * (2 * p.Wp[level] + 2 * (p.Hp[level] - 2)) * (pitch / 4);
-        hipLaunchKernelGGL(zero_border_kernel, dim3(grid_for(total)), dim3(256), 0, stream, static_cast<u32x4*>(b), q.n,
+        hipLaunchKernelGGL(zero_border_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, static_cast<u32x4*>(b), q.n,
                            p.Hp[level], p.Wp[level], pitch / 4);
         return pope_check_launch();
     };
@@ -280,7 +273,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     auto gather = [&](Buf in, int level_in, Buf out, int taps) -> int {
         const int cch = kBufs[in].pitch / 32;
         const long long total = (long long)p.rows[level_in + 1] * taps * cch * 8;
-        hipLaunchKernelGGL(gather_s2_kernel, dim3(grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(buf[in]),
+        hipLaunchKernelGGL(gather_s2_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(buf[in]),
                            reinterpret_cast<u32x4*>(buf[out]), q.n, p.Hp[level_in], p.Wp[level_in], cch, taps);
         return pope_check_launch();
     };
@@ -327,9 +320,9 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     // stem (resnet_fpn.py:60-62,101)
     {
         const long long total = (long long)p.rows[1] * 8;
-        if (f32) hipLaunchKernelGGL(stem_gather_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream, q.img,
+        if (f32) hipLaunchKernelGGL(stem_gather_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.img,
                                     reinterpret_cast<_Float16*>(buf[G0]), q.n, q.H, q.W, q.range_flag);
-        else hipLaunchKernelGGL(stem_gather_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, q.img,
+        else hipLaunchKernelGGL(stem_gather_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.img,
                                 reinterpret_cast<_Float16*>(buf[G0]), q.n, q.H, q.W, q.range_flag);
         if ((rc = pope_check_launch())) return rc;
     }
@@ -354,9 +347,9 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if ((rc = gemm(buf[P2C], 224, 16, 256, 2, nullptr, reinterpret_cast<float*>(buf[F2]), 256, 1.f, nullptr, 0, false, 224))) return rc;
     {
         const long long total = (long long)q.n * (p.Hp[2] - 2) * (p.Wp[2] - 2) * (256 / 4);
-        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
+        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
                                     256, q.out_c, 256, reinterpret_cast<_Float16*>(buf[T2A]), 256, 256, q.n, p.Hp[2], p.Wp[2], q.range_flag);
-        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
+        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
                                 256, q.out_c, 256, reinterpret_cast<_Float16*>(buf[T2A]), 256, 256, q.n, p.Hp[2], p.Wp[2], q.range_flag);
         if ((rc = pope_check_launch())) return rc;
         if ((rc = zero_border(buf[T2A], 2, 256))) return rc;
@@ -371,10 +364,10 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if ((rc = gemm(buf[P1B], 128, 19, 196, 1, nullptr, reinterpret_cast<float*>(buf[F1]), 224, 1.f, nullptr, 0, false, 128))) return rc;
     {
         const long long total = (long long)q.n * (p.Hp[1] - 2) * (p.Wp[1] - 2) * (224 / 4);
-        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
+        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
                                     224, reinterpret_cast<const float*>(buf[X2O]), 224, reinterpret_cast<_Float16*>(buf[T1A]), 224, 196, q.n,
                                     p.Hp[1], p.Wp[1], q.range_flag);
-        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
+        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
                                 224, reinterpret_cast<const float*>(buf[X2O]), 224, reinterpret_cast<_Float16*>(buf[T1A]), 224, 196, q.n,
                                 p.Hp[1], p.Wp[1], q.range_flag);
         if ((rc = pope_check_launch())) return rc;

@@ -9,6 +9,7 @@
 // The two Linear layers run on the f16x3 planes GEMM (gemm_planes.hip); everything else is one gather or reduce kernel.
 #include "common.h"
 #include "kernels.h"
+#include "linear.h"
 
 namespace {
 
@@ -131,17 +132,11 @@ __global__ __launch_bounds__(256) void fine_match_kernel(const float* __restrict
     }
 }
 
-inline int grid_for(long long total) {
-    const long long b = (total + 255) / 256, cap = 64ll * pope_cu_count();
-    return int(b < 1 ? 1 : (b < cap ? b : cap));
-}
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 }  // namespace
 
 size_t pope_fine_preprocess_workspace(int M, int WW, int Cc, int Cf) {
     if (M <= 0) return 0;
-    return align256(size_t(2) * M * Cc * 4) + align256(size_t(2) * M * Cf * 4) + align256(size_t(2) * M * WW * 2 * Cf * 4);
+    return pope_align256(size_t(2) * M * Cc * 4) + pope_align256(size_t(2) * M * Cf * 4) + pope_align256(size_t(2) * M * WW * 2 * Cf * 4);
 }
 
 int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
@@ -152,36 +147,33 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
     if (f32 ? (!q.down_w || !q.merge_w) : (!q.down_wp || !q.merge_wp)) return POPE_ERR_ARG;
     const int WW = q.Wn * q.Wn;
     if (q.ws_bytes < pope_fine_preprocess_workspace(q.M, WW, q.Cc, q.Cf)) return POPE_ERR_WORKSPACE;
-    char* ws = static_cast<char*>(q.ws);
-    _Float16* cpl = reinterpret_cast<_Float16*>(ws); ws += align256(size_t(2) * q.M * q.Cc * 4);
-    float* c_win = reinterpret_cast<float*>(ws); ws += align256(size_t(2) * q.M * q.Cf * 4);
-    _Float16* mpl = reinterpret_cast<_Float16*>(ws);
+    pope_carver ws{static_cast<char*>(q.ws)};
+    _Float16* cpl = ws.take<_Float16>(size_t(2) * q.M * q.Cc * 4);
+    float* c_win = ws.take<float>(size_t(2) * q.M * q.Cf * 4);
+    _Float16* mpl = ws.take<_Float16>(size_t(2) * q.M * WW * 2 * q.Cf * 4);
     // POPE_PREC_F32_MFMA (the range guard's re-run): fp32 rows in the same buffers, both Linears on gemm_f32.hip
-    if (f32) hipLaunchKernelGGL(fine_gather_coarse_kernel<false>, dim3(grid_for(2ll * q.M * q.Cc / 4)), dim3(256), 0, stream, q.fc0, q.fc1,
+    if (f32) hipLaunchKernelGGL(fine_gather_coarse_kernel<false>, dim3(pope_grid_for(2ll * q.M * q.Cc / 4)), dim3(256), 0, stream, q.fc0, q.fc1,
                                 q.b_ids, q.i_ids, q.j_ids, q.M, q.L, q.S, q.Cc, cpl, q.range_flag);
-    else hipLaunchKernelGGL(fine_gather_coarse_kernel<true>, dim3(grid_for(2ll * q.M * q.Cc / 4)), dim3(256), 0, stream, q.fc0, q.fc1,
+    else hipLaunchKernelGGL(fine_gather_coarse_kernel<true>, dim3(pope_grid_for(2ll * q.M * q.Cc / 4)), dim3(256), 0, stream, q.fc0, q.fc1,
                             q.b_ids, q.i_ids, q.j_ids, q.M, q.L, q.S, q.Cc, cpl, q.range_flag);
-    int rc = pope_check_launch();
-    if (rc) return rc;
-    GemmParams g = {};
-    g.a_pl = cpl; g.w_pl = q.down_wp; g.bias = q.down_b; g.C = c_win;
-    g.A = reinterpret_cast<const float*>(cpl); g.W = q.down_w;
-    g.M = 2 * q.M; g.N = q.Cf; g.K = q.Cc; g.lda = q.Cc; g.ldw = q.Cc; g.ldc = q.Cf;
-    g.epilogue = EPI_BIAS; g.nbatch = 1;
-    if ((rc = f32 ? pope_launch_gemm_nt_f32(g, stream) : pope_launch_gemm_planes(g, stream))) return rc;
+    POPE_TRY(pope_check_launch());
+    // a bias-only Linear on either GEMM: both views of the operands are set (fp32 rows or planes in the same buffers), the fp32
+    // output has no residual and reports no range
+    auto linear = [&](const void* a, const void* wp, const float* wf, const float* bias, float* C, int M, int N, int K) {
+        GemmParams g = pope_linear_params(LINEAR_PLANES, a, wp, bias, C, nullptr, M, N, K, EPI_BIAS);
+        g.A = static_cast<const float*>(a); g.W = wf;
+        g.ldres = 0; g.range_bit = 0; g.nbatch = 1;
+        return f32 ? pope_launch_gemm_nt_f32(g, stream) : pope_launch_gemm_planes(g, stream);
+    };
+    POPE_TRY(linear(cpl, q.down_wp, q.down_w, q.down_b, c_win, 2 * q.M, q.Cf, q.Cc));
     FineMap m0 = {q.f0, q.s0[0], q.s0[1], q.s0[2], q.s0[3], q.H0, q.W0, q.wc0};
     FineMap m1 = {q.f1, q.s1[0], q.s1[1], q.s1[2], q.s1[3], q.H1, q.W1, q.wc1};
-    if (f32) hipLaunchKernelGGL(fine_gather_windows_kernel<false>, dim3(grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
+    if (f32) hipLaunchKernelGGL(fine_gather_windows_kernel<false>, dim3(pope_grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
                                 c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag);
-    else hipLaunchKernelGGL(fine_gather_windows_kernel<true>, dim3(grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
+    else hipLaunchKernelGGL(fine_gather_windows_kernel<true>, dim3(pope_grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
                             c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag);
-    if ((rc = pope_check_launch())) return rc;
-    GemmParams h = {};
-    h.a_pl = mpl; h.w_pl = q.merge_wp; h.bias = q.merge_b; h.C = q.out;
-    h.A = reinterpret_cast<const float*>(mpl); h.W = q.merge_w;
-    h.M = 2 * q.M * WW; h.N = q.Cf; h.K = 2 * q.Cf; h.lda = 2 * q.Cf; h.ldw = 2 * q.Cf; h.ldc = q.Cf;
-    h.epilogue = EPI_BIAS; h.nbatch = 1;
-    return f32 ? pope_launch_gemm_nt_f32(h, stream) : pope_launch_gemm_planes(h, stream);
+    POPE_TRY(pope_check_launch());
+    return linear(mpl, q.merge_wp, q.merge_w, q.merge_b, q.out, 2 * q.M * WW, q.Cf, 2 * q.Cf);
 }
 
 int pope_launch_fine_match(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,

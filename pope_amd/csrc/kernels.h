@@ -1,4 +1,4 @@
-// Internal launcher interface between the kernel translation units and the C ABI (capi.hip).
+// Internal launcher interface between the kernel translation units and the C ABI (capi.hip, vit_forward.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -142,6 +142,12 @@ int pope_launch_layernorm_rowln_order(const float* x, const float* w, const floa
 // all-zero CLS row, row b*ntok + 1 + n the flattened patch n; zero K padding)
 int pope_launch_im2col_planes(const float* img, void* a_planes, int B, int H, int W, int patch, int kp, unsigned* range_flag,
                               hipStream_t stream);
+// the whole patch embed (vit_forward.hip), tokens [B * ntok, dim] fp32: the arguments of pope_patch_embed_f32 / _planes_f32
+int pope_launch_patch_embed_f32(const float* img, const float* proj_w, const float* posb, float* tokens, int B, int H, int W,
+                                int patch, int dim, hipStream_t stream);
+int pope_launch_patch_embed_planes(const float* img, const void* proj_w_planes, const float* posb, float* tokens, int B, int H, int W,
+                                   int patch, int dim, void* a_planes_scratch, size_t scratch_bytes, unsigned* range_flag,
+                                   hipStream_t stream);
 // matcher operand: planes of feat / divisor (a true fp32 division, coarse_matching.py:109) for n blocks of `rows` rows
 // with `bs` elements between blocks; output compact [n*rows, cols]
 int pope_launch_div_planes(const float* src, long long bs, void* planes, int n, int rows, int cols, float divisor, float scale,

@@ -14,6 +14,7 @@
 // 4 x (self, cross) transformer is 16 calls instead of ~200 torch ops.
 #include "common.h"
 #include "kernels.h"
+#include "linear.h"
 
 namespace {
 
@@ -222,15 +223,13 @@ __global__ __launch_bounds__(256) void ln_add_kernel(float* __restrict__ x, cons
     }
 }
 
-inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 size_t pope_loftr_layer_workspace(int n, int L, int S, int C, int H) {
     const size_t rx = size_t(n) * L, rs = size_t(n) * S, D = C / H, chunks = (S + LA_CHUNK - 1) / LA_CHUNK;
-    return al(rx * C * 4) /*xp*/ + al(rs * C * 4) /*sp*/ + al(rx * C * 4) /*q, later merge out*/ + al(rs * 2 * C * 4) /*kv*/ +
-           al(size_t(n) * H * chunks * (D * D + D) * 4) + al(size_t(n) * H * (D * D + D) * 4) + al(rx * C * 4) /*msg, later mlp out*/ +
-           al(rx * C * 4) /*msg planes*/ + al(rx * 2 * C * 4) /*cat planes*/ + al(rx * 2 * C * 4) /*hidden planes*/;
+    return pope_align256(rx * C * 4) /*xp*/ + pope_align256(rs * C * 4) /*sp*/ + pope_align256(rx * C * 4) /*q, later merge out*/ + pope_align256(rs * 2 * C * 4) /*kv*/ +
+           pope_align256(size_t(n) * H * chunks * (D * D + D) * 4) + pope_align256(size_t(n) * H * (D * D + D) * 4) + pope_align256(rx * C * 4) /*msg, later mlp out*/ +
+           pope_align256(rx * C * 4) /*msg planes*/ + pope_align256(rx * 2 * C * 4) /*cat planes*/ + pope_align256(rx * 2 * C * 4) /*hidden planes*/;
 }
 
 int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
@@ -245,36 +244,30 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     const size_t rx = size_t(p.n) * p.L, rs = size_t(p.n) * p.S;
     if (rx > 0x7fffffffull / (2 * C) || rs > 0x7fffffffull / (2 * C)) return POPE_ERR_ARG;
     const int chunks = (p.S + LA_CHUNK - 1) / LA_CHUNK, per = D * D + D;
-    char* w = static_cast<char*>(p.ws);
-    auto take = [&](size_t bytes) { char* r = w; w += al(bytes); return r; };
-    void* xp = take(rx * C * 4);
-    void* sp = take(rs * C * 4);
-    float* q = reinterpret_cast<float*>(take(rx * C * 4));
-    float* kv = reinterpret_cast<float*>(take(rs * 2 * C * 4));
-    float* part = reinterpret_cast<float*>(take(size_t(p.n) * H * chunks * per * 4));
-    float* kvf = reinterpret_cast<float*>(take(size_t(p.n) * H * per * 4));
-    float* msg = reinterpret_cast<float*>(take(rx * C * 4));
-    void* msgp = take(rx * C * 4);
-    void* catp = take(rx * 2 * C * 4);
-    void* hidp = take(rx * 2 * C * 4);
+    pope_carver ws{static_cast<char*>(p.ws)};
+    void* xp = ws.take(rx * C * 4);
+    void* sp = ws.take(rs * C * 4);
+    float* q = ws.take<float>(rx * C * 4);
+    float* kv = ws.take<float>(rs * 2 * C * 4);
+    float* part = ws.take<float>(size_t(p.n) * H * chunks * per * 4);
+    float* kvf = ws.take<float>(size_t(p.n) * H * per * 4);
+    float* msg = ws.take<float>(rx * C * 4);
+    void* msgp = ws.take(rx * C * 4);
+    void* catp = ws.take(rx * 2 * C * 4);
+    void* hidp = ws.take(rx * 2 * C * 4);
     const bool self = p.source == p.x && p.S == p.L;
-    int rc;
-#define LT(call) do { if ((rc = (call))) return rc; } while (0)
     // POPE_PREC_F32_MFMA (the range guard's re-run): the same sequence with fp32 operands on gemm_f32.hip — "planes" buffers
     // hold plain fp32 rows (same bytes), no operand split, no range contract
     auto gemm = [&](const void* a_pl, const void* w_pl, float* Cf, void* Cp, int M, int N, int K, int epi) {
-        GemmParams g = {};
-        if (f32) {
-            g.A = static_cast<const float*>(a_pl); g.W = static_cast<const float*>(w_pl);
-            g.C = Cf ? Cf : static_cast<float*>(Cp);
-            g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-            g.epilogue = EPI_CONV; g.act_slope = epi == EPI_BIAS_RELU ? 0.f : 1.f;
+        if (f32) {   // gemm_f32.hip has BIAS_RELU as EPI_CONV's activation: slope 0 = ReLU, 1 = identity
+            GemmParams g = pope_linear_params(LINEAR_F32, a_pl, w_pl, nullptr, Cf ? Cf : static_cast<float*>(Cp), nullptr, M, N, K, EPI_CONV);
+            g.act_slope = epi == EPI_BIAS_RELU ? 0.f : 1.f;
+            g.ldres = 0;
             return pope_launch_gemm_nt_f32(g, stream);
         }
-        g.a_pl = a_pl; g.w_pl = w_pl; g.C = Cf; g.c_pl = Cp;
-        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-        g.epilogue = epi;
-        g.range_flag = p.range_flag; g.range_bit = POPE_RANGE_GELU;
+        GemmParams g = pope_linear_params(LINEAR_PLANES, a_pl, w_pl, nullptr, Cf, Cp, M, N, K, epi, nullptr, nullptr, 0, p.range_flag);
+        g.ldres = 0;
+        g.range_bit = POPE_RANGE_GELU;   // the hidden planes of the MLP are this layer's only packed output
         return pope_launch_gemm_planes(g, stream);
     };
     // 1. operands of the projections
@@ -282,8 +275,8 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
         xp = p.x;
         sp = const_cast<float*>(p.source);
     } else {
-        LT(pope_launch_split_planes(p.x, xp, int(rx), C, K_PLANES_ACT_SCALE, p.range_flag, stream));
-        if (!self) LT(pope_launch_split_planes(p.source, sp, int(rs), C, K_PLANES_ACT_SCALE, p.range_flag, stream));
+        POPE_TRY(pope_launch_split_planes(p.x, xp, int(rx), C, K_PLANES_ACT_SCALE, p.range_flag, stream));
+        if (!self) POPE_TRY(pope_launch_split_planes(p.source, sp, int(rs), C, K_PLANES_ACT_SCALE, p.range_flag, stream));
     }
     const void* Wq = f32 ? static_cast<const void*>(p.q_w) : p.q_wp;
     const void* Wkv = f32 ? static_cast<const void*>(p.kv_w) : p.kv_wp;
@@ -291,8 +284,8 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     const void* W0 = f32 ? static_cast<const void*>(p.mlp0_w) : p.mlp0_wp;
     const void* W1 = f32 ? static_cast<const void*>(p.mlp1_w) : p.mlp1_wp;
     // 2. q = x Wq^T ; [k | v] = source [Wk ; Wv]^T
-    LT(gemm(xp, Wq, q, nullptr, int(rx), C, C, EPI_BIAS));
-    LT(gemm(self ? xp : sp, Wkv, kv, nullptr, int(rs), 2 * C, C, EPI_BIAS));
+    POPE_TRY(gemm(xp, Wq, q, nullptr, int(rx), C, C, EPI_BIAS));
+    POPE_TRY(gemm(self ? xp : sp, Wkv, kv, nullptr, int(rs), 2 * C, C, EPI_BIAS));
     // 3. per-head state, 4. message
     // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
 #define LA_REDUCE(DD, MK) hipLaunchKernelGGL((linattn_reduce_kernel<DD, MK>), dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, \
@@ -315,7 +308,7 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
 #undef LA_APPLY_D
 #undef LA_APPLY
     // 5. merge (-> q buffer), 6. cat[x, LN1(merge)] as planes
-    LT(gemm(msgp, Wm, q, nullptr, int(rx), C, C, EPI_BIAS));
+    POPE_TRY(gemm(msgp, Wm, q, nullptr, int(rx), C, C, EPI_BIAS));
     const dim3 rows4(unsigned((rx + 3) / 4));
     const float cat_scale = f32 ? 1.0f : K_PLANES_ACT_SCALE;
 #define LN_CAT(NV, PL) hipLaunchKernelGGL((ln_cat_planes_kernel<NV, PL>), rows4, dim3(256), 0, stream, p.x, q, p.norm1_w, p.norm1_b, \
@@ -324,10 +317,9 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     else { if (f32) LN_CAT(2, false); else LN_CAT(2, true); }
 #undef LN_CAT
     // 7. MLP: relu(cat W0^T) -> planes ; W1 -> fp32 (msg buffer) ; 8. x += LN2(.)
-    LT(gemm(catp, W0, nullptr, hidp, int(rx), 2 * C, 2 * C, EPI_BIAS_RELU));
-    LT(gemm(hidp, W1, msg, nullptr, int(rx), C, 2 * C, EPI_BIAS));
+    POPE_TRY(gemm(catp, W0, nullptr, hidp, int(rx), 2 * C, 2 * C, EPI_BIAS_RELU));
+    POPE_TRY(gemm(hidp, W1, msg, nullptr, int(rx), C, 2 * C, EPI_BIAS));
     if (C == 256) hipLaunchKernelGGL(ln_add_kernel<4>, rows4, dim3(256), 0, stream, p.x, msg, p.norm2_w, p.norm2_b, int(rx), p.ln_eps);
     else hipLaunchKernelGGL(ln_add_kernel<2>, rows4, dim3(256), 0, stream, p.x, msg, p.norm2_w, p.norm2_b, int(rx), p.ln_eps);
-#undef LT
     return pope_check_launch();
 }

@@ -293,13 +293,12 @@ __global__ __launch_bounds__(64) void five_point_kernel(const double* __restrict
         for (int j = 0; j < 9; ++j) E_out[(size_t(s) * 10 + k) * 9 + j] = k < n ? E[k][j] : 0.0;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 }  // namespace
 
 size_t pope_pose_workspace(int B, long long M) {
     const size_t m = size_t(M < 1 ? 1 : M), nb = size_t(B < 1 ? 1 : B);
-    return align256(m * sizeof(Pt)) + 2 * align256(m) + align256(nb * NT * 10 * 9 * sizeof(double)) + align256(nb * NT * 10 * sizeof(int));
+    return pope_align256(m * sizeof(Pt)) + 2 * pope_align256(m) + pope_align256(nb * NT * 10 * 9 * sizeof(double)) + pope_align256(nb * NT * 10 * sizeof(int));
 }
 
 int pope_launch_estimate_pose(PoseParams q, void* ws, size_t ws_bytes, hipStream_t stream) {
@@ -309,10 +308,10 @@ int pope_launch_estimate_pose(PoseParams q, void* ws, size_t ws_bytes, hipStream
     if (ws_bytes < pope_pose_workspace(q.B, q.M)) return POPE_ERR_WORKSPACE;
     const size_t m = size_t(q.M < 1 ? 1 : q.M);
     char* p = static_cast<char*>(ws);
-    q.xn = p; p += align256(m * sizeof(Pt));
-    q.mask_ws = reinterpret_cast<unsigned char*>(p); p += align256(m);
-    q.cheir_ws = reinterpret_cast<unsigned char*>(p); p += align256(m);
-    q.cand_ws = reinterpret_cast<double*>(p); p += align256(size_t(q.B) * NT * 10 * 9 * sizeof(double));
+    q.xn = p; p += pope_align256(m * sizeof(Pt));
+    q.mask_ws = reinterpret_cast<unsigned char*>(p); p += pope_align256(m);
+    q.cheir_ws = reinterpret_cast<unsigned char*>(p); p += pope_align256(m);
+    q.cand_ws = reinterpret_cast<double*>(p); p += pope_align256(size_t(q.B) * NT * 10 * 9 * sizeof(double));
     q.cmeta_ws = reinterpret_cast<int*>(p);
     hipLaunchKernelGGL(pose_kernel, dim3(q.B), dim3(NT), 0, stream, q);
     return pope_check_launch();

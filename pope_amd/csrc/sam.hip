@@ -20,18 +20,19 @@
 // chain at two waves per SIMD, not by the staging.)
 // Two precisions (pope_hip.h): POPE_PREC_F16X3 as above; POPE_PREC_F16 = plain f16 operands, one MFMA per product
 // (template flag PLAIN here and in gemm_planes.hip), fp32 accumulators / softmax / LayerNorm / residual stream in both.
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
+#include "linear.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using pope_attn::f16x4;
+using pope_attn::f16x8;
+using pope_attn::s16x4;
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
@@ -39,22 +40,9 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 constexpr float L2E = 1.44269504088896340736f;
 constexpr float A_SCALE = K_PLANES_ACT_SCALE;
 
-inline int grid_for(long long total, int per_block = 256) {
-    long long b = (total + per_block - 1) / per_block;
-    const long long cap = 64ll * pope_cu_count();
-    return int(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
-__device__ __forceinline__ f16x8 cat(f16x4 a, f16x4 b) { return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
+using pope_attn::cat;
+using pope_attn::mfma_f16;
+using pope_attn::vmax3;
 
 // ---- patch embed operand: image [B, 3, S, S] -> activation planes [B * g * g, 3 * P * P], k = (c, ky, kx) as
 // Conv2d's weight.reshape(dim, -1) (image_encoder.py:385-393); P % 8 == 0
@@ -861,11 +849,11 @@ size_t pope_sam_encoder_workspace(const SamEncParams& q) {
         AttnPlan p;
         const int ws = pass ? g : (q.window > 0 ? q.window : g);
         if (!plan_attention(q.B, g, ws, q.heads, hd, p)) return 0;
-        ops += align256(p.qp) + align256(p.kp) + align256(p.vp) + align256(p.tab) + align256(rows * sizeof(int));
+        ops += pope_align256(p.qp) + pope_align256(p.kp) + pope_align256(p.vp) + pope_align256(p.tab) + pope_align256(rows * sizeof(int));
     }
     const size_t gp = size_t(g) + 2;
-    return align256(rows * q.dim * 4) /* x */ + align256(rows * q.dim * 4) /* xn planes */ + align256(big) + ops +
-           align256(rows * q.out_chans * 4) /* neck 1x1 */ + 2 * align256(size_t(q.B) * gp * gp * q.out_chans * 4);
+    return pope_align256(rows * q.dim * 4) /* x */ + pope_align256(rows * q.dim * 4) /* xn planes */ + pope_align256(big) + ops +
+           pope_align256(rows * q.out_chans * 4) /* neck 1x1 */ + 2 * pope_align256(size_t(q.B) * gp * gp * q.out_chans * 4);
 }
 
 int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
@@ -890,28 +878,27 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
     if (!plan_attention(q.B, g, q.window > 0 ? q.window : g, q.heads, hd, plan_w) || !plan_attention(q.B, g, g, q.heads, hd, plan_g))
         return POPE_ERR_ARG;
 
-    char* base = static_cast<char*>(q.ws);
-    auto take = [&](size_t bytes) { char* p = base; base += align256(bytes); return p; };
-    float* x = reinterpret_cast<float*>(take(size_t(rows) * dim * 4));
-    void* xn_pl = take(size_t(rows) * dim * 4);
+    pope_carver ws{static_cast<char*>(q.ws)};
+    float* x = ws.take<float>(size_t(rows) * dim * 4);
+    void* xn_pl = ws.take(size_t(rows) * dim * 4);
     size_t big_bytes = size_t(rows) * 4 * dim * 4;
     if (size_t(rows) * hidden * 4 > big_bytes) big_bytes = size_t(rows) * hidden * 4;
     if (size_t(rows) * kp * 4 > big_bytes) big_bytes = size_t(rows) * kp * 4;
-    char* big = take(big_bytes);
+    char* big = ws.take<char>(big_bytes);
     void* att_pl = big;   // attention output (the proj GEMM's operand); fc1's output reuses the buffer
     void* hid_pl = big;
     struct OpSet { _Float16 *q, *k, *v; void* tab; int* map; };
     OpSet ops_w, ops_g;
     for (auto pr : {std::make_pair(&plan_w, &ops_w), std::make_pair(&plan_g, &ops_g)}) {
-        pr.second->q = reinterpret_cast<_Float16*>(take(pr.first->qp));
-        pr.second->k = reinterpret_cast<_Float16*>(take(pr.first->kp));
-        pr.second->v = reinterpret_cast<_Float16*>(take(pr.first->vp));
-        pr.second->tab = take(pr.first->tab);
-        pr.second->map = reinterpret_cast<int*>(take(size_t(rows) * sizeof(int)));
+        pr.second->q = ws.take<_Float16>(pr.first->qp);
+        pr.second->k = ws.take<_Float16>(pr.first->kp);
+        pr.second->v = ws.take<_Float16>(pr.first->vp);
+        pr.second->tab = ws.take(pr.first->tab);
+        pr.second->map = ws.take<int>(size_t(rows) * sizeof(int));
     }
-    float* t1 = reinterpret_cast<float*>(take(size_t(rows) * oc * 4));
-    void* t1_pl = take(brows * oc * 4);
-    float* t2 = reinterpret_cast<float*>(take(brows * oc * 4));
+    float* t1 = ws.take<float>(size_t(rows) * oc * 4);
+    void* t1_pl = ws.take(brows * oc * 4);
+    float* t2 = ws.take<float>(brows * oc * 4);
 
     // LayerNorm eps of the blocks (build_sam.py:71 passes 1e-6; the constructor's default norm_layer has 1e-5) and of the
     // neck's LayerNorm2d (common.py:28: 1e-6)
@@ -923,19 +910,10 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
     if (q.precision != POPE_PREC_F16X3 && q.precision != POPE_PREC_F16) return POPE_ERR_ARG;
     const bool plain = q.precision == POPE_PREC_F16;
     if (plain && ((dim & 63) || (hidden & 63) || (kp & 63))) return POPE_ERR_ARG;
-    int rc;
-#define POPE_TRY(call) do { if ((rc = (call))) return rc; } while (0)
     auto gemm = [&](const void* a_pl, const void* w_pl, const float* bias, float* Cf, void* c_pl, int N, int K, int epi,
                     const float* gamma, const float* res, int res_mod) {
-        GemmParams gp_ = {};
-        gp_.range_flag = flag;
-        gp_.range_bit = epi == EPI_BIAS_GELU ? POPE_RANGE_GELU : POPE_RANGE_QKV;
-        gp_.a_pl = a_pl; gp_.w_pl = w_pl; gp_.bias = bias; gp_.C = Cf; gp_.c_pl = c_pl;
-        const int Kc = plain ? K / 2 : K;   // plain: columns are counted in pairs (GemmParams::plain)
-        gp_.lda = Kc; gp_.ldw = Kc; gp_.ldc = plain && c_pl ? N / 2 : N; gp_.M = rows; gp_.N = N; gp_.K = Kc;
-        gp_.epilogue = epi; gp_.gamma = gamma; gp_.res = res; gp_.ldres = N; gp_.res_mod = res_mod;
-        gp_.plain = plain;
-        return pope_launch_gemm_planes(gp_, stream);
+        return pope_launch_gemm_planes(pope_linear_params(plain ? LINEAR_PLAIN : LINEAR_PLANES, a_pl, w_pl, bias, Cf, c_pl, rows, N, K, epi,
+                                                          gamma, res, res_mod, flag), stream);
     };
     auto layernorm = [&](const float* w, const float* b) -> int {   // LN(x) -> xn_pl as this precision's GEMM operand
         if (!plain) return pope_launch_layernorm_planes(x, dim, w, b, xn_pl, rows, dim, eps, flag, stream);
@@ -946,10 +924,10 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
     {
         const long long total = (long long)rows * (kp / 8);
         if (plain)
-            hipLaunchKernelGGL(sam_im2col_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, q.image,
+            hipLaunchKernelGGL(sam_im2col_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.image,
                                reinterpret_cast<_Float16*>(big), q.B, q.img, q.patch, flag);
         else
-            hipLaunchKernelGGL(sam_im2col_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream, q.image,
+            hipLaunchKernelGGL(sam_im2col_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.image,
                                reinterpret_cast<_Float16*>(big), q.B, q.img, q.patch, flag);
         POPE_TRY(pope_check_launch());
         if (q.pos) POPE_TRY(gemm(big, q.patch_wp, q.patch_b, x, nullptr, dim, kp, EPI_BIAS_LS_RES, q.ones, q.pos, g * g));
@@ -971,11 +949,11 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
             const AttnGeom& a = p.geom;
             const int k_row = plain ? a.DQ : a.DQ + a.HDP;
             if (!p.bias) {   // (bias mode: K' has no one-hot columns)
-                hipLaunchKernelGGL(sam_onehot_kernel, dim3(grid_for((long long)a.B * a.nw * a.nw * a.heads * a.Nq)), dim3(256), 0, stream,
+                hipLaunchKernelGGL(sam_onehot_kernel, dim3(pope_grid_for((long long)a.B * a.nw * a.nw * a.heads * a.Nq)), dim3(256), 0, stream,
                                    os.k, a, k_row);
                 POPE_TRY(pope_check_launch());
             }
-            hipLaunchKernelGGL(sam_rowmap_kernel, dim3(grid_for(rows)), dim3(256), 0, stream, os.map, a);
+            hipLaunchKernelGGL(sam_rowmap_kernel, dim3(pope_grid_for(rows)), dim3(256), 0, stream, os.map, a);
             POPE_TRY(pope_check_launch());
         }
     }
@@ -1008,9 +986,9 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
             if (a.nw * a.ws > a.g) {   // ... the rows of the edge windows' zero-padded tokens from the bias ...
                 const long long total = (long long)a.B * (a.nw * a.ws * a.nw * a.ws - a.g * a.g) * a.heads * 3 * (hd / 8);
                 if (plain)
-                    hipLaunchKernelGGL(sam_pad_tokens_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, k.qkv_b, Qp, Kp, Vp, a, flag);
+                    hipLaunchKernelGGL(sam_pad_tokens_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, k.qkv_b, Qp, Kp, Vp, a, flag);
                 else
-                    hipLaunchKernelGGL(sam_pad_tokens_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream, k.qkv_b, Qp, Kp, Vp, a, flag);
+                    hipLaunchKernelGGL(sam_pad_tokens_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, k.qkv_b, Qp, Kp, Vp, a, flag);
                 POPE_TRY(pope_check_launch());
             }
             // ... and the relative-position columns of Q' from the Q' rows
@@ -1068,17 +1046,17 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
     // neck (image_encoder.py:89-105): 1x1 conv (no bias) -> LayerNorm2d -> 3x3 conv pad 1 (no bias) -> LayerNorm2d
     if (plain) {
         const long long n4 = (long long)rows * dim / 4;
-        hipLaunchKernelGGL(sam_to_f16_kernel, dim3(grid_for(n4)), dim3(256), 0, stream, x, static_cast<_Float16*>(xn_pl), n4, flag);
+        hipLaunchKernelGGL(sam_to_f16_kernel, dim3(pope_grid_for(n4)), dim3(256), 0, stream, x, static_cast<_Float16*>(xn_pl), n4, flag);
         POPE_TRY(pope_check_launch());
     } else {
         POPE_TRY(pope_launch_split_planes(x, xn_pl, rows, dim, A_SCALE, flag, stream));
     }
     POPE_TRY(gemm(xn_pl, q.neck0_wp, nullptr, t1, nullptr, oc, dim, EPI_BIAS, nullptr, nullptr, 0));
     if (plain)
-        hipLaunchKernelGGL((sam_ln2d_kernel<true, true>), dim3(grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w,
+        hipLaunchKernelGGL((sam_ln2d_kernel<true, true>), dim3(pope_grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w,
                            q.neck1_b, t1_pl, q.B, g, oc, neck_eps, flag);
     else
-        hipLaunchKernelGGL((sam_ln2d_kernel<true, false>), dim3(grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w,
+        hipLaunchKernelGGL((sam_ln2d_kernel<true, false>), dim3(pope_grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w,
                            q.neck1_b, t1_pl, q.B, g, oc, neck_eps, flag);
     POPE_TRY(pope_check_launch());
     {
@@ -1097,9 +1075,8 @@ int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream) {
         c.nbatch = 1;
         POPE_TRY(pope_launch_gemm_planes(c, stream));
     }
-    hipLaunchKernelGGL((sam_ln2d_kernel<false, false>), dim3(grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out,
+    hipLaunchKernelGGL((sam_ln2d_kernel<false, false>), dim3(pope_grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out,
                        q.B, g, oc, neck_eps, nullptr);
     POPE_TRY(pope_check_launch());
-#undef POPE_TRY
     return POPE_OK;
 }

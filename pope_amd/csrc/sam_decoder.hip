@@ -17,6 +17,7 @@
 // batch-invariant bit for bit.
 #include "common.h"
 #include "kernels.h"
+#include "linear.h"
 
 namespace {
 
@@ -33,12 +34,6 @@ constexpr int CHUNK = 16;        // prompts per pass over the image side (worksp
 constexpr int HDC = 16;          // head dim of the cross attentions
 constexpr int HDS = 32;          // head dim of the self attention
 constexpr int HEADS = 8;
-
-#define SD_TRY(x)                   \
-    do {                            \
-        const int st_ = (x);        \
-        if (st_ != POPE_OK) return st_; \
-    } while (0)
 
 // one value into an activation planes tensor [rows, ld] (layout: kernels.h GemmParams::a_pl), scale 8
 __device__ __forceinline__ void sd_put_planes(_Float16* pl, int ld, size_t row, int c, float v, bool& bad) {
@@ -420,7 +415,7 @@ struct Ws {
     template <typename T>
     T* take(size_t elems) {
         T* r = reinterpret_cast<T*>(p ? p + off : nullptr);
-        off += (elems * sizeof(T) + 255) & ~size_t(255);
+        off += pope_align256(elems * sizeof(T));
         return r;
     }
 };
@@ -476,18 +471,10 @@ struct Ctx {
 
 // C[M, N] = A . W^T + bias over K: planes GEMM (A activation planes, W weight planes) or, f32, the fp32 GEMM
 int gemm(const Ctx& c, const void* A, const void* W, const float* bias, float* C, int M, int N, int K) {
-    GemmParams g{};
-    g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N;
-    g.bias = bias; g.C = C; g.epilogue = EPI_BIAS;
-    if (c.f32) {
-        g.A = static_cast<const float*>(A);
-        g.W = static_cast<const float*>(W);
-        return pope_launch_gemm_nt_f32(g, c.s);
-    }
-    g.a_pl = A; g.w_pl = W;
-    g.range_flag = c.flag;
-    return pope_launch_gemm_planes(g, c.s);
+    GemmParams g = pope_linear_params(c.f32 ? LINEAR_F32 : LINEAR_PLANES, A, W, bias, C, nullptr, M, N, K, EPI_BIAS, nullptr, nullptr, 0,
+                                      c.f32 ? nullptr : c.flag);
+    g.ldres = 0; g.range_bit = 0;   // no residual; an fp32 output reports no range
+    return c.f32 ? pope_launch_gemm_nt_f32(g, c.s) : pope_launch_gemm_planes(g, c.s);
 }
 
 int lin(const Ctx& c, const float* X, int ldx, const float* add, int add_cols, const float* W, const float* b, const float* res,
@@ -565,21 +552,21 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
     if (shared) {   // layer 0's image-only projections, once per call
         hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, 1), dim3(256), 0, stream, a.image, a.image_pe, a.dense, 0LL, B.keys0,
                            B.opA0, B.opB0, f32, B.pe_t, a.range_flag);
-        SD_TRY(pope_check_launch());
+        POPE_TRY(pope_check_launch());
         const void* A0 = c.f32 ? static_cast<const void*>(B.keys0) : B.opA0;
-        SD_TRY(gemm(c, B.opB0, w->layers_host[0].img_qk_wp, w->layers_host[0].img_qk_b, B.qk0, NPIX, D, D));
-        SD_TRY(gemm(c, A0, w->layers_host[0].img_v_wp, w->layers_host[0].img_v_b, B.v0, NPIX, DI, D));
+        POPE_TRY(gemm(c, B.opB0, w->layers_host[0].img_qk_wp, w->layers_host[0].img_qk_b, B.qk0, NPIX, D, D));
+        POPE_TRY(gemm(c, A0, w->layers_host[0].img_v_wp, w->layers_host[0].img_v_b, B.v0, NPIX, DI, D));
     }
     const void* opA = c.f32 ? static_cast<const void*>(B.keys) : B.opA;
     for (int pg0 = 0; pg0 < a.P; pg0 += CHUNK) {
         const int cp = a.P - pg0 < CHUNK ? a.P - pg0 : CHUNK, R = T * cp, rows = cp * NPIX;
         hipLaunchKernelGGL(sd_tokens_kernel, dim3((R * D + 255) / 256), dim3(256), 0, stream, w->tokens,
                            a.n_sparse ? a.sparse + size_t(pg0) * a.n_sparse * D : nullptr, a.n_sparse, T, R, B.qry, B.tpe);
-        SD_TRY(pope_check_launch());
+        POPE_TRY(pope_check_launch());
         if (!shared) {
             hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, cp), dim3(256), 0, stream, a.image, a.image_pe,
                                a.dense + pg0 * a.dense_stride, a.dense_stride, B.keys, B.opA, B.opB, f32, B.pe_t, a.range_flag);
-            SD_TRY(pope_check_launch());
+            POPE_TRY(pope_check_launch());
         }
         for (int l = 0; l < 2; ++l) {
             const pope_sam_decoder_layer_weights& L = w->layers_host[l];
@@ -589,41 +576,41 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
                 qk = B.qk0; v = B.v0; res = B.keys0;
                 qps = vps = rps = 0;
             } else {
-                SD_TRY(gemm(c, B.opB, L.img_qk_wp, L.img_qk_b, B.qk, rows, D, D));
-                SD_TRY(gemm(c, opA, L.img_v_wp, L.img_v_b, B.v, rows, DI, D));
+                POPE_TRY(gemm(c, B.opB, L.img_qk_wp, L.img_qk_b, B.qk, rows, D, D));
+                POPE_TRY(gemm(c, opA, L.img_v_wp, L.img_v_b, B.v, rows, DI, D));
             }
             // self-attention; layer 0 (skip_first_layer_pe): no pe, and its output replaces the queries
-            SD_TRY(lin(c, B.qry, D, l ? B.tpe : nullptr, 2 * D, L.sa_qkv_w, L.sa_qkv_b, nullptr, B.tqkv, 3 * D, R, 3 * D, D, false));
+            POPE_TRY(lin(c, B.qry, D, l ? B.tpe : nullptr, 2 * D, L.sa_qkv_w, L.sa_qkv_b, nullptr, B.tqkv, 3 * D, R, 3 * D, D, false));
             hipLaunchKernelGGL(sd_self_attn_kernel, dim3(HEADS, cp), dim3(64), 0, stream, B.tqkv, B.tatt, T, __builtin_sqrtf(float(HDS)));
-            SD_TRY(pope_check_launch());
-            SD_TRY(lin(c, B.tatt, D, nullptr, 0, L.sa_o_w, L.sa_o_b, l ? B.qry : nullptr, B.tmp, D, R, D, D, false));
-            SD_TRY(ln_tok(c, B.tmp, B.qry, L.norm1_w, L.norm1_b, teps, R));
+            POPE_TRY(pope_check_launch());
+            POPE_TRY(lin(c, B.tatt, D, nullptr, 0, L.sa_o_w, L.sa_o_b, l ? B.qry : nullptr, B.tmp, D, R, D, D, false));
+            POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm1_w, L.norm1_b, teps, R));
             // tokens -> image
-            SD_TRY(lin(c, B.qry, D, B.tpe, DI, L.t2i_q_w, L.t2i_q_b, nullptr, B.tq, DI, R, DI, D, false));
-            SD_TRY(t2i(c, B.tq, qk, D, qps, v, vps, B.tatt, T, cp));
-            SD_TRY(lin(c, B.tatt, DI, nullptr, 0, L.t2i_o_w, L.t2i_o_b, B.qry, B.tmp, D, R, D, DI, false));
-            SD_TRY(ln_tok(c, B.tmp, B.qry, L.norm2_w, L.norm2_b, teps, R));
+            POPE_TRY(lin(c, B.qry, D, B.tpe, DI, L.t2i_q_w, L.t2i_q_b, nullptr, B.tq, DI, R, DI, D, false));
+            POPE_TRY(t2i(c, B.tq, qk, D, qps, v, vps, B.tatt, T, cp));
+            POPE_TRY(lin(c, B.tatt, DI, nullptr, 0, L.t2i_o_w, L.t2i_o_b, B.qry, B.tmp, D, R, D, DI, false));
+            POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm2_w, L.norm2_b, teps, R));
             // MLP (ReLU)
-            SD_TRY(lin(c, B.qry, D, nullptr, 0, L.mlp1_w, L.mlp1_b, nullptr, B.th, MLP, R, MLP, D, true));
-            SD_TRY(lin(c, B.th, MLP, nullptr, 0, L.mlp2_w, L.mlp2_b, B.qry, B.tmp, D, R, D, MLP, false));
-            SD_TRY(ln_tok(c, B.tmp, B.qry, L.norm3_w, L.norm3_b, teps, R));
+            POPE_TRY(lin(c, B.qry, D, nullptr, 0, L.mlp1_w, L.mlp1_b, nullptr, B.th, MLP, R, MLP, D, true));
+            POPE_TRY(lin(c, B.th, MLP, nullptr, 0, L.mlp2_w, L.mlp2_b, B.qry, B.tmp, D, R, D, MLP, false));
+            POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm3_w, L.norm3_b, teps, R));
             // image -> tokens: k from tokens + pe, v from tokens
-            SD_TRY(lin(c, B.qry, D, B.tpe, DI, L.i2t_kv_w, L.i2t_kv_b, nullptr, B.tkv, D, R, D, D, false));
+            POPE_TRY(lin(c, B.qry, D, B.tpe, DI, L.i2t_kv_w, L.i2t_kv_b, nullptr, B.tkv, D, R, D, D, false));
             hipLaunchKernelGGL(sd_i2t_attn_kernel, dim3(NPIX / 32, cp), dim3(256), 0, stream, qk + DI, qps, B.tkv, T,
                                static_cast<void*>(B.att), f32, a.range_flag);
-            SD_TRY(pope_check_launch());
-            SD_TRY(gemm(c, B.att, L.i2t_o_wp, L.i2t_o_b, B.y, rows, D, DI));
+            POPE_TRY(pope_check_launch());
+            POPE_TRY(gemm(c, B.att, L.i2t_o_wp, L.i2t_o_b, B.y, rows, D, DI));
             hipLaunchKernelGGL(sd_res_ln_kernel, dim3(rows / 4), dim3(256), 0, stream, res, rps, B.y, L.norm4_w, L.norm4_b, teps, B.pe_t,
                                B.keys, B.opA, B.opB, f32, rows, a.range_flag);
-            SD_TRY(pope_check_launch());
+            POPE_TRY(pope_check_launch());
         }
         // final token -> image attention: k into qk (ld 128), v into v
-        SD_TRY(gemm(c, B.opB, w->fin_k_wp, w->fin_k_b, B.qk, rows, DI, D));
-        SD_TRY(gemm(c, opA, w->fin_v_wp, w->fin_v_b, B.v, rows, DI, D));
-        SD_TRY(lin(c, B.qry, D, B.tpe, DI, w->fin_q_w, w->fin_q_b, nullptr, B.tq, DI, R, DI, D, false));
-        SD_TRY(t2i(c, B.tq, B.qk, DI, (long long)NPIX * DI, B.v, (long long)NPIX * DI, B.tatt, T, cp));
-        SD_TRY(lin(c, B.tatt, DI, nullptr, 0, w->fin_o_w, w->fin_o_b, B.qry, B.tmp, D, R, D, DI, false));
-        SD_TRY(ln_tok(c, B.tmp, B.qry, w->norm_final_w, w->norm_final_b, teps, R));
+        POPE_TRY(gemm(c, B.opB, w->fin_k_wp, w->fin_k_b, B.qk, rows, DI, D));
+        POPE_TRY(gemm(c, opA, w->fin_v_wp, w->fin_v_b, B.v, rows, DI, D));
+        POPE_TRY(lin(c, B.qry, D, B.tpe, DI, w->fin_q_w, w->fin_q_b, nullptr, B.tq, DI, R, DI, D, false));
+        POPE_TRY(t2i(c, B.tq, B.qk, DI, (long long)NPIX * DI, B.v, (long long)NPIX * DI, B.tatt, T, cp));
+        POPE_TRY(lin(c, B.tatt, DI, nullptr, 0, w->fin_o_w, w->fin_o_b, B.qry, B.tmp, D, R, D, DI, false));
+        POPE_TRY(ln_tok(c, B.tmp, B.qry, w->norm_final_w, w->norm_final_b, teps, R));
         if (a.hs_out && hipMemcpyAsync(a.hs_out + size_t(pg0) * T * D, B.qry, size_t(R) * D * sizeof(float), hipMemcpyDeviceToDevice,
                                        stream) != hipSuccess)
             return POPE_ERR_LAUNCH;
@@ -632,20 +619,20 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
             return POPE_ERR_LAUNCH;
         // hypernetwork MLPs (mask token i -> hyper[:, i]) and the IoU head (iou token -> the C columns the output keeps)
         for (int i = 0; i < NMASK; ++i) {
-            SD_TRY(lin(c, B.qry + (1 + i) * D, T * D, nullptr, 0, w->hyper_w[3 * i], w->hyper_b[3 * i], nullptr, B.h1, D, cp, D, D, true));
-            SD_TRY(lin(c, B.h1, D, nullptr, 0, w->hyper_w[3 * i + 1], w->hyper_b[3 * i + 1], nullptr, B.h2, D, cp, D, D, true));
-            SD_TRY(lin(c, B.h2, D, nullptr, 0, w->hyper_w[3 * i + 2], w->hyper_b[3 * i + 2], nullptr, B.hyper + i * 32, NMASK * 32, cp,
+            POPE_TRY(lin(c, B.qry + (1 + i) * D, T * D, nullptr, 0, w->hyper_w[3 * i], w->hyper_b[3 * i], nullptr, B.h1, D, cp, D, D, true));
+            POPE_TRY(lin(c, B.h1, D, nullptr, 0, w->hyper_w[3 * i + 1], w->hyper_b[3 * i + 1], nullptr, B.h2, D, cp, D, D, true));
+            POPE_TRY(lin(c, B.h2, D, nullptr, 0, w->hyper_w[3 * i + 2], w->hyper_b[3 * i + 2], nullptr, B.hyper + i * 32, NMASK * 32, cp,
                        32, D, false));
         }
-        SD_TRY(lin(c, B.qry, T * D, nullptr, 0, w->iou_w[0], w->iou_b[0], nullptr, B.h1, D, cp, D, D, true));
-        SD_TRY(lin(c, B.h1, D, nullptr, 0, w->iou_w[1], w->iou_b[1], nullptr, B.h2, D, cp, D, D, true));
-        SD_TRY(lin(c, B.h2, D, nullptr, 0, w->iou_w[2] + size_t(m0) * D, w->iou_b[2] + m0, nullptr, a.iou + size_t(pg0) * C, C, cp, C,
+        POPE_TRY(lin(c, B.qry, T * D, nullptr, 0, w->iou_w[0], w->iou_b[0], nullptr, B.h1, D, cp, D, D, true));
+        POPE_TRY(lin(c, B.h1, D, nullptr, 0, w->iou_w[1], w->iou_b[1], nullptr, B.h2, D, cp, D, D, true));
+        POPE_TRY(lin(c, B.h2, D, nullptr, 0, w->iou_w[2] + size_t(m0) * D, w->iou_b[2] + m0, nullptr, a.iou + size_t(pg0) * C, C, cp, C,
                    D, false));
         // upscaling: first ConvTranspose as a GEMM (N = 4 taps x 64), then the fused tail
-        SD_TRY(gemm(c, opA, w->up1_wp, w->up1_b, B.y, rows, D, D));
+        POPE_TRY(gemm(c, opA, w->up1_wp, w->up1_b, B.y, rows, D, D));
         hipLaunchKernelGGL(sd_tail_kernel, dim3(NPIX * 4 / 256, cp), dim3(256), 0, stream, B.y, w->up_ln_w, w->up_ln_b, ueps, w->up2_w,
                            w->up2_b, B.hyper, m0, C, a.masks + size_t(pg0) * C * (16 * NPIX));
-        SD_TRY(pope_check_launch());
+        POPE_TRY(pope_check_launch());
     }
     return POPE_OK;
 }

@@ -8,14 +8,9 @@
 // (tests/test_gpu_sam.py).
 #include "common.h"
 #include "kernels.h"
+#include "linear.h"
 
 namespace {
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-inline int grid_for(long long total, int per_block = 256) {
-    const long long b = (total + per_block - 1) / per_block, cap = 64ll * pope_cu_count();
-    return int(b < 1 ? 1 : (b < cap ? b : cap));
-}
 
 // image [B, 3, S, S] -> rows [B g g, 3 P P] in the order of Conv2d's weight.reshape(dim, -1) (c, ky, kx); P % 4 == 0
 __global__ __launch_bounds__(256) void sam32_im2col_kernel(const float* __restrict__ img, float* __restrict__ out, int B, int S, int P) {
@@ -176,36 +171,29 @@ int pope_launch_sam_encoder_f32mfma(const SamEncParams& q, hipStream_t stream) {
     const int rows = q.B * g * g;
     const size_t gp = size_t(g) + 2, brows = size_t(q.B) * gp * gp;
     // the workspace of the f16x3 path (pope_sam_encoder_workspace), re-read as: x | xn | big | scratch (the operand sets) ...
-    char* base = static_cast<char*>(q.ws);
-    char* const ws_end = base + q.ws_bytes;
-    auto take = [&](size_t bytes) { char* p = base; base += align256(bytes); return p; };
-    float* x = reinterpret_cast<float*>(take(size_t(rows) * dim * 4));
-    float* xn = reinterpret_cast<float*>(take(size_t(rows) * dim * 4));
+    pope_carver carve{static_cast<char*>(q.ws)};
+    char* const ws_end = carve.at + q.ws_bytes;
+    float* x = carve.take<float>(size_t(rows) * dim * 4);
+    float* xn = carve.take<float>(size_t(rows) * dim * 4);
     size_t big_bytes = size_t(rows) * 4 * dim * 4;
     if (size_t(rows) * hidden * 4 > big_bytes) big_bytes = size_t(rows) * hidden * 4;
     if (size_t(rows) * kp * 4 > big_bytes) big_bytes = size_t(rows) * kp * 4;
-    float* big = reinterpret_cast<float*>(take(big_bytes));
+    float* big = carve.take<float>(big_bytes);
     // ... and, from the END (where the f16x3 path keeps them too), the neck buffers; the attention output sits between
-    float* t2 = reinterpret_cast<float*>(ws_end - align256(brows * oc * 4));
-    float* t1b = reinterpret_cast<float*>(reinterpret_cast<char*>(t2) - align256(brows * oc * 4));
-    float* t1 = reinterpret_cast<float*>(reinterpret_cast<char*>(t1b) - align256(size_t(rows) * oc * 4));
-    float* att = reinterpret_cast<float*>(base);
+    float* t2 = reinterpret_cast<float*>(ws_end - pope_align256(brows * oc * 4));
+    float* t1b = reinterpret_cast<float*>(reinterpret_cast<char*>(t2) - pope_align256(brows * oc * 4));
+    float* t1 = reinterpret_cast<float*>(reinterpret_cast<char*>(t1b) - pope_align256(size_t(rows) * oc * 4));
+    float* att = reinterpret_cast<float*>(carve.at);
     if (reinterpret_cast<char*>(att) + size_t(rows) * dim * 4 > reinterpret_cast<char*>(t1)) return POPE_ERR_WORKSPACE;
     if (size_t(rows + 256) * (hidden > 3 * dim ? hidden : 3 * dim) * 4 >= (1ull << 32) - 512) return POPE_ERR_ARG;
 
     const float eps = q.block_eps > 0.f ? q.block_eps : 1e-6f, neck_eps = q.neck_eps > 0.f ? q.neck_eps : 1e-6f;
-    int rc;
-#define POPE_TRY(call) do { if ((rc = (call))) return rc; } while (0)
     auto gemm = [&](const float* A, int M, const void* W, const float* bias, float* Cf, int N, int K, int epi, const float* gamma,
                     const float* res) {
-        GemmParams p = {};
-        p.A = A; p.W = static_cast<const float*>(W); p.bias = bias; p.C = Cf;
-        p.lda = K; p.ldw = K; p.ldc = N; p.M = M; p.N = N; p.K = K;
-        p.epilogue = epi; p.gamma = gamma; p.res = res; p.ldres = N;
-        return pope_launch_gemm_nt_f32(p, stream);
+        return pope_launch_gemm_nt_f32(pope_linear_params(LINEAR_F32, A, W, bias, Cf, nullptr, M, N, K, epi, gamma, res), stream);
     };
     // patch embed + absolute position table (image_encoder.py:108-110)
-    hipLaunchKernelGGL(sam32_im2col_kernel, dim3(grid_for((long long)rows * (kp / 4))), dim3(256), 0, stream, q.image, big, q.B, q.img, q.patch);
+    hipLaunchKernelGGL(sam32_im2col_kernel, dim3(pope_grid_for((long long)rows * (kp / 4))), dim3(256), 0, stream, q.image, big, q.B, q.img, q.patch);
     POPE_TRY(pope_check_launch());
     for (int b = 0; b < q.B; ++b) {   // the position table is per token, the same for every image: one GEMM per image
         const size_t r0 = size_t(b) * g * g;
@@ -240,7 +228,7 @@ int pope_launch_sam_encoder_f32mfma(const SamEncParams& q, hipStream_t stream) {
     }
     // neck (image_encoder.py:89-105): 1x1 conv (no bias) -> LayerNorm2d -> 3x3 conv pad 1 (no bias) -> LayerNorm2d
     POPE_TRY(gemm(x, rows, q.neck0_wp, nullptr, t1, oc, dim, EPI_BIAS, nullptr, nullptr));
-    hipLaunchKernelGGL(sam32_ln2d_kernel<true>, dim3(grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w, q.neck1_b, t1b, q.B, g,
+    hipLaunchKernelGGL(sam32_ln2d_kernel<true>, dim3(pope_grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w, q.neck1_b, t1b, q.B, g,
                        oc, neck_eps);
     POPE_TRY(pope_check_launch());
     {
@@ -255,9 +243,8 @@ int pope_launch_sam_encoder_f32mfma(const SamEncParams& q, hipStream_t stream) {
         c.conv_wp = Wp;
         POPE_TRY(pope_launch_gemm_nt_f32(c, stream));
     }
-    hipLaunchKernelGGL(sam32_ln2d_kernel<false>, dim3(grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out, q.B, g, oc,
+    hipLaunchKernelGGL(sam32_ln2d_kernel<false>, dim3(pope_grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out, q.B, g, oc,
                        neck_eps);
     POPE_TRY(pope_check_launch());
-#undef POPE_TRY
     return POPE_OK;
 }

@@ -5,7 +5,7 @@ fp64 at its edges, and bit for bit against its small-batch twin.
     x  = res + gamma * (A . W^T + bias)          fp32 residual stream (may alias res; res_mod > 0: row % res_mod of a table)
     xn = LayerNorm(x; ln_w, ln_b, eps)           activation planes, or fp32 (the final norm)
 on RM x 384 row tiles (RM = 192 or 128, chosen per launch from the CU count) in a persistent stream over min(tiles, CUs)
-workgroups.  The ViT runs it past the `small` switch of capi.hip; below the switch it runs the twin instead:
+workgroups.  The ViT runs it past the `small` switch of vit_forward.hip; below the switch it runs the twin instead:
 `pope_linear_planes_f32(..., EPI_BIAS_LS_RES)` (tile16) followed by `pope_layernorm_rowln_order_f32`, claimed bit-identical.
 Every threshold here is computed from the device's CU count by a Python mirror of the launcher; torch.profiler confirms the
 geometry and the RES_TABLE instantiation by kernel name.  Each case checks x against fp64 computed from the decoded planes
@@ -57,7 +57,7 @@ def rowln_grid(M, cu):
 
 
 def vit_small(rows, cu):
-    """capi.hip vit_forward_impl: below this the ViT runs the twin (tile16 LS_RES GEMM + layernorm_rowln_order)."""
+    """vit_forward.hip vit_forward_impl: below this the ViT runs the twin (tile16 LS_RES GEMM + layernorm_rowln_order)."""
     return 3 * _cdiv(rows, 128) <= 2 * cu
 
 
