@@ -6,18 +6,24 @@ DINOv2-S/14 patch descriptors for both images of every pair (476x630 centre crop
 dense dual-softmax / mutual-NN matching of the 1530x1530 descriptor pairs (BASELINE config 3:
 "Extract + dense cosine-sim matcher + mutual-NN on 640x480 pairs, batch=128").
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2           # the headline line alone
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full    # + self-check, other precisions and models, legs, CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W      # no launcher: starts that same command itself (self_launch)
 
 Pairs are independent: every rank works on its own batch (weak scaling, no data-path collective);
 the only exchange is the RCCL all_gather of per-pair match counts at the end of each step.
-Rank 0 prints ONE JSON line.  After the timed region the step's own outputs are spot-checked (pairs of the batch
-re-run one at a time must reproduce them bit for bit): `"verified": true`, non-zero exit otherwise.  At N = 1 the
-default run also times a short strict-fp32 leg (`strict_f32`), BASELINE config 5's two encoders (`config5`) and the CPU
-oracle (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed step returned as .npy files (dump_outputs), so
-that two builds can be compared output for output on the same seeded inputs.
+Rank 0 prints ONE JSON line.  A plain run does what the headline figure needs and no more: set-up, warm-up, the timed
+steps (with the in-situ HIP events of the `kernels` / `roofline` entries, which are part of those steps), the output dump
+and the line.  `--dump-outputs DIR` writes what the last timed step returned as .npy files (dump_outputs), so that two
+builds can be compared output for output on the same seeded inputs.
+
+`--full` adds everything else the benchmark measures or checks, after the timed region: the step's own outputs are
+spot-checked (pairs of the batch re-run one at a time must reproduce them bit for bit): `"verified": true`, non-zero exit
+otherwise; and at N = 1 a short strict-fp32 leg (`strict_f32`), BASELINE config 5's two encoders (`config5`), the
+secondary legs of bench_legs.py and the CPU oracle (`cpu_baseline`).  The `--no-*` options drop single parts of a `--full`
+run.
 
 `--workload linemod` (BASELINE config 4): one step = one pass over the 5 796 pair ids of the LINEMOD evaluation list
 (tests/golden/linemod_pairs.json; pixels synthetic, keyed by pair id), sharded contiguously over the ranks, walked
@@ -207,7 +213,7 @@ def self_launch(n):
     return proc.wait()
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -216,19 +222,24 @@ def main():
                     help="batch128 = BASELINE config 3 (the headline metric); linemod = config 4 (whole pair list per step)")
     ap.add_argument("--pairs", type=int, default=128, help="pairs per GPU per step (BASELINE config 3) / per batch (linemod)")
     ap.add_argument("--chunk", type=int, default=64, help="images per ViT launch sequence (BASELINE config 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the self-check of the step's "
+                         "outputs (`verified`) and, at N = 1, the strict-fp32 leg, BASELINE config 5, the legs of bench_legs.py "
+                         "and the CPU baseline; the --no-* options below drop single parts of such a run")
     ap.add_argument("--cpu-pairs", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle runs (`cpu_baseline` entries)")
     ap.add_argument("--no-kernel-table", action="store_true")
-    ap.add_argument("--no-strict-f32", action="store_true", help="skip the short strict-fp32 leg of the N = 1 run")
+    ap.add_argument("--no-strict-f32", action="store_true", help="--full: skip the short strict-fp32 leg of the N = 1 run")
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the short BASELINE config 5 leg (DINOv2 ViT-L/14 and the SAM ViT-H image encoder) of the N = 1 run")
+                    help="--full: skip the short BASELINE config 5 leg (DINOv2 ViT-L/14 and the SAM ViT-H image encoder) of the N = 1 run")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the LoFTR Matcher / driver-step / pose legs of the N = 1 run (bench_legs.py)")
+                    help="--full: skip the LoFTR Matcher / driver-step / pose legs of the N = 1 run (bench_legs.py)")
     ap.add_argument("--only", choices=["loftr_matcher", "driver_step", "pose"], default=None,
-                    help="profiling only: run just this leg (no headline line; prints the leg's JSON)")
+                    help="profiling only: run just this leg (loftr_matcher, driver_step: no headline line, prints the leg's JSON; "
+                         "pose: the headline run followed by the pose leg)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="profiling only: skip the self-check (its batch-1 launches would enter rocprof's per-kernel averages); "
-                         "the line then carries \"verified\": null")
+                    help="--full, profiling only: skip the self-check (its batch-1 launches would enter rocprof's per-kernel "
+                         "averages); the line then carries \"verified\": null, as a plain run's does")
     ap.add_argument("--from-host", action="store_true",
                     help="add a leg that starts from uint8 640x480 frames in pinned HOST memory (PCIe upload on a copy stream, "
                          "crop + normalise on the GPU); reported as `from_host`, never as `value`")
@@ -246,6 +257,34 @@ def main():
                     help="after the timed steps, write what the last timed step returned (rank 0's share) as DIR/<name>.npy, "
                          "float32 / float64, under 64 MB in all (a fixed seeded sample of rows of the largest arrays, "
                          "their row numbers in DIR/<name>_rows.npy); the same arguments give the same inputs on every run")
+    return ap
+
+
+def extras(args, world=1, linemod=False):
+    """What a run does beyond set-up, warm-up, the timed steps, the dump and the line: the names of its parts.  A plain run
+    has none; `--full` has the self-check on every rank and, on one GPU with the batch128 workload, every leg that its
+    `--no-*` option does not drop (the CPU baseline: any workload); `--from-host` and `--only pose` ask for their leg by name."""
+    one = world == 1 and not linemod
+    todo = set()
+    if args.full and not args.no_verify:
+        todo.add("verify")
+    if args.full and one and args.precision != "f32" and not args.no_strict_f32:
+        todo.add("strict_f32")
+    if one and args.from_host:
+        todo.add("from_host")
+    if args.full and one and not args.no_config5:
+        todo.add("config5")
+    if one and ((args.full and not args.no_legs) or args.only == "pose"):
+        todo.add("pose")
+        if args.only is None:
+            todo.add("legs")
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        todo.add("cpu_baseline")
+    return todo
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -386,14 +425,16 @@ def main():
         shapes = dump_outputs(dict(out, list_counts=counts) if linemod else out, args.dump_outputs)
         print(f"bench.py: wrote {len(shapes)} arrays to {args.dump_outputs}: {shapes}", file=sys.stderr)
 
-    # ---- self-check of the timed step's own outputs (every rank; all must pass) --------------------------------
+    # ---- self-check of the timed step's own outputs (--full; every rank; all must pass) ------------------------
+    todo = extras(args, world, linemod)
+    verify = "verify" in todo
     if linemod:
         v_img0, v_img1 = last["img"]
         picks = sorted({0, len(out["counts"]) // 2, len(out["counts"]) - 1})
     else:
         v_img0, v_img1 = img0, img1
         picks = sorted({0, args.pairs // 2, args.pairs - 1})
-    failures = [] if args.no_verify else verify_step(model, v_img0, v_img1, out, picks)
+    failures = verify_step(model, v_img0, v_img1, out, picks) if verify else []
     if counts.numel() != pairs_per_step_total:
         failures.append(f"gathered {counts.numel()} counts for {pairs_per_step_total} pairs")
     if model.overflow_events:
@@ -401,7 +442,7 @@ def main():
     ok = torch.tensor([0 if failures else 1], dtype=torch.int32, device=coll_device)
     if world > 1:
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-    verified = None if args.no_verify else bool(int(ok))
+    verified = bool(int(ok)) if verify else None
 
     total_pairs = pairs_per_step_total * args.steps
     value = total_pairs / elapsed
@@ -423,8 +464,9 @@ def main():
         "achieved_tflops_whole_step": round(value * flops_per_pair() / 1e12 / world, 2),
         "matches_per_pair_mean": round(float(counts.float().mean()), 1),
         "verified": verified,
-        "verified_note": f"pairs {picks} of the last timed step re-run one at a time (batch-1 ViT + batch-1 matcher): "
-                         "descriptors, match indices and confidences bit-identical; counts consistent; no range-guard event",
+        "verified_note": (f"pairs {picks} of the last timed step re-run one at a time (batch-1 ViT + batch-1 matcher): "
+                          "descriptors, match indices and confidences bit-identical; counts consistent; no range-guard event")
+                         if verify else "not checked: the self-check of the timed step's outputs runs with --full (without --no-verify)",
     }
     if linemod:
         result["batches_per_rank_per_step"] = n_batches
@@ -443,15 +485,16 @@ def main():
     elif tab and rank == 0:
         result["kernels"] = tab
 
-    # ---- N = 1 extras: strict-fp32 leg (driver-observed figure for the fp32-MFMA mode) and the CPU oracle -------
-    if rank == 0 and world == 1 and not linemod and args.precision != "f32" and not args.no_strict_f32:
+    # ---- N = 1 extras of a --full run: strict-fp32 leg (driver-observed figure for the fp32-MFMA mode), config 5, the
+    # legs of bench_legs.py and the CPU oracle (--from-host and --only pose ask for their leg by name) ---------------
+    if "strict_f32" in todo:
         result["strict_f32"] = strict_f32_leg(model, pipe, img0, img1, args)
-    if rank == 0 and world == 1 and not linemod and args.from_host:
+    if "from_host" in todo:
         result["from_host"] = from_host_leg(pipe, args, device)
-    if rank == 0 and world == 1 and not linemod and not args.no_config5:
+    if "config5" in todo:
         torch.cuda.empty_cache()
         result["config5"] = config5_leg(device)
-    if rank == 0 and world == 1 and not linemod and (not args.no_legs or args.only == "pose"):
+    if "pose" in todo:
         import bench_legs
         cpu = not args.no_cpu_baseline
         torch.cuda.empty_cache()
@@ -459,7 +502,7 @@ def main():
             result["pose"] = bench_legs.pose_leg(pipe, img0, img1, device, cpu_baseline=cpu)
         except Exception as e:  # noqa: BLE001 — reported in place, the headline line stands
             result["pose"] = {"error": f"{type(e).__name__}: {e}"}
-        if args.only is None:
+        if "legs" in todo:
             try:   # BASELINE config 2: extraction only, one 64-image batch
                 result["extract_only"] = bench_legs.extract_only_leg(model, img0, device, chunk=args.chunk)
             except Exception as e:  # noqa: BLE001
@@ -536,7 +579,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 result["loftr_matcher"] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N = 1 only (the other ranks would idle)
+    if "cpu_baseline" in todo:  # reported at N = 1 only (the other ranks would idle)
         result["cpu_baseline"] = cpu_baseline(args.cpu_pairs)
     if world > 1:
         dist.barrier()

@@ -8,7 +8,7 @@ if [ "$1" = "-r" ]; then ROUNDS=$2; shift 2; fi
 mkdir -p gpurun_out
 for r in $(seq $ROUNDS); do
   for lib in "$@"; do
-    POPE_LIB_PATH=$(realpath $lib) timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-strict-f32 --no-legs --no-config5 \
+    POPE_LIB_PATH=$(realpath $lib) timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-strict-f32 --no-legs --no-config5 \
         > gpurun_out/ab_tmp.json 2> gpurun_out/ab_tmp.err || { grep -q '"metric"' gpurun_out/ab_tmp.json || { echo "$lib FAILED"; tail -5 gpurun_out/ab_tmp.err; exit 1; }; }   # (a lab build that fails the self-check still prints its line)
     python3 - "$lib" <<'PY'
 import json, sys

@@ -15,6 +15,6 @@ import bench_legs
 r = bench_legs.attention_ramp_leg(torch.device("cuda:0"))
 print(" ".join(f"{k}: {v['ms']:.3f} ms ({v['exact_pass_rate']:.2f})" for k, v in r["ramps_log2_units_per_tile"].items()))
 PY
-    POPE_LIB_PATH=$lib timeout -k 10 200 python bench.py --no-legs --no-config5 --no-strict-f32 --no-cpu-baseline 2>/dev/null | python -c "
+    POPE_LIB_PATH=$lib timeout -k 10 200 python bench.py --full --no-legs --no-config5 --no-strict-f32 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys;b=json.loads(sys.stdin.read());print('   headline', b['value'], b['roofline']['avg_ms_per_launch'], b['verified'])" | sed "s|^|[${lib:-product}] |"
 done

@@ -59,7 +59,7 @@ def test_bench_gpus_2_without_launcher(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                          "--pairs", "4", "--chunk", "4", "--rehearse-on-one-gpu", "--no-kernel-table"],
+                          "--pairs", "4", "--chunk", "4", "--rehearse-on-one-gpu", "--no-kernel-table", "--full"],
                          capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
