@@ -503,6 +503,24 @@ int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const in
  * (area = (x1 - x0) * (y1 - y0), iou = inter / (area_i + area_j - inter), fp32).  keep[n] int32 receives the kept indices
  * in score order, count[1] their number (both DEVICE). */
 int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_threshold, int* keep, int* count, void* stream);
+/* segment_anything/utils/amg.py:remove_small_regions, as automatic_mask_generator.py:postprocess_small_regions calls it
+ * twice per mask (mode "holes", then "islands"), for a whole batch of bit-packed masks in ONE launch and without OpenCV.
+ * packed[n, H, ceil(W / 32)] uint32 in the layout pope_sam_postprocess_f32 writes (bit (x & 31) of word (x >> 5); pad bits
+ * are not pixels and are ignored).  Per mask, with 8-connected components inside the H x W image:
+ *   holes: every component of the COMPLEMENT with fewer than min_area pixels is filled (the outer background is a component
+ *     like any other: a mask with fewer than min_area background pixels becomes all foreground);
+ *   islands, on the filled mask: every component with fewer than min_area pixels is removed; if all are that small, the
+ *     largest stays, on an exact tie the one whose first pixel comes first in raster order.
+ * Outputs: packed_out[n, H, ceil(W / 32)] (pad bits zero; packed_out == packed cleans in place, any other overlap is refused);
+ * unchanged[n] int32 = 1 unless one of the two steps met a component below min_area (0 even if the mask comes out identical,
+ * as for a single small island); boxes[n, 4] int32 XYXY of the cleaned mask (inclusive maxima, 0 0 0 0 for an empty mask:
+ * batched_mask_to_box); area[n] int32.  H * W < 2^24, min_area >= 0; n == 0 is a no-op.  One workgroup cleans one mask and at
+ * most 32 masks are in flight, so the workspace stops growing at n = 32; a mask's outputs depend neither on n nor on its
+ * place in the batch, and integer atomics only make them independent of the launch order.  workspace: 4-byte aligned. */
+size_t pope_sam_small_regions_workspace_bytes(int n, int H, int W);   /* 0 for an unsupported geometry or n <= 0 */
+int pope_sam_small_regions_u32(const unsigned* packed, int n, int H, int W, int min_area,
+                               unsigned* packed_out, int* unchanged, int* boxes, int* area,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- caller-side preprocessing, batched ------------------------------------------------- */
 

@@ -468,6 +468,19 @@ int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_t
     return pope_launch_sam_nms(boxes, scores, n, iou_threshold, keep, count, static_cast<hipStream_t>(stream));
 }
 
+size_t pope_sam_small_regions_workspace_bytes(int n, int H, int W) { return pope_sam_small_regions_workspace(n, H, W); }
+
+int pope_sam_small_regions_u32(const unsigned* packed, int n, int H, int W, int min_area, unsigned* packed_out, int* unchanged,
+                               int* boxes, int* area, void* workspace, size_t workspace_bytes, void* stream) {
+    SamRegionsArgs a{};
+    a.packed = packed; a.n = n; a.H = H; a.W = W; a.min_area = min_area;
+    a.packed_out = packed_out; a.unchanged = unchanged; a.boxes = boxes; a.area = area; a.ws = workspace; a.ws_bytes = workspace_bytes;
+    if (const int rc = pope_sam_small_regions_check(a)) return rc;   // before any HIP call
+    if (n == 0) return POPE_OK;
+    StreamDevice on_device(stream);
+    return pope_launch_sam_small_regions(a, static_cast<hipStream_t>(stream));
+}
+
 int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount,
                            const int* hk, int kh, const int* vstart, const int* vcount, const int* vk, int kv, int top, int left,
                            int ch, int cw, int row0, int nrows, const float* mean_host, const float* std_host, float* out,

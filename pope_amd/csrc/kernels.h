@@ -393,3 +393,17 @@ struct SamPostArgs {
 size_t pope_sam_postprocess_workspace(int img, int H, int W);
 int pope_launch_sam_postprocess(const SamPostArgs& a, hipStream_t stream);
 int pope_launch_sam_nms(const float* boxes, const float* scores, int n, float thresh, int* keep, int* count, hipStream_t stream);
+
+// SAM generator small-region clean-up (sam_regions.hip): the arguments of pope_sam_small_regions_u32
+struct SamRegionsArgs {
+    const unsigned* packed;
+    int n, H, W, min_area;
+    unsigned* packed_out;
+    int *unchanged, *boxes, *area;
+    void* ws;
+    size_t ws_bytes;
+};
+int pope_sam_small_regions_chunk();   // masks in flight: the workspace does not grow beyond that many
+size_t pope_sam_small_regions_workspace(int n, int H, int W);
+int pope_sam_small_regions_check(const SamRegionsArgs& a);   // no HIP call
+int pope_launch_sam_small_regions(const SamRegionsArgs& a, hipStream_t stream);

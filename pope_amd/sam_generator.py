@@ -5,7 +5,9 @@ and `build_sam.py`, for a single crop and point / box prompts.  The generator's 
 call (`pope_sam_postprocess_f32`, pope_amd/csrc/sam_postprocess.hip): from the 256 x 256 low-res logits of the masks that pass
 the IoU filter straight to per-mask counts, boxes, stability scores and bit-packed masks, without the 1024 x 1024 or the
 frame-sized fp32 tensors of `Sam.postprocess_masks`; the logits are bit-equal to torch's CPU `F.interpolate` (pope_amd/sam_amg.py
-restates the arithmetic), so counts, boxes and masks are exact.  Box NMS is `pope_sam_nms_f32`.  There is no torch fallback.
+restates the arithmetic), so counts, boxes and masks are exact.  Box NMS is `pope_sam_nms_f32`; the small-region clean-up is one
+launch over the packed masks of the NMS survivors (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip).  There is no
+torch fallback.
 
 Not supported: crop layers (`crop_n_layers > 0`), mask prompts, `output_mode="coco_rle"`.
 """
@@ -24,6 +26,7 @@ from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer
 from .sam_encoder import ImageEncoderViT
 
 NMS_MAX = 2048   # boxes per pope_sam_nms_f32 call
+CLEAN_CHUNK = 32  # masks in flight in pope_sam_small_regions_u32: its workspace stops growing there
 
 
 # ---- device ops ----------------------------------------------------------------------------------------------------------
@@ -384,15 +387,46 @@ class SamAutomaticMaskGenerator:
         return anns
 
 
+def pack_on_device(masks):
+    """bool [n, H, W] -> int32 words [n, H, ceil(W / 32)] (torch, on the masks' device), pad bits zero."""
+    n, H, W = masks.shape
+    words = sam_amg.row_words(W)
+    bits = F.pad(masks.to(torch.int32), (0, words * 32 - W)).view(n, H, words, 32)
+    shifts = torch.arange(32, device=masks.device, dtype=torch.int32)
+    return (bits << shifts).sum(-1).to(torch.int32)      # distinct bits: the sum is their OR (bit 31 counts as -2^31)
+
+
+def clean_masks_packed(packed, W, min_area):
+    """`remove_small_regions` (holes, then islands, 8-connectivity) of a batch of bit-packed masks in one launch
+    (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip), without a host read: int32 words [n, H, ceil(W / 32)] ->
+    (cleaned words, unchanged bool [n], boxes int32 [n, 4] XYXY of the cleaned masks, area int32 [n])."""
+    require_cuda(packed, "clean_masks_packed")
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != sam_amg.row_words(W):
+        raise TypeError(f"clean_masks_packed: expected int32 words [n, H, {sam_amg.row_words(W)}] for W = {W}, "
+                        f"got {packed.dtype} {tuple(packed.shape)}")
+    packed = packed.contiguous()
+    n, H, _ = packed.shape
+    dev = packed.device
+    out = torch.empty_like(packed)
+    unchanged = torch.empty(n, dtype=torch.int32, device=dev)
+    boxes = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    area = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out, unchanged.to(torch.bool), boxes, area
+    need = int(_lib.lib().pope_sam_small_regions_workspace_bytes(n, H, int(W)))
+    if need <= 0 or min_area < 0:
+        raise ValueError(f"clean_masks_packed: unsupported geometry or threshold (masks {H} x {W}, min_area {min_area})")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with on_device_of(packed):
+        check(_lib.lib().pope_sam_small_regions_u32(ptr(packed), n, H, int(W), int(min_area), ptr(out), ptr(unchanged), ptr(boxes),
+                                                    ptr(area), ptr(ws), ws.numel(), stream_of(dev)), "pope_sam_small_regions_u32")
+    return out, unchanged.to(torch.bool), boxes, area
+
+
 def clean_masks(masks, min_area):
     """Holes, then islands, below `min_area` removed from bool [n, H, W] (device): (masks, unchanged bool [n])."""
-    out, same = [], []
-    for m in masks:
-        m, c0 = sam_amg.remove_small_regions(m, min_area, "holes")
-        m, c1 = sam_amg.remove_small_regions(m, min_area, "islands")
-        out.append(m)
-        same.append(not (c0 or c1))
-    return torch.stack(out), torch.tensor(same, device=masks.device)
+    packed, unchanged, _, _ = clean_masks_packed(pack_on_device(masks), masks.shape[2], min_area)
+    return unpack_on_device(packed, masks.shape[2]), unchanged
 
 
 def mask_boxes(masks):
@@ -409,14 +443,12 @@ def mask_boxes(masks):
 
 
 def postprocess_small_regions(data, W, min_area, nms_thresh):
-    """automatic_mask_generator.py:325-375 on the device: small holes and islands removed (8-connectivity), changed masks score
-    0 and unchanged ones 1 in a second NMS, boxes (and masks) of the changed survivors recomputed.  Returns (data, masks)."""
-    masks = unpack_on_device(data["packed"], W)
-    masks, unchanged = clean_masks(masks, min_area)
-    boxes = mask_boxes(masks)
+    """automatic_mask_generator.py:325-375 on the device: small holes and islands removed (8-connectivity) from the packed
+    masks by `clean_masks_packed`, changed masks score 0 and unchanged ones 1 in a second NMS on the cleaned masks' boxes, boxes
+    of the changed survivors replaced; only the survivors are unpacked.  Returns (data, masks)."""
+    packed, unchanged, boxes, _ = clean_masks_packed(data["packed"], W, min_area)
     keep = box_nms(boxes, unchanged.to(torch.float32), nms_thresh)
-    changed = ~unchanged
-    new_boxes = torch.where(changed[:, None], boxes, data["boxes"])
+    new_boxes = torch.where(unchanged[:, None], data["boxes"], boxes)
     data = dict(data, boxes=new_boxes)
     data = {k: v[keep] for k, v in data.items() if k != "packed"}
-    return data, masks[keep]
+    return data, unpack_on_device(packed[keep], W)

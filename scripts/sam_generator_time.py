@@ -5,12 +5,18 @@
      the per-mask Python loop that turns change indices into count lists is host work and is left out of both);
  (3) `generate()` of one frame split into encoder / decoder / post-processing (synthetic ViT-B weights, filters off, so the
      whole batch reaches NMS; min_mask_region_area=0).
+With --min-mask-region-area N > 0 additionally, 3 warm-up calls and the median of 10 each:
+ (4) the small-region clean-up stage alone (`postprocess_small_regions`: clean-up, second NMS, unpacking of the survivors) on
+     the NMS survivors of `synth.sam_generator_case("frame")`;
+ (5) the same stage on 64 random-blob masks of 480 x 640 (a box-blurred noise field cut at a quantile);
+ (6) `generate()` of one 480 x 640 frame with `min_mask_region_area=N` (filters off, as in (3)).
 Prints medians, minima and the bytes/s of (1) against its floor: the low-res logits read once plus the packed masks written.
-usage: python scripts/sam_generator_time.py [--reps 20] [--skip-generate]"""
+usage: python scripts/sam_generator_time.py [--reps 20] [--skip-generate] [--skip-postprocess] [--min-mask-region-area 250]"""
 import argparse
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -50,14 +56,61 @@ def reference_tail(low, input_size, hw, thr=0.0, off=1.0):
     return stability, boxes, change
 
 
+def box_blur(f, k):
+    """Box filter of odd width k along both axes of [H, W] (edges replicated)."""
+    r = k // 2
+    for ax in (0, 1):
+        p = np.concatenate([np.repeat(np.take(f, [0], ax), r + 1, ax), f, np.repeat(np.take(f, [-1], ax), r, ax)], ax)
+        c = np.cumsum(p, ax, dtype=np.float64)
+        n = f.shape[ax]
+        f = (np.take(c, range(k, k + n), ax) - np.take(c, range(0, n), ax)) / k
+    return f
+
+
+def blob_masks(n, H, W, seed=11):
+    rng = np.random.default_rng(seed)
+    out = np.empty((n, H, W), bool)
+    for i in range(n):
+        k = (41, 61, 81)[i % 3]
+        f = box_blur(box_blur(rng.standard_normal((H, W)), k), k)
+        out[i] = f > np.quantile(f, (0.5, 0.8, 0.3, 0.9)[i % 4])
+    return out
+
+
+def time_cleanup(dev, min_area):
+    """Rows (4) and (5): `postprocess_small_regions` alone, device events around the call."""
+    low, iou, input_size, hw = synth.sam_generator_case("frame")
+    d = sg.process_low_res(low.to(dev), iou.to(dev), input_size, hw, 0.9, 0.95, 0.0, 1.0)
+    keep = sg.box_nms(d["boxes"], d["iou_preds"], 0.35)
+    frame = {k: d[k][keep].contiguous() for k in ("index", "boxes", "packed")}
+    blobs = torch.as_tensor(sam_amg.pack_masks(blob_masks(64, *hw)).view(np.int32), device=dev)
+    blob = {"index": torch.arange(64, device=dev), "boxes": sg.mask_boxes(sg.unpack_on_device(blobs, hw[1])), "packed": blobs}
+    for name, data in (("(4) clean-up stage, frame survivors", frame), ("(5) clean-up stage, 64 random blobs", blob)):
+        out, masks = sg.postprocess_small_regions(data, hw[1], min_area, 0.35)
+        med, lo, hi = timed(lambda: sg.postprocess_small_regions(data, hw[1], min_area, 0.35), 10, 3)
+        print(f"{name:40s} n = {data['index'].numel():3d} -> {masks.shape[0]:3d} kept, {int(masks.sum())} pixels set   "
+              f"median {med:.3f} ms  min {lo:.3f}  max {hi:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skip-generate", action="store_true")
+    ap.add_argument("--skip-postprocess", action="store_true", help="leave out (1) and (2)")
+    ap.add_argument("--min-mask-region-area", type=int, default=0, help="> 0: time the small-region clean-up, rows (4) to (6)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     dev = "cuda:0"
     M, (H, W) = 768, (480, 640)
+    if a.min_mask_region_area > 0:
+        time_cleanup(dev, a.min_mask_region_area)
+    if not a.skip_postprocess:
+        time_postprocess(dev, a.reps, M, H, W)
+    if not a.skip_generate:
+        time_generate(dev, H, W, a.min_mask_region_area)
+
+
+def time_postprocess(dev, reps, M, H, W):
     low, iou, input_size, hw = synth.sam_generator_case("frame", M=M)
     low, iou = low.to(dev), iou.to(dev)
     floor = M * 256 * 256 * 4 + M * H * sam_amg.row_words(W) * 4
@@ -74,15 +127,17 @@ def main():
     same = bool(torch.equal(stats[:, 3:7], boxes_ref)) and bool(torch.equal(torch.nan_to_num(stats[:, 7].view(torch.float32), -1),
                                                                             torch.nan_to_num(st_ref, -1)))
     print(f"boxes and stability scores of the fused pass equal the torch path on this GPU: {same}")
-    k_med, k_min, k_max = timed(fused_kernel, a.reps)
-    s_med, s_min, s_max = timed(fused_stage, a.reps)
-    r_med, r_min, r_max = timed(lambda: reference_tail(low, input_size, hw), max(5, a.reps // 2))
+    k_med, k_min, k_max = timed(fused_kernel, reps)
+    s_med, s_min, s_max = timed(fused_stage, reps)
+    r_med, r_min, r_max = timed(lambda: reference_tail(low, input_size, hw), max(5, reps // 2))
     print(f"(1) fused kernels only      median {k_med:.3f} ms  min {k_min:.3f}  max {k_max:.3f}   "
           f"{floor / k_med / 1e6:.1f} GB/s of the {floor / 1e6:.1f} MB floor (min: {floor / k_min / 1e6:.1f} GB/s)")
     print(f"(1) fused + filters + NMS   median {s_med:.3f} ms  min {s_min:.3f}  max {s_max:.3f}")
     print(f"(2) torch reference path    median {r_med:.3f} ms  min {r_min:.3f}  max {r_max:.3f}   ratio (2)/(1) = {r_med / s_med:.1f}")
-    if a.skip_generate:
-        return
+
+
+def time_generate(dev, H, W, min_area):
+    hw = (H, W)
     sam = sg.build_sam_vit_b()
     sd = {"image_encoder." + k: v for k, v in synth.synthetic_sam_encoder_state_dict(seed=0, dim=768, depth=12, heads=12,
                                                                                       global_idx=(2, 5, 8, 11)).items()}
@@ -108,6 +163,16 @@ def main():
     p = timed(post, 5, 1)
     for name, t in (("encoder (set_image, host resize included)", e), ("decoder (256 prompts x 3)", c), ("post-processing", p)):
         print(f"(3) {name:44s} median {t[0]:.3f} ms  min {t[1]:.3f}")
+    if min_area > 0:
+        full = sg.SamAutomaticMaskGenerator(sam, pred_iou_thresh=0.0, stability_score_thresh=0.0, min_mask_region_area=min_area)
+        off = timed(lambda: gen.generate(frame), 10, 3)
+        t0 = time.perf_counter()
+        full.generate(frame)                                   # ends in a device-to-host copy
+        reps, warm = (10, 3) if time.perf_counter() - t0 < 2.0 else (3, 1)      # a call of seconds: fewer of them
+        on = timed(lambda: full.generate(frame), reps, warm)
+        print(f"(6) {warm} warm-up, {reps} timed calls")
+        print(f"(6) generate(), min_mask_region_area=0: {len(gen.generate(frame))} records   median {off[0]:.3f} ms  min {off[1]:.3f}")
+        print(f"(6) generate(), min_mask_region_area={min_area}: {len(full.generate(frame))} records   median {on[0]:.3f} ms  min {on[1]:.3f}")
 
 
 if __name__ == "__main__":
