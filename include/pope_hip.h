@@ -503,6 +503,14 @@ int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const in
  * (area = (x1 - x0) * (y1 - y0), iou = inter / (area_i + area_j - inter), fp32).  keep[n] int32 receives the kept indices
  * in score order, count[1] their number (both DEVICE). */
 int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_threshold, int* keep, int* count, void* stream);
+/* pope_sam_nms_f32 for S independent segments in ONE launch (one workgroup per segment; the same device function, so a segment's
+ * result is bit for bit that of pope_sam_nms_f32 on its boxes).  boxes[n, 4], scores[n]; seg_offsets[S + 1] int32 (DEVICE,
+ * non-decreasing, within [0, n]): segment s owns boxes seg_offsets[s] .. seg_offsets[s + 1] - 1, at most 2048 of them.
+ * keep[n] int32: the kept boxes of segment s start at keep[seg_offsets[s]], in score order, as GLOBAL indices into n;
+ * count[S] their numbers (0 for an empty segment).  The offsets are clamped to [0, n] on the device; a segment longer than 2048
+ * is not run and gets count -1 (callers that know the offsets on the host refuse it before the call).  S == 0 is a no-op. */
+int pope_sam_nms_segments_f32(const float* boxes, const float* scores, const int* seg_offsets, int S, int n, float iou_threshold,
+                              int* keep, int* count, void* stream);
 /* segment_anything/utils/amg.py:remove_small_regions, as automatic_mask_generator.py:postprocess_small_regions calls it
  * twice per mask (mode "holes", then "islands"), for a whole batch of bit-packed masks in ONE launch and without OpenCV.
  * packed[n, H, ceil(W / 32)] uint32 in the layout pope_sam_postprocess_f32 writes (bit (x & 31) of word (x >> 5); pad bits
@@ -521,6 +529,21 @@ size_t pope_sam_small_regions_workspace_bytes(int n, int H, int W);   /* 0 for a
 int pope_sam_small_regions_u32(const unsigned* packed, int n, int H, int W, int min_area,
                                unsigned* packed_out, int* unchanged, int* boxes, int* area,
                                void* workspace, size_t workspace_bytes, void* stream);
+/* segment_anything/utils/amg.py:mask_to_rle_pytorch for a batch of bit-packed masks.  packed[n, H, ceil(W / 32)] uint32 in the
+ * layout pope_sam_postprocess_f32 and pope_sam_small_regions_u32 write (bit (x & 31) of word (x >> 5); pad bits are not pixels
+ * and are ignored).  Per mask, flattened COLUMN-major (i = x * H + y) with a clear virtual pixel before i = 0: with
+ * t_0 < .. < t_k the indices where a pixel differs from its predecessor (a column's first pixel from the previous column's
+ * last), counts = [t_0, t_1 - t_0, .., H * W - t_k]: k + 2 entries, a leading 0 when pixel (0, 0) is set, [H * W] for a mask
+ * without a transition.  The output is ragged, so the entry is called twice:
+ *   counts == NULL: lengths[n] int32 receives the number of entries of every mask (at most H * W + 1);
+ *   counts != NULL: offsets[n + 1] int64 (DEVICE; the exclusive scan of the lengths, offsets[n] = their sum) and
+ *     capacity = the number of uint32 entries `counts` holds; mask i's counts are written at [offsets[i], offsets[i + 1]).
+ *     offsets[n] is read back first (one stream synchronisation): offsets[n] > capacity returns POPE_ERR_WORKSPACE and writes
+ *     nothing (no clipping); no mask writes outside [offsets[i], min(offsets[i + 1], capacity)) whatever the offsets say.
+ * H, W <= 2^14; n == 0 is a no-op.  One workgroup encodes one mask, without workspace and without atomics (integer arithmetic
+ * only): a mask's output depends neither on n nor on its place in the batch. */
+int pope_sam_rle_u32(const unsigned* packed, int n, int H, int W, int* lengths, const long long* offsets, unsigned* counts,
+                     long long capacity, void* stream);
 
 /* ---- caller-side preprocessing, batched ------------------------------------------------- */
 

@@ -156,6 +156,8 @@ PROTOTYPES = {
     "pope_sam_postprocess_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_double]
                                  + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "pope_sam_nms_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pope_sam_nms_segments_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pope_sam_rle_u32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_longlong, C.c_void_p]),
     "pope_sam_small_regions_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_sam_small_regions_u32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "pope_preprocess_u8_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3

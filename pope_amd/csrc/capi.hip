@@ -468,6 +468,14 @@ int pope_sam_nms_f32(const float* boxes, const float* scores, int n, float iou_t
     return pope_launch_sam_nms(boxes, scores, n, iou_threshold, keep, count, static_cast<hipStream_t>(stream));
 }
 
+int pope_sam_nms_segments_f32(const float* boxes, const float* scores, const int* seg_offsets, int S, int n, float iou_threshold,
+                              int* keep, int* count, void* stream) {
+    if (S < 0 || n < 0 || (S > 0 && (!seg_offsets || !count)) || (S > 0 && n > 0 && (!boxes || !scores || !keep))) return POPE_ERR_ARG;
+    if (S == 0) return POPE_OK;      // before any HIP call
+    StreamDevice on_device(stream);
+    return pope_launch_sam_nms_segments(boxes, scores, seg_offsets, S, n, iou_threshold, keep, count, static_cast<hipStream_t>(stream));
+}
+
 size_t pope_sam_small_regions_workspace_bytes(int n, int H, int W) { return pope_sam_small_regions_workspace(n, H, W); }
 
 int pope_sam_small_regions_u32(const unsigned* packed, int n, int H, int W, int min_area, unsigned* packed_out, int* unchanged,
@@ -479,6 +487,16 @@ int pope_sam_small_regions_u32(const unsigned* packed, int n, int H, int W, int 
     if (n == 0) return POPE_OK;
     StreamDevice on_device(stream);
     return pope_launch_sam_small_regions(a, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_rle_u32(const unsigned* packed, int n, int H, int W, int* lengths, const long long* offsets, unsigned* counts,
+                     long long capacity, void* stream) {
+    SamRleArgs a{};
+    a.packed = packed; a.n = n; a.H = H; a.W = W; a.lengths = lengths; a.offsets = offsets; a.counts = counts; a.capacity = capacity;
+    if (const int rc = pope_sam_rle_check(a)) return rc;   // before any HIP call
+    if (n == 0) return POPE_OK;
+    StreamDevice on_device(stream);
+    return pope_launch_sam_rle(a, static_cast<hipStream_t>(stream));
 }
 
 int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount,

@@ -393,6 +393,8 @@ struct SamPostArgs {
 size_t pope_sam_postprocess_workspace(int img, int H, int W);
 int pope_launch_sam_postprocess(const SamPostArgs& a, hipStream_t stream);
 int pope_launch_sam_nms(const float* boxes, const float* scores, int n, float thresh, int* keep, int* count, hipStream_t stream);
+int pope_launch_sam_nms_segments(const float* boxes, const float* scores, const int* seg_offsets, int S, int n, float thresh,
+                                 int* keep, int* count, hipStream_t stream);
 
 // SAM generator small-region clean-up (sam_regions.hip): the arguments of pope_sam_small_regions_u32
 struct SamRegionsArgs {
@@ -407,3 +409,15 @@ int pope_sam_small_regions_chunk();   // masks in flight: the workspace does not
 size_t pope_sam_small_regions_workspace(int n, int H, int W);
 int pope_sam_small_regions_check(const SamRegionsArgs& a);   // no HIP call
 int pope_launch_sam_small_regions(const SamRegionsArgs& a, hipStream_t stream);
+
+// SAM generator run-length encoding (sam_rle.hip): the arguments of pope_sam_rle_u32
+struct SamRleArgs {
+    const unsigned* packed;
+    int n, H, W;
+    int* lengths;               // counts == nullptr: the lengths are written
+    const long long* offsets;   // counts != nullptr: [n + 1], device
+    unsigned* counts;
+    long long capacity;
+};
+int pope_sam_rle_check(const SamRleArgs& a);   // no HIP call
+int pope_launch_sam_rle(const SamRleArgs& a, hipStream_t stream);

@@ -187,54 +187,80 @@ __global__ __launch_bounds__(kThreads) void sam_post_kernel(PostK k) {
 
 // Greedy NMS of n <= kNmsMax boxes in one workgroup: stable rank by score (descending), then a serial walk over the ranked
 // boxes; each kept box marks what it suppresses in parallel.  IoU exactly as torchvision's nms kernel computes it in fp32.
-__global__ __launch_bounds__(1024) void sam_nms_kernel(const float* boxes, const float* scores, int n, float thresh, int* keep,
-                                                       int* count) {
-    __shared__ float4 sb[kNmsMax];
-    __shared__ float sarea[kNmsMax];
-    __shared__ float sscore[kNmsMax];
-    __shared__ int sorder[kNmsMax];
-    __shared__ unsigned char dead[kNmsMax];
+// `boxes`, `scores` and `keep` point at the workgroup's own boxes; the kept indices are written as `base` + local index.
+struct NmsShared {
+    float4 sb[kNmsMax];
+    float sarea[kNmsMax];
+    float sscore[kNmsMax];
+    int sorder[kNmsMax];
+    unsigned char dead[kNmsMax];
+};
+
+__device__ inline void sam_nms_workgroup(NmsShared& sh, const float* boxes, const float* scores, int n, float thresh, int base,
+                                         int* keep, int* count) {
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += 1024) {
         const float s = scores[i];
-        sscore[i] = s == s ? s : -INFINITY;   // a nan score ranks last (keeps the ranks a permutation)
-        dead[i] = 0;
+        sh.sscore[i] = s == s ? s : -INFINITY;   // a nan score ranks last (keeps the ranks a permutation)
+        sh.dead[i] = 0;
     }
     __syncthreads();
     for (int i = tid; i < n; i += 1024) {
-        const float s = sscore[i];
+        const float s = sh.sscore[i];
         int rank = 0;
         for (int q = 0; q < n; ++q) {
-            const float sq = sscore[q];
+            const float sq = sh.sscore[q];
             rank += (sq > s) || (sq == s && q < i);
         }
-        sorder[rank] = i;
+        sh.sorder[rank] = i;
     }
     __syncthreads();
     for (int r = tid; r < n; r += 1024) {
-        const float* b = boxes + size_t(sorder[r]) * 4;
-        sb[r] = make_float4(b[0], b[1], b[2], b[3]);
-        sarea[r] = __fmul_rn(b[2] - b[0], b[3] - b[1]);
+        const float* b = boxes + size_t(sh.sorder[r]) * 4;
+        sh.sb[r] = make_float4(b[0], b[1], b[2], b[3]);
+        sh.sarea[r] = __fmul_rn(b[2] - b[0], b[3] - b[1]);
     }
     __syncthreads();
     int kept = 0;
     for (int i = 0; i < n; ++i) {
-        if (dead[i]) continue;   // workgroup-uniform: dead[] only changes between barriers
-        if (tid == 0) keep[kept] = sorder[i];
+        if (sh.dead[i]) continue;   // workgroup-uniform: dead[] only changes between barriers
+        if (tid == 0) keep[kept] = base + sh.sorder[i];
         ++kept;
-        const float4 bi = sb[i];
-        const float ai = sarea[i];
+        const float4 bi = sh.sb[i];
+        const float ai = sh.sarea[i];
         for (int q = i + 1 + tid; q < n; q += 1024) {
-            const float4 bq = sb[q];
+            const float4 bq = sh.sb[q];
             const float w = fmaxf(0.0f, fminf(bi.z, bq.z) - fmaxf(bi.x, bq.x));
             const float h = fmaxf(0.0f, fminf(bi.w, bq.w) - fmaxf(bi.y, bq.y));
             const float inter = __fmul_rn(w, h);
-            const float ovr = __fdiv_rn(inter, (ai + sarea[q]) - inter);
-            if (ovr > thresh) dead[q] = 1;
+            const float ovr = __fdiv_rn(inter, (ai + sh.sarea[q]) - inter);
+            if (ovr > thresh) sh.dead[q] = 1;
         }
         __syncthreads();
     }
     if (tid == 0) *count = kept;
+}
+
+__global__ __launch_bounds__(1024) void sam_nms_kernel(const float* boxes, const float* scores, int n, float thresh, int* keep,
+                                                       int* count) {
+    __shared__ NmsShared sh;
+    sam_nms_workgroup(sh, boxes, scores, n, thresh, 0, keep, count);
+}
+
+// S independent segments, one workgroup each: segment s owns boxes seg_offsets[s] .. seg_offsets[s + 1] - 1 of the n.  The
+// offsets are device data, so they are clamped to [0, n] here; a segment that does not fit the LDS arrays is not run at all.
+__global__ __launch_bounds__(1024) void sam_nms_segments_kernel(const float* boxes, const float* scores, const int* seg_offsets,
+                                                                int n, float thresh, int* keep, int* count) {
+    __shared__ NmsShared sh;
+    const int s = blockIdx.x;
+    int b = seg_offsets[s], e = seg_offsets[s + 1];
+    b = b < 0 ? 0 : (b > n ? n : b);
+    e = e < b ? b : (e > n ? n : e);
+    if (e - b > kNmsMax) {           // workgroup-uniform
+        if (threadIdx.x == 0) count[s] = -1;
+        return;
+    }
+    sam_nms_workgroup(sh, boxes + size_t(b) * 4, scores + b, e - b, thresh, b, keep + b, count + s);
 }
 
 // Largest band (16, 8, .. 1 output rows) whose stage-1 rows fit the LDS budget; the tables are recomputed on the host with the
@@ -298,5 +324,13 @@ int pope_launch_sam_postprocess(const SamPostArgs& a, hipStream_t stream) {
 int pope_launch_sam_nms(const float* boxes, const float* scores, int n, float thresh, int* keep, int* count, hipStream_t stream) {
     if (n < 0 || n > kNmsMax || !count || (n > 0 && (!boxes || !scores || !keep))) return POPE_ERR_ARG;
     hipLaunchKernelGGL(sam_nms_kernel, dim3(1), dim3(1024), 0, stream, boxes, scores, n, thresh, keep, count);
+    return pope_check_launch();
+}
+
+int pope_launch_sam_nms_segments(const float* boxes, const float* scores, const int* seg_offsets, int S, int n, float thresh,
+                                 int* keep, int* count, hipStream_t stream) {
+    if (S < 0 || n < 0 || (S > 0 && (!seg_offsets || !count)) || (S > 0 && n > 0 && (!boxes || !scores || !keep))) return POPE_ERR_ARG;
+    if (S == 0) return POPE_OK;
+    hipLaunchKernelGGL(sam_nms_segments_kernel, dim3(S), dim3(1024), 0, stream, boxes, scores, seg_offsets, n, thresh, keep, count);
     return pope_check_launch();
 }

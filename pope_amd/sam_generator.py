@@ -6,8 +6,10 @@ call (`pope_sam_postprocess_f32`, pope_amd/csrc/sam_postprocess.hip): from the 2
 the IoU filter straight to per-mask counts, boxes, stability scores and bit-packed masks, without the 1024 x 1024 or the
 frame-sized fp32 tensors of `Sam.postprocess_masks`; the logits are bit-equal to torch's CPU `F.interpolate` (pope_amd/sam_amg.py
 restates the arithmetic), so counts, boxes and masks are exact.  Box NMS is `pope_sam_nms_f32`; the small-region clean-up is one
-launch over the packed masks of the NMS survivors (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip).  There is no
-torch fallback.
+launch over the packed masks of the NMS survivors (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip).  `generate_batch` takes the
+frames of several queries at once: one encoder call, the decoder per frame, then one tail for all frames (`box_nms_segments` =
+`pope_sam_nms_segments_f32`, one workgroup per frame; the clean-up over all survivors; run lengths by `pope_sam_rle_u32`,
+pope_amd/csrc/sam_rle.hip, so that `uncompressed_rle` downloads counts instead of masks).  There is no torch fallback.
 
 Not supported: crop layers (`crop_n_layers > 0`), mask prompts, `output_mode="coco_rle"`.
 """
@@ -81,6 +83,61 @@ def box_nms(boxes, scores, iou_threshold):
         check(_lib.lib().pope_sam_nms_f32(ptr(boxes), ptr(scores), n, float(iou_threshold), ptr(keep), ptr(count), stream_of(dev)),
               "pope_sam_nms_f32")
     return keep[:int(count.item())].to(torch.int64)
+
+
+def box_nms_segments(boxes, scores, seg_offsets, iou_threshold):
+    """`box_nms` of S independent segments in one launch (`pope_sam_nms_segments_f32`, one workgroup per segment, the device
+    function of `pope_sam_nms_f32`).  boxes [n, 4], scores [n] (device); seg_offsets: S + 1 non-decreasing host integers from 0
+    to n, segment s = boxes seg_offsets[s] .. seg_offsets[s + 1] - 1, at most `NMS_MAX` of them.  Returns (keep int32 [n],
+    counts int32 [S]), both on the device and without a host read: the kept boxes of segment s are
+    keep[seg_offsets[s] : seg_offsets[s] + counts[s]], global indices into n in score order."""
+    require_cuda(boxes, "box_nms_segments")
+    n = boxes.shape[0]
+    seg = np.asarray(seg_offsets.cpu() if isinstance(seg_offsets, torch.Tensor) else seg_offsets, dtype=np.int64).reshape(-1)
+    if seg.size < 1 or seg[0] != 0 or seg[-1] != n or (np.diff(seg) < 0).any():
+        raise ValueError(f"box_nms_segments: seg_offsets must rise from 0 to n = {n}, got {seg.tolist()}")
+    if seg.size > 1 and int(np.diff(seg).max()) > NMS_MAX:
+        raise ValueError(f"box_nms_segments: at most {NMS_MAX} boxes per segment, got {int(np.diff(seg).max())}")
+    S = seg.size - 1
+    dev = boxes.device
+    boxes = boxes.to(torch.float32).contiguous()
+    scores = scores.to(device=dev, dtype=torch.float32).contiguous()
+    keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    counts = torch.zeros(S, dtype=torch.int32, device=dev)
+    if S == 0:
+        return keep[:n], counts
+    seg_dev = torch.as_tensor(seg.astype(np.int32)).to(dev)
+    with on_device_of(boxes):
+        check(_lib.lib().pope_sam_nms_segments_f32(ptr(boxes), ptr(scores), ptr(seg_dev), S, n, float(iou_threshold), ptr(keep),
+                                                   ptr(counts), stream_of(dev)), "pope_sam_nms_segments_f32")
+    return keep[:n], counts
+
+
+def rle_from_packed(packed, W):
+    """`mask_to_rle_pytorch` of bit-packed masks on the device (`pope_sam_rle_u32`, pope_amd/csrc/sam_rle.hip): int32 words
+    [n, H, ceil(W / 32)] -> list of {"size": [H, W], "counts": [...]}: column-major run lengths, starting with a run of zeros.
+    Two calls (lengths, then counts at the scanned offsets); only the lengths and the counts are downloaded."""
+    require_cuda(packed, "rle_from_packed")
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != sam_amg.row_words(W):
+        raise TypeError(f"rle_from_packed: expected int32 words [n, H, {sam_amg.row_words(W)}] for W = {W}, "
+                        f"got {packed.dtype} {tuple(packed.shape)}")
+    packed = packed.contiguous()
+    n, H, _ = packed.shape
+    if n == 0:
+        return []
+    dev = packed.device
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    with on_device_of(packed):
+        check(_lib.lib().pope_sam_rle_u32(ptr(packed), n, H, int(W), ptr(lengths), None, None, 0, stream_of(dev)), "pope_sam_rle_u32")
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(lengths.cpu().numpy(), out=offsets[1:])
+        total = int(offsets[-1])
+        counts = torch.empty(total, dtype=torch.int32, device=dev)
+        offsets_dev = torch.as_tensor(offsets).to(dev)
+        check(_lib.lib().pope_sam_rle_u32(ptr(packed), n, H, int(W), None, ptr(offsets_dev), ptr(counts), total, stream_of(dev)),
+              "pope_sam_rle_u32")
+    counts = counts.cpu().numpy()
+    return [{"size": [H, int(W)], "counts": counts[offsets[i]:offsets[i + 1]].tolist()} for i in range(n)]
 
 
 # ---- Sam -----------------------------------------------------------------------------------------------------------------
@@ -333,13 +390,10 @@ class SamAutomaticMaskGenerator:
         low, iou = pr.predict_low_res(in_points[:, None, :], in_labels[:, None], multimask_output=True)
         return low.flatten(0, 1), iou.flatten(0, 1)
 
-    @torch.no_grad()
-    def generate(self, image: np.ndarray, keep_low_res: bool = False) -> List[Dict[str, Any]]:
-        """HWC uint8 image -> list of records (`segmentation`, `area`, `bbox` XYWH, `predicted_iou`, `point_coords`,
-        `stability_score`, `crop_box`), in the reference's order."""
-        H, W = image.shape[:2]
+    # the point-batch loop of one frame whose features the predictor holds: the filtered per-mask data of `process_low_res`
+    def _decode_frame(self, hw, keep_low_res=False):
+        H, W = hw
         pr = self.predictor
-        pr.set_image(image)
         points_all = self.point_grids[0] * np.array([[W, H]])
         lows, ious, parts, pts, base = [], [], [], [], 0
         for b in range(0, len(points_all), self.points_per_batch):
@@ -354,37 +408,96 @@ class SamAutomaticMaskGenerator:
             base += low.shape[0]
             parts.append(d)
             pts.append(np.repeat(points, 3, axis=0))
-        pr.reset_image()
         if keep_low_res:
             self.last_low_res = (torch.cat(lows), torch.cat(ious))
         data = {k: torch.cat([p[k] for p in parts]) for k in ("index", "iou_preds", "stability_score", "boxes", "area", "packed")}
-        return self._finish(data, np.concatenate(pts), (H, W))
+        return data, np.concatenate(pts)
 
-    def _finish(self, data, points, hw):
-        """NMS, small regions, encoding and the records, from the filtered per-mask results of `process_low_res`."""
+    @torch.no_grad()
+    def generate(self, image: np.ndarray, keep_low_res: bool = False) -> List[Dict[str, Any]]:
+        """HWC uint8 image -> list of records (`segmentation`, `area`, `bbox` XYWH, `predicted_iou`, `point_coords`,
+        `stability_score`, `crop_box`), in the reference's order."""
+        H, W = image.shape[:2]
+        pr = self.predictor
+        pr.set_image(image)
+        data, points = self._decode_frame((H, W), keep_low_res)
+        pr.reset_image()
+        return self._finish(data, [0, data["index"].numel()], points, (H, W))[0]
+
+    @torch.no_grad()
+    def generate_batch(self, images: List[np.ndarray]) -> List[List[Dict[str, Any]]]:
+        """`generate` for a list of HWC uint8 frames of one common size: the image encoder runs over the stacked frames, the
+        decoder and the fused post-processing per frame, NMS, small regions and the encoding once for all frames.  The list for
+        frame q is record for record what `generate(images[q])` returns."""
+        images = list(images)
+        if not images:
+            return []
+        H, W = images[0].shape[:2]
+        if any(im.shape[:2] != (H, W) for im in images):
+            raise ValueError("generate_batch: all frames must have one size, got "
+                             + ", ".join(sorted({f"{im.shape[0]} x {im.shape[1]}" for im in images})))
+        pr = self.predictor
+        enc = pr.model.image_encoder
+        resized = np.stack([pr.transform.apply_image(im[..., ::-1] if pr.model.image_format != "RGB" else im) for im in images])
+        x = torch.as_tensor(resized, device=pr.device).permute(0, 3, 1, 2).contiguous()
+        x = pr.model.preprocess(x).contiguous()
+        events = enc.overflow_events
+        features = enc(x)
+        if enc.overflow_events != events:
+            # the range guard re-ran the whole call on the fp32 MFMA: encode frame by frame, so that a frame's features do not
+            # depend on a neighbour's overflow (generate() of that frame alone would not have been re-run)
+            features = torch.cat([enc(x[q:q + 1]) for q in range(len(images))])
+        parts, seg, points = [], [0], None
+        for q in range(len(images)):
+            pr.reset_image()
+            pr.original_size, pr.input_size = (H, W), tuple(resized.shape[1:3])
+            pr.features, pr.is_image_set = features[q:q + 1], True
+            data, points = self._decode_frame((H, W))
+            parts.append(data)
+            seg.append(seg[-1] + data["index"].numel())
+        pr.reset_image()
+        data = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return self._finish(data, seg, points, (H, W))
+
+    def _finish(self, data, seg, points, hw):
+        """NMS, small regions, encoding and the records of S frames at once, from their concatenated filtered per-mask results
+        of `process_low_res` (frame s = rows seg[s] .. seg[s + 1] - 1): one list of records per frame.  The host reads the
+        segments' survivor counts (once per NMS), the per-mask scalars and either the run lengths or the dense masks."""
         H, W = hw
-        keep = box_nms(data["boxes"], data["iou_preds"], self.box_nms_thresh)
-        data = {k: v[keep] for k, v in data.items()}
-        masks = None
+        keep, counts = box_nms_segments(data["boxes"], data["iou_preds"], seg, self.box_nms_thresh)
+        sel, seg = select_segments(keep, counts, seg)
+        data = {k: v[sel] for k, v in data.items()}
         if self.min_mask_region_area > 0 and data["index"].numel() > 0:
-            data, masks = postprocess_small_regions(data, W, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
-        if masks is None:
-            masks = unpack_on_device(data["packed"], W)
-        masks = masks.cpu().numpy()
-        host = {k: data[k].cpu().numpy() for k in ("index", "iou_preds", "stability_score", "boxes")}
-        anns = []
-        for i in range(len(masks)):
-            rle = sam_amg.mask_to_rle(masks[i])
-            anns.append({
-                "segmentation": masks[i] if self.output_mode == "binary_mask" else rle,
-                "area": sam_amg.area_from_rle(rle),
+            data, seg = postprocess_small_regions_segments(data, seg, W, self.min_mask_region_area,
+                                                           max(self.box_nms_thresh, self.crop_nms_thresh))
+        host = {k: data[k].cpu().numpy() for k in ("index", "iou_preds", "stability_score", "boxes", "area")}
+        if self.output_mode == "binary_mask":
+            segm = unpack_on_device(data["packed"], W).cpu().numpy()
+        else:
+            segm = rle_from_packed(data["packed"], W)
+        out = []
+        for s in range(len(seg) - 1):
+            out.append([{
+                "segmentation": segm[i],
+                "area": int(host["area"][i]),
                 "bbox": sam_amg.box_xyxy_to_xywh(host["boxes"][i]),
                 "predicted_iou": float(host["iou_preds"][i]),
                 "point_coords": [points[int(host["index"][i])].tolist()],
                 "stability_score": float(host["stability_score"][i]),
                 "crop_box": [0, 0, W, H],
-            })
-        return anns
+            } for i in range(int(seg[s]), int(seg[s + 1]))])
+        return out
+
+
+def select_segments(keep, counts, seg):
+    """The survivors of `box_nms_segments` as one index list: (rows int64 on the device, segment after segment in score order;
+    the survivors' own seg_offsets as host integers).  Reads `counts` (one synchronisation)."""
+    counts = counts.cpu().numpy().astype(np.int64)
+    if (counts < 0).any():
+        raise ValueError("box_nms_segments: a segment holds more boxes than one workgroup takes")
+    pos = np.concatenate([np.arange(int(seg[s]), int(seg[s]) + int(c)) for s, c in enumerate(counts)] + [np.zeros(0, np.int64)])
+    new_seg = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return keep[torch.as_tensor(pos.astype(np.int64)).to(keep.device)].to(torch.int64), new_seg
 
 
 def pack_on_device(masks):
@@ -452,3 +565,16 @@ def postprocess_small_regions(data, W, min_area, nms_thresh):
     data = dict(data, boxes=new_boxes)
     data = {k: v[keep] for k, v in data.items() if k != "packed"}
     return data, unpack_on_device(packed[keep], W)
+
+
+def postprocess_small_regions_segments(data, seg, W, min_area, nms_thresh):
+    """`postprocess_small_regions` for the concatenated NMS survivors of several frames (frame s = rows seg[s] .. seg[s + 1] - 1):
+    one clean-up launch over all masks, one segmented second NMS, nothing unpacked.  Returns (data of the survivors with the
+    cleaned `packed` words, the cleaned masks' `area` and the boxes of the changed ones replaced; their seg_offsets)."""
+    packed, unchanged, boxes, area = clean_masks_packed(data["packed"], W, min_area)
+    keep, counts = box_nms_segments(boxes, unchanged.to(torch.float32), seg, nms_thresh)
+    sel, seg = select_segments(keep, counts, seg)
+    new_boxes = torch.where(unchanged[:, None], data["boxes"], boxes)
+    data = dict(data, boxes=new_boxes, area=area, packed=packed)
+    return {k: v[sel] for k, v in data.items()}, seg
+

@@ -10,8 +10,15 @@ With --min-mask-region-area N > 0 additionally, 3 warm-up calls and the median o
      the NMS survivors of `synth.sam_generator_case("frame")`;
  (5) the same stage on 64 random-blob masks of 480 x 640 (a box-blurred noise field cut at a quantile);
  (6) `generate()` of one 480 x 640 frame with `min_mask_region_area=N` (filters off, as in (3)).
+With --frames Q[,Q..] only the following, as WALL time (host work included, a device synchronisation before the clock starts
+and one at the end; one warm-up, median of 5), synthetic ViT-B weights, 480 x 640 frames, filters off, box NMS 0.35,
+`min_mask_region_area=250`, in both output modes:
+ (7) Q sequential `generate()` calls against `generate_batch` of the same Q frames (`--sequential-only`: the first alone, which
+     is what a commit without `generate_batch` can run);
+ (8) the tail alone (`_finish`: NMS through records) on one frame's filtered masks.
 Prints medians, minima and the bytes/s of (1) against its floor: the low-res logits read once plus the packed masks written.
-usage: python scripts/sam_generator_time.py [--reps 20] [--skip-generate] [--skip-postprocess] [--min-mask-region-area 250]"""
+usage: python scripts/sam_generator_time.py [--reps 20] [--skip-generate] [--skip-postprocess] [--min-mask-region-area 250]
+       python scripts/sam_generator_time.py --frames 1,4,8 [--sequential-only]"""
 import argparse
 import os
 import statistics
@@ -98,9 +105,14 @@ def main():
     ap.add_argument("--skip-generate", action="store_true")
     ap.add_argument("--skip-postprocess", action="store_true", help="leave out (1) and (2)")
     ap.add_argument("--min-mask-region-area", type=int, default=0, help="> 0: time the small-region clean-up, rows (4) to (6)")
+    ap.add_argument("--frames", default="", help="Q[,Q..]: rows (7) and (8) only, wall time of Q frames")
+    ap.add_argument("--sequential-only", action="store_true", help="with --frames: generate() calls only, no generate_batch")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     dev = "cuda:0"
+    if a.frames:
+        time_frames(dev, [int(q) for q in a.frames.split(",")], a.sequential_only)
+        return
     M, (H, W) = 768, (480, 640)
     if a.min_mask_region_area > 0:
         time_cleanup(dev, a.min_mask_region_area)
@@ -136,14 +148,64 @@ def time_postprocess(dev, reps, M, H, W):
     print(f"(2) torch reference path    median {r_med:.3f} ms  min {r_min:.3f}  max {r_max:.3f}   ratio (2)/(1) = {r_med / s_med:.1f}")
 
 
-def time_generate(dev, H, W, min_area):
-    hw = (H, W)
+def synthetic_vit_b(dev):
     sam = sg.build_sam_vit_b()
     sd = {"image_encoder." + k: v for k, v in synth.synthetic_sam_encoder_state_dict(seed=0, dim=768, depth=12, heads=12,
                                                                                       global_idx=(2, 5, 8, 11)).items()}
     sd.update(synth.synthetic_sam_decoder_state_dict(seed=0))
     sam.load_state_dict(sd, strict=True)
-    sam = sam.to(dev)
+    return sam.to(dev)
+
+
+def wall(fn, reps=5, warmup=1):
+    """Wall-clock ms of fn(), host work included: synchronised before the clock starts and before it stops."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out), min(out)
+
+
+def time_frames(dev, qs, sequential_only, H=480, W=640, min_area=250):
+    """Rows (7) and (8)."""
+    sam = synthetic_vit_b(dev)
+    frames = [(torch.rand(H, W, 3, generator=torch.Generator().manual_seed(5 + q)) * 255).to(torch.uint8).numpy()
+              for q in range(max(qs))]
+    for mode in ("uncompressed_rle", "binary_mask"):
+        gen = sg.SamAutomaticMaskGenerator(sam, pred_iou_thresh=0.0, stability_score_thresh=0.0, min_mask_region_area=min_area,
+                                           output_mode=mode)
+        print(f"{mode}: records per frame {[len(gen.generate(f)) for f in frames]}")
+        for q in qs:
+            seq = wall(lambda: [gen.generate(f) for f in frames[:q]])
+            line = f"(7) {mode:16s} Q = {q}: {q} x generate() median {seq[0]:.2f} ms  min {seq[1]:.2f}"
+            if not sequential_only:
+                bat = wall(lambda: gen.generate_batch(frames[:q]))
+                line += f"   generate_batch median {bat[0]:.2f} ms  min {bat[1]:.2f}   sequential / batch = {seq[0] / bat[0]:.2f}"
+            print(line)
+        # the tail alone, on the filtered masks of one frame
+        gen.predictor.set_image(frames[0])
+        pr = gen.predictor
+        points = gen.point_grids[0] * np.array([[W, H]])
+        low, iou = gen._decode(points, (H, W))
+        d = sg.process_low_res(low, iou, pr.input_size, (H, W), 0.0, 0.0, 0.0, 1.0)
+        data = {k: d[k] for k in ("index", "iou_preds", "stability_score", "boxes", "area", "packed")}
+        pts = np.repeat(points, 3, axis=0)
+        gen.predictor.reset_image()
+        if hasattr(gen, "generate_batch"):
+            tail = wall(lambda: gen._finish(data, [0, data["index"].numel()], pts, (H, W)))
+        else:
+            tail = wall(lambda: gen._finish(data, pts, (H, W)))
+        print(f"(8) {mode:16s} tail of one frame, {data['index'].numel()} masks in: median {tail[0]:.2f} ms  min {tail[1]:.2f}")
+
+
+def time_generate(dev, H, W, min_area):
+    hw = (H, W)
+    sam = synthetic_vit_b(dev)
     gen = sg.SamAutomaticMaskGenerator(sam, pred_iou_thresh=0.0, stability_score_thresh=0.0, min_mask_region_area=0)
     frame = (torch.rand(H, W, 3, generator=torch.Generator().manual_seed(5)) * 255).to(torch.uint8).numpy()
     pr = gen.predictor
