@@ -7,7 +7,8 @@ vote (order-dependent by definition) and ONE Matcher call over the occupied slot
 `locate_and_match` takes already-preprocessed tensors; `locate_and_match_u8` starts from the uint8 crops;
 `locate_match_pose_u8` is the whole per-pair body of the loop after SAM: frame + proposal boxes in, pose out — proposal
 crops and their intrinsics (crops.py), preprocessing (preprocess.py), DINOv2 vote, LoFTR matches and the essential-matrix
-RANSAC (pose.py) all on the card.  SAM proposal generation itself is upstream of the path (SURVEY.md §8 'OUT').
+RANSAC (pose.py) all on the card.  `locate_pose_from_frames` / `locate_pose_from_frame` start one step earlier, at the raw
+frame: the SAM mask generator's proposals (sam_generator.py:propose_batch, boxes only) feed the batched step.
 
 The `*_batch` functions take Q independent queries per call: one DINOv2 forward, the vote on the device (ops.vote_top3_batch),
 ONE Matcher call over 3 Q pairs, the per-slot tally and best-slot choice on the device (ops.slot_tally), one pose launch and a
@@ -278,3 +279,51 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
         n = int(off[q + 1] - off[q])
         out["pose"] = (R[q], t[q], inl[off[q]:off[q + 1]]) if n >= 5 and int(n_inl[q]) > 0 else None
     return outs
+
+
+# ---- from the raw frames: the mask generator's proposals feed the batched step -------------------------------------------------
+@torch.no_grad()
+def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
+                            ransac_conf=0.99, out_size=256, max_proposals=None):
+    """The whole per-query body of the loop, eval_linemod_json.py:62-160, for Q queries in one call: `refs_bgr` [Q, H0, W0, 3]
+    uint8 (the reference crops), `frames_bgr` [Q, H, W, 3] uint8 (an array, a tensor or Q frames of one size), `K0` / `K1` as in
+    `locate_match_pose_batch_u8`.  `mask_generator` is a `sam_generator.SamAutomaticMaskGenerator` on the device of the other
+    two models (ValueError otherwise).
+
+    `mask_generator.propose_batch(frames)` -> the XYWH boxes of every frame's records, the only part of a record the loop reads
+    (:73; no mask is unpacked, encoded or downloaded) -> `locate_match_pose_batch_u8`.  The frames reach the generator
+    unchanged, in BGR channel order: the reference hands the frame of `cv2.imread` to `MASK_GEN.generate` as it is (:66-69),
+    and the same proposals come only from the same input.  `max_proposals` keeps the first `max_proposals` boxes of each frame
+    in record order (None: all of them, as the reference does).
+
+    Returns `locate_match_pose_batch_u8`'s list of Q dicts, each with one more key: `proposals`, the int64 [P_q, 4] XYWH boxes
+    of that query.  A frame without a proposal yields the empty result (`best_proposal` -1, `pose` None)."""
+    dev = next(dinov2_model.parameters()).device
+    devices = {"mask_generator": torch.device(mask_generator.predictor.device), "dinov2_model": dev,
+               "matcher": next(matcher.parameters()).device}
+    if len(set(devices.values())) > 1:
+        raise ValueError("locate_pose_from_frames: the models must be on one device, got "
+                         + ", ".join(f"{k} on {v}" for k, v in devices.items()))
+    if max_proposals is not None and int(max_proposals) < 0:
+        raise ValueError(f"locate_pose_from_frames: max_proposals is None or a count, got {max_proposals}")
+    if isinstance(frames_bgr, torch.Tensor):
+        frames_bgr = frames_bgr.cpu().numpy()
+    frames = [np.asarray(f.cpu() if torch.is_tensor(f) else f) for f in frames_bgr]
+    if len(frames) != len(refs_bgr):
+        raise ValueError(f"locate_pose_from_frames: {len(refs_bgr)} references, {len(frames)} frames")
+    proposals = mask_generator.propose_batch(frames)            # mixed frame sizes raise there
+    if max_proposals is not None:
+        proposals = [p[:int(max_proposals)] for p in proposals]
+    outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, np.stack(frames) if frames else frames, proposals, K0, K1,
+                                      conf_thr, ransac_thr, ransac_conf, out_size)
+    for out, p in zip(outs, proposals):
+        out["proposals"] = p
+    return outs
+
+
+def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
+                           ransac_conf=0.99, out_size=256, max_proposals=None):
+    """`locate_pose_from_frames` for one query: `ref_bgr` [H0, W0, 3], `frame_bgr` [H, W, 3], `K0` / `K1` [3, 3]; one dict."""
+    ref, frame = (np.asarray(a.cpu() if torch.is_tensor(a) else a)[None] for a in (ref_bgr, frame_bgr))
+    return locate_pose_from_frames(mask_generator, dinov2_model, matcher, ref, frame, K0, K1, conf_thr, ransac_thr, ransac_conf,
+                                   out_size, max_proposals)[0]

@@ -2,8 +2,10 @@
 eval_linemod_json.py:1).  Exports, under the reference's names, everything of that namespace that
 lies on the accelerated path, including the caller-side geometry either side of it: the proposal crops
 and their intrinsics (`get_image_crop_resize`, `get_K_crop_resize`; batched: `crop_proposals`) and the pose solver
-(`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`).  Names that belong to out-of-scope stages (the SAM
-proposal generator, dataset helpers) are not re-implemented here — the reference's own modules keep providing them.
+(`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`), the SAM proposal generator the drivers build from it
+(`sam_model_registry`, the `build_sam_vit_*` builders, `SamPredictor`, `SamAutomaticMaskGenerator`, `get_model_info`) and the
+call that joins the two: `locate_pose_from_frames` / `locate_pose_from_frame`, reference crop and raw frame in, pose out.  Names
+that belong to out-of-scope stages (dataset helpers) are not re-implemented here — the reference's own modules keep providing them.
 
 Unlike the reference façade, importing this module has no side effects (the reference builds the
 LoFTR `matcher` singleton from weights/matcher.pth at import, pope_model_api.py:177-185).
@@ -19,11 +21,23 @@ import torch.nn.functional as F  # noqa: F401
 from .crops import crop_proposals, expand_box, get_affine_transform, get_image_crop_resize, get_K_crop_resize  # noqa: F401
 from .dinov2_utils import get_cls_token_torch, load_dinov2_model, set_torch_image  # noqa: F401
 from .driver import (locate_and_match, locate_and_match_batch, locate_and_match_batch_u8, locate_match_pose_batch_u8,  # noqa: F401
-                     locate_match_pose_u8)
+                     locate_match_pose_u8, locate_pose_from_frame, locate_pose_from_frames)
 from .matcher import CoarseMatching, Matcher, default_cfg, dense_match  # noqa: F401
 from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch  # noqa: F401
 from .pipeline import PairPipeline, gather_counts, shard_range  # noqa: F401
 from .pose import estimate_pose, estimate_pose_batch, relative_pose_error  # noqa: F401
+from .sam_generator import (SamAutomaticMaskGenerator, SamPredictor, build_sam, build_sam_vit_b, build_sam_vit_h,  # noqa: F401
+                            build_sam_vit_l, sam_model_registry)
+
+
+def get_model_info(type="b"):
+    """(checkpoint path, `sam_model_registry` key) of the SAM size "b", "l" or "h", as the reference façade names them
+    (pope_model_api.py:109-121)."""
+    info = {"b": ("weights/sam_vit_b_01ec64.pth", "vit_b"), "l": ("weights/sam_vit_l_0b3195.pth", "vit_l"),
+            "h": ("weights/sam_vit_h_4b8939.pth", "vit_h")}
+    if not isinstance(type, str) or type not in info:
+        raise NotImplementedError
+    return info[type]
 
 
 def build_matcher(weights="weights/matcher.pth", device="cuda:0", state_dict=None):

@@ -9,7 +9,9 @@ restates the arithmetic), so counts, boxes and masks are exact.  Box NMS is `pop
 launch over the packed masks of the NMS survivors (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip).  `generate_batch` takes the
 frames of several queries at once: one encoder call, the decoder per frame, then one tail for all frames (`box_nms_segments` =
 `pope_sam_nms_segments_f32`, one workgroup per frame; the clean-up over all survivors; run lengths by `pope_sam_rle_u32`,
-pope_amd/csrc/sam_rle.hip, so that `uncompressed_rle` downloads counts instead of masks).  There is no torch fallback.
+pope_amd/csrc/sam_rle.hip, so that `uncompressed_rle` downloads counts instead of masks).  `propose` / `propose_batch` are the
+same calls stopped after the second NMS: the records' boxes alone, no mask unpacked, encoded or downloaded (the frame-to-pose
+query of pope_amd/driver.py reads nothing else).  There is no torch fallback.
 
 Not supported: crop layers (`crop_n_layers > 0`), mask prompts, `output_mode="coco_rle"`.
 """
@@ -432,9 +434,36 @@ class SamAutomaticMaskGenerator:
         images = list(images)
         if not images:
             return []
+        return self._finish(*self._decode_frames(images, "generate_batch"))
+
+    @torch.no_grad()
+    def propose(self, image: np.ndarray) -> np.ndarray:
+        """The `bbox` values of `generate(image)` alone, in record order: int64 [P, 4] XYWH ([0, 4] when nothing survives)."""
+        H, W = image.shape[:2]
+        pr = self.predictor
+        pr.set_image(image)
+        data, _ = self._decode_frame((H, W))
+        pr.reset_image()
+        return self._finish_boxes(data, [0, data["index"].numel()], (H, W))[0]
+
+    @torch.no_grad()
+    def propose_batch(self, images: List[np.ndarray]) -> List[np.ndarray]:
+        """The proposals of `generate_batch(images)` without its records: one int64 [P_q, 4] XYWH array per frame, row i the
+        `bbox` of record i of that frame, whatever the `output_mode`.  The encoder, the decoder and the tail up to the second
+        NMS are those of `generate_batch`; no mask is unpacked, encoded or downloaded, the host reads the survivor counts of
+        the NMS calls and the survivors' boxes."""
+        images = list(images)
+        if not images:
+            return []
+        data, seg, _, hw = self._decode_frames(images, "propose_batch")
+        return self._finish_boxes(data, seg, hw)
+
+    # the front of the batched calls: one encoder call over the stacked frames, then the decoder frame by frame.  Returns the
+    # arguments of `_finish`: (concatenated filtered per-mask data, its seg_offsets, the prompt point of every mask, (H, W))
+    def _decode_frames(self, images, what):
         H, W = images[0].shape[:2]
         if any(im.shape[:2] != (H, W) for im in images):
-            raise ValueError("generate_batch: all frames must have one size, got "
+            raise ValueError(f"{what}: all frames must have one size, got "
                              + ", ".join(sorted({f"{im.shape[0]} x {im.shape[1]}" for im in images})))
         pr = self.predictor
         enc = pr.model.image_encoder
@@ -457,19 +486,37 @@ class SamAutomaticMaskGenerator:
             seg.append(seg[-1] + data["index"].numel())
         pr.reset_image()
         data = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
-        return self._finish(data, seg, points, (H, W))
+        return data, seg, points, (H, W)
+
+    def _survivors(self, data, seg, hw, keys):
+        """The tail both `_finish` and `_finish_boxes` run, for S frames at once from their concatenated filtered per-mask
+        results of `process_low_res` (frame s = rows seg[s] .. seg[s + 1] - 1): segmented NMS, small regions, second NMS.
+        Returns (the columns `keys` of the survivors, on the device; their seg_offsets).  The host reads the segments'
+        survivor counts, once per NMS.  `packed` is gathered only where the clean-up or the caller needs it."""
+        keep, counts = box_nms_segments(data["boxes"], data["iou_preds"], seg, self.box_nms_thresh)
+        sel, seg = select_segments(keep, counts, seg)
+        clean = self.min_mask_region_area > 0 and sel.numel() > 0
+        need = set(keys) | ({"boxes", "packed"} if clean else set())
+        data = {k: data[k][sel] for k in need}
+        if clean:
+            data, seg = postprocess_small_regions_segments(data, seg, hw[1], self.min_mask_region_area,
+                                                           max(self.box_nms_thresh, self.crop_nms_thresh))
+        return {k: data[k] for k in keys}, seg
+
+    def _finish_boxes(self, data, seg, hw):
+        """The proposals-only tail: one int64 [P_s, 4] XYWH array per frame, the `bbox` values of `_finish`'s records.  The only
+        downloads are the survivor counts and the survivors' boxes."""
+        data, seg = self._survivors(data, seg, hw, ("boxes",))
+        xyxy = data["boxes"].cpu().numpy().astype(np.int64).reshape(-1, 4)
+        xywh = np.concatenate([xyxy[:, :2], xyxy[:, 2:] - xyxy[:, :2]], axis=1)     # `sam_amg.box_xyxy_to_xywh` of every row
+        return [xywh[int(seg[s]):int(seg[s + 1])] for s in range(len(seg) - 1)]
 
     def _finish(self, data, seg, points, hw):
         """NMS, small regions, encoding and the records of S frames at once, from their concatenated filtered per-mask results
         of `process_low_res` (frame s = rows seg[s] .. seg[s + 1] - 1): one list of records per frame.  The host reads the
         segments' survivor counts (once per NMS), the per-mask scalars and either the run lengths or the dense masks."""
         H, W = hw
-        keep, counts = box_nms_segments(data["boxes"], data["iou_preds"], seg, self.box_nms_thresh)
-        sel, seg = select_segments(keep, counts, seg)
-        data = {k: v[sel] for k, v in data.items()}
-        if self.min_mask_region_area > 0 and data["index"].numel() > 0:
-            data, seg = postprocess_small_regions_segments(data, seg, W, self.min_mask_region_area,
-                                                           max(self.box_nms_thresh, self.crop_nms_thresh))
+        data, seg = self._survivors(data, seg, hw, ("index", "iou_preds", "stability_score", "boxes", "area", "packed"))
         host = {k: data[k].cpu().numpy() for k in ("index", "iou_preds", "stability_score", "boxes", "area")}
         if self.output_mode == "binary_mask":
             segm = unpack_on_device(data["packed"], W).cpu().numpy()
