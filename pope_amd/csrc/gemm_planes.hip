@@ -467,14 +467,17 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 } else if constexpr (EPI == EPI_SAM_QKV) {
                     v = (v * inv + bias) * sq_scale;
                     pope_amax4x2(amax, v);
-                    const unsigned o = col_ok && row0 + 4 * i < unsigned(g.M) ? (sq_dest[i] * unsigned(sq_row_h) + unsigned(sq_c)) * 2u : DROP;
+                    const bool live = col_ok && row0 + 4 * i < unsigned(g.M);
+                    const unsigned o = live ? (sq_dest[i] * unsigned(sq_row_h) + unsigned(sq_c)) * 2u : DROP;
                     if constexpr (PLAIN) {
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, __builtin_convertvector(v, f16x4)), rsq, o, 0, 0);
                     } else {
                         f16x4 hi, lo;
                         pope_split4(v, hi, lo);
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), rsq, o, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), rsq, o + unsigned(sq_lo) * 2u, 0, 0);
+                        // DROP + 2 sq_lo wraps past 2^32 from sq_lo = 128 on (the deep score depths: 192 / 208) and lands in row 0 of the
+                        // operand: a dropped row's lo half is dropped by its own select
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), rsq, live ? o + unsigned(sq_lo) * 2u : DROP, 0, 0);
                     }
                     continue;
                 } else if constexpr (EPI == EPI_QKV_F16) {   // attention operands: f16 row-major, no activation scale
