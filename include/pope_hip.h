@@ -477,6 +477,24 @@ int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w_host, const f
                                  const float* sparse, int P, int n_sparse, const float* dense, long long dense_stride,
                                  int multimask, float* masks, float* iou, float* hs_out, float* keys_out,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* The same decoder over the prompts of N images in one call (Sam.forward's workload: a few prompts on each of several
+ * images).  images[N, 256, 64, 64] fp32; prompt_image_host[P]: a HOST int array in any order, entry p the image of prompt p
+ * (0 <= entry < N is checked on the host: a bad index is POPE_ERR_ARG before any launch); dense[256, 64, 64] with
+ * dense_stride 0, the broadcast PromptEncoder returns without a mask (any other stride is POPE_ERR_ARG); the other arguments
+ * as above, without hs_out / keys_out.  Layer 0's image-only projections run once per image (GEMMs over up to 16 x 4 096
+ * rows), the 16-prompt chunks fill across images (a chunk's image indices travel as a kernel argument: no device copy, no
+ * synchronisation, no allocation), and range_flag covers the whole call.  masks / iou of prompt p are bit-identical to
+ * pope_sam_decoder_forward_f32 on prompt p with images[prompt_image_host[p]] alone, whatever N, P, the order of the prompts
+ * and the chunk a prompt falls in, in both precisions.  The workspace holds the layer-0 buffers once per image (18 MB each)
+ * on top of the 16-prompt chunk; the query returns 0 for an unsupported geometry or argument (N <= 0, a NULL or
+ * out-of-range prompt_image_host, dense_stride != 0). */
+size_t pope_sam_decoder_images_workspace_bytes(const pope_sam_decoder_weights* w_host, int N, const int* prompt_image_host,
+                                               int P, int n_sparse, long long dense_stride);
+int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w_host, const float* images, int N,
+                                        const float* image_pe, const float* sparse, const int* prompt_image_host, int P,
+                                        int n_sparse, const float* dense, long long dense_stride, int multimask, float* masks,
+                                        float* iou, void* workspace, size_t workspace_bytes, unsigned* range_flag,
+                                        void* stream);
 
 /* ---- SAM automatic mask generator: post-processing of one decoder call ------------------------------------------ */
 

@@ -152,6 +152,11 @@ PROTOTYPES = {
     "pope_sam_decoder_forward_f32": (C.c_int, [C.POINTER(SamDecoderWeights)] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p,
                                                                                                   C.c_longlong, C.c_int]
                                      + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_sam_decoder_images_workspace_bytes": (C.c_size_t, [C.POINTER(SamDecoderWeights), C.c_int, c_int_p, C.c_int, C.c_int,
+                                                             C.c_longlong]),
+    "pope_sam_decoder_forward_images_f32": (C.c_int, [C.POINTER(SamDecoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                      c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int]
+                                            + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_sam_postprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_sam_postprocess_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_double]
                                  + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),

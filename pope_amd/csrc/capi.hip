@@ -449,6 +449,27 @@ int pope_sam_decoder_forward_f32(const pope_sam_decoder_weights* w, const float*
     return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
 }
 
+size_t pope_sam_decoder_images_workspace_bytes(const pope_sam_decoder_weights* w, int N, const int* prompt_image_host, int P,
+                                               int n_sparse, long long dense_stride) {
+    return pope_sam_decoder_images_workspace(w, N, prompt_image_host, P, n_sparse, dense_stride);
+}
+
+int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w, const float* images, int N, const float* image_pe,
+                                        const float* sparse, const int* prompt_image_host, int P, int n_sparse, const float* dense,
+                                        long long dense_stride, int multimask, float* masks, float* iou, void* workspace,
+                                        size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    SamDecArgs a{};
+    a.w = w; a.image = images; a.image_pe = image_pe; a.sparse = sparse; a.dense = dense;
+    a.P = P; a.n_sparse = n_sparse; a.multimask = multimask; a.dense_stride = dense_stride;
+    a.n_images = N; a.prompt_image = prompt_image_host;
+    a.masks = masks; a.iou = iou;
+    a.ws = workspace; a.ws_bytes = workspace_bytes; a.range_flag = range_flag;
+    // before any HIP call: the images, their count, every prompt's image index and the broadcast
+    if (!images || pope_sam_decoder_images_workspace(w, N, prompt_image_host, P, n_sparse, dense_stride) == 0) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
+}
+
 size_t pope_sam_postprocess_workspace_bytes(int img_size, int H, int W) { return pope_sam_postprocess_workspace(img_size, H, W); }
 
 int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const int* selection, int n_sel, int img_size, int ih, int iw,

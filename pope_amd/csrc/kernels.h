@@ -363,11 +363,14 @@ int pope_launch_slot_tally(const long long* m_bids, const float* mconf, const fl
                            long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,
                            hipStream_t stream);
 
-// SAM mask decoder (sam_decoder.hip): the arguments of pope_sam_decoder_forward_f32
+// SAM mask decoder (sam_decoder.hip): the arguments of pope_sam_decoder_forward_f32 and, with prompt_image (HOST [P]: the image
+// of each prompt) and image = n_images embeddings, of pope_sam_decoder_forward_images_f32
 struct SamDecArgs {
     const pope_sam_decoder_weights* w;
     const float *image, *image_pe, *sparse, *dense;
     int P, n_sparse, multimask;
+    int n_images;
+    const int* prompt_image;
     long long dense_stride;
     float *masks, *iou, *hs_out, *keys_out;
     void* ws;
@@ -375,6 +378,8 @@ struct SamDecArgs {
     unsigned* range_flag;
 };
 size_t pope_sam_decoder_workspace(const pope_sam_decoder_weights* w, int P, int n_sparse, int shared);
+size_t pope_sam_decoder_images_workspace(const pope_sam_decoder_weights* w, int n_images, const int* prompt_image, int P, int n_sparse,
+                                         long long dense_stride);
 int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream);
 
 // SAM generator post-processing (sam_postprocess.hip): the arguments of pope_sam_postprocess_f32

@@ -8,8 +8,10 @@
 //   t2i.v           = planes(keys) . W^T          (N = 128)
 //   tokens: self-attention, token->image attention (sd_t2i_attn), MLP (ReLU), i2t k / v
 //   image->token attention (sd_i2t_attn) -> planes -> out_proj GEMM -> + keys, norm4     (sd_res_ln)
-// Layer 0 with a broadcast dense embedding (batch stride 0): keys = image + dense is the same for every prompt, so its two
-// projections run once per call on 4 096 rows and the per-prompt kernels read them with a prompt stride of 0.
+// Layer 0 with a broadcast dense embedding (batch stride 0): keys = image + dense depends on the image alone, so its two
+// projections run once per image and call, and the per-prompt kernels read them at the image of their prompt (SdImageOf: a
+// chunk's image indices, a kernel argument by value).  pope_sam_decoder_forward_images_f32 is that path over several images:
+// the chunks fill across images, and a prompt's arithmetic does not know which other images the call holds.
 // Upscaling: ConvTranspose 2x2/2 (256 -> 64) as a GEMM with N = 4 taps x 64 (row = pixel of the 64 x 64 grid, column =
 // tap * 64 + channel), then sd_tail: LayerNorm2d + GELU, the second ConvTranspose (64 -> 32) + GELU and the dot with the 4
 // hypernetwork vectors per prompt, written straight into low_res_masks.
@@ -56,24 +58,31 @@ __device__ __forceinline__ void sd_emit(void* opA, void* opB, bool f32, size_t r
     }
 }
 
+// the layer-0 tensors a chunk's prompts read: slot i[p] of the per-image (or, past layer 0, per-prompt: i[p] = p) buffers
+struct SdImageOf {
+    int i[CHUNK];
+};
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, o));
     return v;
 }
 
-// src = image + dense (image_embeddings / image_pe / dense are channel-major [256, 4096]; dense of prompt p at p * ds) ->
-// keys [np, 4096, 256] fp32 + operands; pe_t [4096, 256] = image_pe transposed (block z == 0 writes it)
-__global__ __launch_bounds__(256) void sd_prep_kernel(const float* __restrict__ img, const float* __restrict__ pe,
+// src = image + dense (image_embeddings / image_pe / dense are channel-major [256, 4096]; block z reads the image at z * is
+// and the dense embedding at z * ds: prompts of one image (is 0) or images under a broadcast (ds 0)) ->
+// keys [nz, 4096, 256] fp32 + operands; pe_t [4096, 256] = image_pe transposed (block z == 0 writes it)
+__global__ __launch_bounds__(256) void sd_prep_kernel(const float* __restrict__ img, long long is, const float* __restrict__ pe,
                                                       const float* __restrict__ dense, long long ds, float* __restrict__ keys,
                                                       void* opA, void* opB, int f32, float* __restrict__ pe_t, unsigned* flag) {
     __shared__ float ti[32][33], tp[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int n0 = blockIdx.x * 32, c0 = blockIdx.y * 32, p = blockIdx.z;
     const float* dp = dense + p * ds;
+    const float* ip = img + p * is;
     for (int i = ty; i < 32; i += 8) {
         const size_t e = size_t(c0 + i) * NPIX + n0 + tx;
-        ti[i][tx] = img[e] + dp[e];
+        ti[i][tx] = ip[e] + dp[e];
         tp[i][tx] = pe[e];
     }
     __syncthreads();
@@ -89,16 +98,17 @@ __global__ __launch_bounds__(256) void sd_prep_kernel(const float* __restrict__ 
     pope_range_flag(flag, POPE_RANGE_LAYERNORM, bad);
 }
 
-// keys[p, n] = LayerNorm(res[p * rps + n] + y[p, n]) (norm4, eps) and its operands; one wave per row, 4 columns per lane
-__global__ __launch_bounds__(256) void sd_res_ln_kernel(const float* res, long long rps, const float* __restrict__ y,
+// keys[p, n] = LayerNorm(res[im.i[p] * rps + n] + y[p, n]) (norm4, eps) and its operands; one wave per row, 4 columns per
+// lane; a block's 4 rows are of one prompt (4 | 4 096)
+__global__ __launch_bounds__(256) void sd_res_ln_kernel(const float* res, long long rps, SdImageOf im, const float* __restrict__ y,
                                                         const float* __restrict__ w, const float* __restrict__ b, float eps,
                                                         const float* __restrict__ pe_t, float* keys, void* opA, void* opB, int f32,
                                                         int rows, unsigned* flag) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const int p = row / NPIX, n = row - p * NPIX;
+    const int p = blockIdx.x / (NPIX / 4), n = row - p * NPIX;
     const int c = lane * 4;
-    const f32x4 r = *reinterpret_cast<const f32x4*>(res + p * rps + size_t(n) * D + c);
+    const f32x4 r = *reinterpret_cast<const f32x4*>(res + im.i[p] * rps + size_t(n) * D + c);
     const f32x4 a = *reinterpret_cast<const f32x4*>(y + size_t(row) * D + c);
     const f32x4 x = r + a;
     const float mean = wave_sum((x[0] + x[1]) + (x[2] + x[3])) * (1.f / D);
@@ -215,10 +225,12 @@ __global__ __launch_bounds__(64) void sd_self_attn_kernel(const float* __restric
     for (int d = 0; d < HDS; ++d) op[d] = o[d] / l;
 }
 
-// token -> image attention of one (head, prompt): q [R, 128] (tokens), K rows of ld ldk at K + p * kps, V rows of ld 128 at
-// V + p * vps (a stride of 0: the shared layer-0 projections), out [R, 128].  Each thread owns keys tid + 256 i.
+// token -> image attention of one (head, prompt): q [R, 128] (tokens), K rows of ld ldk at K + im.i[p] * kps, V rows of ld
+// 128 at V + im.i[p] * vps (layer 0 under a broadcast: the projections of the prompt's image), out [R, 128].  Each thread owns
+// keys tid + 256 i.
 __global__ __launch_bounds__(256) void sd_t2i_attn_kernel(const float* __restrict__ q, const float* __restrict__ K, int ldk, long long kps,
-                                                          const float* __restrict__ V, long long vps, float* __restrict__ out, int T) {
+                                                          const float* __restrict__ V, long long vps, SdImageOf im,
+                                                          float* __restrict__ out, int T) {
     __shared__ float qs[MAX_T][HDC];
     __shared__ float sc[NPIX];
     __shared__ float red[4][HDC + 1];
@@ -226,8 +238,8 @@ __global__ __launch_bounds__(256) void sd_t2i_attn_kernel(const float* __restric
     const int h = blockIdx.x, p = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     for (int i = tid; i < T * HDC; i += 256) qs[i / HDC][i % HDC] = q[(size_t(p) * T + i / HDC) * DI + h * HDC + i % HDC];
     __syncthreads();
-    const float* kb = K + p * kps + h * HDC;
-    const float* vb = V + p * vps + h * HDC;
+    const float* kb = K + im.i[p] * kps + h * HDC;
+    const float* vb = V + im.i[p] * vps + h * HDC;
     for (int t = 0; t < T; ++t) {
         float m = -INFINITY;
 #pragma unroll 4
@@ -282,16 +294,17 @@ __global__ __launch_bounds__(256) void sd_t2i_attn_kernel(const float* __restric
     }
 }
 
-// image -> token attention: 4 096 queries of a prompt (Q rows of ld 256 at Q + p * qps) against its T tokens
+// image -> token attention: 4 096 queries of a prompt (Q rows of ld 256 at Q + im.i[p] * qps) against its T tokens
 // (kv [R, 256] = k | v); thread = (pixel, head); out [np * 4096, 128] as planes, or fp32 (f32)
-__global__ __launch_bounds__(256) void sd_i2t_attn_kernel(const float* __restrict__ Q, long long qps, const float* __restrict__ kv, int T,
+__global__ __launch_bounds__(256) void sd_i2t_attn_kernel(const float* __restrict__ Q, long long qps, SdImageOf im,
+                                                          const float* __restrict__ kv, int T,
                                                           void* out, int f32, unsigned* flag) {
     __shared__ float ks[MAX_T * D];
     const int p = blockIdx.y, tid = threadIdx.x;
     for (int i = tid; i < T * D; i += 256) ks[i] = kv[size_t(p) * T * D + i];
     __syncthreads();
     const int n = blockIdx.x * 32 + (tid >> 3), h = tid & 7;
-    const float* qr = Q + p * qps + size_t(n) * D + h * HDC;
+    const float* qr = Q + im.i[p] * qps + size_t(n) * D + h * HDC;
     float qv[HDC];
 #pragma unroll
     for (int d4 = 0; d4 < HDC; d4 += 4) {
@@ -428,17 +441,18 @@ struct Buffers {
     float *qry, *tpe, *tmp, *tatt, *tqkv, *th, *tq, *tkv, *h1, *h2, *hyper;
 };
 
-Buffers carve(char* base, int cp, int T, bool shared, size_t* total) {
+// n_img > 0: the layer-0 buffers of n_img images (a broadcast dense embedding)
+Buffers carve(char* base, int cp, int T, int n_img, size_t* total) {
     Ws w{base};
     Buffers b{};
     const size_t img = size_t(NPIX) * D;
     b.pe_t = w.take<float>(img);
-    if (shared) {
-        b.keys0 = w.take<float>(img);
-        b.opA0 = w.take<float>(img);
-        b.opB0 = w.take<float>(img);
-        b.qk0 = w.take<float>(img);
-        b.v0 = w.take<float>(size_t(NPIX) * DI);
+    if (n_img > 0) {
+        b.keys0 = w.take<float>(img * n_img);
+        b.opA0 = w.take<float>(img * n_img);
+        b.opB0 = w.take<float>(img * n_img);
+        b.qk0 = w.take<float>(img * n_img);
+        b.v0 = w.take<float>(size_t(NPIX) * DI * n_img);
     }
     b.keys = w.take<float>(img * cp);
     b.opA = w.take<float>(img * cp);   // planes of [rows, 256]: 4 bytes per element, like fp32
@@ -490,8 +504,9 @@ int ln_tok(const Ctx& c, const float* x, float* out, const float* w, const float
     return pope_check_launch();
 }
 
-int t2i(const Ctx& c, const float* q, const float* K, int ldk, long long kps, const float* V, long long vps, float* out, int T, int np) {
-    hipLaunchKernelGGL(sd_t2i_attn_kernel, dim3(HEADS, np), dim3(256), 0, c.s, q, K, ldk, kps, V, vps, out, T);
+int t2i(const Ctx& c, const float* q, const float* K, int ldk, long long kps, const float* V, long long vps, const SdImageOf& im,
+        float* out, int T, int np) {
+    hipLaunchKernelGGL(sd_t2i_attn_kernel, dim3(HEADS, np), dim3(256), 0, c.s, q, K, ldk, kps, V, vps, im, out, T);
     return pope_check_launch();
 }
 
@@ -528,7 +543,18 @@ bool weights_ok(const pope_sam_decoder_weights* w) {
 size_t pope_sam_decoder_workspace(const pope_sam_decoder_weights* w, int P, int n_sparse, int shared) {
     if (!geometry_ok(w) || P <= 0 || n_sparse < 0 || n_sparse > MAX_SPARSE) return 0;
     size_t total = 0;
-    carve(nullptr, P < CHUNK ? P : CHUNK, NBASE + n_sparse, shared != 0, &total);
+    carve(nullptr, P < CHUNK ? P : CHUNK, NBASE + n_sparse, shared ? 1 : 0, &total);
+    return total;
+}
+
+size_t pope_sam_decoder_images_workspace(const pope_sam_decoder_weights* w, int n_images, const int* prompt_image, int P, int n_sparse,
+                                         long long dense_stride) {
+    if (!geometry_ok(w) || n_images <= 0 || !prompt_image || P <= 0 || n_sparse < 0 || n_sparse > MAX_SPARSE) return 0;
+    if (dense_stride != 0) return 0;   // the broadcast only
+    for (int p = 0; p < P; ++p)
+        if (prompt_image[p] < 0 || prompt_image[p] >= n_images) return 0;
+    size_t total = 0;
+    carve(nullptr, P < CHUNK ? P : CHUNK, NBASE + n_sparse, n_images, &total);
     return total;
 }
 
@@ -539,9 +565,14 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
     if (!a.image || !a.image_pe || !a.dense || !a.masks || !a.iou || !a.ws) return POPE_ERR_ARG;
     if (a.dense_stride != 0 && a.dense_stride != (long long)D * NPIX) return POPE_ERR_ARG;
     const bool shared = a.dense_stride == 0;
+    // several images (prompt_image: prompt -> image): the broadcast only, and before any launch no index outside the images
+    const int NI = a.prompt_image ? a.n_images : 1;
+    if (a.prompt_image && (a.hs_out || a.keys_out ||
+                           pope_sam_decoder_images_workspace(w, NI, a.prompt_image, a.P, a.n_sparse, a.dense_stride) == 0))
+        return POPE_ERR_ARG;
     const int T = NBASE + a.n_sparse, cp_max = a.P < CHUNK ? a.P : CHUNK;
     size_t need = 0;
-    const Buffers B = carve(static_cast<char*>(a.ws), cp_max, T, shared, &need);
+    const Buffers B = carve(static_cast<char*>(a.ws), cp_max, T, shared ? NI : 0, &need);
     if (a.ws_bytes < need) return POPE_ERR_WORKSPACE;
     const Ctx c{w->precision == POPE_PREC_F32_MFMA, a.range_flag, stream};
     const int f32 = c.f32 ? 1 : 0;
@@ -549,32 +580,44 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
     const int C = a.multimask ? NMASK - 1 : 1, m0 = a.multimask ? 1 : 0;
     const size_t img = size_t(NPIX) * D;
 
-    if (shared) {   // layer 0's image-only projections, once per call
-        hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, 1), dim3(256), 0, stream, a.image, a.image_pe, a.dense, 0LL, B.keys0,
-                           B.opA0, B.opB0, f32, B.pe_t, a.range_flag);
+    SdImageOf own{}, im0{};   // a prompt's own slot of the per-prompt buffers; layer 0 under a broadcast: its image (0: the one image)
+    for (int p = 0; p < CHUNK; ++p) own.i[p] = p;
+    // layer 0's image-only projections, once per image and call; at most CHUNK images per GEMM: the row counts of the
+    // per-prompt GEMMs below, whose rows do not depend on the rows beside them
+    for (int i0 = 0; shared && i0 < NI; i0 += CHUNK) {
+        const int ni = NI - i0 < CHUNK ? NI - i0 : CHUNK;
+        const size_t o = size_t(i0) * img, ov = size_t(i0) * NPIX * DI;
+        float* keys0 = B.keys0 + o;
+        void* opA0 = static_cast<float*>(B.opA0) + o;   // planes of [rows, 256]: 4 bytes per element, like fp32
+        void* opB0 = static_cast<float*>(B.opB0) + o;
+        hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, ni), dim3(256), 0, stream, a.image + o, (long long)img, a.image_pe,
+                           a.dense, 0LL, keys0, opA0, opB0, f32, B.pe_t, a.range_flag);
         POPE_TRY(pope_check_launch());
-        const void* A0 = c.f32 ? static_cast<const void*>(B.keys0) : B.opA0;
-        POPE_TRY(gemm(c, B.opB0, w->layers_host[0].img_qk_wp, w->layers_host[0].img_qk_b, B.qk0, NPIX, D, D));
-        POPE_TRY(gemm(c, A0, w->layers_host[0].img_v_wp, w->layers_host[0].img_v_b, B.v0, NPIX, DI, D));
+        const void* A0 = c.f32 ? static_cast<const void*>(keys0) : opA0;
+        POPE_TRY(gemm(c, opB0, w->layers_host[0].img_qk_wp, w->layers_host[0].img_qk_b, B.qk0 + o, ni * NPIX, D, D));
+        POPE_TRY(gemm(c, A0, w->layers_host[0].img_v_wp, w->layers_host[0].img_v_b, B.v0 + ov, ni * NPIX, DI, D));
     }
     const void* opA = c.f32 ? static_cast<const void*>(B.keys) : B.opA;
     for (int pg0 = 0; pg0 < a.P; pg0 += CHUNK) {
         const int cp = a.P - pg0 < CHUNK ? a.P - pg0 : CHUNK, R = T * cp, rows = cp * NPIX;
+        if (a.prompt_image)
+            for (int p = 0; p < cp; ++p) im0.i[p] = a.prompt_image[pg0 + p];
         hipLaunchKernelGGL(sd_tokens_kernel, dim3((R * D + 255) / 256), dim3(256), 0, stream, w->tokens,
                            a.n_sparse ? a.sparse + size_t(pg0) * a.n_sparse * D : nullptr, a.n_sparse, T, R, B.qry, B.tpe);
         POPE_TRY(pope_check_launch());
         if (!shared) {
-            hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, cp), dim3(256), 0, stream, a.image, a.image_pe,
+            hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, cp), dim3(256), 0, stream, a.image, 0LL, a.image_pe,
                                a.dense + pg0 * a.dense_stride, a.dense_stride, B.keys, B.opA, B.opB, f32, B.pe_t, a.range_flag);
             POPE_TRY(pope_check_launch());
         }
         for (int l = 0; l < 2; ++l) {
             const pope_sam_decoder_layer_weights& L = w->layers_host[l];
             const float *qk = B.qk, *v = B.v, *res = B.keys;
-            long long qps = (long long)img, vps = (long long)NPIX * DI, rps = (long long)img;
-            if (l == 0 && shared) {
+            const long long qps = (long long)img, vps = (long long)NPIX * DI, rps = (long long)img;
+            const bool first = l == 0 && shared;
+            const SdImageOf& im = first ? im0 : own;
+            if (first) {
                 qk = B.qk0; v = B.v0; res = B.keys0;
-                qps = vps = rps = 0;
             } else {
                 POPE_TRY(gemm(c, B.opB, L.img_qk_wp, L.img_qk_b, B.qk, rows, D, D));
                 POPE_TRY(gemm(c, opA, L.img_v_wp, L.img_v_b, B.v, rows, DI, D));
@@ -587,7 +630,7 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
             POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm1_w, L.norm1_b, teps, R));
             // tokens -> image
             POPE_TRY(lin(c, B.qry, D, B.tpe, DI, L.t2i_q_w, L.t2i_q_b, nullptr, B.tq, DI, R, DI, D, false));
-            POPE_TRY(t2i(c, B.tq, qk, D, qps, v, vps, B.tatt, T, cp));
+            POPE_TRY(t2i(c, B.tq, qk, D, qps, v, vps, im, B.tatt, T, cp));
             POPE_TRY(lin(c, B.tatt, DI, nullptr, 0, L.t2i_o_w, L.t2i_o_b, B.qry, B.tmp, D, R, D, DI, false));
             POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm2_w, L.norm2_b, teps, R));
             // MLP (ReLU)
@@ -596,11 +639,11 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
             POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm3_w, L.norm3_b, teps, R));
             // image -> tokens: k from tokens + pe, v from tokens
             POPE_TRY(lin(c, B.qry, D, B.tpe, DI, L.i2t_kv_w, L.i2t_kv_b, nullptr, B.tkv, D, R, D, D, false));
-            hipLaunchKernelGGL(sd_i2t_attn_kernel, dim3(NPIX / 32, cp), dim3(256), 0, stream, qk + DI, qps, B.tkv, T,
+            hipLaunchKernelGGL(sd_i2t_attn_kernel, dim3(NPIX / 32, cp), dim3(256), 0, stream, qk + DI, qps, im, B.tkv, T,
                                static_cast<void*>(B.att), f32, a.range_flag);
             POPE_TRY(pope_check_launch());
             POPE_TRY(gemm(c, B.att, L.i2t_o_wp, L.i2t_o_b, B.y, rows, D, DI));
-            hipLaunchKernelGGL(sd_res_ln_kernel, dim3(rows / 4), dim3(256), 0, stream, res, rps, B.y, L.norm4_w, L.norm4_b, teps, B.pe_t,
+            hipLaunchKernelGGL(sd_res_ln_kernel, dim3(rows / 4), dim3(256), 0, stream, res, rps, im, B.y, L.norm4_w, L.norm4_b, teps, B.pe_t,
                                B.keys, B.opA, B.opB, f32, rows, a.range_flag);
             POPE_TRY(pope_check_launch());
         }
@@ -608,7 +651,7 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
         POPE_TRY(gemm(c, B.opB, w->fin_k_wp, w->fin_k_b, B.qk, rows, DI, D));
         POPE_TRY(gemm(c, opA, w->fin_v_wp, w->fin_v_b, B.v, rows, DI, D));
         POPE_TRY(lin(c, B.qry, D, B.tpe, DI, w->fin_q_w, w->fin_q_b, nullptr, B.tq, DI, R, DI, D, false));
-        POPE_TRY(t2i(c, B.tq, B.qk, DI, (long long)NPIX * DI, B.v, (long long)NPIX * DI, B.tatt, T, cp));
+        POPE_TRY(t2i(c, B.tq, B.qk, DI, (long long)NPIX * DI, B.v, (long long)NPIX * DI, own, B.tatt, T, cp));
         POPE_TRY(lin(c, B.tatt, DI, nullptr, 0, w->fin_o_w, w->fin_o_b, B.qry, B.tmp, D, R, D, DI, false));
         POPE_TRY(ln_tok(c, B.tmp, B.qry, w->norm_final_w, w->norm_final_b, teps, R));
         if (a.hs_out && hipMemcpyAsync(a.hs_out + size_t(pg0) * T * D, B.qry, size_t(R) * D * sizeof(float), hipMemcpyDeviceToDevice,

@@ -329,6 +329,84 @@ class MaskDecoder(nn.Module):
         masks, iou, _, _ = self._run(image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings, multimask_output)
         return masks, iou
 
+    # ---- several images in one call --------------------------------------------------------------------------------
+    IMAGES_PER_CALL = 16   # bounds the workspace: the layer-0 buffers are held once per image of a call (18 MB each)
+
+    def forward_images(self, image_embeddings: torch.Tensor, image_pe: torch.Tensor, sparse_prompt_embeddings: torch.Tensor,
+                       dense_prompt_embeddings: torch.Tensor, prompt_image, multimask_output: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`forward` over the prompts of N images: image_embeddings [N, 256, 64, 64], sparse [P, n, 256], dense the broadcast
+        `PromptEncoder` returns without a mask ([1 or P, 256, 64, 64], one value per channel), prompt_image [P] = the image of
+        each prompt (host integers, any order) -> (low_res_masks [P, C, 256, 256], iou_pred [P, C]), prompt for prompt
+        bit-identical to `forward` with that prompt's image alone.  One C call (`pope_sam_decoder_forward_images_f32`) and one
+        range-flag read per group of at most 16 images; a flagged group is handled per image by `forward`, so that one
+        image's overflow neither changes nor re-runs another image's prompts on other arithmetic than its own call would."""
+        for t, name in ((image_embeddings, "image_embeddings"), (image_pe, "image_pe"), (sparse_prompt_embeddings, "sparse_prompt_embeddings"),
+                        (dense_prompt_embeddings, "dense_prompt_embeddings")):
+            require_cuda(t, "MaskDecoder")
+            if t.dtype != torch.float32:
+                raise TypeError(f"MaskDecoder: {name} must be float32, got {t.dtype}")
+        sparse, dense = sparse_prompt_embeddings, dense_prompt_embeddings
+        if image_embeddings.dim() != 4 or tuple(image_embeddings.shape[1:]) != (DIM, GRID, GRID) or tuple(image_pe.shape) != (1, DIM, GRID, GRID):
+            raise ValueError(f"MaskDecoder.forward_images: image_embeddings must be [N, {DIM}, {GRID}, {GRID}] and image_pe "
+                             f"[1, {DIM}, {GRID}, {GRID}], got {tuple(image_embeddings.shape)} and {tuple(image_pe.shape)}")
+        if sparse.dim() != 3 or sparse.shape[2] != DIM or sparse.shape[1] > MAX_SPARSE:
+            raise ValueError(f"MaskDecoder: sparse_prompt_embeddings must be [P, n <= {MAX_SPARSE}, {DIM}], got {tuple(sparse.shape)}")
+        N, P, ns = image_embeddings.shape[0], sparse.shape[0], sparse.shape[1]
+        if dense.dim() != 4 or tuple(dense.shape[1:]) != (DIM, GRID, GRID) or dense.shape[0] not in (1, P) or \
+                not (dense.shape[0] == 1 or dense.stride(0) == 0):
+            raise ValueError("MaskDecoder.forward_images: dense_prompt_embeddings must be the broadcast PromptEncoder returns "
+                             f"without a mask ([1 or P, {DIM}, {GRID}, {GRID}], batch stride 0), got {tuple(dense.shape)}")
+        which = np.asarray(prompt_image.cpu() if isinstance(prompt_image, torch.Tensor) else prompt_image, dtype=np.int64).reshape(-1)
+        if which.size != P or (P and (which.min() < 0 or which.max() >= N)):
+            raise ValueError(f"MaskDecoder.forward_images: prompt_image must hold {P} image indices in [0, {N})")
+        Cm = self.num_multimask_outputs if multimask_output else 1
+        dev = image_embeddings.device
+        masks = torch.empty(P, Cm, 4 * GRID, 4 * GRID, device=dev, dtype=torch.float32)
+        iou = torch.empty(P, Cm, device=dev, dtype=torch.float32)
+        if P == 0:
+            return masks, iou
+        img, pe, sparse, dense = image_embeddings.contiguous(), image_pe.contiguous(), sparse.contiguous(), dense[:1].contiguous()
+        for i0 in range(0, N, self.IMAGES_PER_CALL):
+            i1 = min(N, i0 + self.IMAGES_PER_CALL)
+            rows = np.nonzero((which >= i0) & (which < i1))[0]
+            if rows.size == 0:
+                continue
+            if i0 == 0 and i1 == N and rows.size == P:   # one group, every prompt: straight into the outputs
+                self._run_images(img, pe, sparse, dense, which, multimask_output, masks, iou)
+                continue
+            idx = torch.as_tensor(rows, device=dev)
+            m, q = masks.new_empty(rows.size, *masks.shape[1:]), iou.new_empty(rows.size, Cm)
+            self._run_images(img[i0:i1], pe, sparse[idx].contiguous(), dense, which[rows] - i0, multimask_output, m, q)
+            masks[idx], iou[idx] = m, q
+        return masks, iou
+
+    def _run_images(self, img, pe, sparse, dense, which, multimask_output, masks, iou):
+        """One `pope_sam_decoder_forward_images_f32` call into masks / iou; on a range event the group's images one by one."""
+        N, P, ns, dev = img.shape[0], sparse.shape[0], sparse.shape[1], img.device
+        w = self._weights()
+        host = (C.c_int * P)(*(int(v) for v in which))
+        need = int(_lib.lib().pope_sam_decoder_images_workspace_bytes(C.byref(w), N, host, P, ns, 0))
+        if need <= 0:
+            raise ValueError(f"pope_amd SAM decoder: unsupported call (N = {N}, P = {P}, n_sparse = {ns}, at most {MAX_SPARSE})")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._ws
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        with on_device_of(img):
+            check(_lib.lib().pope_sam_decoder_forward_images_f32(
+                C.byref(w), ptr(img), N, ptr(pe), ptr(sparse) if ns else None, host, P, ns, ptr(dense), 0,
+                int(bool(multimask_output)), ptr(masks), ptr(iou), ptr(ws), ws.numel(), C.c_void_p(flag.data_ptr()),
+                stream_of(dev)), "pope_sam_decoder_forward_images_f32")
+        if not int(flag.item()):   # one sync per call
+            return
+        # The flag does not say whose value left the range.  Each image's own call does: it counts the event, raises or warns
+        # and re-runs in f32 exactly as the per-image loop would, and leaves the other images on the arithmetic they asked for.
+        for i in np.unique(which):
+            idx = torch.as_tensor(np.nonzero(which == i)[0], device=dev)
+            m, q = self.forward(img[int(i)][None], pe, sparse[idx], dense.expand(idx.numel(), -1, -1, -1), multimask_output)
+            masks[idx], iou[idx] = m, q
+
     def forward_with_taps(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings, multimask_output):
         """(masks, iou_pred, hs [P, T, 256], keys [P, 4096, 256]): the transformer's final tokens and image tokens too."""
         return self._run(image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings, multimask_output, taps=True)

@@ -162,6 +162,64 @@ class Sam(nn.Module):
     def device(self) -> Any:
         return self.pixel_mean.device
 
+    @torch.no_grad()
+    def forward(self, batched_input: List[Dict[str, Any]], multimask_output: bool) -> List[Dict[str, torch.Tensor]]:
+        """modeling/sam.py:53-131, the end-to-end batch call.  One record per image: `image` (3 x h x w, already resized to
+        the model's input frame, long side `img_size`), `original_size` (H, W) and the optional prompts `point_coords`
+        [B, n, 2] + `point_labels` [B, n] and `boxes` [B, 4], in the input frame (`mask_inputs` is not supported).  Returns
+        one dict per record: `masks` (bool [B, C, H, W]), `iou_predictions` [B, C], `low_res_logits` [B, C, 256, 256];
+        C = 3 with `multimask_output`, else 1.
+        The images run through the encoder in one call and the prompts of all records through the multi-image decoder
+        (`MaskDecoder.forward_images`, one call per distinct number of sparse embeddings); the masks of records of one
+        geometry are resampled together.  Every record's output is bit for bit what `SamPredictor.set_torch_image` +
+        `predict_torch` give for that record alone."""
+        records = list(batched_input)
+        if not records:
+            return []
+        for x in records:
+            if x.get("mask_inputs", None) is not None:
+                self.prompt_encoder(points=None, boxes=None, masks=x["mask_inputs"])   # raises: mask prompts are not supported
+        dev = self.device
+        for x in records:
+            for k in ("image", "point_coords", "point_labels", "boxes"):
+                t = x.get(k, None)
+                if t is None:
+                    continue
+                require_cuda(t, "Sam.forward")
+                if t.device != dev:
+                    raise ValueError(f"Sam.forward: record tensor `{k}` is on {t.device}, the model on {dev}")
+        embeddings = self.image_encoder(torch.stack([self.preprocess(x["image"]) for x in records], dim=0).contiguous())
+        pe = self.prompt_encoder.get_dense_pe()
+        sparse, dense = [], None
+        for x in records:
+            points = (x["point_coords"], x["point_labels"]) if "point_coords" in x else None
+            sp, dense = self.prompt_encoder(points=points, boxes=x.get("boxes", None), masks=None)
+            sparse.append(sp)
+        # one decoder call per number of sparse embeddings, over the images that have such prompts; a single record has nothing
+        # to share and takes the single-image call (the same bits, less host work: profiles/sam_forward.md)
+        low, iou = [None] * len(records), [None] * len(records)
+        for ns in sorted({sp.shape[1] for sp in sparse}):
+            members = [r for r, sp in enumerate(sparse) if sp.shape[1] == ns]
+            counts = [sparse[r].shape[0] for r in members]
+            if len(records) == 1:
+                m, q = self.mask_decoder(embeddings, pe, sparse[0], dense, multimask_output)
+            else:
+                emb = embeddings if len(members) == len(records) else embeddings[torch.as_tensor(members, device=dev)]
+                which = np.repeat(np.arange(len(members)), counts)
+                m, q = self.mask_decoder.forward_images(emb, pe, torch.cat([sparse[r] for r in members]), dense[:1], which,
+                                                        multimask_output)
+            for r, mr, qr in zip(members, m.split(counts), q.split(counts)):
+                low[r], iou[r] = mr, qr
+        # postprocess_masks once per geometry
+        masks = [None] * len(records)
+        geometry = [(tuple(int(v) for v in x["image"].shape[-2:]), tuple(int(v) for v in x["original_size"])) for x in records]
+        for geo in dict.fromkeys(geometry):
+            members = [r for r, g in enumerate(geometry) if g == geo]
+            up = self.postprocess_masks(torch.cat([low[r] for r in members]), *geo) > self.mask_threshold
+            for r, ur in zip(members, up.split([low[r].shape[0] for r in members])):
+                masks[r] = ur
+        return [{"masks": masks[r], "iou_predictions": iou[r], "low_res_logits": low[r]} for r in range(len(records))]
+
     def preprocess(self, x: torch.Tensor) -> torch.Tensor:
         """Normalize pixel values and pad to the square input."""
         x = (x - self.pixel_mean) / self.pixel_std

@@ -535,6 +535,28 @@ def sam_decoder_case(name):
     raise KeyError(name)
 
 
+def sam_forward_case(device="cpu"):
+    """A seeded `batched_input` of `Sam.forward` (modeling/sam.py:53-131): two records whose images differ in shape and whose
+    prompts differ in kind.  Record 0: a 3 x 768 x 1024 image (original 480 x 640) with 2 boxes; record 1: a 3 x 1024 x 683
+    image (original 600 x 400) with `point_coords` [3, 2, 2] and labels 1 / 0.  Pixel values are floats in 0 .. 255 (smooth
+    gradients plus noise); prompts are in the input frame."""
+    g = torch.Generator().manual_seed(23)
+
+    def image(h, w):
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32) / h, torch.arange(w, dtype=torch.float32) / w, indexing="ij")
+        base = torch.stack([yy, xx, 0.5 * (yy + xx)]) * 160.0 + 40.0
+        return (base + 25.0 * torch.randn(3, h, w, generator=g)).clamp_(0.0, 255.0).contiguous()
+
+    img0, img1 = image(768, 1024), image(1024, 683)
+    lo = torch.rand(2, 2, generator=g) * torch.tensor([600.0, 400.0])
+    boxes = torch.cat([lo, lo + 100 + torch.rand(2, 2, generator=g) * 250], dim=1)
+    coords = torch.rand(3, 2, 2, generator=g) * torch.tensor([683.0, 1024.0])
+    labels = torch.tensor([[1, 0]] * 3, dtype=torch.int)
+    return [{"image": img0.to(device), "original_size": (480, 640), "boxes": boxes.to(device)},
+            {"image": img1.to(device), "original_size": (600, 400), "point_coords": coords.to(device),
+             "point_labels": labels.to(device)}]
+
+
 # ---- SAM automatic mask generator: post-processing ---------------------------------------------------------------------
 # name -> (M masks, frame (H, W)); the resized frame inside the 1024 square follows from ResizeLongestSide
 SAM_GENERATOR_CASES = {"frame": (128, (480, 640)), "portrait": (48, (333, 332))}
