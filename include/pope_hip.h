@@ -388,7 +388,7 @@ int pope_fine_match_scaled_f32(const float* win0, const float* win1, int M, int 
  * patch_wp[dim, 3 patch^2] = proj.weight.reshape(dim, -1); neck0_wp[out_chans, dim]; neck2_wp[out_chans, 9 out_chans]
  * with the taps in (ky, kx, channel) order = weight.permute(0, 2, 3, 1).reshape(out_chans, -1).  pos[g*g, dim] or NULL.
  * rel_h / rel_w: the tables get_rel_pos returns (image_encoder.py:288-316), R[q][k][head_dim] fp32 with q, k < window
- * (window blocks) or < g (global blocks); the bias q.Rh + q.Rw is folded into the score product (sam.hip).
+ * (window blocks) or < g (global blocks); the bias q.Rh + q.Rw is folded into the score product (sam_attention.hip).
  * ones[dim] = 1.0f.  blocks_host: HOST array [depth] of device pointers.  Optional taps as pope_vit_forward_f32
  * (tap_out_host[t][B*g*g, dim] fp32 = output of block tap_blocks_host[t]). */
 typedef struct pope_sam_block_weights {

@@ -12,7 +12,7 @@ enum GemmEpilogue {
     EPI_BIAS_RELU = 5,    // C = max(A.W^T + bias, 0)                (LoFTR encoder MLP, transformer.py:24-28; gemm_planes.hip only)
     EPI_SIM = 4,          // batched similarity (planes kernel): C[b] = (A[b].W[b]^T * alpha) / divisor, no bias
     EPI_SIM_MASK = 10,    // kernel-side instantiation of EPI_SIM with GemmParams::sim_mask0 / sim_mask1 (callers pass EPI_SIM)
-    EPI_SAM_QKV = 7,      // SAM block's QKV projection written straight into the attention operand planes (sam.hip; gemm_planes.hip only)
+    EPI_SAM_QKV = 7,      // SAM block's QKV projection written straight into the attention operand planes (sam_attention.hip; gemm_planes.hip only)
     EPI_QKV_F16 = 8,      // plain f16 only (POPE_PREC_F16 ViT blocks): C = (A.W^T + bias) * (col < sam_dim ? sam_qscale : 1) -> f16 row-major
                           // [M, N] with NO activation scale: the operand of attention_f16.hip (q carries head_dim^-0.5 * log2 e before its ONE rounding)
     EPI_CONV_UP = 9,      // kernel-side instantiation of EPI_CONV with GemmParams::up_src (callers pass EPI_CONV)
@@ -162,10 +162,11 @@ int pope_launch_gemm_nt_f16x3(const GemmParams& g, hipStream_t stream);
 int pope_launch_layernorm_f32(const float* x, int ldx, const float* w, const float* b, float* y, int ldy,
                               int rows, int dim, float eps, hipStream_t stream);
 
-// POPE_PREC_F16 pieces of the DINOv2 path (sam.hip, attention_f16.hip): LayerNorm -> f16 row-major (value * 8); attention on the f16
-// operands of the QKV epilogue, f16 row-major output (value * 8)
+// POPE_PREC_F16 pieces of the DINOv2 and SAM paths (layernorm.hip, attention_f16.hip): LayerNorm -> f16 row-major (value * 8), the
+// plain conversion fp32 -> f16 (value * 8) of n4 quads; attention on the f16 operands of the QKV epilogue, f16 row-major output (value * 8)
 int pope_launch_layernorm_f16(const float* x, const float* w, const float* b, void* y_f16, int rows, int dim, float eps, unsigned* flag,
                               hipStream_t stream);
+int pope_launch_to_f16(const float* x, void* y_f16, long long n4, unsigned* flag, hipStream_t stream);
 // round 4: f16 qkv in (EPI_QKV_F16), LDS-direct K / V staging, four stages, software-pipelined (attention_f16.hip)
 int pope_launch_attention_f16_dma(const void* qkv_f16, void* out_f16, int B, int N, int heads, hipStream_t stream);
 // Multi-head softmax attention over qkv[B, N, 3, heads, 64] -> out[B, N, heads*64].
@@ -297,43 +298,50 @@ int pope_launch_fine_match_scaled(const float* win0, const float* win1, int M, i
 size_t pope_loftr_layer_workspace(int n, int L, int S, int C, int H);
 int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream);
 
-// SAM image encoder (sam.hip; segment_anything/segment_anything/modeling/image_encoder.py:17-118).  Weight planes: scale
-// K_PLANES_W_SCALE, torch Linear layout [out, in]; every pointer is a device pointer except `blocks`, `tap_blocks`, `tap_out`.
-struct SamBlockParams {
-    const float *norm1_w, *norm1_b;
-    const void* qkv_wp; const float* qkv_b;      // [3 dim, dim], [3 dim]
-    const void* proj_wp; const float* proj_b;    // [dim, dim], [dim]
-    const float *rel_h, *rel_w;                  // gathered tables R[q][k][head_dim] (get_rel_pos, image_encoder.py:288-316): [s, s, hd]
-                                                 // with s = window (window blocks) or grid (global blocks)
-    const float *norm2_w, *norm2_b;
-    const void* fc1_wp; const float* fc1_b;      // [hidden, dim]
-    const void* fc2_wp; const float* fc2_b;      // [dim, hidden]
-    int global;                                  // 1: global attention (window_size 0, image_encoder.py:77)
-};
-struct SamEncParams {
+// SAM image encoder (sam.hip; segment_anything/segment_anything/modeling/image_encoder.py:17-118): the arguments of
+// pope_sam_encoder_forward_f32.  The weights are read from the ABI's struct as it is (pope_hip.h: what every `*_wp` holds per precision).
+struct SamEncArgs {
+    const pope_sam_encoder_weights* w;
     const float* image;   // [B, 3, img, img] fp32
     float* out;           // [B, out_chans, g, g] fp32, g = img / patch
-    int B, img, patch, dim, depth, heads, hidden, out_chans, window;
-    int precision;        // POPE_PREC_F16X3 (weights = planes) | POPE_PREC_F16 (weights = f16 row-major, value * 256) |
-                          // POPE_PREC_F32_MFMA (weights = fp32 matrices: the range guard's re-run, sam_f32.hip)
-    float block_eps, neck_eps;   // LayerNorm eps of the blocks / of the neck's LayerNorm2d (<= 0: 1e-6)
-    const void* patch_wp; const float* patch_b;   // [dim, 3 patch^2], [dim]
-    const float* pos;                             // [g g, dim] or null (use_abs_pos = False)
-    const float* ones;                            // [dim] of 1.0f (no LayerScale in this ViT)
-    const SamBlockParams* blocks;                 // host array [depth]
-    const void* neck0_wp;                         // [out_chans, dim]
-    const float *neck1_w, *neck1_b;
-    const void* neck2_wp;                         // [out_chans, 9 out_chans], taps (ky, kx, channel)
-    const float *neck3_w, *neck3_b;
-    int n_taps; const int* tap_blocks; float* const* tap_out;   // optional block outputs [B g g, dim] fp32
+    int B;
+    int n_taps; const int* tap_blocks; float* const* tap_out;   // optional block outputs [B g g, dim] fp32 (host arrays)
     void* ws; size_t ws_bytes;
     unsigned* range_flag;
 };
-size_t pope_sam_encoder_workspace(const SamEncParams& q);
-int pope_launch_sam_encoder(const SamEncParams& q, hipStream_t stream);
-// POPE_PREC_F32_MFMA twin (sam_f32.hip): every `*_wp` is a plain fp32 [out, in] matrix; same workspace; arguments validated by
-// pope_launch_sam_encoder, which dispatches here
-int pope_launch_sam_encoder_f32mfma(const SamEncParams& q, hipStream_t stream);
+size_t pope_sam_encoder_workspace(const pope_sam_encoder_weights* w, int B);
+// every POPE_ERR_ARG / POPE_ERR_WORKSPACE is returned before the first HIP call
+int pope_launch_sam_encoder(const SamEncArgs& a, hipStream_t stream);
+
+// Attention of one SAM encoder block on the f16 matrix cores (sam_attention.hip), POPE_PREC_F16X3 or (plain) POPE_PREC_F16:
+// the plan of a geometry (window side ws; ws = g: a global block), its operand regions in the caller's workspace, the
+// once-per-pass preparation and one block.
+struct SamAttnPlan {
+    int B = 0, g = 0, ws = 0, heads = 0, hd = 0;   // images, token grid g x g, window side, heads, head dim
+    int nstep = 0;                                 // score depth / 16
+    bool bias = false;               // relative-position terms as a bias table (sam_attn_kernel<.., BIAS>), not as columns of Q' / K'
+    size_t qp = 0, kp = 0, vp = 0, tab = 0, map = 0;   // bytes: operand planes Q', K', V, the bias table (0 without one), the row map
+    int hpg = 0, n_tasks = 0;        // the relative-position kernel's heads per wave and task count
+    bool launchable = false;         // false: an operand reaches 4 GiB or the task count 2^31 (the caller splits the batch)
+};
+struct SamAttnOperands { void *q, *k, *v, *tab; int* map; };   // 256-byte aligned regions of qp, kp, vp, tab, map bytes
+bool pope_sam_attn_plan(int B, int g, int ws, int heads, int hd, SamAttnPlan& p);   // false: no kernel holds hd + 2 ws score columns; no HIP call
+// prepare and block take a plan that pope_sam_attn_plan accepted; block returns POPE_ERR_ARG, before any launch, for one that is
+// not `launchable` or whose bias table has no region
+int pope_sam_attn_prepare(const SamAttnPlan& p, const SamAttnOperands& o, bool plain, hipStream_t stream);
+// xn = norm1(x) as the precision's GEMM operand [B g g, dim] -> att_out, the proj GEMM's operand; reads k.qkv_wp, qkv_b, rel_h, rel_w
+int pope_sam_attn_block(const SamAttnPlan& p, const SamAttnOperands& o, bool plain, const void* xn, const pope_sam_block_weights& k,
+                        void* att_out, unsigned* flag, hipStream_t stream);
+
+// POPE_PREC_F32_MFMA pieces of the SAM encoder (sam_f32.hip): every operand fp32
+int pope_launch_sam32_im2col(const float* img, float* out, int B, int S, int P, hipStream_t stream);   // -> rows [B g g, 3 P P]; P % 4 == 0
+int pope_sam32_attention_check(int B, int g, int ws, int heads, int hd);   // head dim, grid size and LDS size of the launch below; no HIP call
+// qkv [B g g, 3 dim] -> out [B g g, dim]; rel_h / rel_w [ws, ws, hd].  The caller has passed pope_sam32_attention_check.
+int pope_launch_sam32_attention(const float* qkv, const float* qkv_bias, const float* rel_h, const float* rel_w, float* out, int B, int g,
+                                int ws, int heads, int hd, hipStream_t stream);
+// LayerNorm2d: bordered_out: in [B g g, C] -> out [B, g + 2, g + 2, C] with a zero border; else in bordered -> out NCHW [B, C, g, g]
+int pope_launch_sam32_ln2d(const float* in, const float* w, const float* b, float* out, int B, int g, int C, float eps, bool bordered_out,
+                           hipStream_t stream);
 
 // Batched relative pose (pose.hip; src/utils/metrics.py:69-94): one workgroup per pair
 struct PoseParams {

@@ -2,6 +2,7 @@
 // used as norm1/norm2 in block.py:56,68 and as the final norm, vision_transformer.py:230).
 // HBM-bound streaming op: one wave per row, the row lives in registers (float2 per lane per
 // 128 columns), two-pass mean / centred variance, wave-shuffle reductions, no LDS.
+// Beside it the other operand producers: the same LayerNorm as f16x3 planes or plain f16 rows, the plain converters, im2col.
 #include "common.h"
 #include "kernels.h"
 
@@ -367,6 +368,61 @@ __global__ __launch_bounds__(256) void layernorm_rowln_order_kernel(const float*
         pope_range_flag(flag, POPE_RANGE_LAYERNORM,
                         ok && (!(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY)));
 }
+
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+constexpr float A_SCALE = K_PLANES_ACT_SCALE;
+// ---- precision "f16": LayerNorm over the last dim -> f16 row-major (value * 8), one wave per row (dim % 128 == 0, <= 2048);
+// and the plain conversion fp32 -> f16 (value * 8) of the neck's input
+template <int NV>
+__global__ __launch_bounds__(256) void sam_ln_f16_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ b, _Float16* __restrict__ y, int rows,
+                                                         float eps, unsigned* range_flag) {
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    constexpr int nv = NV, dim = NV * 128;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + (size_t)row * dim;
+    f32x2 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < nv; ++i) {
+        v[i] = *reinterpret_cast<const f32x2*>(xr + i * 128 + lane * 2);
+        s += v[i][0] + v[i][1];
+    }
+    const float mean = wave_sum(s) / float(dim);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < nv; ++i) {
+        const float d0 = v[i][0] - mean, d1 = v[i][1] - mean;
+        q += d0 * d0 + d1 * d1;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / float(dim) + eps);
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < nv; ++i) {
+        const int c = i * 128 + lane * 2;
+        const f32x2 ww = *reinterpret_cast<const f32x2*>(w + c), bb = *reinterpret_cast<const f32x2*>(b + c);
+        f32x2 o;
+        o[0] = ((v[i][0] - mean) * rstd * ww[0] + bb[0]) * A_SCALE;
+        o[1] = ((v[i][1] - mean) * rstd * ww[1] + bb[1]) * A_SCALE;
+        amax = pope_amax2(amax, o);
+        *reinterpret_cast<f16x2*>(y + (size_t)row * dim + c) = __builtin_convertvector(o, f16x2);
+    }
+    pope_range_flag(range_flag, POPE_RANGE_LAYERNORM, !(amax < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY));
+}
+
+__global__ __launch_bounds__(256) void sam_to_f16_kernel(const float* __restrict__ x, _Float16* __restrict__ y, long long n4,
+                                                         unsigned* range_flag) {
+    float amax = 0.f;
+    for (long long id = blockIdx.x * 256ll + threadIdx.x; id < n4; id += 256ll * gridDim.x) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * id);
+        amax = pope_amax4(amax, v);
+        if (!((v[0] + v[1]) + (v[2] + v[3]) == (v[0] + v[1]) + (v[2] + v[3]))) amax = INFINITY;
+        *reinterpret_cast<f16x4*>(y + 4 * id) = __builtin_convertvector(v * A_SCALE, f16x4);
+    }
+    pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
+}
 }  // namespace
 
 int pope_launch_range_check(const float* x, size_t n, float scale, unsigned* flag, unsigned bit, hipStream_t stream) {
@@ -469,5 +525,28 @@ int pope_launch_layernorm_rowln_order(const float* x, const float* w, const floa
     const dim3 grid((rows + 15) / 16), block(256);
     if (y_planes) hipLaunchKernelGGL(layernorm_rowln_order_kernel<true>, grid, block, 0, stream, x, w, b, y_planes, rows, eps, flag);
     else hipLaunchKernelGGL(layernorm_rowln_order_kernel<false>, grid, block, 0, stream, x, w, b, static_cast<void*>(y_f32), rows, eps, flag);
+    return pope_check_launch();
+}
+
+// y = LayerNorm(x) * w + b as f16 row-major (value * 8): the A operand of the plain-f16 GEMMs (POPE_PREC_F16)
+int pope_launch_layernorm_f16(const float* x, const float* w, const float* b, void* y_f16, int rows, int dim, float eps, unsigned* flag,
+                              hipStream_t stream) {
+    if (!x || !w || !b || !y_f16 || rows <= 0) return POPE_ERR_ARG;
+#define POPE_SAM_LN(NV)                                                                                                       \
+    case NV:                                                                                                                  \
+        hipLaunchKernelGGL(sam_ln_f16_kernel<NV>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, w, b, static_cast<_Float16*>(y_f16), \
+                           rows, eps, flag);                                                                                  \
+        break;
+    switch (dim % 128 ? 0 : dim / 128) {
+        POPE_SAM_LN(2) POPE_SAM_LN(3) POPE_SAM_LN(4) POPE_SAM_LN(5) POPE_SAM_LN(6) POPE_SAM_LN(8) POPE_SAM_LN(10) POPE_SAM_LN(12) POPE_SAM_LN(16)
+        default: return POPE_ERR_ARG;
+    }
+#undef POPE_SAM_LN
+    return pope_check_launch();
+}
+
+int pope_launch_to_f16(const float* x, void* y_f16, long long n4, unsigned* flag, hipStream_t stream) {
+    if (!x || !y_f16 || n4 <= 0) return POPE_ERR_ARG;
+    hipLaunchKernelGGL(sam_to_f16_kernel, dim3(pope_grid_for(n4)), dim3(256), 0, stream, x, static_cast<_Float16*>(y_f16), n4, flag);
     return pope_check_launch();
 }

@@ -1,6 +1,6 @@
 // SAM image encoder, POPE_PREC_F32_MFMA: the range guard's re-run and the strict-fp32 mode of ImageEncoderViT
-// (segment_anything/segment_anything/modeling/image_encoder.py:107-118).  Same launch sequence as sam.hip with fp32
-// operands everywhere: every Linear / convolution on gemm_f32.hip (v_mfma_f32_32x32x2_f32: the reference's own fp32
+// (segment_anything/segment_anything/modeling/image_encoder.py:107-118).  The kernels of sam.hip's launch sequence that are this
+// route's own, fp32 operands everywhere: every Linear / convolution runs on gemm_f32.hip (v_mfma_f32_32x32x2_f32: the reference's own fp32
 // arithmetic, no range contract), LayerNorm by layernorm.hip's fp32 kernel, and a plain fp32 attention kernel for the
 // window / global blocks with the decomposed relative-position terms (image_encoder.py:217-235, 325-358).  It shares the
 // f16x3 path's workspace (the operand-plane regions serve as scratch).  Speed is not a goal here — this is the path a
@@ -8,7 +8,6 @@
 // (tests/test_gpu_sam.py).
 #include "common.h"
 #include "kernels.h"
-#include "linear.h"
 
 namespace {
 
@@ -162,89 +161,40 @@ __global__ __launch_bounds__(256) void sam32_ln2d_kernel(const float* __restrict
     }
 }
 
+size_t sam32_attention_lds(int ws, int hd) { return size_t(2 * ATT_KT * hd + 64 * (2 * ws + 1)) * sizeof(float); }
+long long sam32_attention_blocks(int B, int g, int ws, int heads) {
+    const int nw = (g + ws - 1) / ws, qtiles = (ws * ws + 63) / 64;
+    return (long long)B * nw * nw * heads * qtiles;
+}
+
 }  // namespace
 
-int pope_launch_sam_encoder_f32mfma(const SamEncParams& q, hipStream_t stream) {
-    const int g = q.img / q.patch, hd = q.dim / q.heads, dim = q.dim, hidden = q.hidden, oc = q.out_chans;
-    const int kp = 3 * q.patch * q.patch;
-    if ((q.patch & 3) || (hd != 64 && hd != 80)) return POPE_ERR_ARG;
-    const int rows = q.B * g * g;
-    const size_t gp = size_t(g) + 2, brows = size_t(q.B) * gp * gp;
-    // the workspace of the f16x3 path (pope_sam_encoder_workspace), re-read as: x | xn | big | scratch (the operand sets) ...
-    pope_carver carve{static_cast<char*>(q.ws)};
-    char* const ws_end = carve.at + q.ws_bytes;
-    float* x = carve.take<float>(size_t(rows) * dim * 4);
-    float* xn = carve.take<float>(size_t(rows) * dim * 4);
-    size_t big_bytes = size_t(rows) * 4 * dim * 4;
-    if (size_t(rows) * hidden * 4 > big_bytes) big_bytes = size_t(rows) * hidden * 4;
-    if (size_t(rows) * kp * 4 > big_bytes) big_bytes = size_t(rows) * kp * 4;
-    float* big = carve.take<float>(big_bytes);
-    // ... and, from the END (where the f16x3 path keeps them too), the neck buffers; the attention output sits between
-    float* t2 = reinterpret_cast<float*>(ws_end - pope_align256(brows * oc * 4));
-    float* t1b = reinterpret_cast<float*>(reinterpret_cast<char*>(t2) - pope_align256(brows * oc * 4));
-    float* t1 = reinterpret_cast<float*>(reinterpret_cast<char*>(t1b) - pope_align256(size_t(rows) * oc * 4));
-    float* att = reinterpret_cast<float*>(carve.at);
-    if (reinterpret_cast<char*>(att) + size_t(rows) * dim * 4 > reinterpret_cast<char*>(t1)) return POPE_ERR_WORKSPACE;
-    if (size_t(rows + 256) * (hidden > 3 * dim ? hidden : 3 * dim) * 4 >= (1ull << 32) - 512) return POPE_ERR_ARG;
+int pope_launch_sam32_im2col(const float* img, float* out, int B, int S, int P, hipStream_t stream) {
+    const long long total = (long long)B * (S / P) * (S / P) * (3 * P * P / 4);
+    hipLaunchKernelGGL(sam32_im2col_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, out, B, S, P);
+    return pope_check_launch();
+}
 
-    const float eps = q.block_eps > 0.f ? q.block_eps : 1e-6f, neck_eps = q.neck_eps > 0.f ? q.neck_eps : 1e-6f;
-    auto gemm = [&](const float* A, int M, const void* W, const float* bias, float* Cf, int N, int K, int epi, const float* gamma,
-                    const float* res) {
-        return pope_launch_gemm_nt_f32(pope_linear_params(LINEAR_F32, A, W, bias, Cf, nullptr, M, N, K, epi, gamma, res), stream);
-    };
-    // patch embed + absolute position table (image_encoder.py:108-110)
-    hipLaunchKernelGGL(sam32_im2col_kernel, dim3(pope_grid_for((long long)rows * (kp / 4))), dim3(256), 0, stream, q.image, big, q.B, q.img, q.patch);
-    POPE_TRY(pope_check_launch());
-    for (int b = 0; b < q.B; ++b) {   // the position table is per token, the same for every image: one GEMM per image
-        const size_t r0 = size_t(b) * g * g;
-        if (q.pos) POPE_TRY(gemm(big + r0 * kp, g * g, q.patch_wp, q.patch_b, x + r0 * dim, dim, kp, EPI_BIAS_LS_RES, q.ones, q.pos));
-        else POPE_TRY(gemm(big + r0 * kp, g * g, q.patch_wp, q.patch_b, x + r0 * dim, dim, kp, EPI_BIAS, nullptr, nullptr));
-    }
-    for (int i = 0; i < q.depth; ++i) {
-        const SamBlockParams& k = q.blocks[i];
-        const int ws = (k.global || q.window <= 0) ? g : q.window;
-        // x = x + attn(norm1(x))                                         image_encoder.py:166-179
-        POPE_TRY(pope_launch_layernorm_f32(x, dim, k.norm1_w, k.norm1_b, xn, dim, rows, dim, eps, stream));
-        POPE_TRY(gemm(xn, rows, k.qkv_wp, k.qkv_b, big, 3 * dim, dim, EPI_BIAS, nullptr, nullptr));
-        {
-            const int nw = (g + ws - 1) / ws, qtiles = (ws * ws + 63) / 64;
-            const long long blocks = (long long)q.B * nw * nw * q.heads * qtiles;
-            if (blocks > 0x7fffffffll) return POPE_ERR_ARG;
-            const size_t lds = size_t(2 * ATT_KT * hd + 64 * (2 * ws + 1)) * sizeof(float);
-            if (lds > 64 * 1024) return POPE_ERR_ARG;
-            if (hd == 80) hipLaunchKernelGGL(sam32_attn_kernel<80>, dim3((unsigned)blocks), dim3(64), lds, stream, big, k.qkv_b, k.rel_h, k.rel_w, att, q.B, g, ws, q.heads);
-            else hipLaunchKernelGGL(sam32_attn_kernel<64>, dim3((unsigned)blocks), dim3(64), lds, stream, big, k.qkv_b, k.rel_h, k.rel_w, att, q.B, g, ws, q.heads);
-            POPE_TRY(pope_check_launch());
-        }
-        POPE_TRY(gemm(att, rows, k.proj_wp, k.proj_b, x, dim, dim, EPI_BIAS_LS_RES, q.ones, x));
-        // x = x + mlp(norm2(x))                                          image_encoder.py:181; common.py:13-25
-        POPE_TRY(pope_launch_layernorm_f32(x, dim, k.norm2_w, k.norm2_b, xn, dim, rows, dim, eps, stream));
-        POPE_TRY(gemm(xn, rows, k.fc1_wp, k.fc1_b, big, hidden, dim, EPI_BIAS_GELU, nullptr, nullptr));
-        POPE_TRY(gemm(big, rows, k.fc2_wp, k.fc2_b, x, dim, hidden, EPI_BIAS_LS_RES, q.ones, x));
-        for (int t = 0; t < q.n_taps; ++t)
-            if (q.tap_blocks[t] == i && q.tap_out[t] &&
-                hipMemcpyAsync(q.tap_out[t], x, size_t(rows) * dim * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-                return POPE_ERR_LAUNCH;
-    }
-    // neck (image_encoder.py:89-105): 1x1 conv (no bias) -> LayerNorm2d -> 3x3 conv pad 1 (no bias) -> LayerNorm2d
-    POPE_TRY(gemm(x, rows, q.neck0_wp, nullptr, t1, oc, dim, EPI_BIAS, nullptr, nullptr));
-    hipLaunchKernelGGL(sam32_ln2d_kernel<true>, dim3(pope_grid_for((long long)brows, 4)), dim3(256), 0, stream, t1, q.neck1_w, q.neck1_b, t1b, q.B, g,
-                       oc, neck_eps);
-    POPE_TRY(pope_check_launch());
-    {
-        GemmParams c = {};
-        const int Wp = g + 2;
-        const size_t shift = size_t(Wp) + 1;   // output row R is pixel R + Wp + 1 (conv.hip)
-        c.A = t1b; c.W = static_cast<const float*>(q.neck2_wp); c.bias = nullptr;
-        c.lda = oc; c.ldw = 9 * oc; c.ldc = oc;
-        c.M = int(brows - (2 * size_t(Wp) + 2)); c.N = oc; c.K = 9 * oc;
-        c.epilogue = EPI_CONV; c.act_slope = 1.0f;   // identity
-        c.C = t2 + shift * oc;
-        c.conv_wp = Wp;
-        POPE_TRY(pope_launch_gemm_nt_f32(c, stream));
-    }
-    hipLaunchKernelGGL(sam32_ln2d_kernel<false>, dim3(pope_grid_for((long long)rows, 4)), dim3(256), 0, stream, t2, q.neck3_w, q.neck3_b, q.out, q.B, g, oc,
-                       neck_eps);
-    POPE_TRY(pope_check_launch());
+int pope_sam32_attention_check(int B, int g, int ws, int heads, int hd) {
+    if (hd != 64 && hd != 80) return POPE_ERR_ARG;
+    if (sam32_attention_blocks(B, g, ws, heads) > 0x7fffffffll || sam32_attention_lds(ws, hd) > 64 * 1024) return POPE_ERR_ARG;
     return POPE_OK;
+}
+
+int pope_launch_sam32_attention(const float* qkv, const float* qkv_bias, const float* rel_h, const float* rel_w, float* out, int B, int g,
+                                int ws, int heads, int hd, hipStream_t stream) {
+    const dim3 grid((unsigned)sam32_attention_blocks(B, g, ws, heads));
+    const size_t lds = sam32_attention_lds(ws, hd);
+    if (hd == 80) hipLaunchKernelGGL(sam32_attn_kernel<80>, grid, dim3(64), lds, stream, qkv, qkv_bias, rel_h, rel_w, out, B, g, ws, heads);
+    else hipLaunchKernelGGL(sam32_attn_kernel<64>, grid, dim3(64), lds, stream, qkv, qkv_bias, rel_h, rel_w, out, B, g, ws, heads);
+    return pope_check_launch();
+}
+
+int pope_launch_sam32_ln2d(const float* in, const float* w, const float* b, float* out, int B, int g, int C, float eps, bool bordered_out,
+                           hipStream_t stream) {
+    const long long pixels = (long long)B * (bordered_out ? (g + 2) * (g + 2) : g * g);
+    const dim3 grid(pope_grid_for(pixels, 4));
+    if (bordered_out) hipLaunchKernelGGL(sam32_ln2d_kernel<true>, grid, dim3(256), 0, stream, in, w, b, out, B, g, C, eps);
+    else hipLaunchKernelGGL(sam32_ln2d_kernel<false>, grid, dim3(256), 0, stream, in, w, b, out, B, g, C, eps);
+    return pope_check_launch();
 }

@@ -4,7 +4,7 @@ Drop-in for `segment_anything.modeling.image_encoder.ImageEncoderViT`
 (segment_anything/segment_anything/modeling/image_encoder.py:17-118): same constructor arguments, same state-dict
 keys (so `build_sam.py:102-105` checkpoints load with strict=True), same forward contract
 (`[B, 3, img, img]` fp32 -> `[B, out_chans, img/16, img/16]`).  The modules below are parameter containers only: the
-forward pass is ONE C-ABI call (`pope_sam_encoder_forward_f32`, pope_amd/csrc/sam.hip) — there is no torch fallback.
+forward pass is ONE C-ABI call (`pope_sam_encoder_forward_f32`, pope_amd/csrc/sam.hip; its attention: sam_attention.hip) — there is no torch fallback.
 """
 import ctypes as C
 from typing import Optional, Tuple, Type
@@ -129,7 +129,7 @@ class ImageEncoderViT(nn.Module):
         # "f16x3" (default): fp32 operands as hi + lo f16, three MFMAs per product — fp32-level results (1e-5 from the
         # reference).  "f16": BASELINE config 5's dtype — plain f16 operands, ONE MFMA per product, fp32 accumulation and an
         # fp32 residual stream / softmax / LayerNorm; results at f16 level (a few 1e-3 from the fp32 reference).
-        # "f32": every contraction on the fp32 MFMA (sam_f32.hip) — the reference's arithmetic, no range contract, ~10x slower:
+        # "f32": every contraction on the fp32 MFMA (sam.hip's sequence on sam_f32.hip's kernels) — the reference's arithmetic, no range contract, ~10x slower:
         # what a range-guard event of the other two modes is re-run in.
         self.precision = "f16x3"
         self.on_overflow = "rerun_f32"  # f16x3 / f16 range guard: "rerun_f32" (warn, run the call again on the fp32 MFMA) | "raise"

@@ -181,7 +181,7 @@ def test_contract_errors(hip_lib, golden_dir):
 
 @pytest.mark.parametrize("name", ["sam_hd64_224", "sam_hd80_256", "sam_vit_b_1024", "sam_vit_h_1024"])
 def test_fp32_mfma_twin_matches_reference_fixture(hip_lib, golden_dir, name):
-    """precision = "f32" (sam_f32.hip: every contraction on the fp32 MFMA, a plain fp32 window / global attention with the
+    """precision = "f32" (sam.hip's sequence on sam_f32.hip's kernels: every contraction on the fp32 MFMA, a plain fp32 window / global attention with the
     decomposed relative-position terms, fp32 LayerNorm2d and convolutions): the reference module's own arithmetic — held to
     the same fixture bounds as f16x3 — and the path a range-guard event is re-run in."""
     fx = np.load(os.path.join(golden_dir, name + ".npz"))

@@ -1,5 +1,5 @@
-"""GPU: the SAM encoder's attention at every window side where `plan_attention` / `pope_launch_sam_encoder` (sam.hip)
-switch kernels, against oracle/sam_encoder_ref.py evaluated in float64 on the CPU.
+"""GPU: the SAM encoder's attention at every window side where `pope_sam_attn_plan` / `pope_sam_attn_block`
+(sam_attention.hip) switch kernels, against oracle/sam_encoder_ref.py evaluated in float64 on the CPU.
 
 The shipped models and fixtures run window sides 7, 14, 15, 16 and 64 only, and 64 x 64 global blocks take the bias table, so
 the deep score depth (NSTEP 12 / 13), the 8-wave workgroup without the bias table, the second column block of
@@ -129,7 +129,7 @@ def test_f16_matches_oracle(hip_lib, hd, g, window):
 
 @pytest.mark.parametrize("hd,g,window", ODD_CASES)
 def test_f32_twin_matches_fp64_oracle(hip_lib, hd, g, window):
-    """sam_f32.hip (what a range-guard event re-runs on) at the first deep-depth and the first 8-wave side."""
+    """The fp32 route (sam.hip's sequence on sam_f32.hip's kernels: what a range-guard event re-runs on) at the first deep-depth and the first 8-wave side."""
     e_hip, e_vs_ref, err, e_ref = run_case(hd, g, window, "f32")
     assert e_hip < 4 * e_ref + 2e-5
     assert e_vs_ref <= ATOL_X
