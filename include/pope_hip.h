@@ -122,6 +122,20 @@ int pope_linear_rowln_f32(const void* a_planes, const void* w_planes, int M, int
 int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const float* bias, void* y_planes, float* y_f32,
                                    int rows, float eps, unsigned* range_flag, void* stream);
 
+/* Test entries of the remaining GEMM operand producers, one kernel each.  A call outside the stated shapes returns
+ * POPE_ERR_ARG before any HIP call.
+ * LayerNorm written as plain f16 rows y_f16[rows, dim] = f16(y * POPE_PLANES_ACT_SCALE), the A operand of the POPE_PREC_F16
+ * GEMMs (range-guarded: POPE_RANGE_LAYERNORM).  dim as pope_layernorm_f32: 128..768 in steps of 128, 1024, 1280, 1536, 2048. */
+int pope_layernorm_f16(const float* x, const float* weight, const float* bias, void* y_f16, int rows, int dim, float eps,
+                       unsigned* range_flag, void* stream);
+/* y_f16[i] = f16(x[i] * POPE_PLANES_ACT_SCALE), i < n; n % 4 == 0, x 16-byte and y_f16 8-byte aligned (POPE_RANGE_INPUT). */
+int pope_to_f16(const float* x, void* y_f16, long long n, unsigned* range_flag, void* stream);
+/* The matcher's feature planes: n blocks of [rows, cols] fp32, batch_stride floats apart (even, >= rows * cols), to compact
+ * planes [n * rows, cols] of (src / divisor) * scale — the division first, in fp32, as coarse_matching.py:109 rounds it; scale a
+ * power of two.  cols % 32 == 0 (POPE_RANGE_MATCH). */
+int pope_div_planes_f32(const float* src, long long batch_stride, void* planes, int n, int rows, int cols, float divisor,
+                        float scale, unsigned* range_flag, void* stream);
+
 /* PatchEmbed.forward + prepare_tokens_with_masks — patch_embed.py:69-82,
  * vision_transformer.py:191-200.  img[B,3,H,W]; proj_w[dim, 3*patch*patch];
  * posb[ntok, dim] = {cls_token + pos[0]; conv_bias + pos[n]} with pos already interpolated to

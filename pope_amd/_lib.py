@@ -90,6 +90,10 @@ PROTOTYPES = {
     "pope_linear_rowln_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
                               + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 4),
     "pope_layernorm_rowln_order_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "pope_layernorm_f16": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "pope_to_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "pope_div_planes_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_void_p]),
     "pope_patch_embed_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "pope_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pope_attention_prec_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

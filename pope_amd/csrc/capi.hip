@@ -114,6 +114,31 @@ int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const fl
     return pope_launch_layernorm_rowln_order(x, weight, bias, y_planes, y_f32, rows, eps, range_flag, static_cast<hipStream_t>(stream));
 }
 
+// the operand producers of the plain-f16 GEMMs and of the matcher, one launch each; checked before the stream's device is touched
+int pope_layernorm_f16(const float* x, const float* weight, const float* bias, void* y_f16, int rows, int dim, float eps,
+                       unsigned* range_flag, void* stream) {
+    const int nv = dim / 128;   // the instantiated widths of the LayerNorm launchers
+    const bool width_ok = dim > 0 && !(dim & 127) && (nv <= 6 || nv == 8 || nv == 10 || nv == 12 || nv == 16);
+    if (!x || !weight || !bias || !y_f16 || rows <= 0 || !width_ok) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_layernorm_f16(x, weight, bias, y_f16, rows, dim, eps, range_flag, static_cast<hipStream_t>(stream));
+}
+
+int pope_to_f16(const float* x, void* y_f16, long long n, unsigned* range_flag, void* stream) {
+    if (!x || !y_f16 || n <= 0 || (n & 3)) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_to_f16(x, y_f16, n / 4, range_flag, static_cast<hipStream_t>(stream));
+}
+
+int pope_div_planes_f32(const float* src, long long batch_stride, void* planes, int n, int rows, int cols, float divisor, float scale,
+                        unsigned* range_flag, void* stream) {
+    if (!src || !planes || n <= 0 || rows <= 0 || cols <= 0 || (cols & 31) || (batch_stride & 1) ||
+        batch_stride < (long long)rows * cols)
+        return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_div_planes(src, batch_stride, planes, n, rows, cols, divisor, scale, range_flag, static_cast<hipStream_t>(stream));
+}
+
 int pope_patch_embed_f32(const float* img, const float* proj_w, const float* posb, float* tokens, int B, int H,
                          int W, int patch, int dim, void* stream) {
     StreamDevice on_device(stream);

@@ -538,7 +538,7 @@ int pope_launch_layernorm_f16(const float* x, const float* w, const float* b, vo
                            rows, eps, flag);                                                                                  \
         break;
     switch (dim % 128 ? 0 : dim / 128) {
-        POPE_SAM_LN(2) POPE_SAM_LN(3) POPE_SAM_LN(4) POPE_SAM_LN(5) POPE_SAM_LN(6) POPE_SAM_LN(8) POPE_SAM_LN(10) POPE_SAM_LN(12) POPE_SAM_LN(16)
+        POPE_SAM_LN(1) POPE_SAM_LN(2) POPE_SAM_LN(3) POPE_SAM_LN(4) POPE_SAM_LN(5) POPE_SAM_LN(6) POPE_SAM_LN(8) POPE_SAM_LN(10) POPE_SAM_LN(12) POPE_SAM_LN(16)
         default: return POPE_ERR_ARG;
     }
 #undef POPE_SAM_LN
