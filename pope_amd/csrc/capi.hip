@@ -117,9 +117,7 @@ int pope_layernorm_rowln_order_f32(const float* x, const float* weight, const fl
 // the operand producers of the plain-f16 GEMMs and of the matcher, one launch each; checked before the stream's device is touched
 int pope_layernorm_f16(const float* x, const float* weight, const float* bias, void* y_f16, int rows, int dim, float eps,
                        unsigned* range_flag, void* stream) {
-    const int nv = dim / 128;   // the instantiated widths of the LayerNorm launchers
-    const bool width_ok = dim > 0 && !(dim & 127) && (nv <= 6 || nv == 8 || nv == 10 || nv == 12 || nv == 16);
-    if (!x || !weight || !bias || !y_f16 || rows <= 0 || !width_ok) return POPE_ERR_ARG;
+    if (!x || !weight || !bias || !y_f16 || rows <= 0 || !pope_ln_width_ok(dim)) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
     return pope_launch_layernorm_f16(x, weight, bias, y_f16, rows, dim, eps, range_flag, static_cast<hipStream_t>(stream));
 }

@@ -114,7 +114,9 @@ static inline bool pope_opt_in_lds(K kernel, size_t bytes, pope_dev_mask& done) 
 // v_fma_mixlo/mixhi_f16 read the f16 half of `hi` directly and write the f16 result into one half of the destination:
 // four instructions produce the four lo halves of a quad (instead of 4 x v_cvt_f32_f16 + 4 x v_sub + 2 x v_cvt_pk) —
 // bit-identical results, 6 instead of 12 VALU instructions per quad.
+typedef _Float16 pope_f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 pope_f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 pope_f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned pope_split_lo_pair(float v0, float v1, unsigned hi_pair) {
     // two statements: the first result may share v0's register (v0 is dead after it) — the allocator decides; hi_pair
     // stays live across both, so the half-written destination never aliases it
@@ -129,6 +131,39 @@ __device__ __forceinline__ void pope_split4(f32x4 v, pope_f16x4& hi, pope_f16x4&
     const u32x2s hp = __builtin_bit_cast(u32x2s, hi);
     const u32x2s lp = {pope_split_lo_pair(v[0], v[1], hp[0]), pope_split_lo_pair(v[2], v[3], hp[1])};
     lo = __builtin_bit_cast(pope_f16x4, lp);
+}
+
+// ---- f16x3 planes layout (prose: kernels.h GemmParams::a_pl) ---------------------------------------------------------
+// Column c of a planes row sits at half pope_planes_col(c) of the row's 2 * ld halves (hi plane), its lo twin 32 halves on.
+constexpr __host__ __device__ int pope_planes_col(int c) { return (c >> 5) * 64 + (c & 31); }
+// Split-and-store of 1, 2, 4 or 8 consecutive, ALREADY SCALED values at columns c.. of the planes row starting at `row`
+// (c a multiple of the count: the values stay inside one 32-column chunk and the vector stores are aligned).
+__device__ __forceinline__ void pope_planes_store(_Float16* row, int c, float y) {
+    const _Float16 hi = _Float16(y);
+    _Float16* o = row + pope_planes_col(c);
+    o[0] = hi;
+    o[32] = _Float16(y - float(hi));
+}
+__device__ __forceinline__ void pope_planes_store(_Float16* row, int c, f32x2 y) {
+    const pope_f16x2 hi = __builtin_convertvector(y, pope_f16x2);
+    _Float16* o = row + pope_planes_col(c);
+    *reinterpret_cast<pope_f16x2*>(o) = hi;
+    *reinterpret_cast<pope_f16x2*>(o + 32) = __builtin_convertvector(y - __builtin_convertvector(hi, f32x2), pope_f16x2);
+}
+__device__ __forceinline__ void pope_planes_store(_Float16* row, int c, f32x4 y) {
+    pope_f16x4 hi, lo;
+    pope_split4(y, hi, lo);
+    _Float16* o = row + pope_planes_col(c);
+    *reinterpret_cast<pope_f16x4*>(o) = hi;
+    *reinterpret_cast<pope_f16x4*>(o + 32) = lo;
+}
+__device__ __forceinline__ void pope_planes_store(_Float16* row, int c, f32x4 y0, f32x4 y1) {
+    pope_f16x4 h0, l0, h1, l1;
+    pope_split4(y0, h0, l0);
+    pope_split4(y1, h1, l1);
+    _Float16* o = row + pope_planes_col(c);
+    *reinterpret_cast<pope_f16x8*>(o) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    *reinterpret_cast<pope_f16x8*>(o + 32) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // ---- f16x3 range guard ------------------------------------------------------------------------------------------
@@ -152,6 +187,26 @@ __device__ __forceinline__ void pope_amax4x2(f32x2& m, f32x4 v) {
 __device__ __forceinline__ float pope_amax2(float m, f32x2 v) {
     return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), m);
 }
+// A converter's guard over the SCALED values it converts: bad() if and only if one of them was NaN or reached
+// POPE_F16_OVERFLOW in magnitude.  fmax drops a NaN, so NaNs are caught apart: a sum of the values is NaN when one of
+// them is (or when it is inf - inf, which the maximum has already caught).
+struct pope_range_acc {
+    float amax = 0.f;
+    bool nan = false;
+    __device__ __forceinline__ void add(float y) {
+        amax = __builtin_fmaxf(amax, __builtin_fabsf(y));
+        nan |= !(y == y);
+    }
+    __device__ __forceinline__ void add(f32x2 y) {
+        amax = pope_amax2(amax, y);
+        nan |= !(y[0] + y[1] == y[0] + y[1]);
+    }
+    __device__ __forceinline__ void add(f32x4 y) {
+        amax = pope_amax4(amax, y);
+        nan |= !((y[0] + y[1]) + (y[2] + y[3]) == (y[0] + y[1]) + (y[2] + y[3]));
+    }
+    __device__ __forceinline__ bool bad() const { return nan || !(amax < POPE_F16_OVERFLOW); }
+};
 
 static inline int pope_check_launch() {
     hipError_t e = hipGetLastError();

@@ -15,8 +15,6 @@
 
 namespace {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
@@ -35,7 +33,7 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const float* __restric
         const long long row = id >> 3;
         const int xo = int(row % Wp), yo = int((row / Wp) % Hp), b = int(row / ((long long)Wp * Hp));
         const bool interior = xo >= 1 && xo < Wp - 1 && yo >= 1 && yo < Hp - 1;
-        f16x8 hi, lo;
+        pope_f16x8 hi, lo;
         float raw[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -51,9 +49,11 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const float* __restric
             lo[e] = _Float16(s - float(hi[e]));
         }
         if constexpr (PLANES) {
+            // its own split and store (the same map as pope_planes_col(8 * t)): through pope_planes_store this kernel measured
+            // 3 % slower on its own, see profiles/operand_producers.md
             _Float16* o = out + row * 128 + (t >> 2) * 64 + (t & 3) * 8;
-            *reinterpret_cast<f16x8*>(o) = hi;
-            *reinterpret_cast<f16x8*>(o + 32) = lo;
+            *reinterpret_cast<pope_f16x8*>(o) = hi;
+            *reinterpret_cast<pope_f16x8*>(o + 32) = lo;
         } else {
             float* o = reinterpret_cast<float*>(out) + row * 64 + 8 * t;
             *reinterpret_cast<f32x4*>(o) = f32x4{raw[0], raw[1], raw[2], raw[3]};
@@ -128,12 +128,12 @@ __global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* _
             return *reinterpret_cast<const f32x4*>(src + (((size_t)b * Hsp + yy + 1) * Wsp + xx + 1) * lds + c);
         };
         const size_t prow = ((size_t)b * Hp + y + 1) * Wp + x + 1;
-        _Float16* o = out + prow * 2 * Cp + (c >> 5) * 64 + (c & 31);
+        _Float16* o = out + prow * 2 * Cp + pope_planes_col(c);
         float* of = reinterpret_cast<float*>(out) + prow * Cp + c;
         if (c >= C) {
             if constexpr (PLANES) {
-                *reinterpret_cast<f16x4*>(o) = f16x4{0, 0, 0, 0};
-                *reinterpret_cast<f16x4*>(o + 32) = f16x4{0, 0, 0, 0};
+                *reinterpret_cast<pope_f16x4*>(o) = pope_f16x4{0, 0, 0, 0};
+                *reinterpret_cast<pope_f16x4*>(o + 32) = pope_f16x4{0, 0, 0, 0};
             } else {
                 *reinterpret_cast<f32x4*>(of) = f32x4{0.f, 0.f, 0.f, 0.f};
             }
@@ -151,10 +151,7 @@ __global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* _
             if (!(v[e] == v[e])) amax = INFINITY;
         }
         if constexpr (PLANES) {
-            f16x4 hi, lo;
-            pope_split4(v * A_SCALE, hi, lo);
-            *reinterpret_cast<f16x4*>(o) = hi;
-            *reinterpret_cast<f16x4*>(o + 32) = lo;
+            pope_planes_store(out + prow * 2 * Cp, c, v * A_SCALE);
         } else {
             *reinterpret_cast<f32x4*>(of) = v;
         }

@@ -13,7 +13,6 @@
 
 namespace {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr float A_SCALE = K_PLANES_ACT_SCALE;
 
 template <bool PLANES = true>   // false (the fp32 twin): `row` is a row of floats of the same byte pitch
@@ -27,11 +26,7 @@ __device__ __forceinline__ void store_planes4(_Float16* row, int c, f32x4 v, flo
         amax = fmaxf(amax, fabsf(v[e]));
         if (!(v[e] == v[e])) amax = INFINITY;
     }
-    f16x4 hi, lo;
-    pope_split4(v * A_SCALE, hi, lo);
-    _Float16* o = row + (c >> 5) * 64 + (c & 31);
-    *reinterpret_cast<f16x4*>(o) = hi;
-    *reinterpret_cast<f16x4*>(o + 32) = lo;
+    pope_planes_store(row, c, v * A_SCALE);
 }
 
 // rows [2M, Cc] of the matched coarse features (feat_c0[b, i] then feat_c1[b, j]) as activation planes

@@ -341,7 +341,7 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
                             f16x4 hi, lo;
                             pope_split4(ys, hi, lo);
                             const int c = ni * 16 + 4 * q4;   // column within the wave's 96 = three planes chunks of 128 bytes
-                            _Float16* hp = reinterpret_cast<_Float16*>(wreg) + er * 200 + (c >> 5) * 64 + (c & 31);
+                            _Float16* hp = reinterpret_cast<_Float16*>(wreg) + er * 200 + pope_planes_col(c);
                             *reinterpret_cast<f16x4*>(hp) = hi;
                             *reinterpret_cast<f16x4*>(hp + 32) = lo;
                         } else {
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
                         f16x4 hi, lo;
                         pope_split4(v * A_SCALE, hi, lo);
                         const int c = ni * 16 + 4 * q4;   // column within the wave's 96 = three planes chunks of 128 bytes
-                        _Float16* hp = reinterpret_cast<_Float16*>(wreg) + er * 200 + (c >> 5) * 64 + (c & 31);
+                        _Float16* hp = reinterpret_cast<_Float16*>(wreg) + er * 200 + pope_planes_col(c);
                         *reinterpret_cast<f16x4*>(hp) = hi;
                         *reinterpret_cast<f16x4*>(hp + 32) = lo;
                     }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/pope_hip.h"  // POPE_RANGE_* bits of the f16x3 range-guard word
 
 enum GemmEpilogue {
@@ -55,7 +57,7 @@ struct GemmParams {
     // kernel needs a_pl and w_pl; when c_pl is set its epilogue writes planes (scale 8) instead of fp32 C.
     // Layout of a planes tensor [rows, ld]: row-major, 2*ld halves per row, per 32-column chunk the
     // 32 hi halves then the 32 lo halves (128 contiguous bytes = one cache line per row and K-step):
-    //   offset(row, col, plane) = row*2*ld + (col>>5)*64 + plane*32 + (col&31).
+    //   offset(row, col, plane) = row*2*ld + pope_planes_col(col) + plane*32   (common.h, with the producers' pope_planes_store).
     const void* a_pl;
     const void* w_pl;
     void* c_pl;
@@ -130,6 +132,19 @@ bool pope_gemm_rowln_supported(const GemmParams& g);
 bool pope_gemm_rowln_args_ok(const GemmParams& g);
 int pope_launch_gemm_rowln(const GemmParams& g, hipStream_t stream);
 constexpr float K_PLANES_ACT_SCALE = 8.0f, K_PLANES_W_SCALE = 256.0f;  // == POPE_PLANES_*_SCALE of pope_hip.h
+
+// The row widths the wave-per-row LayerNorm kernels are instantiated for, in units of 128 columns (5, 10: the SAM ViT-H width
+// 1280 and its test twin 640).  pope_ln_dispatch calls f(std::integral_constant<int, NV>) for dim == 128 NV and returns
+// false, without a call, for every other dim; pope_ln_width_ok asks the same list without a call.
+template <typename F, int... NV>
+inline bool pope_ln_dispatch(int dim, F&& f, std::integer_sequence<int, NV...>) {
+    return ((dim == 128 * NV && (f(std::integral_constant<int, NV>{}), true)) || ...);
+}
+template <typename F>
+inline bool pope_ln_dispatch(int dim, F&& f) {
+    return pope_ln_dispatch(dim, f, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 10, 12, 16>{});
+}
+inline bool pope_ln_width_ok(int dim) { return pope_ln_dispatch(dim, [](auto) {}); }
 
 // y = LayerNorm(x) written as f16 planes (scale POPE_PLANES_ACT_SCALE), [rows, dim] halves each.
 int pope_launch_layernorm_planes(const float* x, int ldx, const float* w, const float* b, void* y_pl,

@@ -1,14 +1,58 @@
-// Row LayerNorm, fp32 (nn.LayerNorm(dim, eps=1e-6): dinov2/dinov2/models/vision_transformer.py:90;
-// used as norm1/norm2 in block.py:56,68 and as the final norm, vision_transformer.py:230).
-// HBM-bound streaming op: one wave per row, the row lives in registers (float2 per lane per
-// 128 columns), two-pass mean / centred variance, wave-shuffle reductions, no LDS.
-// Beside it the other operand producers: the same LayerNorm as f16x3 planes or plain f16 rows, the plain converters, im2col.
+// The operand producers of the GEMMs: row LayerNorm (nn.LayerNorm(dim, eps=1e-6): dinov2/dinov2/models/vision_transformer.py:90;
+// norm1/norm2 in block.py:56,68 and the final norm, vision_transformer.py:230) as fp32 rows, f16x3 planes or plain f16 rows,
+// the plain fp32 -> planes / f16 converters and the patch embed's im2col.  All HBM-bound streaming kernels.  The planes
+// layout and its split-and-store (pope_planes_store) and the converters' range guard (pope_range_acc) are common.h's.
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
-template <int NV>  // dim = NV * 128
+// ---- wave-per-row LayerNorm: the row lives in registers (float2 per lane per 128 columns, dim = NV * 128), two-pass mean /
+// centred variance, wave-shuffle reductions, no LDS.  The planes and the f16 kernel below share these pieces and differ in how
+// they normalise the two sums, in their store and in their flag.
+template <int NV>
+__device__ __forceinline__ float ln_load_sum(const float* xr, int lane, f32x2 (&v)[NV]) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i] = *reinterpret_cast<const f32x2*>(xr + i * 128 + lane * 2);
+        s += v[i][0] + v[i][1];
+    }
+    return wave_sum(s);
+}
+template <int NV>
+__device__ __forceinline__ float ln_centred_sq_sum(const f32x2 (&v)[NV], float mean) {
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float d0 = v[i][0] - mean, d1 = v[i][1] - mean;
+        q += d0 * d0 + d1 * d1;
+    }
+    return wave_sum(q);
+}
+// store(c, y): y = ((x - mean) * rstd * w + b) * scale of columns c, c + 1
+template <int NV, typename Store>
+__device__ __forceinline__ void ln_affine(const f32x2 (&v)[NV], float mean, float rstd, const float* w, const float* b, int lane,
+                                          float scale, Store store) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 128 + lane * 2;
+        const f32x2 ww = *reinterpret_cast<const f32x2*>(w + c);
+        const f32x2 bb = *reinterpret_cast<const f32x2*>(b + c);
+        f32x2 y;
+        y[0] = ((v[i][0] - mean) * rstd * ww[0] + bb[0]) * scale;
+        y[1] = ((v[i][1] - mean) * rstd * ww[1] + bb[1]) * scale;
+        store(c, y);
+    }
+}
+// a non-finite row (inf / NaN from an earlier overflow) has a non-finite mean or rstd; fmax ignores NaN
+__device__ __forceinline__ bool ln_out_of_range(float amax, float mean, float rstd) {
+    return !(amax < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY);
+}
+
+// The fp32 rows: kept spelled out on purpose.  On the shared pieces the NV = 6 kernel was about 0.4 % slower at 16384 x 768
+// (four more v_mov_b32 from register allocation), see profiles/operand_producers.md.
+template <int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx,
                                                          const float* __restrict__ w,
                                                          const float* __restrict__ b, float* __restrict__ y,
@@ -47,9 +91,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // Same LayerNorm, output as f16 hi/lo planes for the f16x3 GEMMs (y*scale = hi + lo): the split is
 // done once here, in an HBM-bound kernel with idle VALU, instead of per K-step in every GEMM tile.
 template <int NV>
@@ -61,46 +102,22 @@ __global__ __launch_bounds__(256) void layernorm_planes_kernel(const float* __re
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + size_t(row) * ldx;
     f32x2 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i] = *reinterpret_cast<const f32x2*>(xr + i * 128 + lane * 2);
-        s += v[i][0] + v[i][1];
-    }
     constexpr float inv_d = 1.0f / float(NV * 128);
-    const float mean = wave_sum(s) * inv_d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float d0 = v[i][0] - mean, d1 = v[i][1] - mean;
-        q += d0 * d0 + d1 * d1;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + eps);
-    _Float16* yr = ypl + size_t(row) * (2 * NV * 128);  // planes layout: per 32-column chunk [32 hi | 32 lo]
+    const float mean = ln_load_sum(x + size_t(row) * ldx, lane, v) * inv_d;
+    const float rstd = 1.0f / sqrtf(ln_centred_sq_sum(v, mean) * inv_d + eps);
+    _Float16* yr = ypl + size_t(row) * (2 * NV * 128);
     float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 128 + lane * 2;
-        const f32x2 ww = *reinterpret_cast<const f32x2*>(w + c);
-        const f32x2 bb = *reinterpret_cast<const f32x2*>(b + c);
-        f32x2 y;
-        y[0] = ((v[i][0] - mean) * rstd * ww[0] + bb[0]) * scale;
-        y[1] = ((v[i][1] - mean) * rstd * ww[1] + bb[1]) * scale;
+    ln_affine(v, mean, rstd, w, b, lane, scale, [&](int c, f32x2 y) {
         amax = pope_amax2(amax, y);
-        const f16x2 hi = __builtin_convertvector(y, f16x2);
-        const f16x2 lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x2), f16x2);
-        *reinterpret_cast<f16x2*>(yr + (c >> 5) * 64 + (c & 31)) = hi;
-        *reinterpret_cast<f16x2*>(yr + (c >> 5) * 64 + 32 + (c & 31)) = lo;
-    }
-    // a non-finite row (inf / NaN from an earlier overflow) has a non-finite mean or rstd; fmax ignores NaN
-    pope_range_flag(flag, POPE_RANGE_LAYERNORM, !(amax < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY));
+        pope_planes_store(yr, c, y);
+    });
+    pope_range_flag(flag, POPE_RANGE_LAYERNORM, ln_out_of_range(amax, mean, rstd));
 }
 
 // Same, two rows per wave (one per 32-lane half), 16-byte loads: dim = NV4 * 128 <= 512.  The 8-byte loads of the
-// wave-per-row version reach 5.0 TB/s; a float4 copy reaches 6.3 on this chip.
-typedef _Float16 f16x4_ln __attribute__((ext_vector_type(4)));
+// wave-per-row version reach 5.0 TB/s; a float4 copy reaches 6.3 on this chip.  Its own body: the quads associate both sums
+// differently from the pairs above (and the output bits are pinned), and a dead half-wave must still take part in the shuffles.
 __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll
     for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
@@ -146,51 +163,38 @@ __global__ __launch_bounds__(256) void layernorm_planes_half_kernel(const float*
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = ((v[i][e] - mean) * rstd * ww[e] + bb[e]) * scale;
         amax = pope_amax4(amax, y);
-        const f16x4_ln hi = __builtin_convertvector(y, f16x4_ln);
-        const f16x4_ln lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x4), f16x4_ln);
-        *reinterpret_cast<f16x4_ln*>(yr + (c >> 5) * 64 + (c & 31)) = hi;
-        *reinterpret_cast<f16x4_ln*>(yr + (c >> 5) * 64 + 32 + (c & 31)) = lo;
+        pope_planes_store(yr, c, y);
     }
-    pope_range_flag(flag, POPE_RANGE_LAYERNORM, !(amax < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY));
+    pope_range_flag(flag, POPE_RANGE_LAYERNORM, ln_out_of_range(amax, mean, rstd));
 }
 
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ src, _Float16* __restrict__ pl,
                                                             size_t n2, int ld, float scale, unsigned* flag) {
-    float amax = 0.f;
-    bool nonfinite = false;
+    pope_range_acc range;
     for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n2; i += size_t(gridDim.x) * 256) {
         const size_t e = 2 * i, row = e / ld;
         const int c = int(e - row * ld);
         const f32x2 y = *reinterpret_cast<const f32x2*>(src + e) * scale;
-        amax = pope_amax2(amax, y);
-        nonfinite |= !(y[0] + y[1] == y[0] + y[1]);
-        const f16x2 h = __builtin_convertvector(y, f16x2);
-        _Float16* o = pl + row * 2 * ld + (c >> 5) * 64 + (c & 31);
-        *reinterpret_cast<f16x2*>(o) = h;
-        *reinterpret_cast<f16x2*>(o + 32) = __builtin_convertvector(y - __builtin_convertvector(h, f32x2), f16x2);
+        range.add(y);
+        pope_planes_store(pl + row * 2 * ld, c, y);
     }
-    pope_range_flag(flag, POPE_RANGE_INPUT, nonfinite || !(amax < POPE_F16_OVERFLOW));
+    pope_range_flag(flag, POPE_RANGE_INPUT, range.bad());
 }
 
 __global__ __launch_bounds__(256) void div_planes_kernel(const float* __restrict__ src, long long bs, _Float16* __restrict__ pl,
                                                           int n, int rows, int cols, float divisor, float scale, unsigned* flag) {
     const size_t per = size_t(rows) * cols / 2, n2 = per * n;
-    float amax = 0.f;
-    bool nonfinite = false;
+    pope_range_acc range;
     for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n2; i += size_t(gridDim.x) * 256) {
         const size_t b = i / per, e = (i - b * per) * 2, row = e / cols;
         const int c = int(e - row * cols);
         f32x2 y = *reinterpret_cast<const f32x2*>(src + b * bs + e);
         y[0] = (y[0] / divisor) * scale;   // the division first, exactly as the reference rounds it; scale is a power of two
         y[1] = (y[1] / divisor) * scale;
-        amax = pope_amax2(amax, y);
-        nonfinite |= !(y[0] + y[1] == y[0] + y[1]);
-        const f16x2 hi = __builtin_convertvector(y, f16x2);
-        _Float16* o = pl + (b * rows + row) * 2 * cols + (c >> 5) * 64 + (c & 31);
-        *reinterpret_cast<f16x2*>(o) = hi;
-        *reinterpret_cast<f16x2*>(o + 32) = __builtin_convertvector(y - __builtin_convertvector(hi, f32x2), f16x2);
+        range.add(y);
+        pope_planes_store(pl + (b * rows + row) * 2 * cols, c, y);
     }
-    pope_range_flag(flag, POPE_RANGE_MATCH, nonfinite || !(amax < POPE_F16_OVERFLOW));
+    pope_range_flag(flag, POPE_RANGE_MATCH, range.bad());
 }
 
 // Patch embed operand: one thread per (row, k pair).  Row b*ntok + 1 + (py*gw + px), k = c*p*p + dy*p + dx reads
@@ -199,8 +203,7 @@ __global__ __launch_bounds__(256) void im2col_planes_kernel(const float* __restr
                                                              int B, int H, int W, int patch, int kp, int ntok, int gw, unsigned* flag) {
     const size_t n2 = size_t(B) * ntok * (kp / 2);
     const int k_real = 3 * patch * patch, pp = patch * patch;
-    float amax = 0.f;
-    bool nonfinite = false;
+    pope_range_acc range;
     for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n2; i += size_t(gridDim.x) * 256) {
         const size_t row = i / (kp / 2);
         const int k = int(i - row * (kp / 2)) * 2;
@@ -218,14 +221,10 @@ __global__ __launch_bounds__(256) void im2col_planes_kernel(const float* __restr
             }
         }
         v = v * K_PLANES_ACT_SCALE;
-        amax = pope_amax2(amax, v);
-        nonfinite |= !(v[0] + v[1] == v[0] + v[1]);
-        const f16x2 hi = __builtin_convertvector(v, f16x2);
-        _Float16* o = pl + row * 2 * kp + (k >> 5) * 64 + (k & 31);
-        *reinterpret_cast<f16x2*>(o) = hi;
-        *reinterpret_cast<f16x2*>(o + 32) = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), f16x2);
+        range.add(v);
+        pope_planes_store(pl + row * 2 * kp, k, v);
     }
-    pope_range_flag(flag, POPE_RANGE_PATCH, nonfinite || !(amax < POPE_F16_OVERFLOW));
+    pope_range_flag(flag, POPE_RANGE_PATCH, range.bad());
 }
 
 // The same operand by strips: one workgroup per (image, patch row, group of IM2_P patches).  The 3 * patch image-row
@@ -265,46 +264,31 @@ __global__ __launch_bounds__(256) void im2col_planes_strip_kernel(const float* _
         }
     }
     __syncthreads();
-    float amax = 0.f;
-    bool nonfinite = false;
+    pope_range_acc range;
     const int pieces = kp >> 3;                                            // 8 k values per piece
     const size_t row0 = size_t(b) * ntok + 1 + size_t(py) * gw + px0;
     for (int i = threadIdx.x; i < np * pieces; i += 256) {
         const int p = i / pieces, k0 = (i - p * pieces) << 3;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(seg + p * ks + k0), c4 = *reinterpret_cast<const f32x4*>(seg + p * ks + k0 + 4);
-        f16x8 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = (e < 4 ? a[e] : c4[e - 4]) * K_PLANES_ACT_SCALE;
-            amax = __builtin_fmaxf(amax, __builtin_fabsf(v));
-            nonfinite |= !(v == v);
-            hi[e] = _Float16(v);
-            lo[e] = _Float16(v - float(hi[e]));
-        }
-        _Float16* o = pl + (row0 + p) * 2 * kp + (k0 >> 5) * 64 + (k0 & 31);
-        *reinterpret_cast<f16x8*>(o) = hi;
-        *reinterpret_cast<f16x8*>(o + 32) = lo;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(seg + p * ks + k0) * K_PLANES_ACT_SCALE;
+        const f32x4 c4 = *reinterpret_cast<const f32x4*>(seg + p * ks + k0 + 4) * K_PLANES_ACT_SCALE;
+        range.add(a);
+        range.add(c4);
+        pope_planes_store(pl + (row0 + p) * 2 * kp, k0, a, c4);
     }
     if (py == 0 && grp == 0) {                           // the CLS row of the image: zeros (its value arrives with the pos table)
-        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        const pope_f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
         _Float16* o = pl + size_t(b) * ntok * 2 * kp;
-        for (int i = threadIdx.x; i < 2 * kp / 8; i += 256) *reinterpret_cast<f16x8*>(o + 8 * i) = z;
+        for (int i = threadIdx.x; i < 2 * kp / 8; i += 256) *reinterpret_cast<pope_f16x8*>(o + 8 * i) = z;
     }
-    pope_range_flag(flag, POPE_RANGE_PATCH, nonfinite || !(amax < POPE_F16_OVERFLOW));
+    pope_range_flag(flag, POPE_RANGE_PATCH, range.bad());
 }
 
 __global__ __launch_bounds__(256) void range_check_kernel(const float* __restrict__ x, size_t n, float scale, unsigned* flag,
                                                            unsigned bit) {
-    float amax = 0.f;
-    bool nonfinite = false;
-    for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += size_t(gridDim.x) * 256) {
-        const float v = x[i] * scale;
-        amax = __builtin_fmaxf(amax, __builtin_fabsf(v));
-        nonfinite |= !(v == v);
-    }
-    pope_range_flag(flag, bit, nonfinite || !(amax < POPE_F16_OVERFLOW));
+    pope_range_acc range;
+    for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += size_t(gridDim.x) * 256) range.add(x[i] * scale);
+    pope_range_flag(flag, bit, range.bad());
 }
-
 
 // LayerNorm over 384 columns in EXACTLY the arithmetic of gemm_rowln.hip's fused epilogue — same association of every sum:
 // per 16-lane row group, lane (wn, q4) adds its six column quads ((a0 + a1) + (a2 + a3)) in ascending order, the four q4
@@ -355,11 +339,7 @@ __global__ __launch_bounds__(256) void layernorm_rowln_order_kernel(const float*
         if constexpr (PLANES) {
             const f32x4 ys = y * K_PLANES_ACT_SCALE;
             pope_amax4x2(amax, ys);
-            pope_f16x4 hi, lo;
-            pope_split4(ys, hi, lo);
-            _Float16* hp = static_cast<_Float16*>(out) + size_t(row) * 2 * RN + (c >> 5) * 64 + (c & 31);
-            *reinterpret_cast<pope_f16x4*>(hp) = hi;
-            *reinterpret_cast<pope_f16x4*>(hp + 32) = lo;
+            pope_planes_store(static_cast<_Float16*>(out) + size_t(row) * 2 * RN, c, ys);
         } else {
             *reinterpret_cast<f32x4*>(static_cast<float*>(out) + size_t(row) * RN + c) = y;
         }
@@ -369,59 +349,39 @@ __global__ __launch_bounds__(256) void layernorm_rowln_order_kernel(const float*
                         ok && (!(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY)));
 }
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-constexpr float A_SCALE = K_PLANES_ACT_SCALE;
 // ---- precision "f16": LayerNorm over the last dim -> f16 row-major (value * 8), one wave per row (dim % 128 == 0, <= 2048);
 // and the plain conversion fp32 -> f16 (value * 8) of the neck's input
 template <int NV>
 __global__ __launch_bounds__(256) void sam_ln_f16_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ b, _Float16* __restrict__ y, int rows,
                                                          float eps, unsigned* range_flag) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    constexpr int nv = NV, dim = NV * 128;
+    constexpr int dim = NV * 128;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (size_t)row * dim;
     f32x2 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < nv; ++i) {
-        v[i] = *reinterpret_cast<const f32x2*>(xr + i * 128 + lane * 2);
-        s += v[i][0] + v[i][1];
-    }
-    const float mean = wave_sum(s) / float(dim);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < nv; ++i) {
-        const float d0 = v[i][0] - mean, d1 = v[i][1] - mean;
-        q += d0 * d0 + d1 * d1;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / float(dim) + eps);
+    // Deliberate: a true division by float(dim), where the two kernels above multiply by the constant 1 / dim.  At the widths
+    // that are no power of two (384, 640, 768, 1280, 1536) the two round differently, and the f16 routes' bits are pinned to this one.
+    const float mean = ln_load_sum(x + (size_t)row * dim, lane, v) / float(dim);
+    const float rstd = 1.0f / sqrtf(ln_centred_sq_sum(v, mean) / float(dim) + eps);
+    _Float16* yr = y + (size_t)row * dim;
     float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < nv; ++i) {
-        const int c = i * 128 + lane * 2;
-        const f32x2 ww = *reinterpret_cast<const f32x2*>(w + c), bb = *reinterpret_cast<const f32x2*>(b + c);
-        f32x2 o;
-        o[0] = ((v[i][0] - mean) * rstd * ww[0] + bb[0]) * A_SCALE;
-        o[1] = ((v[i][1] - mean) * rstd * ww[1] + bb[1]) * A_SCALE;
+    ln_affine(v, mean, rstd, w, b, lane, K_PLANES_ACT_SCALE, [&](int c, f32x2 o) {
         amax = pope_amax2(amax, o);
-        *reinterpret_cast<f16x2*>(y + (size_t)row * dim + c) = __builtin_convertvector(o, f16x2);
-    }
-    pope_range_flag(range_flag, POPE_RANGE_LAYERNORM, !(amax < POPE_F16_OVERFLOW) || !(__builtin_fabsf(mean) + rstd < INFINITY));
+        *reinterpret_cast<pope_f16x2*>(yr + c) = __builtin_convertvector(o, pope_f16x2);
+    });
+    pope_range_flag(range_flag, POPE_RANGE_LAYERNORM, ln_out_of_range(amax, mean, rstd));
 }
 
 __global__ __launch_bounds__(256) void sam_to_f16_kernel(const float* __restrict__ x, _Float16* __restrict__ y, long long n4,
                                                          unsigned* range_flag) {
-    float amax = 0.f;
+    pope_range_acc range;
     for (long long id = blockIdx.x * 256ll + threadIdx.x; id < n4; id += 256ll * gridDim.x) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * id);
-        amax = pope_amax4(amax, v);
-        if (!((v[0] + v[1]) + (v[2] + v[3]) == (v[0] + v[1]) + (v[2] + v[3]))) amax = INFINITY;
-        *reinterpret_cast<f16x4*>(y + 4 * id) = __builtin_convertvector(v * A_SCALE, f16x4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * id) * K_PLANES_ACT_SCALE;
+        range.add(v);
+        *reinterpret_cast<pope_f16x4*>(y + 4 * id) = __builtin_convertvector(v, pope_f16x4);
     }
-    pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
+    pope_range_flag(range_flag, POPE_RANGE_INPUT, range.bad());
 }
 }  // namespace
 
@@ -479,19 +439,11 @@ int pope_launch_layernorm_planes(const float* x, int ldx, const float* w, const 
         }
         return pope_check_launch();
     }
-    const dim3 grid((rows + 3) / 4), block(256);
-#define POPE_LNP_CASE(NV)                                                                                    \
-    case NV:                                                                                                 \
-        hipLaunchKernelGGL(layernorm_planes_kernel<NV>, grid, block, 0, stream, x, ldx, w, b, ypl, rows, eps,    \
-                           K_PLANES_ACT_SCALE, flag);                                                     \
-        break;
-    switch (dim / 128) {
-        POPE_LNP_CASE(1) POPE_LNP_CASE(2) POPE_LNP_CASE(3) POPE_LNP_CASE(4) POPE_LNP_CASE(5) POPE_LNP_CASE(6) POPE_LNP_CASE(8)
-        POPE_LNP_CASE(10) POPE_LNP_CASE(12) POPE_LNP_CASE(16)   // 5, 10: the SAM ViT-H width 1280 and its test twin 640
-        default: return POPE_ERR_ARG;
-    }
-#undef POPE_LNP_CASE
-    return pope_check_launch();
+    const bool launched = pope_ln_dispatch(dim, [&](auto nv) {
+        hipLaunchKernelGGL(layernorm_planes_kernel<decltype(nv)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, w, b, ypl,
+                           rows, eps, K_PLANES_ACT_SCALE, flag);
+    });
+    return launched ? pope_check_launch() : POPE_ERR_ARG;
 }
 
 int pope_launch_split_planes(const float* src, void* pl, int rows, int ld, float scale, unsigned* flag, hipStream_t stream) {
@@ -505,18 +457,11 @@ int pope_launch_split_planes(const float* src, void* pl, int rows, int ld, float
 int pope_launch_layernorm_f32(const float* x, int ldx, const float* w, const float* b, float* y, int ldy,
                               int rows, int dim, float eps, hipStream_t stream) {
     if (rows <= 0 || dim <= 0 || (dim & 127) || dim > 2048 || (ldx & 1) || (ldy & 1)) return POPE_ERR_ARG;
-    const dim3 grid((rows + 3) / 4), block(256);
-#define POPE_LN_CASE(NV)                                                                              \
-    case NV:                                                                                          \
-        hipLaunchKernelGGL(layernorm_kernel<NV>, grid, block, 0, stream, x, ldx, w, b, y, ldy, rows, eps); \
-        break;
-    switch (dim / 128) {
-        POPE_LN_CASE(1) POPE_LN_CASE(2) POPE_LN_CASE(3) POPE_LN_CASE(4) POPE_LN_CASE(5) POPE_LN_CASE(6) POPE_LN_CASE(8)
-        POPE_LN_CASE(10) POPE_LN_CASE(12) POPE_LN_CASE(16)   // 5, 10: the SAM ViT-H width 1280 and its test twin 640
-        default: return POPE_ERR_ARG;
-    }
-#undef POPE_LN_CASE
-    return pope_check_launch();
+    const bool launched = pope_ln_dispatch(dim, [&](auto nv) {
+        hipLaunchKernelGGL(layernorm_kernel<decltype(nv)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, w, b, y, ldy, rows,
+                           eps);
+    });
+    return launched ? pope_check_launch() : POPE_ERR_ARG;
 }
 
 int pope_launch_layernorm_rowln_order(const float* x, const float* w, const float* b, void* y_planes, float* y_f32, int rows, float eps,
@@ -532,17 +477,11 @@ int pope_launch_layernorm_rowln_order(const float* x, const float* w, const floa
 int pope_launch_layernorm_f16(const float* x, const float* w, const float* b, void* y_f16, int rows, int dim, float eps, unsigned* flag,
                               hipStream_t stream) {
     if (!x || !w || !b || !y_f16 || rows <= 0) return POPE_ERR_ARG;
-#define POPE_SAM_LN(NV)                                                                                                       \
-    case NV:                                                                                                                  \
-        hipLaunchKernelGGL(sam_ln_f16_kernel<NV>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, w, b, static_cast<_Float16*>(y_f16), \
-                           rows, eps, flag);                                                                                  \
-        break;
-    switch (dim % 128 ? 0 : dim / 128) {
-        POPE_SAM_LN(1) POPE_SAM_LN(2) POPE_SAM_LN(3) POPE_SAM_LN(4) POPE_SAM_LN(5) POPE_SAM_LN(6) POPE_SAM_LN(8) POPE_SAM_LN(10) POPE_SAM_LN(12) POPE_SAM_LN(16)
-        default: return POPE_ERR_ARG;
-    }
-#undef POPE_SAM_LN
-    return pope_check_launch();
+    const bool launched = pope_ln_dispatch(dim, [&](auto nv) {
+        hipLaunchKernelGGL(sam_ln_f16_kernel<decltype(nv)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, w, b,
+                           static_cast<_Float16*>(y_f16), rows, eps, flag);
+    });
+    return launched ? pope_check_launch() : POPE_ERR_ARG;
 }
 
 int pope_launch_to_f16(const float* x, void* y_f16, long long n4, unsigned* flag, hipStream_t stream) {

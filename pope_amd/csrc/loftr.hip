@@ -18,9 +18,6 @@
 
 namespace {
 
-typedef _Float16 f16x2l __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4l __attribute__((ext_vector_type(4)));
-
 constexpr int LA_CHUNK = 64;   // source rows per workgroup of the KV reduction
 
 // elu(x) + 1 as torch evaluates it in fp32: x > 0 ? x : exp(x) - 1, then + 1 (two roundings on the negative side)
@@ -130,10 +127,7 @@ __global__ __launch_bounds__(256) void linattn_apply_kernel(const float* __restr
                 const float sv = m * K_PLANES_ACT_SCALE;
                 amax = fmaxf(amax, fabsf(sv));
                 if (!(sv == sv)) amax = INFINITY;
-                const _Float16 hi = _Float16(sv), lo = _Float16(sv - float(hi));
-                _Float16* o = reinterpret_cast<_Float16*>(msg) + (size_t(n) * L + l) * 2 * C + (col >> 5) * 64 + (col & 31);
-                o[0] = hi;
-                o[32] = lo;
+                pope_planes_store(reinterpret_cast<_Float16*>(msg) + (size_t(n) * L + l) * 2 * C, col, sv);
             }
         } else {
             if (ok) msg[(size_t(n) * L + l) * C + col] = m;
@@ -181,9 +175,7 @@ __global__ __launch_bounds__(256) void ln_cat_planes_kernel(const float* __restr
             const float val = vals[part];
             if constexpr (PLANES) {
                 amax = fmaxf(amax, fabsf(val));
-                const _Float16 hi = _Float16(val);
-                pr[(cc >> 5) * 64 + (cc & 31)] = hi;
-                pr[(cc >> 5) * 64 + 32 + (cc & 31)] = _Float16(val - float(hi));
+                pope_planes_store(pr, cc, val);
             } else {
                 reinterpret_cast<float*>(pl)[size_t(row) * 2 * C + cc] = val;   // scale = 1
             }

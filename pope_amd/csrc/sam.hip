@@ -44,12 +44,7 @@ __global__ __launch_bounds__(256) void sam_im2col_kernel(const float* __restrict
             *reinterpret_cast<f16x8*>(out + (size_t)row * K + k) =
                 cat(__builtin_convertvector(v0 * A_SCALE, f16x4), __builtin_convertvector(v1 * A_SCALE, f16x4));
         } else {
-            f16x4 h0, l0, h1, l1;
-            pope_split4(v0 * A_SCALE, h0, l0);
-            pope_split4(v1 * A_SCALE, h1, l1);
-            _Float16* o = out + (size_t)row * 2 * K + (k >> 5) * 64 + (k & 31);
-            *reinterpret_cast<f16x8*>(o) = cat(h0, h1);
-            *reinterpret_cast<f16x8*>(o + 32) = cat(l0, l1);
+            pope_planes_store(out + (size_t)row * 2 * K, k, v0 * A_SCALE, v1 * A_SCALE);
         }
     }
     pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
@@ -118,11 +113,7 @@ __global__ __launch_bounds__(256) void sam_ln2d_kernel(const float* __restrict__
                 if constexpr (PLAIN) {
                     *reinterpret_cast<f16x4*>(static_cast<_Float16*>(out) + (size_t)pix * C + col) = __builtin_convertvector(r * A_SCALE, f16x4);
                 } else {
-                    f16x4 hi, lo;
-                    pope_split4(r * A_SCALE, hi, lo);
-                    _Float16* dst = static_cast<_Float16*>(out) + (size_t)pix * 2 * C + (col >> 5) * 64 + (col & 31);
-                    *reinterpret_cast<f16x4*>(dst) = hi;
-                    *reinterpret_cast<f16x4*>(dst + 32) = lo;
+                    pope_planes_store(static_cast<_Float16*>(out) + (size_t)pix * 2 * C, col, r * A_SCALE);
                 }
             } else {
                 float* dst = static_cast<float*>(out) + (((size_t)b * C + col) * g + y) * g + x;

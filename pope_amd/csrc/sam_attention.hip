@@ -588,11 +588,7 @@ __global__ __launch_bounds__(64 * WAVES, BIAS && PLAIN && WAVES == 4 ? 3 : 8 / W
             if constexpr (PLAIN) {
                 *reinterpret_cast<f16x4*>(out_pl + trow * a.dim + col) = __builtin_convertvector(v * A_SCALE, f16x4);
             } else {
-                f16x4 hi, lo;
-                pope_split4(v * A_SCALE, hi, lo);
-                _Float16* dst = out_pl + trow * 2 * a.dim + (col >> 5) * 64 + (col & 31);
-                *reinterpret_cast<f16x4*>(dst) = hi;
-                *reinterpret_cast<f16x4*>(dst + 32) = lo;
+                pope_planes_store(out_pl + trow * 2 * a.dim, col, v * A_SCALE);
             }
         }
     }

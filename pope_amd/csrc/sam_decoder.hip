@@ -41,10 +41,7 @@ constexpr int HEADS = 8;
 __device__ __forceinline__ void sd_put_planes(_Float16* pl, int ld, size_t row, int c, float v, bool& bad) {
     const float y = v * K_PLANES_ACT_SCALE;
     bad |= !(__builtin_fabsf(y) < POPE_F16_OVERFLOW);
-    const _Float16 h = static_cast<_Float16>(y);
-    _Float16* o = pl + row * 2 * ld + (c >> 5) * 64 + (c & 31);
-    o[0] = h;
-    o[32] = static_cast<_Float16>(y - static_cast<float>(h));
+    pope_planes_store(pl + row * 2 * ld, c, y);
 }
 
 // the GEMM operands of a keys row: A = keys (planes; f32: the fp32 keys themselves, nothing to write), B = keys + pe
