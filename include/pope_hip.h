@@ -438,15 +438,16 @@ int pope_sam_encoder_forward_f32(const pope_sam_encoder_weights* w_host, const f
                                  int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
-/* ---- SAM mask decoder (point and box prompts) ------------------------------------------------------------------ */
+/* ---- SAM mask decoder (point, box and mask prompts) ------------------------------------------------------------ */
 
 /* MaskDecoder.forward with TwoWayTransformer — segment_anything/segment_anything/modeling/{mask_decoder,transformer}.py as
  * build_sam.py configures them (dim 256, 8 heads, attention_downsample_rate 2, mlp_dim 2048, depth 2, a 64 x 64 embedding,
  * 4 mask tokens, IoU head depth 3 / hidden 256).  image[256, 64, 64] and image_pe[256, 64, 64] fp32 (one image);
  * sparse[P, n_sparse, 256] (0 <= n_sparse <= 11; NULL when 0); dense[P, 256, 64, 64] with dense_stride floats between
  * prompts: 0 (a broadcast, what PromptEncoder returns without a mask: layer 0's image-only projections then run once per
- * call) or 256 * 4096.  multimask != 0: masks[P, 3, 256, 256] = mask tokens 1..3 and iou[P, 3]; else masks[P, 1, 256, 256]
- * = mask token 0 and iou[P, 1] (predict_masks' slices).  Optional hs_out[P, 5 + n_sparse, 256] (final tokens) and
+ * call) or 256 * 4096 (an embedding per prompt, what pope_sam_mask_embed_f32 writes for mask prompts).  multimask != 0:
+ * masks[P, 3, 256, 256] = mask tokens 1..3 and iou[P, 3]; else masks[P, 1, 256, 256] = mask token 0 and iou[P, 1]
+ * (predict_masks' slices).  Optional hs_out[P, 5 + n_sparse, 256] (final tokens) and
  * keys_out[P, 4096, 256] (final image tokens).  The prompts run in chunks: the workspace is bounded by 16 prompts, and a
  * prompt's outputs are bit-identical whatever P and wherever it falls.
  * precision POPE_PREC_F16X3: the image-side Linears (`*_wp`) on weight planes (scale 256), their activations as planes
@@ -509,6 +510,28 @@ int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w_host, 
                                         int n_sparse, const float* dense, long long dense_stride, int multimask, float* masks,
                                         float* iou, void* workspace, size_t workspace_bytes, unsigned* range_flag,
                                         void* stream);
+
+/* ---- SAM prompt encoder: mask prompts --------------------------------------------------------------------------- */
+
+/* PromptEncoder._embed_masks — segment_anything/segment_anything/modeling/prompt_encoder.py:51-59, 102-105: mask_downscaling =
+ * Conv2d(1 -> 4, k2, s2), LayerNorm2d(4), GELU (erf), Conv2d(4 -> 16, k2, s2), LayerNorm2d(16), GELU, Conv2d(16 -> 256, k1), in
+ * ONE kernel without an intermediate in memory: an output pixel depends on one 4 x 4 patch of its mask.
+ * masks[P, 1, 256, 256] fp32 (16-byte aligned) -> dense[P, 256, 64, 64] fp32 (16-byte aligned), channel-major: the per-prompt
+ * dense embedding pope_sam_decoder_forward_f32 takes with dense_stride = 256 * 4096.  The weights are DEVICE pointers in
+ * torch's native layouts; LayerNorm2d is common.py's: mean and biased variance over the channels, (x - u) / sqrt(s + eps),
+ * then weight and bias per channel.  Every output element is computed by one thread in a fixed order (taps in (dy, dx, c_in)
+ * order from the bias, hidden channels 0..15 in order, each step one fused multiply-add), so a prompt's embedding is
+ * bit-identical whatever P and wherever it stands in the batch.  Non-finite input gives non-finite output (no check).
+ * No workspace.  P <= 0, a NULL pointer (the struct, any weight, masks, dense) or another geometry than
+ * (mask_in_chans, embed_dim, grid) = (16, 256, 64) returns POPE_ERR_ARG before any HIP call. */
+typedef struct pope_sam_mask_embed_weights {
+    int mask_in_chans, embed_dim, grid;        /* 16, 256, 64 */
+    float ln1_eps, ln2_eps;                    /* LayerNorm2d eps (1e-6) */
+    const float *conv1_w /* [4, 1, 2, 2] */, *conv1_b, *ln1_w, *ln1_b;
+    const float *conv2_w /* [16, 4, 2, 2] */, *conv2_b, *ln2_w, *ln2_b;
+    const float *conv3_w /* [256, 16] */, *conv3_b;
+} pope_sam_mask_embed_weights;
+int pope_sam_mask_embed_f32(const pope_sam_mask_embed_weights* w_host, const float* masks, int P, float* dense, void* stream);
 
 /* ---- SAM automatic mask generator: post-processing of one decoder call ------------------------------------------ */
 

@@ -66,6 +66,11 @@ class SamDecoderWeights(C.Structure):
         ("hyper_w", C.c_void_p * 12), ("hyper_b", C.c_void_p * 12), ("iou_w", C.c_void_p * 3), ("iou_b", C.c_void_p * 3)]
 
 
+class SamMaskEmbedWeights(C.Structure):
+    _fields_ = [("mask_in_chans", C.c_int), ("embed_dim", C.c_int), ("grid", C.c_int), ("ln1_eps", C.c_float), ("ln2_eps", C.c_float)] + [
+        (n, C.c_void_p) for n in ("conv1_w", "conv1_b", "ln1_w", "ln1_b", "conv2_w", "conv2_b", "ln2_w", "ln2_b", "conv3_w", "conv3_b")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pope_hip.h
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
@@ -161,6 +166,7 @@ PROTOTYPES = {
     "pope_sam_decoder_forward_images_f32": (C.c_int, [C.POINTER(SamDecoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                       c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int]
                                             + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_sam_mask_embed_f32": (C.c_int, [C.POINTER(SamMaskEmbedWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_sam_postprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_sam_postprocess_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_double]
                                  + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),

@@ -466,6 +466,12 @@ int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w, const
     return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
 }
 
+int pope_sam_mask_embed_f32(const pope_sam_mask_embed_weights* w, const float* masks, int P, float* dense, void* stream) {
+    if (const int rc = pope_sam_mask_embed_check(w, masks, P, dense)) return rc;   // before any HIP call
+    StreamDevice on_device(stream);
+    return pope_launch_sam_mask_embed(w, masks, P, dense, static_cast<hipStream_t>(stream));
+}
+
 size_t pope_sam_postprocess_workspace_bytes(int img_size, int H, int W) { return pope_sam_postprocess_workspace(img_size, H, W); }
 
 int pope_sam_postprocess_f32(const float* low_res, int M, int h, int w, const int* selection, int n_sel, int img_size, int ih, int iw,

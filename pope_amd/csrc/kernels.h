@@ -405,6 +405,10 @@ size_t pope_sam_decoder_images_workspace(const pope_sam_decoder_weights* w, int 
                                          long long dense_stride);
 int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream);
 
+// SAM prompt encoder, mask prompts (sam_prompt.hip): pope_sam_mask_embed_f32
+int pope_sam_mask_embed_check(const pope_sam_mask_embed_weights* w, const float* masks, int P, const float* dense);   // no HIP call
+int pope_launch_sam_mask_embed(const pope_sam_mask_embed_weights* w, const float* masks, int P, float* dense, hipStream_t stream);
+
 // SAM generator post-processing (sam_postprocess.hip): the arguments of pope_sam_postprocess_f32
 struct SamPostArgs {
     const float* low;

@@ -1,15 +1,16 @@
-"""SAM prompt encoder and mask decoder on the HIP library (point and box prompts).
+"""SAM prompt encoder and mask decoder on the HIP library (point, box and mask prompts).
 
 Drop-ins for `segment_anything.modeling.{prompt_encoder.PromptEncoder, mask_decoder.MaskDecoder, transformer.TwoWayTransformer}`:
 same constructor arguments, same parameter and buffer names (a `Sam` checkpoint's `prompt_encoder.*` and `mask_decoder.*` keys
 load with strict=True), same forward contracts.  The decoder modules are parameter containers only: `MaskDecoder.forward` is
-ONE C-ABI call (`pope_sam_decoder_forward_f32`, pope_amd/csrc/sam_decoder.hip), with no torch fallback.  The prompt encoder is
-O(P n 256) work and stays in torch on the device (as LoFTR's position code does); its dense positional encoding is cached
-per device.
+ONE C-ABI call (`pope_sam_decoder_forward_f32`, pope_amd/csrc/sam_decoder.hip), with no torch fallback.  The prompt encoder's
+point and box embeddings are O(P n 256) work and stay in torch on the device (as LoFTR's position code does); its dense
+positional encoding is cached per device.  Its mask embedding (`mask_downscaling`, 4 MiB written per prompt) is ONE C-ABI call
+(`pope_sam_mask_embed_f32`, pope_amd/csrc/sam_prompt.hip), with no torch fallback either.
 
 Supported geometry: the decoder every `build_sam` variant builds (dim 256, 8 heads, attention_downsample_rate 2, mlp_dim 2048,
-depth 2, a 64 x 64 embedding, 4 mask tokens, IoU head depth 3 / hidden 256) and at most 11 sparse embeddings per prompt.
-Mask prompts are not supported.
+depth 2, a 64 x 64 embedding, 4 mask tokens, IoU head depth 3 / hidden 256), at most 11 sparse embeddings per prompt, and mask
+prompts of 256 x 256 with mask_in_chans 16.
 """
 import ctypes as C
 from typing import Optional, Tuple, Type
@@ -28,6 +29,17 @@ GRID, DIM, MAX_SPARSE = 64, 256, 11
 
 def _unsupported(what):
     raise NotImplementedError(f"pope_amd SAM decoder: {what} (the build_sam.py decoder geometry only)")
+
+
+def require_gpu_mask(masks, who):
+    """The first check of every entry that takes a mask prompt (None passes): the mask embedding has no torch path, so a mask
+    that is not on a GPU is refused before anything else is looked at."""
+    if masks is None:
+        return
+    if not isinstance(masks, torch.Tensor):
+        raise TypeError(f"{who}: a mask prompt must be a float32 tensor, got {type(masks).__name__}")
+    if not masks.is_cuda:
+        raise NotImplementedError(f"pope_amd {who}: mask prompts run on the HIP library only (the mask is on {masks.device})")
 
 
 class MLPBlock(nn.Module):
@@ -443,8 +455,12 @@ class PositionEmbeddingRandom(nn.Module):
 
 
 class PromptEncoder(nn.Module):
-    """prompt_encoder.py:16-168 for point and box prompts: forward(points, boxes, masks=None) -> (sparse [P, n, 256],
-    dense [P, 256, 64, 64], a broadcast of no_mask_embed); get_dense_pe() -> [1, 256, 64, 64], cached per device."""
+    """prompt_encoder.py:16-168: forward(points, boxes, masks) -> (sparse [P, n, 256], dense [P, 256, 64, 64]);
+    get_dense_pe() -> [1, 256, 64, 64], cached per device.  Without a mask, dense is a broadcast of no_mask_embed (batch stride
+    0).  masks: float32 [P, 1, 256, 256] on the module's device (made contiguous if it is a view; TypeError for another dtype,
+    ValueError for another shape or a P that disagrees with the points / boxes); dense is then a fresh contiguous tensor from one
+    C call (`pope_sam_mask_embed_f32`), a prompt's embedding bit-identical whatever P.  Masks alone give sparse [P, 0, 256].
+    There is no torch path for the mask embedding: a mask that is not on a GPU raises NotImplementedError."""
 
     def __init__(self, embed_dim: int, image_embedding_size: Tuple[int, int], input_image_size: Tuple[int, int],
                  mask_in_chans: int, activation: Type[nn.Module] = nn.GELU) -> None:
@@ -459,7 +475,7 @@ class PromptEncoder(nn.Module):
         self.point_embeddings = nn.ModuleList(nn.Embedding(1, embed_dim) for _ in range(self.num_point_embeddings))
         self.not_a_point_embed = nn.Embedding(1, embed_dim)
         self.mask_input_size = (4 * image_embedding_size[0], 4 * image_embedding_size[1])
-        # mask prompts are not supported; the parameters are here so that checkpoints load with strict=True
+        # a parameter container: `_embed_masks` runs the whole chain in one kernel (pope_amd/csrc/sam_prompt.hip)
         self.mask_downscaling = nn.Sequential(
             nn.Conv2d(1, mask_in_chans // 4, kernel_size=2, stride=2),
             LayerNorm2d(mask_in_chans // 4),
@@ -471,15 +487,17 @@ class PromptEncoder(nn.Module):
         )
         self.no_mask_embed = nn.Embedding(1, embed_dim)
         self._pe_cache = {}
+        self._mask_src = None   # where mask_downscaling keeps its parameters (_lib.param_slots)
+        self._mask_w = None     # (slots key, pope_sam_mask_embed_weights, the tensors it points into)
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
-        self._pe_cache = {}
+        self._pe_cache, self._mask_src, self._mask_w = {}, None, None
         return out
 
     def load_state_dict(self, *a, **k):
         out = super().load_state_dict(*a, **k)
-        self._pe_cache = {}
+        self._pe_cache, self._mask_w = {}, None
         return out
 
     def _get_device(self) -> torch.device:
@@ -517,22 +535,84 @@ class PromptEncoder(nn.Module):
         corner_embedding[:, 1, :] += self.point_embeddings[3].weight
         return corner_embedding
 
+    def _mask_weights(self):
+        """The `pope_sam_mask_embed_weights` of `mask_downscaling` (the parameters themselves, torch's layouts), rebuilt when a
+        parameter was replaced or edited in place."""
+        if self._mask_src is None:
+            self._mask_src = _lib.param_slots(self.mask_downscaling)
+        key = _lib.slots_key(self._mask_src)
+        if self._mask_w is not None and self._mask_w[0] == key:
+            return self._mask_w[1]
+        conv1, ln1, act1, conv2, ln2, act2, conv3 = self.mask_downscaling
+        if conv2.out_channels != 16 or any(not isinstance(a, nn.GELU) or a.approximate != "none" for a in (act1, act2)):
+            _unsupported(f"mask prompts with mask_in_chans={conv2.out_channels}, activation {type(act1).__name__} "
+                         "(mask_in_chans 16 and the erf GELU)")
+        keep = []
+
+        def P(t):
+            t = t.detach()
+            if t.dtype != torch.float32:
+                raise TypeError("pope_amd kernels take fp32 parameters")
+            require_cuda(t, "PromptEncoder")
+            t = t.contiguous()
+            keep.append(t)
+            return C.c_void_p(t.data_ptr())
+
+        s = _lib.SamMaskEmbedWeights()
+        s.mask_in_chans, s.embed_dim, s.grid = conv2.out_channels, conv3.out_channels, self.image_embedding_size[0]
+        s.ln1_eps, s.ln2_eps = float(ln1.eps), float(ln2.eps)
+        s.conv1_w, s.conv1_b, s.ln1_w, s.ln1_b = P(conv1.weight), P(conv1.bias), P(ln1.weight), P(ln1.bias)
+        s.conv2_w, s.conv2_b, s.ln2_w, s.ln2_b = P(conv2.weight), P(conv2.bias), P(ln2.weight), P(ln2.bias)
+        s.conv3_w, s.conv3_b = P(conv3.weight), P(conv3.bias)
+        self._mask_w = (key, s, keep)
+        return s
+
+    def _check_masks(self, masks):
+        """dtype and shape of a mask prompt (its device is `forward`'s first check)."""
+        if masks.dtype != torch.float32:
+            raise TypeError(f"PromptEncoder: masks must be float32, got {masks.dtype}")
+        if masks.dim() != 4 or tuple(masks.shape[1:]) != (1, *self.mask_input_size):
+            raise ValueError(f"PromptEncoder: masks must be [B, 1, {self.mask_input_size[0]}, {self.mask_input_size[1]}], "
+                             f"got {tuple(masks.shape)}")
+
+    def _embed_masks(self, masks):
+        """prompt_encoder.py:102-105 in ONE C call (`pope_sam_mask_embed_f32`): [B, 1, 256, 256] -> a fresh [B, 256, 64, 64]."""
+        w = self._mask_weights()
+        masks = masks.contiguous()
+        if masks.data_ptr() % 16:   # a contiguous view into the middle of a storage: the kernel loads 16 bytes at a time
+            masks = masks.clone()
+        dense = torch.empty(masks.shape[0], self.embed_dim, *self.image_embedding_size, device=masks.device, dtype=torch.float32)
+        if masks.shape[0] == 0:
+            return dense
+        with on_device_of(masks):
+            check(_lib.lib().pope_sam_mask_embed_f32(C.byref(w), ptr(masks), masks.shape[0], ptr(dense), stream_of(masks.device)),
+                  "pope_sam_mask_embed_f32")
+        return dense
+
     def forward(self, points: Optional[Tuple[torch.Tensor, torch.Tensor]], boxes: Optional[torch.Tensor],
                 masks: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        if masks is not None:
-            raise NotImplementedError("pope_amd PromptEncoder: mask prompts are not supported (points and boxes only)")
+        require_gpu_mask(masks, "PromptEncoder")   # before every other check
         dev = self._get_device()
         require_cuda(self.point_embeddings[0].weight, "PromptEncoder")
         for t in (points[0] if points is not None else None, points[1] if points is not None else None, boxes):
             if t is not None:
                 require_cuda(t, "PromptEncoder")
-        bs = points[0].shape[0] if points is not None else boxes.shape[0] if boxes is not None else 1
+        bs = points[0].shape[0] if points is not None else boxes.shape[0] if boxes is not None else \
+            masks.shape[0] if masks is not None else 1
+        if masks is not None:
+            self._check_masks(masks)
+            if masks.shape[0] != bs:
+                raise ValueError(f"PromptEncoder: masks holds {masks.shape[0]} prompts, the points / boxes {bs}")
+            if masks.device != dev:
+                raise ValueError(f"PromptEncoder: masks is on {masks.device}, the module on {dev}")
         sparse_embeddings = torch.empty((bs, 0, self.embed_dim), device=dev)
         if points is not None:
             coords, labels = points
             sparse_embeddings = torch.cat([sparse_embeddings, self._embed_points(coords, labels, pad=(boxes is None))], dim=1)
         if boxes is not None:
             sparse_embeddings = torch.cat([sparse_embeddings, self._embed_boxes(boxes)], dim=1)
+        if masks is not None:
+            return sparse_embeddings, self._embed_masks(masks)
         dense_embeddings = self.no_mask_embed.weight.reshape(1, -1, 1, 1).expand(bs, -1, self.image_embedding_size[0],
                                                                                  self.image_embedding_size[1])
         return sparse_embeddings, dense_embeddings

@@ -1,7 +1,7 @@
 """SAM container, predictor and automatic mask generator on the HIP library.
 
 Drop-ins for `segment_anything.{modeling.sam.Sam, predictor.SamPredictor, automatic_mask_generator.SamAutomaticMaskGenerator}`
-and `build_sam.py`, for a single crop and point / box prompts.  The generator's post-processing is one fused HIP pass per decoder
+and `build_sam.py`, for a single crop and point / box / mask prompts.  The generator's post-processing is one fused HIP pass per decoder
 call (`pope_sam_postprocess_f32`, pope_amd/csrc/sam_postprocess.hip): from the 256 x 256 low-res logits of the masks that pass
 the IoU filter straight to per-mask counts, boxes, stability scores and bit-packed masks, without the 1024 x 1024 or the
 frame-sized fp32 tensors of `Sam.postprocess_masks`; the logits are bit-equal to torch's CPU `F.interpolate` (pope_amd/sam_amg.py
@@ -13,7 +13,7 @@ pope_amd/csrc/sam_rle.hip, so that `uncompressed_rle` downloads counts instead o
 same calls stopped after the second NMS: the records' boxes alone, no mask unpacked, encoded or downloaded (the frame-to-pose
 query of pope_amd/driver.py reads nothing else).  There is no torch fallback.
 
-Not supported: crop layers (`crop_n_layers > 0`), mask prompts, `output_mode="coco_rle"`.
+Not supported: crop layers (`crop_n_layers > 0`), `output_mode="coco_rle"`.
 """
 import ctypes as C
 from functools import partial
@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 from . import _lib, sam_amg
 from ._lib import check, on_device_of, ptr, require_cuda, stream_of
-from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer
+from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer, require_gpu_mask
 from .sam_encoder import ImageEncoderViT
 
 NMS_MAX = 2048   # boxes per pope_sam_nms_f32 call
@@ -166,22 +166,22 @@ class Sam(nn.Module):
     def forward(self, batched_input: List[Dict[str, Any]], multimask_output: bool) -> List[Dict[str, torch.Tensor]]:
         """modeling/sam.py:53-131, the end-to-end batch call.  One record per image: `image` (3 x h x w, already resized to
         the model's input frame, long side `img_size`), `original_size` (H, W) and the optional prompts `point_coords`
-        [B, n, 2] + `point_labels` [B, n] and `boxes` [B, 4], in the input frame (`mask_inputs` is not supported).  Returns
-        one dict per record: `masks` (bool [B, C, H, W]), `iou_predictions` [B, C], `low_res_logits` [B, C, 256, 256];
-        C = 3 with `multimask_output`, else 1.
-        The images run through the encoder in one call and the prompts of all records through the multi-image decoder
-        (`MaskDecoder.forward_images`, one call per distinct number of sparse embeddings); the masks of records of one
+        [B, n, 2] + `point_labels` [B, n] and `boxes` [B, 4], in the input frame, and `mask_inputs` (float32 [B, 1, 256, 256]
+        logits, e.g. an earlier call's `low_res_logits` of one mask).  Returns one dict per record: `masks` (bool [B, C, H, W]),
+        `iou_predictions` [B, C], `low_res_logits` [B, C, 256, 256]; C = 3 with `multimask_output`, else 1.
+        The images run through the encoder in one call and the prompts of the records without a mask prompt through the
+        multi-image decoder (`MaskDecoder.forward_images`, one call per distinct number of sparse embeddings); a record with
+        `mask_inputs` has a dense embedding per prompt and takes the single-image decoder call.  The masks of records of one
         geometry are resampled together.  Every record's output is bit for bit what `SamPredictor.set_torch_image` +
         `predict_torch` give for that record alone."""
         records = list(batched_input)
         if not records:
             return []
         for x in records:
-            if x.get("mask_inputs", None) is not None:
-                self.prompt_encoder(points=None, boxes=None, masks=x["mask_inputs"])   # raises: mask prompts are not supported
+            require_gpu_mask(x.get("mask_inputs", None), "Sam.forward")
         dev = self.device
         for x in records:
-            for k in ("image", "point_coords", "point_labels", "boxes"):
+            for k in ("image", "point_coords", "point_labels", "boxes", "mask_inputs"):
                 t = x.get(k, None)
                 if t is None:
                     continue
@@ -190,16 +190,23 @@ class Sam(nn.Module):
                     raise ValueError(f"Sam.forward: record tensor `{k}` is on {t.device}, the model on {dev}")
         embeddings = self.image_encoder(torch.stack([self.preprocess(x["image"]) for x in records], dim=0).contiguous())
         pe = self.prompt_encoder.get_dense_pe()
-        sparse, dense = [], None
-        for x in records:
+        sparse, dense, own_dense = [], None, {}
+        for r, x in enumerate(records):
             points = (x["point_coords"], x["point_labels"]) if "point_coords" in x else None
-            sp, dense = self.prompt_encoder(points=points, boxes=x.get("boxes", None), masks=None)
+            sp, dn = self.prompt_encoder(points=points, boxes=x.get("boxes", None), masks=x.get("mask_inputs", None))
             sparse.append(sp)
-        # one decoder call per number of sparse embeddings, over the images that have such prompts; a single record has nothing
-        # to share and takes the single-image call (the same bits, less host work: profiles/sam_forward.md)
+            if x.get("mask_inputs", None) is not None:
+                own_dense[r] = dn
+            else:
+                dense = dn
         low, iou = [None] * len(records), [None] * len(records)
-        for ns in sorted({sp.shape[1] for sp in sparse}):
-            members = [r for r, sp in enumerate(sparse) if sp.shape[1] == ns]
+        # a record with a mask prompt has a dense embedding per prompt: the single-image call, as `predict_torch` makes it
+        for r, dn in own_dense.items():
+            low[r], iou[r] = self.mask_decoder(embeddings[r:r + 1], pe, sparse[r], dn, multimask_output)
+        # the others: one decoder call per number of sparse embeddings, over the images that have such prompts; a single record
+        # has nothing to share and takes the single-image call (the same bits, less host work: profiles/sam_forward.md)
+        for ns in sorted({sp.shape[1] for r, sp in enumerate(sparse) if r not in own_dense}):
+            members = [r for r, sp in enumerate(sparse) if sp.shape[1] == ns and r not in own_dense]
             counts = [sparse[r].shape[0] for r in members]
             if len(records) == 1:
                 m, q = self.mask_decoder(embeddings, pe, sparse[0], dense, multimask_output)
@@ -337,6 +344,7 @@ class SamPredictor:
     @torch.no_grad()
     def predict_low_res(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True):
         """The prompt encoder and the mask decoder of `predict_torch`: (low_res_masks [B, C, 256, 256], iou_predictions [B, C])."""
+        require_gpu_mask(mask_input, "SamPredictor")
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
         points = (point_coords, point_labels) if point_coords is not None else None
@@ -356,10 +364,9 @@ class SamPredictor:
         return masks, iou_predictions, low_res_masks
 
     def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output=True, return_logits=False):
-        """numpy wrapper of `predict_torch` for one prompt (predictor.py:91-165)."""
-        if mask_input is not None:
-            raise NotImplementedError("pope_amd SamPredictor: mask prompts are not supported")
-        coords = labels = box_t = None
+        """numpy wrapper of `predict_torch` for one prompt (predictor.py:91-165); `mask_input`: [1, 256, 256] logits, e.g. one
+        mask of an earlier call's low-res output."""
+        coords = labels = box_t = mask_t = None
         if point_coords is not None:
             assert point_labels is not None, "point_labels must be supplied if point_coords is supplied."
             pc = self.transform.apply_coords(point_coords, self.original_size)
@@ -367,7 +374,9 @@ class SamPredictor:
             labels = torch.as_tensor(point_labels, dtype=torch.int, device=self.device)[None, :]
         if box is not None:
             box_t = torch.as_tensor(self.transform.apply_boxes(box, self.original_size), dtype=torch.float, device=self.device)[None, :]
-        masks, iou, low = self.predict_torch(coords, labels, box_t, None, multimask_output, return_logits=return_logits)
+        if mask_input is not None:
+            mask_t = torch.as_tensor(mask_input, dtype=torch.float, device=self.device)[None, :, :, :]
+        masks, iou, low = self.predict_torch(coords, labels, box_t, mask_t, multimask_output, return_logits=return_logits)
         return masks[0].cpu().numpy(), iou[0].cpu().numpy(), low[0].cpu().numpy()
 
     def get_image_embedding(self) -> torch.Tensor:

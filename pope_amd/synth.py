@@ -557,6 +557,40 @@ def sam_forward_case(device="cpu"):
              "point_labels": labels.to(device)}]
 
 
+SAM_MASK_PROMPT_CASES = {"box": (6, 0), "points": (17, 1)}   # name -> (P, seed of the masks): tests/golden/sam_mask_prompt.npz
+
+
+def sam_mask_prompt_case(P, seed=0):
+    """Seeded mask prompts [P, 1, 256, 256] fp32 that look like the decoder's low-res logits (what `predict(mask_input=)` is fed):
+    a floor of -8, three Gaussian blobs of amplitude 16 with sigma uniform in 10 .. 60 px at uniform centres, and noise of
+    std 0.5; all from one CPU generator (per prompt: the centres, the sigmas, then the noise)."""
+    g = torch.Generator().manual_seed(seed)
+    n = 256
+    yy, xx = torch.meshgrid(torch.arange(n, dtype=torch.float32), torch.arange(n, dtype=torch.float32), indexing="ij")
+    out = torch.empty(P, 1, n, n)
+    for p in range(P):
+        centre = torch.rand(3, 2, generator=g) * n
+        sigma = 10.0 + 50.0 * torch.rand(3, generator=g)
+        m = torch.full((n, n), -8.0)
+        for (cy, cx), s in zip(centre.tolist(), sigma.tolist()):
+            m += 16.0 * torch.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2.0 * s * s))
+        out[p, 0] = m + 0.5 * torch.randn(n, n, generator=g)
+    return out.contiguous()
+
+
+def sam_mask_prompt_inputs(name):
+    """The prompts of fixture case `name`: (points or None, boxes or None, masks, multimask_output).  "box": the 6 prompts of
+    `sam_decoder_case("box")` (two points and a box each) plus 6 masks, single-mask output; "points": 17 prompts of one
+    positive point each (every 15th of the "grid" case) plus 17 masks, multimask output."""
+    P, seed = SAM_MASK_PROMPT_CASES[name]
+    masks = sam_mask_prompt_case(P, seed)
+    if name == "box":
+        points, boxes, _ = sam_decoder_case("box")
+        return points, boxes, masks, False
+    (coords, labels), _, _ = sam_decoder_case("grid")
+    return (coords[::15][:P].contiguous(), labels[::15][:P].contiguous()), None, masks, True
+
+
 # ---- SAM automatic mask generator: post-processing ---------------------------------------------------------------------
 # name -> (M masks, frame (H, W)); the resized frame inside the 1024 square follows from ResizeLongestSide
 SAM_GENERATOR_CASES = {"frame": (128, (480, 640)), "portrait": (48, (333, 332))}
