@@ -296,6 +296,41 @@ def slots_key(slots):
     return tuple((t.data_ptr(), t._version) if t is not None else None for t in (d.get(n) for d, n in slots))
 
 
+def param_ptr(t, keep, who):
+    """Device pointer of an fp32 parameter (or a tensor derived from parameters) for a weights struct: detached, on a GPU, made
+    contiguous and appended to `keep`, the list that keeps a struct's tensors alive."""
+    import torch
+    t = t.detach()
+    if t.dtype != torch.float32:
+        raise TypeError("pope_amd kernels take fp32 parameters")
+    require_cuda(t, who)
+    t = t.contiguous()
+    keep.append(t)
+    return C.c_void_p(t.data_ptr())
+
+
+def grow_workspace(owner, need, device):
+    """The grow-only byte workspace a module keeps in `owner._ws`, at least `need` bytes on `device`.  The old buffer is dropped
+    before the new one is allocated (which is why this takes the owner and not the buffer: a caller's reference would keep the
+    old one alive through the allocation)."""
+    import torch
+    ws = owner._ws
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = owner._ws = None
+        ws = owner._ws = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def range_event(module, msg, note):
+    """A range-guard event of a module with `overflow_events` and `on_overflow`: counted, then `PopeRangeError(msg)` under
+    "raise", else a warning `msg + note` (the caller then re-runs in f32)."""
+    module.overflow_events += 1
+    if module.on_overflow == "raise":
+        raise PopeRangeError(msg)
+    import warnings
+    warnings.warn(msg + note, stacklevel=2)   # reported at the caller's line, as when the caller warned itself
+
+
 def ptr(t):
     """Device pointer of a contiguous fp32/int tensor (or None)."""
     if t is None:

@@ -3,7 +3,10 @@
 Drop-ins for `segment_anything.modeling.{prompt_encoder.PromptEncoder, mask_decoder.MaskDecoder, transformer.TwoWayTransformer}`:
 same constructor arguments, same parameter and buffer names (a `Sam` checkpoint's `prompt_encoder.*` and `mask_decoder.*` keys
 load with strict=True), same forward contracts.  The decoder modules are parameter containers only: `MaskDecoder.forward` is
-ONE C-ABI call (`pope_sam_decoder_forward_f32`, pope_amd/csrc/sam_decoder.hip), with no torch fallback.  The prompt encoder's
+ONE C-ABI call (`pope_sam_decoder_forward_f32`, pope_amd/csrc/sam_decoder.hip), with no torch fallback, and
+`MaskDecoder.forward_images` one (`pope_sam_decoder_forward_images_f32`) for the prompts of up to 16 images.  Both entries share
+one input check (`_check`) and one launch method (`_launch`: workspace, launch, range flag); they differ in what follows a
+range event (`forward` re-runs in f32, `forward_images` hands the group to `forward` image by image).  The prompt encoder's
 point and box embeddings are O(P n 256) work and stay in torch on the device (as LoFTR's position code does); its dense
 positional encoding is cached per device.  Its mask embedding (`mask_downscaling`, 4 MiB written per prompt) is ONE C-ABI call
 (`pope_sam_mask_embed_f32`, pope_amd/csrc/sam_prompt.hip), with no torch fallback either.
@@ -21,7 +24,6 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, on_device_of, ptr, require_cuda, stream_of
-from .dinov2 import PopeRangeError
 from .sam_encoder import LayerNorm2d
 
 GRID, DIM, MAX_SPARSE = 64, 256, 11
@@ -194,13 +196,7 @@ class MaskDecoder(nn.Module):
         keep = []
 
         def P(t):
-            t = t.detach()
-            if t.dtype != torch.float32:
-                raise TypeError("pope_amd kernels take fp32 parameters")
-            require_cuda(t, "MaskDecoder")
-            t = t.contiguous()
-            keep.append(t)
-            return C.c_void_p(t.data_ptr())
+            return _lib.param_ptr(t, keep, "MaskDecoder")
 
         def cat(*ts):
             return torch.cat([t.detach() for t in ts], 0)
@@ -213,13 +209,8 @@ class MaskDecoder(nn.Module):
                        up0.weight.detach().permute(2, 3, 1, 0).reshape(4 * up0.out_channels, up0.in_channels)]
         amax = float(torch.stack([w.detach().abs().max() for w in image_side]).max())
         if not f32 and not amax * _lib.PLANES_W_SCALE < _lib.F16_MAX:
-            self.overflow_events += 1
-            msg = (f"pope_amd: max |weight| = {amax:g} is outside the f16x3 range contract "
-                   f"(|w| < {_lib.F16_MAX / _lib.PLANES_W_SCALE:g})")
-            if self.on_overflow == "raise":
-                raise PopeRangeError(msg)
-            import warnings
-            warnings.warn(msg + "; this decoder runs with precision='f32'")
+            _lib.range_event(self, f"pope_amd: max |weight| = {amax:g} is outside the f16x3 range contract "
+                             f"(|w| < {_lib.F16_MAX / _lib.PLANES_W_SCALE:g})", "; this decoder runs with precision='f32'")
             w = self._weights("f32")
             self._wcache[precision] = self._wcache["f32"]
             return w
@@ -278,36 +269,68 @@ class MaskDecoder(nn.Module):
         self._wcache[precision] = (key, s, keep)
         return s
 
-    def _workspace(self, w, P, n_sparse, shared, device):
-        need = int(_lib.lib().pope_sam_decoder_workspace_bytes(C.byref(w), P, n_sparse, int(shared)))
-        if need <= 0:
-            raise ValueError(f"pope_amd SAM decoder: unsupported call (n_sparse = {n_sparse}, at most {MAX_SPARSE})")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
-
-    def _inputs(self, image_embeddings, image_pe, sparse, dense):
+    def _check(self, image_embeddings, image_pe, sparse, dense, images=False):
+        """The input check of both entries: device and dtype of the four tensors, the image shapes (one image, N with `images`),
+        the sparse shape, then the entry's own dense rule ([1 or P, ...] for `forward`, the stride-0 broadcast for
+        `forward_images`).  Returns whether dense is one embedding for every prompt (PromptEncoder's no_mask_embed)."""
         for t, name in ((image_embeddings, "image_embeddings"), (image_pe, "image_pe"), (sparse, "sparse_prompt_embeddings"),
                         (dense, "dense_prompt_embeddings")):
             require_cuda(t, "MaskDecoder")
             if t.dtype != torch.float32:
                 raise TypeError(f"MaskDecoder: {name} must be float32, got {t.dtype}")
-        img_shape = (1, DIM, GRID, GRID)
-        if tuple(image_embeddings.shape) != img_shape or tuple(image_pe.shape) != img_shape:
-            raise ValueError(f"MaskDecoder: image_embeddings and image_pe must be {img_shape} (one image), got "
+        one = (1, DIM, GRID, GRID)
+        if images:
+            if image_embeddings.dim() != 4 or tuple(image_embeddings.shape[1:]) != one[1:] or tuple(image_pe.shape) != one:
+                raise ValueError(f"MaskDecoder.forward_images: image_embeddings must be [N, {DIM}, {GRID}, {GRID}] and image_pe "
+                                 f"[1, {DIM}, {GRID}, {GRID}], got {tuple(image_embeddings.shape)} and {tuple(image_pe.shape)}")
+        elif tuple(image_embeddings.shape) != one or tuple(image_pe.shape) != one:
+            raise ValueError(f"MaskDecoder: image_embeddings and image_pe must be {one} (one image), got "
                              f"{tuple(image_embeddings.shape)} and {tuple(image_pe.shape)}")
         if sparse.dim() != 3 or sparse.shape[2] != DIM or sparse.shape[1] > MAX_SPARSE:
             raise ValueError(f"MaskDecoder: sparse_prompt_embeddings must be [P, n <= {MAX_SPARSE}, {DIM}], got {tuple(sparse.shape)}")
-        P = sparse.shape[0]
-        if dense.dim() != 4 or tuple(dense.shape[1:]) != img_shape[1:] or dense.shape[0] not in (1, P):
+        fits = dense.dim() == 4 and tuple(dense.shape[1:]) == one[1:] and dense.shape[0] in (1, sparse.shape[0])
+        shared = fits and (dense.shape[0] == 1 or dense.stride(0) == 0)
+        if images and not shared:
+            raise ValueError("MaskDecoder.forward_images: dense_prompt_embeddings must be the broadcast PromptEncoder returns "
+                             f"without a mask ([1 or P, {DIM}, {GRID}, {GRID}], batch stride 0), got {tuple(dense.shape)}")
+        if not fits:
             raise ValueError(f"MaskDecoder: dense_prompt_embeddings must be [P, {DIM}, {GRID}, {GRID}], got {tuple(dense.shape)}")
-        shared = dense.shape[0] == 1 or dense.stride(0) == 0   # one embedding for every prompt (PromptEncoder's no_mask_embed)
-        dense = dense[:1].contiguous() if shared else dense.contiguous()
-        return image_embeddings.contiguous(), image_pe.contiguous(), sparse.contiguous(), dense, shared
+        return shared
+
+    def _launch(self, w, img, pe, sparse, dense, dense_stride, multimask_output, masks, iou, hs=None, keys=None, which=None):
+        """The one place that calls the decoder's C entries: `pope_sam_decoder_forward_f32` for one image, with `which` (the
+        image of each prompt) `pope_sam_decoder_forward_images_f32` for img [N, ...].  Workspace query, the grow-only workspace,
+        the launch and the one read of the range flag (one sync per call: the range guard of every planes producer of the
+        call).  Returns the range bits."""
+        L = _lib.lib()
+        N, P, ns, dev = img.shape[0], sparse.shape[0], sparse.shape[1], img.device
+        if which is None:
+            need = L.pope_sam_decoder_workspace_bytes(C.byref(w), P, ns, int(dense_stride == 0))
+            what = f"n_sparse = {ns}, at most {MAX_SPARSE}"
+        else:
+            host = (C.c_int * P)(*(int(v) for v in which))
+            need = L.pope_sam_decoder_images_workspace_bytes(C.byref(w), N, host, P, ns, dense_stride)
+            what = f"N = {N}, P = {P}, n_sparse = {ns}, at most {MAX_SPARSE}"
+        if int(need) <= 0:
+            raise ValueError(f"pope_amd SAM decoder: unsupported call ({what})")
+        ws = _lib.grow_workspace(self, int(need), dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        sp, mm, fl = ptr(sparse) if ns else None, int(bool(multimask_output)), C.c_void_p(flag.data_ptr())
+        with on_device_of(img):
+            if which is None:
+                check(L.pope_sam_decoder_forward_f32(
+                    C.byref(w), ptr(img), ptr(pe), sp, P, ns, ptr(dense), dense_stride, mm, ptr(masks), ptr(iou), ptr(hs), ptr(keys),
+                    ptr(ws), ws.numel(), fl, stream_of(dev)), "pope_sam_decoder_forward_f32")
+            else:
+                check(L.pope_sam_decoder_forward_images_f32(
+                    C.byref(w), ptr(img), N, ptr(pe), sp, host, P, ns, ptr(dense), dense_stride, mm, ptr(masks), ptr(iou),
+                    ptr(ws), ws.numel(), fl, stream_of(dev)), "pope_sam_decoder_forward_images_f32")
+        return int(flag.item())
 
     def _run(self, image_embeddings, image_pe, sparse, dense, multimask_output, taps=False, precision=None):
-        img, pe, sparse, dense, shared = self._inputs(image_embeddings, image_pe, sparse, dense)
+        shared = self._check(image_embeddings, image_pe, sparse, dense)
+        img, pe, sparse = image_embeddings.contiguous(), image_pe.contiguous(), sparse.contiguous()
+        dense = dense[:1].contiguous() if shared else dense.contiguous()
         P, ns = sparse.shape[0], sparse.shape[1]
         Cm = self.num_multimask_outputs if multimask_output else 1
         dev = img.device
@@ -317,22 +340,11 @@ class MaskDecoder(nn.Module):
         keys = torch.empty(P, GRID * GRID, DIM, device=dev, dtype=torch.float32) if taps else None
         if P == 0:
             return masks, iou, hs, keys
-        w = self._weights(precision)
-        ws = self._workspace(w, P, ns, shared, dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        with on_device_of(img):
-            check(_lib.lib().pope_sam_decoder_forward_f32(
-                C.byref(w), ptr(img), ptr(pe), ptr(sparse) if ns else None, P, ns, ptr(dense), 0 if shared else DIM * GRID * GRID,
-                int(bool(multimask_output)), ptr(masks), ptr(iou), ptr(hs), ptr(keys), ptr(ws), ws.numel(),
-                C.c_void_p(flag.data_ptr()), stream_of(dev)), "pope_sam_decoder_forward_f32")
-        bits = int(flag.item())   # one sync per call: the range guard of every planes producer of the call
+        bits = self._launch(self._weights(precision), img, pe, sparse, dense, 0 if shared else DIM * GRID * GRID, multimask_output,
+                            masks, iou, hs, keys)
         if bits:
-            self.overflow_events += 1
-            msg = f"pope_amd SAM decoder: a value left the f16x3 range ({_lib.describe_range_bits(bits)})"
-            if self.on_overflow == "raise":
-                raise PopeRangeError(msg)
-            import warnings
-            warnings.warn(msg + "; re-running the call on the fp32 GEMMs")
+            _lib.range_event(self, f"pope_amd SAM decoder: a value left the f16x3 range ({_lib.describe_range_bits(bits)})",
+                             "; re-running the call on the fp32 GEMMs")
             return self._run(image_embeddings, image_pe, sparse, dense, multimask_output, taps, precision="f32")
         return masks, iou, hs, keys
 
@@ -349,28 +361,18 @@ class MaskDecoder(nn.Module):
         """`forward` over the prompts of N images: image_embeddings [N, 256, 64, 64], sparse [P, n, 256], dense the broadcast
         `PromptEncoder` returns without a mask ([1 or P, 256, 64, 64], one value per channel), prompt_image [P] = the image of
         each prompt (host integers, any order) -> (low_res_masks [P, C, 256, 256], iou_pred [P, C]), prompt for prompt
-        bit-identical to `forward` with that prompt's image alone.  One C call (`pope_sam_decoder_forward_images_f32`) and one
+        bit-identical to `forward` with that prompt's image alone.  One image has nothing to share and is `forward` (the same
+        bits, less host work: profiles/sam_forward.md).  Otherwise one C call (the multi-image entry, `_launch`) and one
         range-flag read per group of at most 16 images; a flagged group is handled per image by `forward`, so that one
         image's overflow neither changes nor re-runs another image's prompts on other arithmetic than its own call would."""
-        for t, name in ((image_embeddings, "image_embeddings"), (image_pe, "image_pe"), (sparse_prompt_embeddings, "sparse_prompt_embeddings"),
-                        (dense_prompt_embeddings, "dense_prompt_embeddings")):
-            require_cuda(t, "MaskDecoder")
-            if t.dtype != torch.float32:
-                raise TypeError(f"MaskDecoder: {name} must be float32, got {t.dtype}")
         sparse, dense = sparse_prompt_embeddings, dense_prompt_embeddings
-        if image_embeddings.dim() != 4 or tuple(image_embeddings.shape[1:]) != (DIM, GRID, GRID) or tuple(image_pe.shape) != (1, DIM, GRID, GRID):
-            raise ValueError(f"MaskDecoder.forward_images: image_embeddings must be [N, {DIM}, {GRID}, {GRID}] and image_pe "
-                             f"[1, {DIM}, {GRID}, {GRID}], got {tuple(image_embeddings.shape)} and {tuple(image_pe.shape)}")
-        if sparse.dim() != 3 or sparse.shape[2] != DIM or sparse.shape[1] > MAX_SPARSE:
-            raise ValueError(f"MaskDecoder: sparse_prompt_embeddings must be [P, n <= {MAX_SPARSE}, {DIM}], got {tuple(sparse.shape)}")
-        N, P, ns = image_embeddings.shape[0], sparse.shape[0], sparse.shape[1]
-        if dense.dim() != 4 or tuple(dense.shape[1:]) != (DIM, GRID, GRID) or dense.shape[0] not in (1, P) or \
-                not (dense.shape[0] == 1 or dense.stride(0) == 0):
-            raise ValueError("MaskDecoder.forward_images: dense_prompt_embeddings must be the broadcast PromptEncoder returns "
-                             f"without a mask ([1 or P, {DIM}, {GRID}, {GRID}], batch stride 0), got {tuple(dense.shape)}")
+        self._check(image_embeddings, image_pe, sparse, dense, images=True)
+        N, P = image_embeddings.shape[0], sparse.shape[0]
         which = np.asarray(prompt_image.cpu() if isinstance(prompt_image, torch.Tensor) else prompt_image, dtype=np.int64).reshape(-1)
         if which.size != P or (P and (which.min() < 0 or which.max() >= N)):
             raise ValueError(f"MaskDecoder.forward_images: prompt_image must hold {P} image indices in [0, {N})")
+        if N == 1:
+            return self.forward(image_embeddings, image_pe, sparse, dense[:1], multimask_output)
         Cm = self.num_multimask_outputs if multimask_output else 1
         dev = image_embeddings.device
         masks = torch.empty(P, Cm, 4 * GRID, 4 * GRID, device=dev, dtype=torch.float32)
@@ -393,29 +395,13 @@ class MaskDecoder(nn.Module):
         return masks, iou
 
     def _run_images(self, img, pe, sparse, dense, which, multimask_output, masks, iou):
-        """One `pope_sam_decoder_forward_images_f32` call into masks / iou; on a range event the group's images one by one."""
-        N, P, ns, dev = img.shape[0], sparse.shape[0], sparse.shape[1], img.device
-        w = self._weights()
-        host = (C.c_int * P)(*(int(v) for v in which))
-        need = int(_lib.lib().pope_sam_decoder_images_workspace_bytes(C.byref(w), N, host, P, ns, 0))
-        if need <= 0:
-            raise ValueError(f"pope_amd SAM decoder: unsupported call (N = {N}, P = {P}, n_sparse = {ns}, at most {MAX_SPARSE})")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = self._ws
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        with on_device_of(img):
-            check(_lib.lib().pope_sam_decoder_forward_images_f32(
-                C.byref(w), ptr(img), N, ptr(pe), ptr(sparse) if ns else None, host, P, ns, ptr(dense), 0,
-                int(bool(multimask_output)), ptr(masks), ptr(iou), ptr(ws), ws.numel(), C.c_void_p(flag.data_ptr()),
-                stream_of(dev)), "pope_sam_decoder_forward_images_f32")
-        if not int(flag.item()):   # one sync per call
+        """One multi-image call into masks / iou; on a range event the group's images one by one."""
+        if not self._launch(self._weights(), img, pe, sparse, dense, 0, multimask_output, masks, iou, which=which):
             return
         # The flag does not say whose value left the range.  Each image's own call does: it counts the event, raises or warns
         # and re-runs in f32 exactly as the per-image loop would, and leaves the other images on the arithmetic they asked for.
         for i in np.unique(which):
-            idx = torch.as_tensor(np.nonzero(which == i)[0], device=dev)
+            idx = torch.as_tensor(np.nonzero(which == i)[0], device=img.device)
             m, q = self.forward(img[int(i)][None], pe, sparse[idx], dense.expand(idx.numel(), -1, -1, -1), multimask_output)
             masks[idx], iou[idx] = m, q
 
@@ -550,13 +536,7 @@ class PromptEncoder(nn.Module):
         keep = []
 
         def P(t):
-            t = t.detach()
-            if t.dtype != torch.float32:
-                raise TypeError("pope_amd kernels take fp32 parameters")
-            require_cuda(t, "PromptEncoder")
-            t = t.contiguous()
-            keep.append(t)
-            return C.c_void_p(t.data_ptr())
+            return _lib.param_ptr(t, keep, "PromptEncoder")
 
         s = _lib.SamMaskEmbedWeights()
         s.mask_in_chans, s.embed_dim, s.grid = conv2.out_channels, conv3.out_channels, self.image_embedding_size[0]

@@ -15,7 +15,6 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, on_device_of, ptr, require_cuda, stream_of
-from .dinov2 import PopeRangeError
 
 
 class MLPBlock(nn.Module):
@@ -167,24 +166,14 @@ class ImageEncoderViT(nn.Module):
         keep = []
 
         def P(t):
-            t = t.detach()
-            if t.dtype != torch.float32:
-                raise TypeError("pope_amd kernels take fp32 parameters (f16x3 arithmetic inside)")
-            t = t.contiguous()
-            keep.append(t)
-            return C.c_void_p(t.data_ptr())
+            return _lib.param_ptr(t, keep, "ImageEncoderViT")
 
         lin = [self.patch_embed.proj.weight, self.neck[0].weight, self.neck[2].weight] + [
             t for b in self.blocks for t in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.lin1.weight, b.mlp.lin2.weight)]
         amax = float(torch.stack([t.detach().abs().max() for t in lin]).max())
         if not f32 and not amax * _lib.PLANES_W_SCALE < _lib.F16_MAX:
-            self.overflow_events += 1
-            msg = (f"pope_amd: max |weight| = {amax:g} is outside the f16x3 range contract "
-                   f"(|w| < {_lib.F16_MAX / _lib.PLANES_W_SCALE:g})")
-            if self.on_overflow == "raise":
-                raise PopeRangeError(msg)
-            import warnings
-            warnings.warn(msg + "; this encoder runs with precision='f32'")
+            _lib.range_event(self, f"pope_amd: max |weight| = {amax:g} is outside the f16x3 range contract "
+                             f"(|w| < {_lib.F16_MAX / _lib.PLANES_W_SCALE:g})", "; this encoder runs with precision='f32'")
             w = self._weights("f32")
             self._wcache[precision] = self._wcache["f32"]
             return w
@@ -244,9 +233,7 @@ class ImageEncoderViT(nn.Module):
         need = int(_lib.lib().pope_sam_encoder_workspace_bytes(C.byref(w), b))
         if need <= 0:
             raise ValueError("pope_amd SAM encoder: unsupported geometry (head_dim 64 / 80, dim % 128 == 0, out_chans % 256 == 0)")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return _lib.grow_workspace(self, need, device)
 
     def _run(self, x, taps=(), precision=None):
         require_cuda(x, "ImageEncoderViT")
@@ -274,13 +261,8 @@ class ImageEncoderViT(nn.Module):
                                                               stream_of(x.device)), "pope_sam_encoder_forward_f32")
         bits = int(flag.item())   # one sync per call: the range guard of every planes producer of the launch sequence
         if bits:
-            self.overflow_events += 1
-            what = ", ".join(v for k, v in _lib.RANGE_BITS.items() if bits & k)
-            msg = f"pope_amd SAM encoder: a value left the f16x3 range ({what})"
-            if self.on_overflow == "raise":
-                raise PopeRangeError(msg)
-            import warnings
-            warnings.warn(msg + "; re-running the call on the fp32 MFMA")
+            _lib.range_event(self, f"pope_amd SAM encoder: a value left the f16x3 range ({_lib.describe_range_bits(bits)})",
+                             "; re-running the call on the fp32 MFMA")
             return self._run(x, taps, precision="f32")
         return out, tap_out
 

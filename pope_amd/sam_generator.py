@@ -11,7 +11,10 @@ frames of several queries at once: one encoder call, the decoder per frame, then
 `pope_sam_nms_segments_f32`, one workgroup per frame; the clean-up over all survivors; run lengths by `pope_sam_rle_u32`,
 pope_amd/csrc/sam_rle.hip, so that `uncompressed_rle` downloads counts instead of masks).  `propose` / `propose_batch` are the
 same calls stopped after the second NMS: the records' boxes alone, no mask unpacked, encoded or downloaded (the frame-to-pose
-query of pope_amd/driver.py reads nothing else).  There is no torch fallback.
+query of pope_amd/driver.py reads nothing else).  There is one tail: `generate` / `propose` are the batched tail with one segment.
+`Sam.decode_prompts` is the prompt encoder and the mask decoder of one image, with the image's features as an argument: the
+predictor calls it with the features it holds, the generator with each frame's (it never writes the predictor's state).  There
+is no torch fallback.
 
 Not supported: crop layers (`crop_n_layers > 0`), `output_mode="coco_rle"`.
 """
@@ -68,18 +71,31 @@ def postprocess_batch(low_res, selection, input_size, original_size, mask_thresh
     return stats, bits, dense
 
 
+def _nms_args(boxes, scores, who):
+    """The arguments of both NMS bindings: (boxes and scores as contiguous fp32 on the boxes' device, an int32 keep buffer)."""
+    require_cuda(boxes, who)
+    dev = boxes.device
+    return (boxes.to(torch.float32).contiguous(), scores.to(device=dev, dtype=torch.float32).contiguous(),
+            torch.empty(max(boxes.shape[0], 1), dtype=torch.int32, device=dev))
+
+
+def _packed_words(packed, W, who):
+    """The bit-packed masks of `who`, checked and contiguous: int32 words [n, H, ceil(W / 32)] on a GPU."""
+    require_cuda(packed, who)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != sam_amg.row_words(W):
+        raise TypeError(f"{who}: expected int32 words [n, H, {sam_amg.row_words(W)}] for W = {W}, "
+                        f"got {packed.dtype} {tuple(packed.shape)}")
+    return packed.contiguous()
+
+
 def box_nms(boxes, scores, iou_threshold):
     """Greedy box NMS on the device (`pope_sam_nms_f32`): `torchvision.ops.batched_nms` with one category restated from its
     definition (torchvision is not a dependency, so it is not pinned against the library itself; `sam_amg.nms` is the same
     definition on the CPU).  boxes [n, 4] XYXY, scores [n]; returns the kept indices in score order (int64, on the device)."""
-    require_cuda(boxes, "box_nms")
-    n = boxes.shape[0]
+    boxes, scores, keep = _nms_args(boxes, scores, "box_nms")
+    n, dev = boxes.shape[0], boxes.device
     if n > NMS_MAX:
         raise ValueError(f"box_nms: at most {NMS_MAX} boxes per call, got {n}")
-    dev = boxes.device
-    boxes = boxes.to(torch.float32).contiguous()
-    scores = scores.to(device=dev, dtype=torch.float32).contiguous()
-    keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     with on_device_of(boxes):
         check(_lib.lib().pope_sam_nms_f32(ptr(boxes), ptr(scores), n, float(iou_threshold), ptr(keep), ptr(count), stream_of(dev)),
@@ -93,18 +109,14 @@ def box_nms_segments(boxes, scores, seg_offsets, iou_threshold):
     to n, segment s = boxes seg_offsets[s] .. seg_offsets[s + 1] - 1, at most `NMS_MAX` of them.  Returns (keep int32 [n],
     counts int32 [S]), both on the device and without a host read: the kept boxes of segment s are
     keep[seg_offsets[s] : seg_offsets[s] + counts[s]], global indices into n in score order."""
-    require_cuda(boxes, "box_nms_segments")
-    n = boxes.shape[0]
+    boxes, scores, keep = _nms_args(boxes, scores, "box_nms_segments")
+    n, dev = boxes.shape[0], boxes.device
     seg = np.asarray(seg_offsets.cpu() if isinstance(seg_offsets, torch.Tensor) else seg_offsets, dtype=np.int64).reshape(-1)
     if seg.size < 1 or seg[0] != 0 or seg[-1] != n or (np.diff(seg) < 0).any():
         raise ValueError(f"box_nms_segments: seg_offsets must rise from 0 to n = {n}, got {seg.tolist()}")
     if seg.size > 1 and int(np.diff(seg).max()) > NMS_MAX:
         raise ValueError(f"box_nms_segments: at most {NMS_MAX} boxes per segment, got {int(np.diff(seg).max())}")
     S = seg.size - 1
-    dev = boxes.device
-    boxes = boxes.to(torch.float32).contiguous()
-    scores = scores.to(device=dev, dtype=torch.float32).contiguous()
-    keep = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     counts = torch.zeros(S, dtype=torch.int32, device=dev)
     if S == 0:
         return keep[:n], counts
@@ -119,11 +131,7 @@ def rle_from_packed(packed, W):
     """`mask_to_rle_pytorch` of bit-packed masks on the device (`pope_sam_rle_u32`, pope_amd/csrc/sam_rle.hip): int32 words
     [n, H, ceil(W / 32)] -> list of {"size": [H, W], "counts": [...]}: column-major run lengths, starting with a run of zeros.
     Two calls (lengths, then counts at the scanned offsets); only the lengths and the counts are downloaded."""
-    require_cuda(packed, "rle_from_packed")
-    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != sam_amg.row_words(W):
-        raise TypeError(f"rle_from_packed: expected int32 words [n, H, {sam_amg.row_words(W)}] for W = {W}, "
-                        f"got {packed.dtype} {tuple(packed.shape)}")
-    packed = packed.contiguous()
+    packed = _packed_words(packed, W, "rle_from_packed")
     n, H, _ = packed.shape
     if n == 0:
         return []
@@ -203,18 +211,15 @@ class Sam(nn.Module):
         # a record with a mask prompt has a dense embedding per prompt: the single-image call, as `predict_torch` makes it
         for r, dn in own_dense.items():
             low[r], iou[r] = self.mask_decoder(embeddings[r:r + 1], pe, sparse[r], dn, multimask_output)
-        # the others: one decoder call per number of sparse embeddings, over the images that have such prompts; a single record
-        # has nothing to share and takes the single-image call (the same bits, less host work: profiles/sam_forward.md)
+        # the others: one decoder call per number of sparse embeddings, over the images that have such prompts (one image alone
+        # is the single-image call inside `forward_images`)
         for ns in sorted({sp.shape[1] for r, sp in enumerate(sparse) if r not in own_dense}):
             members = [r for r, sp in enumerate(sparse) if sp.shape[1] == ns and r not in own_dense]
             counts = [sparse[r].shape[0] for r in members]
-            if len(records) == 1:
-                m, q = self.mask_decoder(embeddings, pe, sparse[0], dense, multimask_output)
-            else:
-                emb = embeddings if len(members) == len(records) else embeddings[torch.as_tensor(members, device=dev)]
-                which = np.repeat(np.arange(len(members)), counts)
-                m, q = self.mask_decoder.forward_images(emb, pe, torch.cat([sparse[r] for r in members]), dense[:1], which,
-                                                        multimask_output)
+            emb = embeddings if len(members) == len(records) else embeddings[torch.as_tensor(members, device=dev)]
+            which = np.repeat(np.arange(len(members)), counts)
+            m, q = self.mask_decoder.forward_images(emb, pe, torch.cat([sparse[r] for r in members]), dense[:1], which,
+                                                    multimask_output)
             for r, mr, qr in zip(members, m.split(counts), q.split(counts)):
                 low[r], iou[r] = mr, qr
         # postprocess_masks once per geometry
@@ -226,6 +231,15 @@ class Sam(nn.Module):
             for r, ur in zip(members, up.split([low[r].shape[0] for r in members])):
                 masks[r] = ur
         return [{"masks": masks[r], "iou_predictions": iou[r], "low_res_logits": low[r]} for r in range(len(records))]
+
+    @torch.no_grad()
+    def decode_prompts(self, features, points, boxes, mask_input, multimask_output):
+        """The prompt encoder and the mask decoder for one image: features [1, 256, 64, 64], points (coords [B, n, 2], labels
+        [B, n]) or None, boxes [B, 4] or None, mask_input [B, 1, 256, 256] or None -> (low_res_masks [B, C, 256, 256],
+        iou_predictions [B, C]).  What `SamPredictor.predict_low_res` and the mask generator both run."""
+        sparse, dense = self.prompt_encoder(points=points, boxes=boxes, masks=mask_input)
+        return self.mask_decoder(image_embeddings=features, image_pe=self.prompt_encoder.get_dense_pe(),
+                                 sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense, multimask_output=multimask_output)
 
     def preprocess(self, x: torch.Tensor) -> torch.Tensor:
         """Normalize pixel values and pad to the square input."""
@@ -348,10 +362,7 @@ class SamPredictor:
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
         points = (point_coords, point_labels) if point_coords is not None else None
-        sparse, dense = self.model.prompt_encoder(points=points, boxes=boxes, masks=mask_input)
-        return self.model.mask_decoder(image_embeddings=self.features, image_pe=self.model.prompt_encoder.get_dense_pe(),
-                                       sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense,
-                                       multimask_output=multimask_output)
+        return self.model.decode_prompts(self.features, points, boxes, mask_input, multimask_output)
 
     @torch.no_grad()
     def predict_torch(self, point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor],
@@ -451,27 +462,28 @@ class SamAutomaticMaskGenerator:
         self.last_low_res = None   # (low_res [M, 256, 256], iou_preds [M]) of the last generate(keep_low_res=True) call
 
     # the decoder call of one point batch: (low_res [P * 3, 256, 256], iou [P * 3])
-    def _decode(self, points, im_size):
+    def _decode(self, features, points, im_size):
         pr = self.predictor
         tp = pr.transform.apply_coords(points, im_size)
         in_points = torch.as_tensor(tp, device=pr.device)
         in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=in_points.device)
-        low, iou = pr.predict_low_res(in_points[:, None, :], in_labels[:, None], multimask_output=True)
+        low, iou = pr.model.decode_prompts(features, (in_points[:, None, :], in_labels[:, None]), None, None, True)
         return low.flatten(0, 1), iou.flatten(0, 1)
 
-    # the point-batch loop of one frame whose features the predictor holds: the filtered per-mask data of `process_low_res`
-    def _decode_frame(self, hw, keep_low_res=False):
+    # the point-batch loop of one frame, from its features [1, 256, 64, 64] and its size in the input frame: the filtered
+    # per-mask data of `process_low_res`
+    def _decode_frame(self, features, input_size, hw, keep_low_res=False):
         H, W = hw
         pr = self.predictor
         points_all = self.point_grids[0] * np.array([[W, H]])
         lows, ious, parts, pts, base = [], [], [], [], 0
         for b in range(0, len(points_all), self.points_per_batch):
             points = points_all[b:b + self.points_per_batch]
-            low, iou = self._decode(points, (H, W))
+            low, iou = self._decode(features, points, (H, W))
             if keep_low_res:
                 lows.append(low)
                 ious.append(iou)
-            d = process_low_res(low, iou, pr.input_size, (H, W), self.pred_iou_thresh, self.stability_score_thresh,
+            d = process_low_res(low, iou, input_size, (H, W), self.pred_iou_thresh, self.stability_score_thresh,
                                 pr.model.mask_threshold, self.stability_score_offset, pr.model.image_encoder.img_size)
             d["index"] = d["index"] + base
             base += low.shape[0]
@@ -489,7 +501,7 @@ class SamAutomaticMaskGenerator:
         H, W = image.shape[:2]
         pr = self.predictor
         pr.set_image(image)
-        data, points = self._decode_frame((H, W), keep_low_res)
+        data, points = self._decode_frame(pr.features, pr.input_size, (H, W), keep_low_res)
         pr.reset_image()
         return self._finish(data, [0, data["index"].numel()], points, (H, W))[0]
 
@@ -509,7 +521,7 @@ class SamAutomaticMaskGenerator:
         H, W = image.shape[:2]
         pr = self.predictor
         pr.set_image(image)
-        data, _ = self._decode_frame((H, W))
+        data, _ = self._decode_frame(pr.features, pr.input_size, (H, W))
         pr.reset_image()
         return self._finish_boxes(data, [0, data["index"].numel()], (H, W))[0]
 
@@ -543,15 +555,12 @@ class SamAutomaticMaskGenerator:
             # the range guard re-ran the whole call on the fp32 MFMA: encode frame by frame, so that a frame's features do not
             # depend on a neighbour's overflow (generate() of that frame alone would not have been re-run)
             features = torch.cat([enc(x[q:q + 1]) for q in range(len(images))])
+        pr.reset_image()   # the batched calls leave the predictor as `generate` does: without an image
         parts, seg, points = [], [0], None
         for q in range(len(images)):
-            pr.reset_image()
-            pr.original_size, pr.input_size = (H, W), tuple(resized.shape[1:3])
-            pr.features, pr.is_image_set = features[q:q + 1], True
-            data, points = self._decode_frame((H, W))
+            data, points = self._decode_frame(features[q:q + 1], tuple(resized.shape[1:3]), (H, W))
             parts.append(data)
             seg.append(seg[-1] + data["index"].numel())
-        pr.reset_image()
         data = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
         return data, seg, points, (H, W)
 
@@ -614,24 +623,11 @@ def select_segments(keep, counts, seg):
     return keep[torch.as_tensor(pos.astype(np.int64)).to(keep.device)].to(torch.int64), new_seg
 
 
-def pack_on_device(masks):
-    """bool [n, H, W] -> int32 words [n, H, ceil(W / 32)] (torch, on the masks' device), pad bits zero."""
-    n, H, W = masks.shape
-    words = sam_amg.row_words(W)
-    bits = F.pad(masks.to(torch.int32), (0, words * 32 - W)).view(n, H, words, 32)
-    shifts = torch.arange(32, device=masks.device, dtype=torch.int32)
-    return (bits << shifts).sum(-1).to(torch.int32)      # distinct bits: the sum is their OR (bit 31 counts as -2^31)
-
-
 def clean_masks_packed(packed, W, min_area):
     """`remove_small_regions` (holes, then islands, 8-connectivity) of a batch of bit-packed masks in one launch
     (`pope_sam_small_regions_u32`, pope_amd/csrc/sam_regions.hip), without a host read: int32 words [n, H, ceil(W / 32)] ->
     (cleaned words, unchanged bool [n], boxes int32 [n, 4] XYXY of the cleaned masks, area int32 [n])."""
-    require_cuda(packed, "clean_masks_packed")
-    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != sam_amg.row_words(W):
-        raise TypeError(f"clean_masks_packed: expected int32 words [n, H, {sam_amg.row_words(W)}] for W = {W}, "
-                        f"got {packed.dtype} {tuple(packed.shape)}")
-    packed = packed.contiguous()
+    packed = _packed_words(packed, W, "clean_masks_packed")
     n, H, _ = packed.shape
     dev = packed.device
     out = torch.empty_like(packed)
@@ -650,41 +646,12 @@ def clean_masks_packed(packed, W, min_area):
     return out, unchanged.to(torch.bool), boxes, area
 
 
-def clean_masks(masks, min_area):
-    """Holes, then islands, below `min_area` removed from bool [n, H, W] (device): (masks, unchanged bool [n])."""
-    packed, unchanged, _, _ = clean_masks_packed(pack_on_device(masks), masks.shape[2], min_area)
-    return unpack_on_device(packed, masks.shape[2]), unchanged
-
-
-def mask_boxes(masks):
-    """`batched_mask_to_box` of bool [n, H, W] on its device: int32 [n, 4]."""
-    n, H, W = masks.shape
-    rows, cols = masks.any(2), masks.any(1)
-    ar_h, ar_w = torch.arange(H, device=masks.device), torch.arange(W, device=masks.device)
-    y1 = (rows * ar_h).max(1).values
-    y0 = (rows * ar_h + H * (~rows)).min(1).values
-    x1 = (cols * ar_w).max(1).values
-    x0 = (cols * ar_w + W * (~cols)).min(1).values
-    empty = (x1 < x0) | (y1 < y0)
-    return (torch.stack([x0, y0, x1, y1], 1) * (~empty)[:, None]).to(torch.int32)
-
-
-def postprocess_small_regions(data, W, min_area, nms_thresh):
-    """automatic_mask_generator.py:325-375 on the device: small holes and islands removed (8-connectivity) from the packed
-    masks by `clean_masks_packed`, changed masks score 0 and unchanged ones 1 in a second NMS on the cleaned masks' boxes, boxes
-    of the changed survivors replaced; only the survivors are unpacked.  Returns (data, masks)."""
-    packed, unchanged, boxes, _ = clean_masks_packed(data["packed"], W, min_area)
-    keep = box_nms(boxes, unchanged.to(torch.float32), nms_thresh)
-    new_boxes = torch.where(unchanged[:, None], data["boxes"], boxes)
-    data = dict(data, boxes=new_boxes)
-    data = {k: v[keep] for k, v in data.items() if k != "packed"}
-    return data, unpack_on_device(packed[keep], W)
-
-
 def postprocess_small_regions_segments(data, seg, W, min_area, nms_thresh):
-    """`postprocess_small_regions` for the concatenated NMS survivors of several frames (frame s = rows seg[s] .. seg[s + 1] - 1):
-    one clean-up launch over all masks, one segmented second NMS, nothing unpacked.  Returns (data of the survivors with the
-    cleaned `packed` words, the cleaned masks' `area` and the boxes of the changed ones replaced; their seg_offsets)."""
+    """automatic_mask_generator.py:325-375 on the device, for the concatenated NMS survivors of one or several frames (frame s =
+    rows seg[s] .. seg[s + 1] - 1): small holes and islands removed (8-connectivity) from the packed masks by one
+    `clean_masks_packed` launch over all of them, then one segmented second NMS on the cleaned masks' boxes in which changed
+    masks score 0 and unchanged ones 1; nothing is unpacked.  Returns (data of the survivors with the cleaned `packed` words,
+    the cleaned masks' `area` and the boxes of the changed ones replaced; their seg_offsets)."""
     packed, unchanged, boxes, area = clean_masks_packed(data["packed"], W, min_area)
     keep, counts = box_nms_segments(boxes, unchanged.to(torch.float32), seg, nms_thresh)
     sel, seg = select_segments(keep, counts, seg)

@@ -6,8 +6,9 @@
  (3) `generate()` of one frame split into encoder / decoder / post-processing (synthetic ViT-B weights, filters off, so the
      whole batch reaches NMS; min_mask_region_area=0).
 With --min-mask-region-area N > 0 additionally, 3 warm-up calls and the median of 10 each:
- (4) the small-region clean-up stage alone (`postprocess_small_regions`: clean-up, second NMS, unpacking of the survivors) on
-     the NMS survivors of `synth.sam_generator_case("frame")`;
+ (4) the small-region clean-up stage alone (`postprocess_small_regions_segments` with one segment: clean-up and second NMS;
+     the survivors stay packed, where the single-frame function these rows timed before also unpacked them) on the NMS
+     survivors of `synth.sam_generator_case("frame")`;
  (5) the same stage on 64 random-blob masks of 480 x 640 (a box-blurred noise field cut at a quantile);
  (6) `generate()` of one 480 x 640 frame with `min_mask_region_area=N` (filters off, as in (3)).
 With --frames Q[,Q..] only the following, as WALL time (host work included, a device synchronisation before the clock starts
@@ -49,6 +50,19 @@ def timed(fn, reps, warmup=3):
     return statistics.median(out), min(out), max(out)
 
 
+def mask_boxes(masks):
+    """`batched_mask_to_box` of bool [n, H, W] in torch on its device: int32 [n, 4] (the reference's path, row (2))."""
+    n, H, W = masks.shape
+    rows, cols = masks.any(2), masks.any(1)
+    ar_h, ar_w = torch.arange(H, device=masks.device), torch.arange(W, device=masks.device)
+    y1 = (rows * ar_h).max(1).values
+    y0 = (rows * ar_h + H * (~rows)).min(1).values
+    x1 = (cols * ar_w).max(1).values
+    x0 = (cols * ar_w + W * (~cols)).min(1).values
+    empty = (x1 < x0) | (y1 < y0)
+    return (torch.stack([x0, y0, x1, y1], 1) * (~empty)[:, None]).to(torch.int32)
+
+
 def reference_tail(low, input_size, hw, thr=0.0, off=1.0):
     masks = F.interpolate(low[:, None], (1024, 1024), mode="bilinear", align_corners=False)
     masks = masks[..., :input_size[0], :input_size[1]]
@@ -57,7 +71,7 @@ def reference_tail(low, input_size, hw, thr=0.0, off=1.0):
     union = (masks > (thr - off)).sum(-1, dtype=torch.int16).sum(-1, dtype=torch.int32)
     stability = inter / union
     m = masks > thr
-    boxes = sg.mask_boxes(m)
+    boxes = mask_boxes(m)
     t = m.permute(0, 2, 1).flatten(1)
     change = (t[:, 1:] ^ t[:, :-1]).nonzero()
     return stability, boxes, change
@@ -85,16 +99,17 @@ def blob_masks(n, H, W, seed=11):
 
 
 def time_cleanup(dev, min_area):
-    """Rows (4) and (5): `postprocess_small_regions` alone, device events around the call."""
+    """Rows (4) and (5): `postprocess_small_regions_segments` alone on one segment, device events around the call."""
     low, iou, input_size, hw = synth.sam_generator_case("frame")
     d = sg.process_low_res(low.to(dev), iou.to(dev), input_size, hw, 0.9, 0.95, 0.0, 1.0)
     keep = sg.box_nms(d["boxes"], d["iou_preds"], 0.35)
     frame = {k: d[k][keep].contiguous() for k in ("index", "boxes", "packed")}
     blobs = torch.as_tensor(sam_amg.pack_masks(blob_masks(64, *hw)).view(np.int32), device=dev)
-    blob = {"index": torch.arange(64, device=dev), "boxes": sg.mask_boxes(sg.unpack_on_device(blobs, hw[1])), "packed": blobs}
+    blob = {"index": torch.arange(64, device=dev), "boxes": mask_boxes(sg.unpack_on_device(blobs, hw[1])), "packed": blobs}
     for name, data in (("(4) clean-up stage, frame survivors", frame), ("(5) clean-up stage, 64 random blobs", blob)):
-        out, masks = sg.postprocess_small_regions(data, hw[1], min_area, 0.35)
-        med, lo, hi = timed(lambda: sg.postprocess_small_regions(data, hw[1], min_area, 0.35), 10, 3)
+        seg = [0, data["index"].numel()]
+        masks = sg.unpack_on_device(sg.postprocess_small_regions_segments(data, seg, hw[1], min_area, 0.35)[0]["packed"], hw[1])
+        med, lo, hi = timed(lambda: sg.postprocess_small_regions_segments(data, seg, hw[1], min_area, 0.35), 10, 3)
         print(f"{name:40s} n = {data['index'].numel():3d} -> {masks.shape[0]:3d} kept, {int(masks.sum())} pixels set   "
               f"median {med:.3f} ms  min {lo:.3f}  max {hi:.3f}")
 
@@ -191,7 +206,7 @@ def time_frames(dev, qs, sequential_only, H=480, W=640, min_area=250):
         gen.predictor.set_image(frames[0])
         pr = gen.predictor
         points = gen.point_grids[0] * np.array([[W, H]])
-        low, iou = gen._decode(points, (H, W))
+        low, iou = gen._decode(pr.features, points, (H, W))
         d = sg.process_low_res(low, iou, pr.input_size, (H, W), 0.0, 0.0, 0.0, 1.0)
         data = {k: d[k] for k in ("index", "iou_preds", "stability_score", "boxes", "area", "packed")}
         pts = np.repeat(points, 3, axis=0)
@@ -211,13 +226,13 @@ def time_generate(dev, H, W, min_area):
     pr = gen.predictor
     points = gen.point_grids[0] * np.array([[W, H]])
     pr.set_image(frame)
-    lo, io = gen._decode(points, (H, W))
+    lo, io = gen._decode(pr.features, points, (H, W))
     q = torch.quantile(io, torch.tensor([0.0, 0.25, 0.5, 0.75, 1.0], device=dev)).cpu().numpy().round(3)
     d = sg.process_low_res(lo, io, pr.input_size, hw, 0.0, 0.0)
     sq = np.nanquantile(d["stability_score"].cpu().numpy(), [0, 0.25, 0.5, 0.75, 1]).round(3)
     print(f"synthetic ViT-B: iou_preds quantiles {q.tolist()}, stability quantiles {sq.tolist()}")
     e = timed(lambda: pr.set_image(frame), 5, 1)
-    c = timed(lambda: gen._decode(points, (H, W)), 5, 1)
+    c = timed(lambda: gen._decode(pr.features, points, (H, W)), 5, 1)
 
     def post():
         d = sg.process_low_res(lo, io, pr.input_size, hw, 0.0, 0.0)

@@ -103,6 +103,48 @@ def test_images_entry_rejects_a_bad_map_and_a_per_prompt_dense(models, images):
         md.forward_images(images, pe.get_dense_pe(), sparse, dense.expand(4, -1, -1, -1).contiguous(), [0, 1, 2, 3], True)
 
 
+def test_both_entries_reject_the_same_inputs(models, images):
+    """Inputs that are bad for both entries raise the same exception with the same message from either; nothing is launched."""
+    pe, md = models
+    image_pe = pe.get_dense_pe()
+    sparse, dense = sparse_prompts(pe, 2, 3, seed=3)
+    two, which = images[:2], [0, 1, 1]
+    good = dict(image_pe=image_pe, sparse=sparse, dense=dense)
+    table = {"a float64 image_pe": dict(image_pe=image_pe.double()),
+             "sparse [3, 2, 128]": dict(sparse=sparse[:, :, :128].contiguous()),
+             "12 sparse embeddings": dict(sparse=sparse.repeat(1, 6, 1)),
+             "a float16 dense": dict(dense=dense.half())}
+    for what, bad in table.items():
+        a = dict(good, **bad)
+        with pytest.raises((TypeError, ValueError)) as one:
+            md(two[:1], a["image_pe"], a["sparse"], a["dense"], True)
+        with pytest.raises((TypeError, ValueError)) as many:
+            md.forward_images(two, a["image_pe"], a["sparse"], a["dense"], which, True)
+        print(f"{what}: {one.type.__name__}: {one.value}")
+        assert one.type is many.type and str(one.value) == str(many.value), what
+
+
+def test_one_workspace_serves_both_entries(models, images):
+    """The multi-image call's workspace serves the single-image call after it: the buffer is not reallocated, and both
+    results are those of a module that has run nothing else."""
+    pe, _ = models
+    image_pe = pe.get_dense_pe()
+    sparse, dense = sparse_prompts(pe, 2, 3, seed=3)
+    two, which = images[:2], [0, 1, 1]
+
+    def fresh():
+        return build_models(synth.synthetic_sam_decoder_state_dict(seed=0))[1].to(DEV)
+    md = fresh()
+    got_images = md.forward_images(two, image_pe, sparse, dense, which, True)
+    buf = md._ws.data_ptr()
+    got_one = md(two[:1], image_pe, sparse[:1], dense[:1], True)
+    assert md._ws.data_ptr() == buf
+    want_one = fresh()(two[:1], image_pe, sparse[:1], dense[:1], True)
+    want_images = fresh().forward_images(two, image_pe, sparse, dense, which, True)
+    for got, want in ((got_images, want_images), (got_one, want_one)):
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
 # ---- (b) the range guard: one image's overflow stays that image's ----------------------------------------------------------------
 def test_range_guard_is_per_image(models, images):
     pe, md = models

@@ -119,16 +119,18 @@ def test_small_regions_on_the_device_equal_the_cpu(golden_dir, name):
     show(case=name, survivors=len(masks), changed=int((~want_same).sum()))
     assert (~want_same).any()                        # the synthetic masks do carry small islands / holes
     packed = torch.as_tensor(fx["packed"].view(np.int32), device=DEV)
-    got, got_same = sg.clean_masks(sg.unpack_on_device(packed, W), 250)
-    assert np.array_equal(got.cpu().numpy(), want) and np.array_equal(got_same.cpu().numpy(), want_same)
-    assert np.array_equal(sg.mask_boxes(got).cpu().numpy(), sam_amg.mask_to_box(want))
+    got, got_same, got_boxes, _ = sg.clean_masks_packed(packed, W, 250)
+    assert np.array_equal(sg.unpack_on_device(got, W).cpu().numpy(), want) and np.array_equal(got_same.cpu().numpy(), want_same)
+    assert np.array_equal(got_boxes.cpu().numpy(), sam_amg.mask_to_box(want))
     # the whole second stage: NMS with changed masks scored 0, boxes of the changed survivors recomputed
     pos = {int(m): i for i, m in enumerate(fx["keep_iou"])}
     boxes = fx["boxes"][[pos[int(m)] for m in fx["keep_nms"]]]
     data = {"boxes": torch.as_tensor(boxes, device=DEV), "packed": packed, "index": torch.as_tensor(fx["keep_nms"], device=DEV)}
-    out, out_masks = sg.postprocess_small_regions(data, W, 250, NMS)
+    out, out_seg = sg.postprocess_small_regions_segments(data, [0, len(masks)], W, 250, NMS)
+    out_masks = sg.unpack_on_device(out["packed"], W)
     keep = sam_amg.nms(sam_amg.mask_to_box(want), want_same.astype(np.float32), NMS)
     want_boxes = np.where(want_same[:, None], boxes, sam_amg.mask_to_box(want))[keep]
+    assert out_seg.tolist() == [0, len(keep)]
     assert np.array_equal(out["index"].cpu().numpy(), fx["keep_nms"][keep])
     assert np.array_equal(out["boxes"].cpu().numpy(), want_boxes) and np.array_equal(out_masks.cpu().numpy(), want[keep])
 

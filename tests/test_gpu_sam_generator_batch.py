@@ -112,6 +112,15 @@ def test_batch_of_one_frame(runs, sam, frames, mode):
     assert_same_records(got[0], single[1], mode)
 
 
+def test_batched_calls_leave_the_predictor_reset(runs, sam, frames):
+    """The batched front end takes each frame's features as an argument: the predictor holds no image afterwards, and a
+    `generate` after it is that of a generator which ran nothing before."""
+    gen = sg.SamAutomaticMaskGenerator(sam, **E2E)
+    gen.propose_batch(frames[:1])
+    assert gen.predictor.is_image_set is False and gen.predictor.features is None
+    assert_same_records(gen.generate(frames[0]), runs["binary_mask"][0][0], "binary_mask")
+
+
 def test_rle_from_packed_equals_the_cpu_definition(runs):
     single, _ = runs["binary_mask"]
     masks = np.stack([r["segmentation"] for recs in single for r in recs])

@@ -288,8 +288,8 @@ def test_in_place_and_empty_batch():
                                           _lib.ptr(ws), ws.numel() - 1, None) == -3
     e = sg.clean_masks_packed(packed[:0], 640, 250)
     assert [tuple(t.shape) for t in e] == [(0, 480, 20), (0,), (0, 4), (0,)]
-    m, s = sg.clean_masks(torch.zeros(0, 480, 640, dtype=torch.bool, device=DEV), 250)
-    assert tuple(m.shape) == (0, 480, 640) and tuple(s.shape) == (0,)
+    m, s, _, _ = sg.clean_masks_packed(torch.zeros(0, 480, 20, dtype=torch.int32, device=DEV), 640, 250)
+    assert tuple(sg.unpack_on_device(m, 640).shape) == (0, 480, 640) and tuple(s.shape) == (0,)
 
 
 # ---- the generator's own survivors ---------------------------------------------------------------------------------------

@@ -14,8 +14,7 @@ def test_symbols_are_bound(hip_lib):
         assert name in _lib.PROTOTYPES and hasattr(hip_lib, name)
     assert hip_lib.pope_abi_version() == 9                      # an additive change
     assert list(inspect.signature(sg.clean_masks_packed).parameters) == ["packed", "W", "min_area"]
-    assert list(inspect.signature(sg.clean_masks).parameters) == ["masks", "min_area"]
-    assert list(inspect.signature(sg.postprocess_small_regions).parameters) == ["data", "W", "min_area", "nms_thresh"]
+    assert list(inspect.signature(sg.postprocess_small_regions_segments).parameters) == ["data", "seg", "W", "min_area", "nms_thresh"]
 
 
 def test_workspace_query(hip_lib):
