@@ -48,7 +48,11 @@ enum {
      * hidden+32t .. hidden+32t+31 (values).  N % 64 == 0.  silu(x) = x / (1 + exp(-x)) in fp32 (exp as exp2 of the pre-scaled
      * argument), finite for every finite gate.  pope_linear_planes_f32 (planes or fp32 out, range bit POPE_RANGE_GELU: it marks the
      * FC1 producer) and pope_linear_prec_f32 with POPE_PREC_F32_MFMA take it; gamma and res are ignored. */
-    POPE_EPI_BIAS_SWIGLU = 11
+    POPE_EPI_BIAS_SWIGLU = 11,
+    /* pope_linear_f16 only — the QKV projection of the POPE_PREC_F16 ViT blocks, whose output is the operand of
+     * pope_attention_f16: C = (A.W^T + bias) * (col < N/3 ? 0.125 * log2 e : 1), rounded ONCE to f16 rows with no activation
+     * scale (heads of 64: q carries head_dim^-0.5 * log2 e).  N % 192 == 0; range bit POPE_RANGE_QKV, checked after the scale. */
+    POPE_EPI_QKV_F16 = 8
 };
 
 /* Arithmetic of the contractions.  Both take and return fp32 and accumulate in fp32:
@@ -130,6 +134,19 @@ int pope_layernorm_f16(const float* x, const float* weight, const float* bias, v
                        unsigned* range_flag, void* stream);
 /* y_f16[i] = f16(x[i] * POPE_PLANES_ACT_SCALE), i < n; n % 4 == 0, x 16-byte and y_f16 8-byte aligned (POPE_RANGE_INPUT). */
 int pope_to_f16(const float* x, void* y_f16, long long n, unsigned* range_flag, void* stream);
+/* Test entry of the POPE_PREC_F16 Linears (single-product f16 MFMAs, fp32 accumulate): one call of the router that
+ * pope_vit_forward_f32 and the SAM encoder use, which picks the 256-row LDS-direct mainloop from M >= 2048 (N >= 256) and the
+ * 128 x 128 tile kernel below — bit-identical.  a_f16 [M,K] f16 = value * POPE_PLANES_ACT_SCALE, w_f16 [N,K] f16 = value *
+ * POPE_PLANES_W_SCALE; M, N, K in real columns.  epilogue and output (the other output pointer NULL):
+ *     POPE_EPI_BIAS          -> C [M,N] fp32
+ *     POPE_EPI_BIAS_GELU     -> c_f16 [M,N] f16 = value * POPE_PLANES_ACT_SCALE        (POPE_RANGE_GELU)
+ *     POPE_EPI_QKV_F16       -> c_f16 [M,N] f16, no scale; N % 192 == 0                (POPE_RANGE_QKV)
+ *     POPE_EPI_BIAS_LS_RES   -> C [M,N] fp32 = res + gamma * (A.W^T + bias): res [M,N] (may alias C) with gamma, or with
+ *                               res_mod > 0 residual row = res[row % res_mod] of a [res_mod,N] table (gamma may be NULL: one)
+ * bias may be NULL.  K % 64 == 0, K >= 128; N % 4 == 0 (fp32 out) or N % 64 == 0 (f16 out); M >= 1.  A call outside this
+ * returns POPE_ERR_ARG before any HIP call. */
+int pope_linear_f16(const void* a_f16, const void* w_f16, const float* bias, float* C, void* c_f16, int M, int N, int K,
+                    int epilogue, const float* gamma, const float* res, int res_mod, unsigned* range_flag, void* stream);
 /* The matcher's feature planes: n blocks of [rows, cols] fp32, batch_stride floats apart (even, >= rows * cols), to compact
  * planes [n * rows, cols] of (src / divisor) * scale — the division first, in fp32, as coarse_matching.py:109 rounds it; scale a
  * power of two.  cols % 32 == 0 (POPE_RANGE_MATCH). */

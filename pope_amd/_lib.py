@@ -77,6 +77,7 @@ PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
 PRECISIONS = {"f32": PREC_F32_MFMA, "f16x3": PREC_F16X3, "f16": PREC_F16}
 FFN_KINDS = {"mlp": 0, "swiglu": 1}    # POPE_FFN_*
 EPI_BIAS_SWIGLU = 11                   # POPE_EPI_BIAS_SWIGLU
+EPI_QKV_F16 = 8                        # POPE_EPI_QKV_F16 (pope_linear_f16 only)
 c_uint_p = C.POINTER(C.c_uint)
 F16_MAX = 65504.0
 # bits of an f16x3 range-guard word (pope_hip.h POPE_RANGE_*)
@@ -97,6 +98,7 @@ PROTOTYPES = {
     "pope_layernorm_rowln_order_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "pope_layernorm_f16": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "pope_to_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "pope_linear_f16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_div_planes_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                       C.c_void_p, C.c_void_p]),
     "pope_patch_embed_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),

@@ -128,6 +128,23 @@ int pope_to_f16(const float* x, void* y_f16, long long n, unsigned* range_flag, 
     return pope_launch_to_f16(x, y_f16, n / 4, range_flag, static_cast<hipStream_t>(stream));
 }
 
+// a Linear of the plain-f16 GEMM family through the router the models use (vit_forward.hip's `linear` with LINEAR_PLAIN, sam.hip);
+// checked before the stream's device is touched
+int pope_linear_f16(const void* a_f16, const void* w_f16, const float* bias, float* C, void* c_f16, int M, int N, int K, int epilogue,
+                    const float* gamma, const float* res, int res_mod, unsigned* range_flag, void* stream) {
+    static_assert(int(POPE_EPI_QKV_F16) == int(EPI_QKV_F16), "the public value is the router's");
+    const bool out_f16 = epilogue == POPE_EPI_BIAS_GELU || epilogue == POPE_EPI_QKV_F16;
+    if (!out_f16 && epilogue != POPE_EPI_BIAS && epilogue != POPE_EPI_BIAS_LS_RES) return POPE_ERR_ARG;
+    if (!a_f16 || !w_f16 || (out_f16 ? !c_f16 || C : !C || c_f16)) return POPE_ERR_ARG;
+    if (M <= 0 || N <= 0 || K < 128 || (K & 63) || (N & (out_f16 ? 63 : 3))) return POPE_ERR_ARG;
+    if (epilogue == POPE_EPI_QKV_F16 && N % 192) return POPE_ERR_ARG;
+    if (epilogue == POPE_EPI_BIAS_LS_RES && (!res || (!gamma && res_mod <= 0))) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    GemmParams g = pope_linear_params(LINEAR_PLAIN, a_f16, w_f16, bias, C, c_f16, M, N, K, epilogue, gamma, res, res_mod, range_flag);
+    if (epilogue == EPI_QKV_F16) { g.sam_dim = N / 3; g.sam_qscale = 0.125f * 1.44269504088896340736f; }   // vit_forward.hip's QKV launch
+    return pope_launch_gemm_planes(g, static_cast<hipStream_t>(stream));
+}
+
 int pope_div_planes_f32(const float* src, long long batch_stride, void* planes, int n, int rows, int cols, float divisor, float scale,
                         unsigned* range_flag, void* stream) {
     if (!src || !planes || n <= 0 || rows <= 0 || cols <= 0 || (cols & 31) || (batch_stride & 1) ||

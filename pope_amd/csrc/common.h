@@ -184,6 +184,10 @@ __device__ __forceinline__ void pope_amax4x2(f32x2& m, f32x4 v) {
     m[0] = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), m[0]);
     m[1] = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])), m[1]);
 }
+// fmax drops a NaN.  The plain-f16 GEMM epilogues keep, beside the maxima, a running sum of the values they convert: it is NaN
+// from the first NaN on (or after inf - inf, which the maximum has caught; values below POPE_F16_OVERFLOW cannot sum to inf)
+__device__ __forceinline__ void pope_nan_sum4(f32x2& s, f32x4 v) { s += f32x2{v[0], v[1]} + f32x2{v[2], v[3]}; }   // two packed adds
+__device__ __forceinline__ bool pope_nan_seen(f32x2 s) { return !(s[0] + s[1] == s[0] + s[1]); }
 __device__ __forceinline__ float pope_amax2(float m, f32x2 v) {
     return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), m);
 }

@@ -281,6 +281,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
     __syncthreads();   // all waves have finished reading the last stage: the LDS is the epilogue's now
     float* E = smem + wave * 32 * EPI_ST;
     f32x2 amax = {0.f, 0.f};
+    [[maybe_unused]] f32x2 nsum = {0.f, 0.f};   // plain f16 outputs: NaN catch of the same values (pope_nan_sum4)
 #pragma unroll
     for (int s = 0; s < SUB; ++s) {
         const int m_base = m0 + wm * 64 * SUB + s * 64;
@@ -349,6 +350,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                 } else if constexpr (EPI == EPI_SAM_QKV) {
                     v = (v * inv + bias) * sq_scale;
                     pope_amax4x2(amax, v);
+                    if constexpr (!X3) pope_nan_sum4(nsum, v);
                     const unsigned o = col_ok && row0 + 4 * i < unsigned(g.M) ? (sq_dest[i] * unsigned(sq_row_h) + unsigned(sq_c)) * 2u : DROP;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, __builtin_convertvector(v, f16x4)), rsq, o, 0, 0);
                 } else if constexpr (EPI == EPI_CONV) {
@@ -369,6 +371,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                 } else if constexpr (EPI == EPI_QKV_F16) {   // attention operands: f16 row-major, no activation scale (gemm_planes.hip)
                     v = (v * inv + bias) * qkv_scale;
                     pope_amax4x2(amax, v);
+                    pope_nan_sum4(nsum, v);
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, __builtin_convertvector(v, f16x4)), rc,
                                                           col_ok ? off + unsigned(col) * 2u : DROP, 0, 0);
                 } else if constexpr (EPI == EPI_BIAS_GELU) {
@@ -379,6 +382,7 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
                         store_planes(v);
                     } else if constexpr (OUT_F16) {   // f16 row-major, value * 8
                         pope_amax4x2(amax, v);
+                        pope_nan_sum4(nsum, v);
                         const f16x4 hh = __builtin_convertvector(v * PL_A_SCALE, f16x4);
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hh), rc, col_ok ? off + unsigned(col) * 2u : DROP, 0, 2);
                     } else {
@@ -394,9 +398,9 @@ __global__ __launch_bounds__(PL_THREADS) void gemm_plain256_kernel(const GemmPar
         }
     }
     if constexpr (EPI == EPI_SAM_QKV || EPI == EPI_QKV_F16)   // attention operands carry no scale
-        pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW));
+        pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW) || (!X3 && pope_nan_seen(nsum)));
     else if constexpr (OUT_F16)
-        pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) * PL_A_SCALE < POPE_F16_OVERFLOW));
+        pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) * PL_A_SCALE < POPE_F16_OVERFLOW) || (!X3 && pope_nan_seen(nsum)));
 }
 
 // one workgroup per 256-row x (64 NWN)-column tile

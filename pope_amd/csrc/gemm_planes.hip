@@ -387,6 +387,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
         float* E = epi + wave * 32 * EPI_ST;
         f32x2 amax = {0.f, 0.f};  // OUT_PLANES: largest magnitude written as planes (range guard; rows >= M hold finite
                                   // junk computed from zero-filled operands: bias / gelu(bias), as real rows see)
+        [[maybe_unused]] f32x2 nsum = {0.f, 0.f};   // PLAIN: NaN catch of the same values (pope_nan_sum4)
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh) {
             stage_half(E, mh);
@@ -467,6 +468,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 } else if constexpr (EPI == EPI_SAM_QKV) {
                     v = (v * inv + bias) * sq_scale;
                     pope_amax4x2(amax, v);
+                    if constexpr (PLAIN) pope_nan_sum4(nsum, v);
                     const bool live = col_ok && row0 + 4 * i < unsigned(g.M);
                     const unsigned o = live ? (sq_dest[i] * unsigned(sq_row_h) + unsigned(sq_c)) * 2u : DROP;
                     if constexpr (PLAIN) {
@@ -483,6 +485,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 } else if constexpr (EPI == EPI_QKV_F16) {   // attention operands: f16 row-major, no activation scale
                     v = (v * inv + bias) * qkv_scale;
                     pope_amax4x2(amax, v);
+                    pope_nan_sum4(nsum, v);
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, __builtin_convertvector(v, f16x4)), rc,
                                                           col_ok ? off + unsigned(col) * 2u : DROP, 0, 0);
                     continue;
@@ -503,6 +506,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 }
                 if constexpr (OUT_PLANES && PLAIN) {   // f16 row-major, value * 8
                     pope_amax4x2(amax, v);
+                    pope_nan_sum4(nsum, v);
                     const f16x4 h = __builtin_convertvector(v * A_SCALE, f16x4);
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), rc, col_ok ? off + unsigned(col) * 2u : DROP, 0, 2);
                 } else if constexpr (OUT_PLANES) {
@@ -552,10 +556,12 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
             }
             __builtin_amdgcn_wave_barrier();
         }
+        // (the f16x3 planes forms report magnitudes only: a NaN there passes the maxima)
         if constexpr (EPI == EPI_SAM_QKV || EPI == EPI_QKV_F16)   // attention operands carry no scale
-            pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW));
+            pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) < POPE_F16_OVERFLOW) || (PLAIN && pope_nan_seen(nsum)));
         else if constexpr (OUT_PLANES)
-            pope_range_flag(g.range_flag, g.range_bit, !(__builtin_fmaxf(amax[0], amax[1]) * A_SCALE < POPE_F16_OVERFLOW));
+            pope_range_flag(g.range_flag, g.range_bit,
+                            !(__builtin_fmaxf(amax[0], amax[1]) * A_SCALE < POPE_F16_OVERFLOW) || (PLAIN && pope_nan_seen(nsum)));
         __syncthreads();  // epilogue staging is drained before the stage is written again
     };
 
