@@ -14,8 +14,9 @@
 // K-step waited on, DESIGN.md finding 20), into unpadded rows whose 16-byte chunk index is XOR-ed with row & 7 on the source
 // side: conflict-free 16-row fragment reads; two stages of 64 / 72 KB, ONE barrier per K-step (LDS-scope fence only: a full
 // __syncthreads() would also wait for the epilogue's global stores).  The K-steps of consecutive tiles form one stream: the
-// first K-step of the next tile lands during the epilogue.  With no staging registers the kernel needs 150 - 220 VGPRs instead
-// of 256 with zero slack: every per-lane loop invariant is re-derived per K-step behind an opaque fence so that the allocator
+// first K-step of the next tile lands during the epilogue.  Waves 4 - 7 run the K loop RL_LAG column blocks behind waves 0 - 3,
+// their SIMD partners (see the K-step).  With no staging registers the kernel needs 171 - 178 (128-row tiles) and
+// 235 - 242 (192-row tiles) VGPRs instead of 256 with zero slack: every per-lane loop invariant is re-derived per K-step behind an opaque fence so that the allocator
 // has nothing to spill across the epilogue (a spill reload in the K loop waits for vmcnt(0), i.e. for the loads just issued).
 // Measured (same box, profiles/r04/rowln_dma_ab.txt): FC2+LN 0.400 -> 0.364 ms, proj+LN 0.159 -> 0.150, patch embed 0.288 -> 0.268.
 //
@@ -24,6 +25,8 @@
 // and a 4 KB LDS table across the four column waves; mean first, then the centred second moment (the two-pass form of
 // the stand-alone kernel: no E[x^2] - mean^2 cancellation); x and xn are stored with no load between the stores.
 // Reduction orders depend on the column only: batch invariance and run-to-run determinism are kept.
+#include <type_traits>
+
 #include "gemm_core.h"
 #include "gemm_routes.h"
 
@@ -75,15 +78,29 @@ __device__ __forceinline__ float quad_sum(float v) {
     return a + b;
 }
 
-#ifdef RL_STAMPS  // dev: wall-clock stamps (10 ns ticks) of block 0, per kind of launch (K = 384 / 1536 / other), scripts/rowln_stamps.py
-__device__ unsigned long long g_rl_dbg[3][64];
-#define RL_STAMP(slot)                                                                                             \
+// Wave lag of the K loop, in column blocks (0 .. 3): waves 4 - 7 run this far behind their SIMD partners (see the K-step below).
+// A build constant so that lab libraries can be built for every value (scripts/rowln_ab.sh NAME "-DRL_LAG=n").
+#ifndef RL_LAG
+#define RL_LAG 3
+#endif
+// 1: a late wave issues its staging pieces behind its deferred MFMAs (they are the first instructions behind the barrier);
+// 0 (lab): in front of them, where the in-phase waves issue theirs — measured slower than no lag at all
+#ifndef RL_LAG_STAGE_BEHIND
+#define RL_LAG_STAGE_BEHIND 1
+#endif
+
+#ifdef RL_STAMPS  // dev: wall-clock stamps (10 ns ticks) of block 0, waves 0 and 4, per kind of launch (K = 384 / 1536 / other), scripts/rowln_stamps.py
+__device__ unsigned long long g_rl_dbg[2][3][64];   // [wave 0, wave 4][kind][8 slots per tile]
+#define RL_STAMP_IF(cond, slot)                                                                                    \
     do {                                                                                                           \
-        if (LN && blockIdx.x == 0 && threadIdx.x == 0 && rl_si + (slot) < 64)   /* the LayerNorm modes only */     \
-            g_rl_dbg[g.K == 384 ? 0 : (g.K == 1536 ? 1 : 2)][rl_si + (slot)] = wall_clock64();                     \
+        if (LN && blockIdx.x == 0 && (threadIdx.x & 255) == 0 && (cond) && rl_si + (slot) < 64)   /* the LayerNorm modes only */ \
+            g_rl_dbg[threadIdx.x >> 8][g.K == 384 ? 0 : (g.K == 1536 ? 1 : 2)][rl_si + (slot)] = wall_clock64();   \
     } while (0)
+#define RL_STAMP(slot) RL_STAMP_IF(true, slot)
+#define RL_STAMP_K(slot) RL_STAMP_IF(kt == 1, slot)   // inside the tile's second K-step: 6 = barrier released, 7 = first MFMA issued
 #else
 #define RL_STAMP(slot) do {} while (0)
+#define RL_STAMP_K(slot) do {} while (0)
 #endif
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a full workgroup-scope fence: the compiler puts
@@ -430,32 +447,77 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
     int tile = first, kt = 0, ord = 0, next_tile = tile_of(1);
     RL_STAMP(0);
 
-    for (int s = 0; tile < n_tiles; ++s) {
-        // This wave's pieces of stage s have landed.  After a tile seam of the LayerNorm modes nothing is waited for: the step's
-        // loads were issued before the epilogue, whose residual loads — issued by every lane of every wave, younger, and
-        // returning in order — have been consumed since; waiting here would wait for the acknowledgement of the epilogue's last
-        // stores.  The planes modes (RL_BIAS_PLANES / RL_GELU_PLANES) load nothing in their epilogue unless there is a bias, so
-        // they wait at every K-step.
-        if (!LN || kt != 0 || ord == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
-        rl_barrier();   // ... and everyone's; every wave has left the other stage (K-step s - 1, or the epilogue's buffers)
+    // ---- the K-step of one wave.  ni-major: the A fragments (hi, lo: 8 x 4 registers) stay for the K-step, the W fragments
+    // stream through two at a time (lo, hi of column block ni), each feeding 12 MFMAs.  Per accumulator the order of the
+    // partial products is that of gemm_planes.hip (lo.hi, hi.lo, hi.hi): bit-identical sums.
+    //
+    // WAVE LAG (RL_LAG = 1 .. 3 column blocks; 0: every wave runs the in-phase body).  The two waves of a SIMD (w and w + 4) run
+    // the same program between the same barriers: in phase, both issue their 9 staging pieces and their 14 fragment reads right
+    // behind the barrier and neither has an MFMA ready, then both compete for the matrix pipe.  So waves 4 - 7 run LAG column
+    // blocks late: in a K-step they issue the MFMAs of blocks 0 .. 5 - LAG only, read the W fragments of the last LAG blocks
+    // into registers (dwl / dwh; the A fragments stay in ah / al anyway) and go to the barrier; behind it their first
+    // instructions are those 18 LAG MFMAs, from registers, under which waves 0 - 3 issue their pieces and wait for their first
+    // fragments; the late waves' own pieces and reads of the new stage then fall under the partners' MFMAs.  At the end of a tile
+    // the deferred blocks are issued behind the tile-end barrier, before the epilogue: the lag restarts with every tile.
+    // The staging pieces of a late wave go BEHIND its deferred MFMAs (RL_LAG_STAGE_BEHIND): in front of them, where the in-phase
+    // waves issue theirs, both partners sit in the same 9-piece issue bubble again and the lag buys nothing (every LAG 0.8 - 1 %
+    // SLOWER than no lag there).  Measured, same box, alternating fresh processes, five runs each (profiles/gemm_wave_lag.md):
+    // LAG = 3 takes FC2+LN 0.349 -> 0.330 ms, QKV 0.268 -> 0.258, proj+LN 0.154 -> 0.149, patch embed 0.274 -> 0.272, the step
+    // 1 439 -> 1 463 pairs/s (+1.7 %; +1.3 ... +2.5 % over four boxes); wave 4's first MFMA comes 0.2 - 0.3 us behind the barrier
+    // instead of 1.3 - 1.7.
+    //  - Stage safety: a late wave's last reads of stage s & 1 (the deferred W fragments) are issued under its last column
+    //    block and no MFMA consumes them before the next barrier, so the top of the K-step waits for lgkmcnt(0) explicitly in
+    //    front of the barrier (below); what crosses the barrier is registers whose reads have returned.
+    //  - Barriers: every rl_barrier() stands in code that all eight waves run (top of the K-step, tile end, the two of the
+    //    LayerNorm epilogue); the role bodies and the flush contain none, and the trip counts (tile, kt, nk) are
+    //    workgroup-uniform, so both roles execute the same barrier sequence.
+    //  - Arithmetic: per accumulator nothing changes — block ni of K-step s is still issued before block ni of K-step s + 1,
+    //    in the same lo.hi, hi.lo, hi.hi order: results are bit-identical for every LAG.
+    //  - Finding 13: the role is chosen once per K-step by a scalar branch (wave is readfirstlane'd) between straight-line
+    //    bodies: in phase, late at kt == 0 (nothing pending), late at kt > 0.
+    constexpr int LAG = RL_LAG;
+    static_assert(LAG >= 0 && LAG <= 3 && G::NW == 8, "waves 4 - 7 are the SIMD partners of waves 0 - 3");
+    [[maybe_unused]] const bool late = LAG > 0 && wave >= 4;
+    enum { ROLE_IN_PHASE = 0, ROLE_LATE_FIRST = 1, ROLE_LATE = 2 };
+    f16x8 ah[NMI], al[NMI];                                               // (carried into the next K-step by the late waves)
+    [[maybe_unused]] f16x8 dwl[LAG > 0 ? LAG : 1], dwh[LAG > 0 ? LAG : 1];   // W fragments of the deferred column blocks
+    auto mfma_block = [&](int ni, const f16x8& l, const f16x8& h, [[maybe_unused]] bool first_of_step) {
+#pragma unroll
+        for (int mi = 0; mi < NMI; ++mi) {
+            acc[mi][ni] = mfma16(l, ah[mi], acc[mi][ni]);
+            if (first_of_step && mi == 0) RL_STAMP_K(7);
+        }
+#pragma unroll
+        for (int mi = 0; mi < NMI; ++mi) acc[mi][ni] = mfma16(h, al[mi], acc[mi][ni]);
+#pragma unroll
+        for (int mi = 0; mi < NMI; ++mi) acc[mi][ni] = mfma16(h, ah[mi], acc[mi][ni]);
+    };
+    [[maybe_unused]] auto deferred_blocks = [&]() {
+#pragma unroll
+        for (int j = 0; j < LAG; ++j) mfma_block(6 - LAG + j, dwl[j], dwh[j], j == 0);
+    };
+    auto kstep = [&](auto role_c, int s_, const _Float16* S) {
+        constexpr int ROLE = decltype(role_c)::value;
+        constexpr int NOW = ROLE == ROLE_IN_PHASE ? 6 : 6 - LAG;   // column blocks whose MFMAs are issued in their own K-step
         const bool seam = kt + 1 == nk;
-        dma((s + 1) & 1, seam ? next_tile : tile, seam ? 0 : kt + 1);
-        const _Float16* S = lds + (s & 1) * STAGE_H;
+        if constexpr (ROLE == ROLE_LATE && RL_LAG_STAGE_BEHIND) {
+            deferred_blocks();   // ... of the previous K-step: ah / al, dwl / dwh still hold it
+            __builtin_amdgcn_sched_barrier(0);   // (nothing orders a staging load behind an MFMA otherwise)
+        }
+        dma((s_ + 1) & 1, seam ? next_tile : tile, seam ? 0 : kt + 1);
+        if constexpr (ROLE == ROLE_LATE && !RL_LAG_STAGE_BEHIND) deferred_blocks();
         // fragment t: rows 16 t + l15 of this wave's rows, logical chunk plane * 4 + q4
         int fl_ = pope_lane_id();
         asm volatile("" : "+v"(fl_));
         const int fl15 = fl_ & 15, fq4 = fl_ >> 4;
         const int sw_hi = 8 * (fq4 ^ (fl15 & 7)), sw_lo = 8 * ((4 + fq4) ^ (fl15 & 7));
         const int a_row = (wm * WMR + fl15) * ROWB, w_row = (RM + wn * 96 + fl15) * ROWB;
-        // ni-major: the A fragments (hi, lo: 8 x 4 registers) stay for the K-step, the W fragments stream through two at
-        // a time (lo, hi of column block ni), each feeding 12 MFMAs.  Per accumulator the order of the partial
-        // products is that of gemm_planes.hip (lo.hi, hi.lo, hi.hi): bit-identical sums.
         // Program order is pinned with scheduling fences: the scheduler otherwise hoists all 20 fragment reads to the
         // top of the K-step (80 live registers).
-        f16x8 ah[NMI], al[NMI], wl[2], wh[2];
+        f16x8 wl[2], wh[2];
         // issue order = order of first use (the LDS returns in order): the first MFMA (wl[0] . ah[0]) waits for two reads, every
-        // further one of the first column block for one more — not for the whole 2 NMI + 2 (the waves of the workgroup all read at
-        // this point: 14 reads x 8 waves are 900 cycles of the LDS array)
+        // further one of the first column block for one more — not for the whole 2 NMI + 2 (the in-phase waves of the workgroup
+        // all read at this point: 14 reads x 4 waves are 450 cycles of the LDS array; the late waves follow LAG blocks later)
         wl[0] = *reinterpret_cast<const f16x8*>(S + w_row + sw_lo);
 #pragma unroll
         for (int t = 0; t < NMI; ++t) ah[t] = *reinterpret_cast<const f16x8*>(S + a_row + t * 16 * ROWB + sw_hi);
@@ -464,24 +526,65 @@ __global__ __launch_bounds__(G::RTH) void gemm_rowln16_kernel(const GemmParams g
         for (int t = 0; t < NMI; ++t) al[t] = *reinterpret_cast<const f16x8*>(S + a_row + t * 16 * ROWB + sw_lo);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ni = 0; ni < 6; ++ni) {
+        for (int ni = 0; ni < NOW; ++ni) {
             const int cur = ni & 1, nxt = cur ^ 1;
-            if (ni + 1 < 6) {
+            if (ni + 1 < NOW) {
                 wl[nxt] = *reinterpret_cast<const f16x8*>(S + w_row + (ni + 1) * 16 * ROWB + sw_lo);
                 wh[nxt] = *reinterpret_cast<const f16x8*>(S + w_row + (ni + 1) * 16 * ROWB + sw_hi);
+            } else if constexpr (ROLE != ROLE_IN_PHASE) {   // under the last block of this K-step: the deferred blocks' W fragments
+#pragma unroll
+                for (int j = 0; j < LAG; ++j) {
+                    dwl[j] = *reinterpret_cast<const f16x8*>(S + w_row + (NOW + j) * 16 * ROWB + sw_lo);
+                    dwh[j] = *reinterpret_cast<const f16x8*>(S + w_row + (NOW + j) * 16 * ROWB + sw_hi);
+                }
             }
             if constexpr (LN && !RES_TABLE)
                 if (ni == 2 && g.rl_prefetch && kt >= nk - 1 - G::NPF && kt < nk - 1 && nk > G::NPF) prefetch_res(tile, kt - (nk - 1 - G::NPF));
-#pragma unroll
-            for (int mi = 0; mi < NMI; ++mi) acc[mi][ni] = mfma16(wl[cur], ah[mi], acc[mi][ni]);
-#pragma unroll
-            for (int mi = 0; mi < NMI; ++mi) acc[mi][ni] = mfma16(wh[cur], al[mi], acc[mi][ni]);
-#pragma unroll
-            for (int mi = 0; mi < NMI; ++mi) acc[mi][ni] = mfma16(wh[cur], ah[mi], acc[mi][ni]);
+            mfma_block(ni, wl[cur], wh[cur], ROLE != ROLE_LATE && ni == 0);
             __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    for (int s = 0; tile < n_tiles; ++s) {
+        // This wave's pieces of stage s have landed.  After a tile seam of the LayerNorm modes nothing is waited for: the step's
+        // loads were issued before the epilogue, whose residual loads — issued by every lane of every wave, younger, and
+        // returning in order — have been consumed since; waiting here would wait for the acknowledgement of the epilogue's last
+        // stores.  The planes modes (RL_BIAS_PLANES / RL_GELU_PLANES) load nothing in their epilogue unless there is a bias, so
+        // they wait at every K-step.
+        if (!LN || kt != 0 || ord == 0) __builtin_amdgcn_s_waitcnt(0x0f70);
+        // ... and every LDS read this wave has issued has returned: a late wave's deferred W fragments are reads of stage s - 1
+        // that no MFMA in front of this barrier consumes, and behind it the other waves stage into that stage at once.  The
+        // barrier's LDS-scope release fence does not emit this wait here (it does at the tile end), so it is explicit:
+        // s_waitcnt lgkmcnt(0), vmcnt / expcnt untouched.  (The in-phase waves have nothing outstanding: free for them.)
+        if constexpr (LAG > 0) __builtin_amdgcn_s_waitcnt(0xc07f);
+        rl_barrier();   // ... and everyone's; every wave has left the other stage (K-step s - 1, or the epilogue's buffers)
+        RL_STAMP_K(6);
+        const _Float16* S = lds + (s & 1) * STAGE_H;
+        if constexpr (LAG > 0) {
+            // Three skip branches in a row, not an if / else chain, and the role made opaque between them so that they stay three:
+            // the loop contains the epilogue's lane-dependent branches, so its control flow is linearised anyway, and in a
+            // linearised chain the late bodies' inputs (the accumulators as they enter the K-step) stay live through the in-phase
+            // body: every accumulator then exists twice (256 VGPRs, spills, 86 copies per K-step).  Written as a sequence, each
+            // body takes the accumulators from the merge in front of it.
+            int role = pope_uniform_select(late, pope_uniform_select(kt == 0, int(ROLE_LATE_FIRST), int(ROLE_LATE)), int(ROLE_IN_PHASE));
+            if (role == ROLE_IN_PHASE) kstep(std::integral_constant<int, ROLE_IN_PHASE>{}, s, S);
+            asm volatile("" : "+s"(role));
+            if (role == ROLE_LATE_FIRST) kstep(std::integral_constant<int, ROLE_LATE_FIRST>{}, s, S);
+            asm volatile("" : "+s"(role));
+            if (role == ROLE_LATE) kstep(std::integral_constant<int, ROLE_LATE>{}, s, S);
+        } else {
+            kstep(std::integral_constant<int, ROLE_IN_PHASE>{}, s, S);
         }
         if (++kt == nk) {
             rl_barrier();   // every wave has finished reading stage s & 1: it holds the transposition buffers now
+            if constexpr (LAG > 0) {
+                if (late) deferred_blocks();   // the tile's last K-step, from registers
+                // the fragments end here for both roles: nothing of them is live (or spilled) across the epilogue
+#pragma unroll
+                for (int t = 0; t < NMI; ++t) ah[t] = __builtin_nondeterministic_value(ah[t]), al[t] = __builtin_nondeterministic_value(al[t]);
+#pragma unroll
+                for (int j = 0; j < LAG; ++j) dwl[j] = __builtin_nondeterministic_value(dwl[j]), dwh[j] = __builtin_nondeterministic_value(dwh[j]);
+            }
             if constexpr (LN) epilogue(tile, s & 1);
             else epilogue_planes(tile, s & 1);
             zero_acc();
@@ -518,8 +621,8 @@ int launch_rowln(const GemmParams& g, hipStream_t stream) {
 }  // namespace
 
 #ifdef RL_STAMPS
-extern "C" int pope_lab_rowln_stamps(unsigned long long* host192) {
-    return hipMemcpyFromSymbol(host192, HIP_SYMBOL(g_rl_dbg), sizeof(unsigned long long) * 192) == hipSuccess ? 0 : -1;
+extern "C" int pope_lab_rowln_stamps(unsigned long long* host384) {
+    return hipMemcpyFromSymbol(host384, HIP_SYMBOL(g_rl_dbg), sizeof(unsigned long long) * 384) == hipSuccess ? 0 : -1;
 }
 #endif
 

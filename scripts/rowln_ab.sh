@@ -1,6 +1,7 @@
 #!/bin/bash
-# Dev: lab copies of the library that differ only in the LN-fused GEMM's build flags (tile geometry -DRL_GEO=2|3|96, staging
-# issue -DRL_SPREAD, phase stamps -DRL_STAMPS): scripts/rowln_ab.sh NAME "<flags>" [NAME "<flags>" ...]
+# Dev: lab copies of the library that differ only in the LN-fused GEMM's build flags (wave lag -DRL_LAG=0..3, a late wave's
+# staging in front of its deferred MFMAs -DRL_LAG_STAGE_BEHIND=0, phase stamps -DRL_STAMPS):
+# scripts/rowln_ab.sh NAME "<flags>" [NAME "<flags>" ...]
 # -> scripts/_lab/libpope_NAME.so (git-ignored; travels to the GPU box).  Time them with scripts/ab_bench.sh / rowln_stamps.py.
 set -e
 cd "$(dirname "$0")/../pope_amd/csrc"
