@@ -632,6 +632,26 @@ int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win
                            int top, int left, int ch, int cw, int row0, int nrows,
                            const float* mean_host, const float* std_host, float* out,
                            unsigned char* scratch, size_t scratch_bytes, void* stream);
+/* SAM's input transform for P frames of one size.  The tables are those of pope_preprocess_u8_f32 (DEVICE int32, built by
+ * pope_amd/preprocess.py:resize_tables for Win -> OW and Hin -> OH); the whole resized image is computed.
+ * scratch >= P*Hin*OW*3 bytes (the horizontal pass of every input row).  Null pointers, non-positive sizes and (fp32 entry)
+ * S % 4 != 0, OH > S, OW > S or an `out` that is not 16-byte aligned return POPE_ERR_ARG, a short scratch POPE_ERR_WORKSPACE,
+ * both before any HIP call.
+ *   pope_resize_u8 — ResizeLongestSide.apply_image (segment_anything/utils/transforms.py: Pillow's 8-bit bilinear resample,
+ *     bit-identical): img_hwc[P,Hin,Win,3] uint8 -> out[P,OH,OW,3] uint8.
+ *   pope_sam_preprocess_u8_f32 — the resample, Sam.preprocess (segment_anything/modeling/sam.py) and its pad as one result:
+ *     out[P,3,S,S] fp32, out[p,c,y,x] = ((float)u8 - mean[c]) / std[c] (IEEE subtraction and division, on the 0..255 values)
+ *     for y < OH, x < OW, where u8 is the resampled byte of source channel (flip ? 2 - c : c); every other element of the
+ *     S x S square is +0.0, written by the same launch.  mean_host / std_host[3] = HOST floats per OUTPUT channel. */
+int pope_resize_u8(const unsigned char* img_hwc, int P, int Hin, int Win,
+                   const int* hstart, const int* hcount, const int* hk, int kh,
+                   const int* vstart, const int* vcount, const int* vk, int kv,
+                   int OH, int OW, unsigned char* out, unsigned char* scratch, size_t scratch_bytes, void* stream);
+int pope_sam_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win,
+                               const int* hstart, const int* hcount, const int* hk, int kh,
+                               const int* vstart, const int* vcount, const int* vk, int kv,
+                               int OH, int OW, int S, int flip, const float* mean_host, const float* std_host, float* out,
+                               unsigned char* scratch, size_t scratch_bytes, void* stream);
 /* ToTensor + Normalize of a crop window without resizing (torchvision semantics: x / 255, then (x - mean) / std in
  * fp32) — the dense pair path's 476 x 630 centre crop of a 640 x 480 frame: img_hwc[P,Hin,Win,3] uint8 ->
  * out[P,3,ch,cw] fp32 (16-byte aligned); mean_host / std_host[3] = HOST floats in the channel order of img. */

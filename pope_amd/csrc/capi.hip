@@ -556,6 +556,44 @@ int pope_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win
     return pope_launch_preprocess(p, static_cast<hipStream_t>(stream));
 }
 
+namespace {
+// the arguments both whole-frame resample entries share
+ResizeParams resize_params(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount, const int* hk,
+                           int kh, const int* vstart, const int* vcount, const int* vk, int kv, int OH, int OW, void* out,
+                           unsigned char* scratch, size_t scratch_bytes) {
+    ResizeParams p = {};
+    p.img = img_hwc; p.P = P; p.Hin = Hin; p.Win = Win;
+    p.hstart = hstart; p.hcount = hcount; p.hk = hk; p.kh = kh;
+    p.vstart = vstart; p.vcount = vcount; p.vk = vk; p.kv = kv;
+    p.OH = OH; p.OW = OW; p.out = out; p.tmp = scratch; p.tmp_bytes = scratch_bytes;
+    return p;
+}
+}  // namespace
+
+int pope_resize_u8(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount, const int* hk, int kh,
+                   const int* vstart, const int* vcount, const int* vk, int kv, int OH, int OW, unsigned char* out,
+                   unsigned char* scratch, size_t scratch_bytes, void* stream) {
+    const ResizeParams p = resize_params(img_hwc, P, Hin, Win, hstart, hcount, hk, kh, vstart, vcount, vk, kv, OH, OW, out, scratch,
+                                         scratch_bytes);
+    if (const int rc = pope_resize_check(p)) return rc;   // before any HIP call
+    StreamDevice on_device(stream);
+    return pope_launch_resize(p, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_preprocess_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, const int* hstart, const int* hcount,
+                               const int* hk, int kh, const int* vstart, const int* vcount, const int* vk, int kv, int OH, int OW,
+                               int S, int flip, const float* mean_host, const float* std_host, float* out, unsigned char* scratch,
+                               size_t scratch_bytes, void* stream) {
+    if (!mean_host || !std_host) return POPE_ERR_ARG;
+    ResizeParams p = resize_params(img_hwc, P, Hin, Win, hstart, hcount, hk, kh, vstart, vcount, vk, kv, OH, OW, out, scratch,
+                                   scratch_bytes);
+    p.f32 = true; p.S = S; p.flip = flip;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = mean_host[c]; p.std[c] = std_host[c]; }
+    if (const int rc = pope_resize_check(p)) return rc;   // before any HIP call
+    StreamDevice on_device(stream);
+    return pope_launch_resize(p, static_cast<hipStream_t>(stream));
+}
+
 int pope_crop_normalize_u8_f32(const unsigned char* img_hwc, int P, int Hin, int Win, int top, int left, int ch, int cw,
                                const float* mean_host, const float* std_host, float* out, void* stream) {
     StreamDevice on_device(stream);

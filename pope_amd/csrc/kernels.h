@@ -247,6 +247,22 @@ struct PreprocParams {
     float* out;
 };
 int pope_launch_preprocess(const PreprocParams& p, hipStream_t stream);
+// The same resample of whole frames (preprocess.hip), SAM's input transform: uint8 HWC [P, Hin, Win, 3] -> the resized uint8
+// HWC [P, OH, OW, 3] (f32 = false), or -> fp32 NCHW [P, 3, S, S] with (v - mean) / std inside OH x OW and zeros elsewhere
+struct ResizeParams {
+    const unsigned char* img;
+    int P, Hin, Win;
+    const int *hstart, *hcount, *hk; int kh;   // horizontal tables [OW], [OW], [OW, kh]
+    const int *vstart, *vcount, *vk; int kv;   // vertical tables [OH], [OH], [OH, kv]
+    int OH, OW;
+    bool f32;
+    int S, flip;                               // f32: side of the padded square; channel c reads source channel 2 - c
+    float mean[3], std[3];                     // f32: per OUTPUT channel, on the 0..255 scale
+    void* out;
+    unsigned char* tmp; size_t tmp_bytes;      // [P, Hin, OW, 3]
+};
+int pope_resize_check(const ResizeParams& p);   // no HIP call
+int pope_launch_resize(const ResizeParams& p, hipStream_t stream);
 int pope_launch_gray(const unsigned char* bgr, size_t npix, float* out, hipStream_t stream);
 int pope_launch_crop_warp(const unsigned char* img, int H, int W, int C, const double* minv, const int* win, int P, int oh, int ow,
                           unsigned char* out, hipStream_t stream);

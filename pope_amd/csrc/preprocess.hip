@@ -7,6 +7,12 @@
 // (pope_amd/preprocess.py:resize_tables); ToTensor and Normalize are one fp32 division and one fp32 subtract + division.
 // Only the centre-crop window is computed.  Channel order is taken as given (the drivers pass cv2 BGR frames as RGB).
 // HBM-bound streaming kernels: a thread per output pixel, the three channels of a pixel together, coalesced along x.
+//
+// SAM's input transform (segment_anything utils/transforms.py ResizeLongestSide.apply_image, modeling/sam.py preprocess) is
+// the same resample of the WHOLE frame: the horizontal pass above over every input row, then `resize_v_kernel`, the vertical
+// pass with two epilogues — the resized uint8 HWC image itself (pope_resize_u8), or (v - mean) / std on the 0..255 values
+// into the top-left corner of a zero S x S square, NCHW fp32 (pope_sam_preprocess_u8_f32: resample, normalisation and pad in
+// one result, the pad written by the same launch).  A thread of it owns four consecutive pixels of a row.
 #include "common.h"
 #include "kernels.h"
 
@@ -71,6 +77,92 @@ __global__ __launch_bounds__(256) void resize_v_norm_kernel(const unsigned char*
         out[o] = (float(clip8(a0)) / 255.0f - m0) / s0;
         out[o + plane] = (float(clip8(a1)) / 255.0f - m1) / s1;
         out[o + 2 * plane] = (float(clip8(a2)) / 255.0f - m2) / s2;
+    }
+}
+
+// vertical pass over tmp[p][Hin][OW][3] (the horizontal pass of every input row of a frame) for the whole resized image.  A
+// thread owns the four pixels x0 .. x0 + 3 of one row of the output grid, which is OH x OW for the uint8 epilogue and S x S for
+// the fp32 one; pixels of the grid outside OH x OW are the pad.
+// `vec` (OW % 4 == 0, `tmp` and a uint8 `out` 4-byte aligned): the 12 bytes of a quad are three aligned words, in `tmp` and in `out`.
+//   F32 = false: out[p][y][x][c] uint8, the resample alone (three 4-byte stores when `vec`).
+//   F32 = true:  out[p][c][y][x] fp32 = (float(v[flip ? 2 - c : c]) - mean[c]) / std[c] inside OH x OW and +0.0 outside; one
+//                16-byte store per channel plane (S % 4 == 0, `out` 16-byte aligned), the quad that straddles OW selects per element.
+// The windows are clipped to [0, Hin) and to kv weights whatever the tables say.
+template <bool F32>
+__global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __restrict__ tmp, int P, int Hin,
+                                                        const int* __restrict__ vstart, const int* __restrict__ vcount,
+                                                        const int* __restrict__ vk, int kv, int OH, int OW, int S, int flip, int vec,
+                                                        float m0, float m1, float m2, float s0, float s1, float s2,
+                                                        void* __restrict__ out) {
+    const int gh = F32 ? S : OH, gw = F32 ? S : OW, qw = (gw + 3) / 4;
+    const size_t total = size_t(P) * gh * qw;
+    for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += size_t(gridDim.x) * 256) {
+        const int x0 = 4 * int(i % qw);
+        const size_t py = i / qw;
+        const int y = int(py % gh), p = int(py / gh);
+        const int nx = y < OH ? (OW - x0 < 4 ? OW - x0 : 4) : 0;   // pixels of this quad inside the image (<= 0: all pad)
+        unsigned char v[12] = {};
+        if (nx > 0) {
+            int s = vstart[y], n = vcount[y];
+            if (s < 0) s = 0;
+            if (n > kv) n = kv;
+            if (n > Hin - s) n = Hin - s;
+            const unsigned char* src = tmp + ((size_t(p) * Hin + s) * OW + x0) * 3;
+            const int* k = vk + size_t(y) * kv;
+            int a[12];
+#pragma unroll
+            for (int j = 0; j < 12; ++j) a[j] = 1 << (PIL_BITS - 1);
+            if (vec) {   // nx == 4 in every quad and the 12 bytes of a tap are three aligned words
+                for (int t = 0; t < n; ++t) {
+                    const int w = k[t];
+                    const unsigned* q = reinterpret_cast<const unsigned*>(src + size_t(t) * OW * 3);
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const unsigned u = q[d];
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) a[4 * d + b] += int((u >> (8 * b)) & 255u) * w;
+                    }
+                }
+            } else {
+                for (int t = 0; t < n; ++t) {
+                    const int w = k[t];
+                    const unsigned char* q = src + size_t(t) * OW * 3;
+#pragma unroll
+                    for (int j = 0; j < 12; ++j)
+                        if (j < 3 * nx) a[j] += int(q[j]) * w;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 12; ++j)
+                if (j < 3 * nx) v[j] = clip8(a[j]);
+        }
+        if constexpr (F32) {
+            const size_t plane = size_t(S) * S;
+            float* o = static_cast<float*>(out) + size_t(p) * 3 * plane + size_t(y) * S + x0;
+            const float m[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                f32x4 r;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned char u = flip ? v[3 * e + 2 - c] : v[3 * e + c];
+                    r[e] = e < nx ? __fdiv_rn(__fsub_rn(float(u), m[c]), sd[c]) : 0.0f;
+                }
+                *reinterpret_cast<f32x4*>(o + c * plane) = r;
+            }
+        } else {
+            unsigned char* o = static_cast<unsigned char*>(out) + ((size_t(p) * OH + y) * OW + x0) * 3;
+            if (vec) {   // nx == 4 in every quad
+#pragma unroll
+                for (int d = 0; d < 3; ++d)
+                    reinterpret_cast<unsigned*>(o)[d] = unsigned(v[4 * d]) | unsigned(v[4 * d + 1]) << 8 | unsigned(v[4 * d + 2]) << 16
+                                                        | unsigned(v[4 * d + 3]) << 24;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j)
+                    if (j < 3 * nx) o[j] = v[j];
+            }
+        }
     }
 }
 
@@ -163,6 +255,30 @@ int pope_launch_preprocess(const PreprocParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(resize_v_norm_kernel, dim3(grid_for(size_t(p.P) * p.ch * p.cw)), dim3(256), 0, stream, p.tmp, p.P, p.row0,
                        p.nrows, p.vstart, p.vcount, p.vk, p.kv, p.top, p.ch, p.cw, p.mean[0], p.mean[1], p.mean[2], p.std[0],
                        p.std[1], p.std[2], p.out);
+    return pope_check_launch();
+}
+
+int pope_resize_check(const ResizeParams& p) {
+    if (!p.img || !p.out || !p.tmp || !p.hstart || !p.hcount || !p.hk || !p.vstart || !p.vcount || !p.vk) return POPE_ERR_ARG;
+    if (p.P <= 0 || p.Hin <= 0 || p.Win <= 0 || p.OH <= 0 || p.OW <= 0 || p.kh <= 0 || p.kv <= 0) return POPE_ERR_ARG;
+    if (p.f32 && (p.S <= 0 || (p.S & 3) || p.OH > p.S || p.OW > p.S || (reinterpret_cast<uintptr_t>(p.out) & 15))) return POPE_ERR_ARG;
+    if (p.tmp_bytes < size_t(p.P) * p.Hin * p.OW * 3) return POPE_ERR_WORKSPACE;
+    return POPE_OK;
+}
+
+int pope_launch_resize(const ResizeParams& p, hipStream_t stream) {
+    POPE_TRY(pope_resize_check(p));
+    hipLaunchKernelGGL(resize_h_kernel, dim3(grid_for(size_t(p.P) * p.Hin * p.OW)), dim3(256), 0, stream, p.img, p.P, p.Hin, p.Win,
+                       p.hstart, p.hcount, p.hk, p.kh, 0, p.Hin, 0, p.OW, p.tmp);
+    const int vec = !(p.OW & 3) && !(reinterpret_cast<uintptr_t>(p.tmp) & 3) && (p.f32 || !(reinterpret_cast<uintptr_t>(p.out) & 3));
+    if (p.f32) {
+        hipLaunchKernelGGL(resize_v_kernel<true>, dim3(grid_for(size_t(p.P) * p.S * (p.S / 4))), dim3(256), 0, stream, p.tmp, p.P, p.Hin,
+                           p.vstart, p.vcount, p.vk, p.kv, p.OH, p.OW, p.S, p.flip ? 1 : 0, vec, p.mean[0], p.mean[1], p.mean[2], p.std[0],
+                           p.std[1], p.std[2], p.out);
+    } else {
+        hipLaunchKernelGGL(resize_v_kernel<false>, dim3(grid_for(size_t(p.P) * p.OH * ((p.OW + 3) / 4))), dim3(256), 0, stream, p.tmp, p.P,
+                           p.Hin, p.vstart, p.vcount, p.vk, p.kv, p.OH, p.OW, 0, 0, vec, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, p.out);
+    }
     return pope_check_launch();
 }
 

@@ -19,6 +19,7 @@ import torch
 
 from .dinov2_utils import get_cls_token_torch
 from .ops import cls_cosine, streaming_top3
+from .preprocess import frames_on_device, on_device
 
 
 @torch.no_grad()
@@ -293,8 +294,10 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
     `mask_generator.propose_batch(frames)` -> the XYWH boxes of every frame's records, the only part of a record the loop reads
     (:73; no mask is unpacked, encoded or downloaded) -> `locate_match_pose_batch_u8`.  The frames reach the generator
     unchanged, in BGR channel order: the reference hands the frame of `cv2.imread` to `MASK_GEN.generate` as it is (:66-69),
-    and the same proposals come only from the same input.  `max_proposals` keeps the first `max_proposals` boxes of each frame
-    in record order (None: all of them, as the reference does).
+    and the same proposals come only from the same input.  Frames that already sit in HBM (a uint8 CUDA tensor [Q, H, W, 3] or a
+    list of CUDA frames, on the models' device) stay there: the generator resamples them on the device and the driver step reads
+    the same tensor, no frame is downloaded or passes through Pillow, and the result is that of the numpy call.  `max_proposals`
+    keeps the first `max_proposals` boxes of each frame in record order (None: all of them, as the reference does).
 
     Returns `locate_match_pose_batch_u8`'s list of Q dicts, each with one more key: `proposals`, the int64 [P_q, 4] XYWH boxes
     of that query.  A frame without a proposal yields the empty result (`best_proposal` -1, `pose` None)."""
@@ -306,16 +309,21 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
                          + ", ".join(f"{k} on {v}" for k, v in devices.items()))
     if max_proposals is not None and int(max_proposals) < 0:
         raise ValueError(f"locate_pose_from_frames: max_proposals is None or a count, got {max_proposals}")
-    if isinstance(frames_bgr, torch.Tensor):
-        frames_bgr = frames_bgr.cpu().numpy()
-    frames = [np.asarray(f.cpu() if torch.is_tensor(f) else f) for f in frames_bgr]
+    if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
+        frames_bgr = list(frames_bgr)
+    frames = stack = frames_on_device(frames_bgr, "locate_pose_from_frames")   # frames in HBM stay there, for both calls below
+    if stack is None:
+        if isinstance(frames_bgr, torch.Tensor):
+            frames_bgr = frames_bgr.cpu().numpy()
+        frames = [np.asarray(f.cpu() if torch.is_tensor(f) else f) for f in frames_bgr]
+        stack = np.stack(frames) if frames else frames
     if len(frames) != len(refs_bgr):
         raise ValueError(f"locate_pose_from_frames: {len(refs_bgr)} references, {len(frames)} frames")
     proposals = mask_generator.propose_batch(frames)            # mixed frame sizes raise there
     if max_proposals is not None:
         proposals = [p[:int(max_proposals)] for p in proposals]
-    outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, np.stack(frames) if frames else frames, proposals, K0, K1,
-                                      conf_thr, ransac_thr, ransac_conf, out_size)
+    outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, stack, proposals, K0, K1, conf_thr, ransac_thr, ransac_conf,
+                                      out_size)
     for out, p in zip(outs, proposals):
         out["proposals"] = p
     return outs
@@ -324,6 +332,6 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
 def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
                            ransac_conf=0.99, out_size=256, max_proposals=None):
     """`locate_pose_from_frames` for one query: `ref_bgr` [H0, W0, 3], `frame_bgr` [H, W, 3], `K0` / `K1` [3, 3]; one dict."""
-    ref, frame = (np.asarray(a.cpu() if torch.is_tensor(a) else a)[None] for a in (ref_bgr, frame_bgr))
+    ref, frame = (a[None] if on_device(a) else np.asarray(a.cpu() if torch.is_tensor(a) else a)[None] for a in (ref_bgr, frame_bgr))
     return locate_pose_from_frames(mask_generator, dinov2_model, matcher, ref, frame, K0, K1, conf_thr, ransac_thr, ransac_conf,
                                    out_size, max_proposals)[0]

@@ -5,6 +5,11 @@ path of the reference (segment_anything/segment_anything/dinov2_utils.py:55-78: 
 The resize is Pillow's 8-bit bilinear resample; its per-output-pixel windows and fixed-point weights depend on the
 (input, output) sizes only and are built here on the host in double precision exactly as Pillow's `precompute_coeffs`
 builds them (cached per size pair), so the kernels only do the integer arithmetic.
+
+SAM's input transform is the same resample of whole frames: `resize_u8_batch` is `ResizeLongestSide.apply_image` for frames
+that already sit in HBM, `sam_preprocess_batch` that resize, `Sam.preprocess` and its zero pad as one result (segment_anything
+utils/transforms.py, modeling/sam.py), both bit-identical to the host chain.  `frames_on_device` is how the calls that take
+frames as numpy arrays or tensors (pope_amd/sam_generator.py, pope_amd/driver.py) tell the two apart.
 """
 import ctypes as C
 import math
@@ -14,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import check, on_device_of, require_cuda, stream_of
+from .sam_amg import preprocess_shape
 from .synth import IMAGENET_MEAN, IMAGENET_STD
 
 PRECISION_BITS = 32 - 8 - 2   # Pillow, 8 bits per channel
@@ -88,6 +94,86 @@ def preprocess_batch(images, resize, crop=None, mean=IMAGENET_MEAN, std=IMAGENET
                                                 ch, cw, row0, nrows, m, s, p(out), p(scratch), scratch.numel(), stream_of(dev)),
               "pope_preprocess_u8_f32")
     return out
+
+
+def on_device(x):
+    """The dispatch of every call that takes frames as numpy arrays or as tensors: a tensor that is not on the CPU takes the
+    device path, numpy arrays and CPU tensors the host path."""
+    return isinstance(x, torch.Tensor) and x.device.type != "cpu"
+
+
+def frames_on_device(images, what):
+    """The frames of a call that takes uint8 HWC frames as numpy arrays or as tensors: None when they are host data (numpy
+    arrays, CPU tensors: the caller's host path), else one uint8 [Q, H, W, 3] tensor on the frames' device.  `images` is a
+    [Q, H, W, 3] tensor or a sequence of [H, W, 3] frames.  A sequence that mixes host and device frames, frames of several
+    sizes or on several devices raise ValueError; a device frame of another dtype or rank raises TypeError."""
+    def checked(t, shape):
+        if t.dtype != torch.uint8 or t.dim() != shape.count(",") + 1 or t.shape[-1] != 3:
+            raise TypeError(f"{what}: device frames are uint8 {shape} tensors, got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    if isinstance(images, torch.Tensor):
+        return checked(images, "[Q, H, W, 3]") if on_device(images) else None
+    images = list(images)
+    where = [on_device(im) for im in images]
+    if not any(where):
+        return None
+    if not all(where):
+        raise ValueError(f"{what}: the frames of one call are all host arrays or all device tensors")
+    for im in images:
+        checked(im, "[H, W, 3]")
+    if len({tuple(im.shape) for im in images}) > 1 or len({im.device for im in images}) > 1:
+        raise ValueError(f"{what}: all frames must have one size and one device, got "
+                         + ", ".join(sorted({f"{im.shape[0]} x {im.shape[1]} on {im.device}" for im in images})))
+    return torch.stack(images)
+
+
+def _resize_call(images, out_hw_of, who):
+    """What both whole-frame resample bindings pass first, for the output size out_hw_of(H, W): (contiguous frames, (OH, OW), the
+    table and size arguments of the C entry up to OW, a scratch tensor for the horizontal pass)."""
+    require_cuda(images, who)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise TypeError(f"{who} expects a uint8 [P, H, W, 3] tensor")
+    images = images.contiguous()
+    P, Hin, Win, _ = images.shape
+    OH, OW = (int(v) for v in out_hw_of(Hin, Win))
+    if P <= 0 or min(Hin, Win, OH, OW) <= 0:
+        raise ValueError(f"{who}: empty batch or size ({P} frames of {Hin} x {Win} to {OH} x {OW})")
+    dev = images.device
+    hs, hc, hk, kh, _, _ = _device_tables(Win, OW, dev)
+    vs, vc, vk, kv, _, _ = _device_tables(Hin, OH, dev)
+    scratch = torch.empty(P * Hin * OW * 3, dtype=torch.uint8, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    return images, (OH, OW), (p(images), P, Hin, Win, p(hs), p(hc), p(hk), kh, p(vs), p(vc), p(vk), kv, OH, OW), scratch
+
+
+@torch.no_grad()
+def resize_u8_batch(images, out_hw):
+    """[P, H, W, 3] uint8 (CUDA tensor) -> [P, OH, OW, 3] uint8: Pillow's 8-bit bilinear `Image.resize((OW, OH))` of every
+    frame (`ResizeLongestSide.apply_image` when `out_hw` is its `get_preprocess_shape`), bit-identical."""
+    images, (OH, OW), args, scratch = _resize_call(images, lambda h, w: out_hw, "resize_u8_batch")
+    out = torch.empty(images.shape[0], OH, OW, 3, dtype=torch.uint8, device=images.device)
+    with on_device_of(images):
+        check(_lib.lib().pope_resize_u8(*args, C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                        stream_of(images.device)), "pope_resize_u8")
+    return out
+
+
+@torch.no_grad()
+def sam_preprocess_batch(images, img_size, mean, std, flip=False):
+    """SAM's input transform for [P, H, W, 3] uint8 frames (CUDA tensor) in one call: `ResizeLongestSide(img_size).apply_image`,
+    then `Sam.preprocess` ((x - mean) / std on the 0..255 values, zero pad to the square) -> (x fp32 [P, 3, img_size, img_size],
+    input_size = the resized (h, w)).  `mean` / `std`: three floats per model channel; `flip` reads the frame's channels in
+    reverse order (a BGR frame for an RGB model).  Bit-identical to the host chain, the pad is +0.0."""
+    S = int(img_size)
+    images, input_size, args, scratch = _resize_call(images, lambda h, w: preprocess_shape(h, w, S), "sam_preprocess_batch")
+    out = torch.empty(images.shape[0], 3, S, S, dtype=torch.float32, device=images.device)
+    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    with on_device_of(images):
+        check(_lib.lib().pope_sam_preprocess_u8_f32(*args, S, int(bool(flip)), m, s, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(scratch.data_ptr()), scratch.numel(), stream_of(images.device)),
+              "pope_sam_preprocess_u8_f32")
+    return out, input_size
 
 
 def set_torch_images(images, center_crop=False, device="cuda"):

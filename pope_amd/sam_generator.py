@@ -16,6 +16,12 @@ query of pope_amd/driver.py reads nothing else).  There is one tail: `generate` 
 predictor calls it with the features it holds, the generator with each frame's (it never writes the predictor's state).  There
 is no torch fallback.
 
+Frames are dispatched by type alone.  A numpy array or a CPU tensor is resized by Pillow on the host, uploaded and normalised
+by `Sam.preprocess`.  A uint8 CUDA tensor stays in HBM: `SamPredictor.set_image`, `generate`, `propose` ([H, W, 3]) and
+`generate_batch`, `propose_batch` ([Q, H, W, 3] or a list of frames of one size) make one `pope_sam_preprocess_u8_f32` call
+(pope_amd/preprocess.py:sam_preprocess_batch: Pillow's resample, the normalisation and the pad in one result, bit-equal to
+the host chain), `ResizeLongestSide.apply_image` returns the resized uint8 tensor (`pope_resize_u8`).
+
 Not supported: crop layers (`crop_n_layers > 0`), `output_mode="coco_rle"`.
 """
 import ctypes as C
@@ -28,7 +34,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, sam_amg
-from ._lib import check, on_device_of, ptr, require_cuda, stream_of
+from ._lib import check, on_device_of, params_key, ptr, require_cuda, stream_of
+from .preprocess import frames_on_device, on_device, resize_u8_batch, sam_preprocess_batch
 from .sam_decoder import MaskDecoder, PromptEncoder, TwoWayTransformer, require_gpu_mask
 from .sam_encoder import ImageEncoderViT
 
@@ -297,7 +304,8 @@ sam_model_registry = {"default": build_sam_vit_h, "vit_h": build_sam_vit_h, "vit
 # ---- predictor -----------------------------------------------------------------------------------------------------------
 class ResizeLongestSide:
     """utils/transforms.py: `apply_image` is torchvision's `resize(to_pil_image(image), size)`, i.e. Pillow's 8-bit bilinear
-    resample, run on the host once per frame."""
+    resample: on the host once per frame for a numpy array or a CPU tensor, `pope_resize_u8` for a uint8 CUDA tensor (the
+    same bytes)."""
 
     def __init__(self, target_length: int) -> None:
         self.target_length = target_length
@@ -306,10 +314,32 @@ class ResizeLongestSide:
     def get_preprocess_shape(oldh: int, oldw: int, long_side_length: int) -> Tuple[int, int]:
         return sam_amg.preprocess_shape(oldh, oldw, long_side_length)
 
-    def apply_image(self, image: np.ndarray) -> np.ndarray:
+    def apply_image(self, image):
+        """[H, W, 3] uint8 numpy array or CPU tensor -> the resized numpy array; a uint8 CUDA tensor [H, W, 3] or [P, H, W, 3]
+        -> the resized CUDA tensor of the same rank (what a caller permutes into a `Sam.forward` record)."""
+        if on_device(image):
+            if image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-1] != 3:
+                raise TypeError(f"apply_image: a device image is a uint8 [H, W, 3] or [P, H, W, 3] tensor, got {image.dtype} "
+                                f"{tuple(image.shape)}")
+            stack = image if image.dim() == 4 else image[None]
+            out = resize_u8_batch(stack, self.get_preprocess_shape(int(stack.shape[1]), int(stack.shape[2]), self.target_length))
+            return out if image.dim() == 4 else out[0]
         from PIL import Image
         h, w = self.get_preprocess_shape(image.shape[0], image.shape[1], self.target_length)
         return np.array(Image.fromarray(np.ascontiguousarray(image)).resize((w, h), Image.BILINEAR))
+
+    def apply_coords_torch(self, coords: torch.Tensor, original_size: Tuple[int, ...]) -> torch.Tensor:
+        """`apply_coords` for a tensor [..., 2] on any device: a float32 copy, scaled (the factors are rounded to float32)."""
+        old_h, old_w = original_size
+        new_h, new_w = self.get_preprocess_shape(old_h, old_w, self.target_length)
+        coords = coords.detach().to(torch.float, copy=True)
+        coords[..., 0] = coords[..., 0] * (new_w / old_w)
+        coords[..., 1] = coords[..., 1] * (new_h / old_h)
+        return coords
+
+    def apply_boxes_torch(self, boxes: torch.Tensor, original_size: Tuple[int, ...]) -> torch.Tensor:
+        """`apply_boxes` for a tensor [B, 4] on any device."""
+        return self.apply_coords_torch(boxes.reshape(-1, 2, 2), original_size).reshape(-1, 4)
 
     def apply_coords(self, coords: np.ndarray, original_size: Tuple[int, ...]) -> np.ndarray:
         old_h, old_w = original_size
@@ -330,14 +360,23 @@ class SamPredictor:
     def __init__(self, sam_model: Sam) -> None:
         self.model = sam_model
         self.transform = ResizeLongestSide(sam_model.image_encoder.img_size)
+        self._pixel_stats = (None, None, None)   # (params_key, mean, std): host copies of the model's two pixel buffers
         self.reset_image()
 
     @property
     def device(self) -> torch.device:
         return self.model.device
 
-    def set_image(self, image: np.ndarray, image_format: str = "RGB") -> None:
+    def set_image(self, image, image_format: str = "RGB") -> None:
+        """`image`: [H, W, 3] uint8, a numpy array or a CPU tensor (Pillow on the host, upload, `Sam.preprocess`) or a CUDA tensor
+        on the model's device (one `pope_sam_preprocess_u8_f32` call); the state it leaves is the same, bit for bit."""
         assert image_format in ["RGB", "BGR"], f"image_format must be in ['RGB', 'BGR'], is {image_format}."
+        if on_device(image):
+            if image.dim() != 3:
+                raise TypeError(f"set_image: a device image is a uint8 [H, W, 3] tensor, got {tuple(image.shape)}")
+            x, input_size = self.preprocess_frames(frames_on_device(image[None], "set_image"), image_format, "set_image")
+            self._set_encoder_input(x, input_size, image.shape[:2])
+            return
         if image_format != self.model.image_format:
             image = image[..., ::-1]
         input_image = self.transform.apply_image(image)
@@ -345,14 +384,34 @@ class SamPredictor:
         self.set_torch_image(t, image.shape[:2])
 
     @torch.no_grad()
+    def preprocess_frames(self, stack, image_format: str, what: str):
+        """The device form of `transform.apply_image` + `model.preprocess` for frames of one size: `stack` is what
+        `preprocess.frames_on_device` returns (uint8 [Q, H, W, 3], not on the CPU) -> (the encoder's input
+        [Q, 3, img_size, img_size], input_size).  Frames on another device than the model raise ValueError."""
+        if stack.device != torch.device(self.device):
+            raise ValueError(f"{what}: the frames are on {stack.device}, the model on {self.device}")
+        model = self.model
+        key = params_key((model.pixel_mean, model.pixel_std))
+        if self._pixel_stats[0] != key:   # host copies of the two buffers, read once per value (a download is a synchronisation)
+            self._pixel_stats = (key, model.pixel_mean.flatten().tolist(), model.pixel_std.flatten().tolist())
+        return sam_preprocess_batch(stack, model.image_encoder.img_size, self._pixel_stats[1], self._pixel_stats[2],
+                                    flip=image_format != model.image_format)
+
+    @torch.no_grad()
     def set_torch_image(self, transformed_image: torch.Tensor, original_image_size: Tuple[int, ...]) -> None:
         size = self.model.image_encoder.img_size
         assert (len(transformed_image.shape) == 4 and transformed_image.shape[1] == 3
                 and max(*transformed_image.shape[2:]) == size), f"set_torch_image input must be BCHW with long side {size}."
+        self._set_encoder_input(self.model.preprocess(transformed_image).contiguous(), transformed_image.shape[-2:],
+                                original_image_size)
+
+    # the encoder call both `set_image` paths end in: x [1, 3, img_size, img_size], normalised and padded
+    @torch.no_grad()
+    def _set_encoder_input(self, x, input_size, original_size) -> None:
         self.reset_image()
-        self.original_size = tuple(int(v) for v in original_image_size)
-        self.input_size = tuple(transformed_image.shape[-2:])
-        self.features = self.model.image_encoder(self.model.preprocess(transformed_image).contiguous())
+        self.original_size = tuple(int(v) for v in original_size)
+        self.input_size = tuple(int(v) for v in input_size)
+        self.features = self.model.image_encoder(x)
         self.is_image_set = True
 
     @torch.no_grad()
@@ -495,9 +554,9 @@ class SamAutomaticMaskGenerator:
         return data, np.concatenate(pts)
 
     @torch.no_grad()
-    def generate(self, image: np.ndarray, keep_low_res: bool = False) -> List[Dict[str, Any]]:
-        """HWC uint8 image -> list of records (`segmentation`, `area`, `bbox` XYWH, `predicted_iou`, `point_coords`,
-        `stability_score`, `crop_box`), in the reference's order."""
+    def generate(self, image, keep_low_res: bool = False) -> List[Dict[str, Any]]:
+        """HWC uint8 image (a numpy array, or a CUDA tensor on the model's device) -> list of records (`segmentation`, `area`,
+        `bbox` XYWH, `predicted_iou`, `point_coords`, `stability_score`, `crop_box`), in the reference's order."""
         H, W = image.shape[:2]
         pr = self.predictor
         pr.set_image(image)
@@ -509,14 +568,16 @@ class SamAutomaticMaskGenerator:
     def generate_batch(self, images: List[np.ndarray]) -> List[List[Dict[str, Any]]]:
         """`generate` for a list of HWC uint8 frames of one common size: the image encoder runs over the stacked frames, the
         decoder and the fused post-processing per frame, NMS, small regions and the encoding once for all frames.  The list for
-        frame q is record for record what `generate(images[q])` returns."""
-        images = list(images)
-        if not images:
+        frame q is record for record what `generate(images[q])` returns.  The frames are numpy arrays or CPU tensors (resized on
+        the host), or they sit on the model's device: a uint8 [Q, H, W, 3] CUDA tensor or a list of [H, W, 3] CUDA tensors
+        (one `pope_sam_preprocess_u8_f32` call for the stack, the same records).  A list that mixes the two raises ValueError."""
+        images = images if on_device(images) else list(images)
+        if not len(images):
             return []
         return self._finish(*self._decode_frames(images, "generate_batch"))
 
     @torch.no_grad()
-    def propose(self, image: np.ndarray) -> np.ndarray:
+    def propose(self, image) -> np.ndarray:
         """The `bbox` values of `generate(image)` alone, in record order: int64 [P, 4] XYWH ([0, 4] when nothing survives)."""
         H, W = image.shape[:2]
         pr = self.predictor
@@ -530,9 +591,9 @@ class SamAutomaticMaskGenerator:
         """The proposals of `generate_batch(images)` without its records: one int64 [P_q, 4] XYWH array per frame, row i the
         `bbox` of record i of that frame, whatever the `output_mode`.  The encoder, the decoder and the tail up to the second
         NMS are those of `generate_batch`; no mask is unpacked, encoded or downloaded, the host reads the survivor counts of
-        the NMS calls and the survivors' boxes."""
-        images = list(images)
-        if not images:
+        the NMS calls and the survivors' boxes.  Frames on the device as in `generate_batch`."""
+        images = images if on_device(images) else list(images)
+        if not len(images):
             return []
         data, seg, _, hw = self._decode_frames(images, "propose_batch")
         return self._finish_boxes(data, seg, hw)
@@ -540,15 +601,22 @@ class SamAutomaticMaskGenerator:
     # the front of the batched calls: one encoder call over the stacked frames, then the decoder frame by frame.  Returns the
     # arguments of `_finish`: (concatenated filtered per-mask data, its seg_offsets, the prompt point of every mask, (H, W))
     def _decode_frames(self, images, what):
-        H, W = images[0].shape[:2]
-        if any(im.shape[:2] != (H, W) for im in images):
-            raise ValueError(f"{what}: all frames must have one size, got "
-                             + ", ".join(sorted({f"{im.shape[0]} x {im.shape[1]}" for im in images})))
         pr = self.predictor
         enc = pr.model.image_encoder
-        resized = np.stack([pr.transform.apply_image(im[..., ::-1] if pr.model.image_format != "RGB" else im) for im in images])
-        x = torch.as_tensor(resized, device=pr.device).permute(0, 3, 1, 2).contiguous()
-        x = pr.model.preprocess(x).contiguous()
+        stack = frames_on_device(images, what)
+        if stack is not None:
+            # frames in HBM: resample, normalisation and pad of the whole stack in one call
+            H, W = (int(v) for v in stack.shape[1:3])
+            x, input_size = pr.preprocess_frames(stack, "RGB", what)
+        else:
+            H, W = images[0].shape[:2]
+            if any(im.shape[:2] != (H, W) for im in images):
+                raise ValueError(f"{what}: all frames must have one size, got "
+                                 + ", ".join(sorted({f"{im.shape[0]} x {im.shape[1]}" for im in images})))
+            resized = np.stack([pr.transform.apply_image(im[..., ::-1] if pr.model.image_format != "RGB" else im) for im in images])
+            x = torch.as_tensor(resized, device=pr.device).permute(0, 3, 1, 2).contiguous()
+            x = pr.model.preprocess(x).contiguous()
+            input_size = tuple(resized.shape[1:3])
         events = enc.overflow_events
         features = enc(x)
         if enc.overflow_events != events:
@@ -558,7 +626,7 @@ class SamAutomaticMaskGenerator:
         pr.reset_image()   # the batched calls leave the predictor as `generate` does: without an image
         parts, seg, points = [], [0], None
         for q in range(len(images)):
-            data, points = self._decode_frame(features[q:q + 1], tuple(resized.shape[1:3]), (H, W))
+            data, points = self._decode_frame(features[q:q + 1], input_size, (H, W))
             parts.append(data)
             seg.append(seg[-1] + data["index"].numel())
         data = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}

@@ -13,8 +13,10 @@ calls of both, (a) and (b) alternate within each repetition, so that drift of th
 (max - min over the repetitions) is reported next to the medians, and the verdict compares the difference of the medians with it.
 Writes the table to --out (default profiles/frame_query.md); --append adds a further run's section to it, such as one at
 `--box-nms-thresh 1.0`, where nothing is suppressed and all 768 masks of a frame are proposals (the synthetic weights leave one
-survivor per frame at 0.35).
-usage: python scripts/frame_query_time.py [--queries 1 4 8] [--reps 7] [--warmup 2] [--box-nms-thresh 0.35] [--out FILE] [--append]"""
+survivor per frame at 0.35).  --cuda-frames hands both forms the frames as one uint8 CUDA tensor, so that SAM's input
+transform runs on the device (`pope_sam_preprocess_u8_f32`) instead of Pillow and an upload.
+usage: python scripts/frame_query_time.py [--queries 1 4 8] [--reps 7] [--warmup 2] [--box-nms-thresh 0.35] [--out FILE] [--append]
+                                          [--cuda-frames]"""
 import argparse
 import os
 import statistics
@@ -58,6 +60,7 @@ def main():
     ap.add_argument("--box-nms-thresh", type=float, default=0.35)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frame_query.md"))
     ap.add_argument("--append", action="store_true", help="add this run's section to --out (a run at other thresholds)")
+    ap.add_argument("--cuda-frames", action="store_true", help="hand both forms the frames as one uint8 CUDA tensor (no Pillow, no upload)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     dev = torch.device("cuda:0")
@@ -67,6 +70,8 @@ def main():
     kw = dict(pred_iou_thresh=0.0, stability_score_thresh=0.0, box_nms_thresh=a.box_nms_thresh, min_mask_region_area=250)
     gen = sg.SamAutomaticMaskGenerator(sam, output_mode="binary_mask", **kw)
     frames = [(torch.rand(H, W, 3, generator=torch.Generator().manual_seed(5 + q)) * 255).to(torch.uint8).numpy() for q in range(Qmax)]
+    if a.cuda_frames:
+        frames = torch.from_numpy(np.stack(frames)).to(dev)
     cases = [synth.synthetic_frame_case(seed=31 + q) for q in range(Qmax)]
     refs, K0, K1 = np.stack([c[0] for c in cases]), np.stack([c[3] for c in cases]), cases[0][4]
 
@@ -101,7 +106,8 @@ def main():
                f"SLOWER: at Q = {slower} the one-call form's median exceeds the two-call form's by more than the spread.")
     print(verdict)
     argv = [v for i, v in enumerate(sys.argv[1:]) if v != "--out" and (i == 0 or sys.argv[i] != "--out")]
-    title = f"## A further run: box NMS {a.box_nms_thresh}, Q = {a.queries}" if a.append else \
+    where = "  The frames are one uint8 CUDA tensor: SAM's input transform runs on the device in both forms." if a.cuda_frames else ""
+    title = f"## A further run: box NMS {a.box_nms_thresh}, Q = {a.queries}{', frames on the device' if a.cuda_frames else ''}" if a.append else \
         "# Frame-to-pose query: one call against `generate_batch` + `locate_match_pose_batch_u8`"
     text = f"""{title}
 
@@ -109,7 +115,7 @@ def main():
 included, a device synchronisation before the clock starts and one before it stops; {a.warmup} warm-up calls of each form, then
 {a.reps} repetitions in which the two forms alternate; median (min .. max).  480 x 640 frames; SAM ViT-B under synthetic weights,
 16 x 16 points, IoU and stability filters off (768 masks of a frame reach NMS), box NMS {a.box_nms_thresh},
-`min_mask_region_area=250`; DINOv2 ViT-S/14 and the LoFTR Matcher under the peaked synthetic weights.
+`min_mask_region_area=250`; DINOv2 ViT-S/14 and the LoFTR Matcher under the peaked synthetic weights.{where}
 
 (a) `locate_pose_from_frames`: `propose_batch` (boxes only) feeds the batched driver step.
 (b) `generate_batch` in `binary_mask` mode, `bbox` from the records, then `locate_match_pose_batch_u8`.
