@@ -375,6 +375,60 @@ int pope_resnetfpn_forward_f32(const pope_resnetfpn_weights* w_host, const float
                                float* out_c, float* out_f, void* workspace, size_t workspace_bytes,
                                unsigned* range_flag, void* stream);
 
+/* Test entry of the convolution forms: ONE layer of the call above (or the SAM neck's 3x3), exactly its launch sequence, on
+ * the caller's device buffers.  A pixel-row tensor [n, Hp, Wp, cch] is NHWC over the ZERO-BORDERED grid Hp = H + 2, Wp = W + 2,
+ * one pixel = one row of cch chunks of 128 bytes: 32 planes columns (POPE_PREC_F16X3), 32 floats (POPE_PREC_F32_MFMA) or 64
+ * plain f16 columns = value * 8 (POPE_PREC_F16).  Weights [N, K] as above (tap-major columns, channels padded to the chunk):
+ * planes x 256, plain fp32, or f16 row-major x 256.  H, W: the interior of the INPUT grid (STEM: the image).
+ *   form              operand a                       runs                                                    output grid
+ *   POPE_CONV3        [n,H+2,W+2,cch]                 implicit 3x3 stride 1, K = 9 cch chunks                  H x W
+ *   POPE_CONV_S2      [n,H+2,W+2,cch]                 taps = 9 (3x3 pad 1) or 1 (1x1), stride 2: straight from a where the
+ *                                                     call fills a round of the CUs, else gather_s2 -> scratch + GEMM    H/2 x W/2
+ *   POPE_CONV1_UP     [n,H+2,W+2,cch]                 1x1 + bilinear x2 (align_corners) of up_src [n,H/2+2,W/2+2,up_lds]
+ *                                                     fp32 (zero-bordered), added before the activation        H x W
+ *   POPE_CONV_STEM    gray image [n,H,W] fp32         7x7 stride 2 pad 3: stem_gather -> scratch [.., 64] + GEMM (K = 64)   H/2 x W/2
+ * out = act(conv + bias [+ res]), act(v) = max(v, 0) + slope min(v, 0).  Exactly one of out_planes [rows, ldc] (planes x 8,
+ * ldc = N rounded up to 32, the padding columns written as zeros; POPE_RANGE_INPUT when a value leaves the f16 range) and
+ * out_f32 [rows, ldc] (ldc >= N, ldc % 4 == 0; columns >= N untouched; no range flag), rows = all pixels of the bordered output
+ * grid.  POPE_PREC_F32_MFMA writes fp32 rows only (out_f32).  zero_border != 0 zeroes the border pixels' rows afterwards; a planes
+ * output of CONV3 / CONV1_UP and every STEM call must ask for it (the next layer reads the border as the padding), CONV_S2 and the
+ * fp32 outputs of CONV3 may leave them undefined.  res (CONV3 only): [rows, ldres] planes, or fp32 rows with POPE_PREC_F32_MFMA.
+ * Served: CONV3 in all three precisions (POPE_PREC_F16: fp32 output, no res), STEM in F16X3 and F32_MFMA, the others F16X3.
+ * Refused with POPE_ERR_ARG before any HIP call:
+ *   - n, H, W < 1; N < 4, N % 4 != 0 or N > 256 (the widest tile of the 256-row routes); cch < 1, or a K of fewer than two
+ *     chunks (CONV1_UP and CONV_S2 with taps = 1 need cch >= 2); STEM with cch != 0 or taps != 0
+ *   - odd H or W for CONV_S2, CONV1_UP (whose epilogue needs Wp >= 4) and STEM
+ *   - a_rows, the pixel rows the operand buffer holds, below n (H+2) (W+2): the loaders dereference every one of them (the
+ *     fp32 loader through a raw pointer, M + 2 Wp + 2 rows)
+ *   - out_planes with ldc != N rounded up to 32, or without zero_border where required; out_f32 with ldc < N or ldc % 4 != 0
+ *   - res or up_src with a pitch below N, ldres % 32 != 0 (planes) / ldres % 4 != 0 (fp32), up_lds % 4 != 0
+ *   - CONV_S2 / STEM without `scratch` (pope_conv_layer_scratch_bytes; a short one is POPE_ERR_WORKSPACE)
+ *   - any buffer of 4 GiB or more (32-bit offsets), any pointer not 16-byte aligned. */
+enum { POPE_CONV3 = 0, POPE_CONV_S2 = 1, POPE_CONV1_UP = 2, POPE_CONV_STEM = 3 };
+typedef struct pope_conv_layer_args {
+    int form, precision;
+    int n, H, W;
+    int cch, taps;                 /* taps: CONV_S2 only (9 or 1), else 0 */
+    const void* a;
+    size_t a_rows;                 /* pixel rows in a's buffer (STEM: ignored) */
+    const void* w;
+    const float* bias;             /* [N] or NULL */
+    int N, ldc;
+    float slope;
+    void* out_planes;
+    float* out_f32;
+    int zero_border;
+    const void* res;               /* CONV3: [rows, ldres] or NULL */
+    int ldres;
+    const float* up_src;           /* CONV1_UP */
+    int up_lds;
+    void* scratch;
+    size_t scratch_bytes;
+    unsigned* range_flag;
+} pope_conv_layer_args;
+size_t pope_conv_layer_scratch_bytes(int form, int n, int H, int W, int cch, int taps);
+int pope_conv_layer_f32(const pope_conv_layer_args* args_host, void* stream);
+
 /* FinePreprocess.forward — src/matcher/loftr_module/fine_preprocess.py:29-59 (fine_concat_coarse_feat = True), for
  * M > 0 matches: Wn x Wn windows (zero padded by Wn/2) of the 1/2-resolution maps centred on the matched coarse
  * cells (i_ids in map 0, j_ids in map 1; cell id = cy * wc + cx, centre pixel = cell * stride), concatenated with

@@ -38,6 +38,15 @@ class ResnetFpnWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 22), ("b", C.c_void_p * 22)]
 
 
+class ConvLayerArgs(C.Structure):
+    """pope_conv_layer_args: one convolution layer on the caller's buffers (pope_conv_layer_f32)."""
+    _fields_ = [("form", C.c_int), ("precision", C.c_int), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cch", C.c_int),
+                ("taps", C.c_int), ("a", C.c_void_p), ("a_rows", C.c_size_t), ("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int),
+                ("ldc", C.c_int), ("slope", C.c_float), ("out_planes", C.c_void_p), ("out_f32", C.c_void_p), ("zero_border", C.c_int),
+                ("res", C.c_void_p), ("ldres", C.c_int), ("up_src", C.c_void_p), ("up_lds", C.c_int), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_size_t), ("range_flag", C.c_void_p)]
+
+
 class SamBlockWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "norm1_b", "qkv_wp", "qkv_b", "proj_wp", "proj_b", "rel_h", "rel_w",
                                            "norm2_w", "norm2_b", "fc1_wp", "fc1_b", "fc2_wp", "fc2_b")] + [("global_attn", C.c_int)]
@@ -78,6 +87,7 @@ PRECISIONS = {"f32": PREC_F32_MFMA, "f16x3": PREC_F16X3, "f16": PREC_F16}
 FFN_KINDS = {"mlp": 0, "swiglu": 1}    # POPE_FFN_*
 EPI_BIAS_SWIGLU = 11                   # POPE_EPI_BIAS_SWIGLU
 EPI_QKV_F16 = 8                        # POPE_EPI_QKV_F16 (pope_linear_f16 only)
+CONV3, CONV_S2, CONV1_UP, CONV_STEM = 0, 1, 2, 3   # POPE_CONV_* forms of pope_conv_layer_f32
 c_uint_p = C.POINTER(C.c_uint)
 F16_MAX = 65504.0
 # bits of an f16x3 range-guard word (pope_hip.h POPE_RANGE_*)
@@ -148,6 +158,8 @@ PROTOTYPES = {
     "pope_resnetfpn_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_resnetfpn_forward_f32": (C.c_int, [C.POINTER(ResnetFpnWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_conv_layer_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
+    "pope_conv_layer_f32": (C.c_int, [C.POINTER(ConvLayerArgs), C.c_void_p]),
     "pope_fine_preprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "pope_fine_preprocess_f32": (C.c_int, [C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 3

@@ -2,6 +2,7 @@
 // of the public structs into the launchers' parameters.  No allocation, no synchronisation.  (The ViT forward: vit_forward.hip.)
 #include "../../include/pope_hip.h"
 #include "common.h"
+#include "conv_layer.h"
 #include "kernels.h"
 #include "linear.h"
 #include "stream_device.h"
@@ -372,6 +373,19 @@ int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float
     p.ln_eps = ln_eps; p.ws = workspace; p.ws_bytes = workspace_bytes; p.range_flag = range_flag;
     p.x_mask = x_mask; p.source_mask = source_mask;
     return pope_launch_loftr_layer(p, static_cast<hipStream_t>(stream));
+}
+
+// one layer of the ResNet-FPN forward (or the SAM neck's 3 x 3) through the layer functions the models call (conv_layer.h);
+// checked before the stream's device is touched
+size_t pope_conv_layer_scratch_bytes(int form, int n, int H, int W, int cch, int taps) {
+    return pope_conv_layer_scratch(form, n, H, W, cch, taps);
+}
+
+int pope_conv_layer_f32(const pope_conv_layer_args* args, void* stream) {
+    if (!args) return POPE_ERR_ARG;
+    if (const int rc = pope_conv_layer_check(*args)) return rc;
+    StreamDevice on_device(stream);
+    return pope_launch_conv_layer(*args, static_cast<hipStream_t>(stream));
 }
 
 size_t pope_resnetfpn_workspace_bytes(int n, int H, int W) {

@@ -9,8 +9,10 @@
 // host (pope_amd/loftr.py), ReLU / LeakyReLU / the BasicBlock shortcut are the GEMM's epilogue (EPI_CONV).
 // The three stride-2 layers (7x7 stem on the gray image, the first 3x3 and the 1x1 shortcut of layer2 / layer3) gather
 // their taps into planes rows first (their outputs are 4x smaller than their inputs), 1x1 convolutions are plain GEMMs
-// over the pixel rows, and the FPN's bilinear x2 (align_corners) + lateral add is one kernel that writes planes.
+// over the pixel rows, and the FPN's bilinear x2 (align_corners) + lateral add is the epilogue of the lateral convolution.
+// The GemmParams of every form and the one-layer launch sequences have names (conv_layer.h); pope_launch_conv_layer runs one of them.
 #include "common.h"
+#include "conv_layer.h"
 #include "kernels.h"
 
 namespace {
@@ -102,19 +104,17 @@ __global__ __launch_bounds__(256) void zero_border_kernel(u32x4* __restrict__ bu
     }
 }
 
-// FPN merge (resnet_fpn.py:109-115): out = lateral + bilinear_x2(src, align_corners=True), written as planes into the
+// FPN merge (resnet_fpn.py:109-115) of the fp32 mode: out = lateral + bilinear_x2(src, align_corners=True), written into the
 // interior of a zero-bordered tensor.  lateral [n, Hp, Wp, ldl] fp32, src [n, Hsp, Wsp, lds] fp32 (half resolution,
-// both zero-bordered), out planes [n, Hp, Wp, Cp]; channels c < C in groups of four (C % 4 == 0).
-template <bool PLANES>   // false: fp32 rows [.., Cp]
-__global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* __restrict__ lat, int ldl, const float* __restrict__ src,
-                                                                  int lds, _Float16* __restrict__ out, int Cp, int C, int n, int Hp,
-                                                                  int Wp, unsigned* range_flag) {
+// both zero-bordered), out fp32 rows [n, Hp, Wp, Cp]; channels c < C in groups of four (C % 4 == 0).  The f16x3 mode has this
+// arithmetic, term for term, in the lateral convolution's epilogue (gemm_planes.hip EPI_CONV_UP).
+__global__ __launch_bounds__(256) void upsample_add_f32_kernel(const float* __restrict__ lat, int ldl, const float* __restrict__ src, int lds,
+                                                               float* __restrict__ out, int Cp, int C, int n, int Hp, int Wp) {
     const int H = Hp - 2, W = Wp - 2, Hs = H / 2, Ws = W / 2, Hsp = Hs + 2, Wsp = Ws + 2;
     const int groups = Cp / 4;   // the channel padding (C <= c < Cp) is written as zeros
     // torch's area_pixel_compute_scale for align_corners: (in - 1) / (out - 1), 0 for a single output pixel
     const float sh = H > 1 ? float(Hs - 1) / float(H - 1) : 0.f, sw = W > 1 ? float(Ws - 1) / float(W - 1) : 0.f;
     const long long total = (long long)n * H * W * groups;
-    float amax = 0.f;
     for (long long id = blockIdx.x * 256ll + threadIdx.x; id < total; id += 256ll * gridDim.x) {
         const int gidx = int(id % groups);
         const long long pix = id / groups;
@@ -128,15 +128,9 @@ __global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* _
             return *reinterpret_cast<const f32x4*>(src + (((size_t)b * Hsp + yy + 1) * Wsp + xx + 1) * lds + c);
         };
         const size_t prow = ((size_t)b * Hp + y + 1) * Wp + x + 1;
-        _Float16* o = out + prow * 2 * Cp + pope_planes_col(c);
-        float* of = reinterpret_cast<float*>(out) + prow * Cp + c;
+        float* of = out + prow * Cp + c;
         if (c >= C) {
-            if constexpr (PLANES) {
-                *reinterpret_cast<pope_f16x4*>(o) = pope_f16x4{0, 0, 0, 0};
-                *reinterpret_cast<pope_f16x4*>(o + 32) = pope_f16x4{0, 0, 0, 0};
-            } else {
-                *reinterpret_cast<f32x4*>(of) = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            *reinterpret_cast<f32x4*>(of) = f32x4{0.f, 0.f, 0.f, 0.f};
             continue;
         }
         const f32x4 v00 = at(y0, x0), v01 = at(y0, x1), v10 = at(y1, x0), v11 = at(y1, x1);
@@ -147,22 +141,16 @@ __global__ __launch_bounds__(256) void upsample_add_planes_kernel(const float* _
             // upsample_bilinear2d: h0lambda * (w0lambda * v00 + w1lambda * v01) + h1lambda * (w0lambda * v10 + w1lambda * v11)
             const float up = ly0 * (lx0 * v00[e] + lx1 * v01[e]) + ly1 * (lx0 * v10[e] + lx1 * v11[e]);
             v[e] = l[e] + up;
-            amax = fmaxf(amax, fabsf(v[e]));
-            if (!(v[e] == v[e])) amax = INFINITY;
         }
-        if constexpr (PLANES) {
-            pope_planes_store(out + prow * 2 * Cp, c, v * A_SCALE);
-        } else {
-            *reinterpret_cast<f32x4*>(of) = v;
-        }
+        *reinterpret_cast<f32x4*>(of) = v;
     }
-    if constexpr (PLANES) pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
 }
 
 struct Plan {
     int n, H, W;
     int Hp[4], Wp[4];           // zero-bordered grids at 1/2, 1/4, 1/8 (index 1..3)
     size_t rows[4];
+    ConvGrid grid(int level) const { return ConvGrid{n, Hp[level], Wp[level]}; }
 };
 inline Plan make_plan(int n, int H, int W) {
     Plan p = {};
@@ -183,7 +171,74 @@ constexpr BufSpec kBufs[NBUF] = {
     {2, 1152}, {2, 128}, {2, 224}, {2, 224}, {2, 224}, {2, 256}, {2, 256}, {2, 256}, {2, 224},
     {3, 2016}, {3, 224}, {3, 256}, {3, 256}, {3, 256}};
 
+// the router of a precision's GEMMs: gemm_f32.hip for POPE_PREC_F32_MFMA, gemm_planes.hip for planes and plain f16
+inline int launch_gemm(int precision, const GemmParams& g, hipStream_t stream) {
+    return precision == POPE_PREC_F32_MFMA ? pope_launch_gemm_nt_f32(g, stream) : pope_launch_gemm_planes(g, stream);
+}
+
 }  // namespace
+
+int pope_conv_zero_border(void* buf, const ConvGrid& grid, int pitch, hipStream_t stream) {
+    const long long total = (long long)grid.n * (2 * grid.Wp + 2 * (grid.Hp - 2)) * (pitch / 4);
+    hipLaunchKernelGGL(zero_border_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, static_cast<u32x4*>(buf), grid.n, grid.Hp,
+                       grid.Wp, pitch / 4);
+    return pope_check_launch();
+}
+
+int pope_conv3_layer(int precision, const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid, void* out_pl,
+                     float* out_f32, int out_pitch, float slope, const void* res, int res_pitch, bool zero_border, unsigned* range_flag,
+                     hipStream_t stream) {
+    const GemmParams g = pope_conv_gemm_params(precision, a, a_pitch, w, bias, 0, N, grid, true, out_pl, out_f32, out_pitch, slope, res,
+                                               res_pitch, range_flag);
+    POPE_TRY(launch_gemm(precision, g, stream));
+    return zero_border ? pope_conv_zero_border(out_pl ? out_pl : out_f32, grid, out_pitch, stream) : POPE_OK;
+}
+
+int pope_conv_s2_layer(int precision, const void* x, int x_pitch, const ConvGrid& in, int taps, const void* w, const float* bias, int N,
+                       void* gathered, void* out, int out_pitch, float slope, bool zero_border, unsigned* range_flag, hipStream_t stream) {
+    const ConvGrid og = in.half();
+    // straight from x's planes (gemm_plain.hip, CONV = 2) where the call fills a round of the CUs; else the taps are gathered: the same bits
+    const GemmParams s2 = pope_conv_s2_params(x, x_pitch, in, taps, w, bias, N, out, out_pitch, slope, range_flag);
+    if (precision == POPE_PREC_F16X3 && pope_wide_conv_s2_supported(s2)) {
+        POPE_TRY(pope_launch_gemm_planes(s2, stream));
+    } else {
+        const int cch = x_pitch / 32;
+        const long long total = (long long)og.rows() * taps * cch * 8;
+        hipLaunchKernelGGL(gather_s2_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, static_cast<const u32x4*>(x),
+                           static_cast<u32x4*>(gathered), in.n, in.Hp, in.Wp, cch, taps);
+        POPE_TRY(pope_check_launch());
+        const GemmParams g = pope_conv_gemm_params(precision, gathered, taps * x_pitch, w, bias, taps * x_pitch, N, og, false, out, nullptr,
+                                                   out_pitch, slope, nullptr, 0, range_flag);
+        POPE_TRY(launch_gemm(precision, g, stream));
+    }
+    return zero_border ? pope_conv_zero_border(out, og, out_pitch, stream) : POPE_OK;
+}
+
+int pope_conv1_up_layer(const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid, const float* up_src,
+                        int up_lds, void* out_pl, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream) {
+    GemmParams g = pope_conv_gemm_params(POPE_PREC_F16X3, a, a_pitch, w, bias, a_pitch, N, grid, false, out_pl, nullptr, out_pitch, slope,
+                                         nullptr, 0, range_flag);
+    pope_conv_up_params(g, up_src, up_lds, grid);
+    POPE_TRY(pope_launch_gemm_planes(g, stream));
+    return pope_conv_zero_border(out_pl, grid, out_pitch, stream);
+}
+
+int pope_conv_stem_layer(int precision, const float* img, int n, int H, int W, void* gathered, const void* w, const float* bias, int N,
+                         void* out, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream) {
+    const ConvGrid grid = {n, H / 2 + 2, W / 2 + 2};
+    const long long total = (long long)grid.rows() * 8;
+    if (precision == POPE_PREC_F32_MFMA)
+        hipLaunchKernelGGL(stem_gather_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
+                           H, W, range_flag);
+    else
+        hipLaunchKernelGGL(stem_gather_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
+                           H, W, range_flag);
+    POPE_TRY(pope_check_launch());
+    const GemmParams g = pope_conv_gemm_params(precision, gathered, 64, w, bias, 64, N, grid, false, out, nullptr, out_pitch, slope, nullptr, 0,
+                                               range_flag);
+    POPE_TRY(launch_gemm(precision, g, stream));
+    return pope_conv_zero_border(out, grid, out_pitch, stream);
+}
 
 size_t pope_resnetfpn_workspace(int n, int H, int W) {
     const Plan p = make_plan(n, H, W);
@@ -217,114 +272,51 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     // gemm_f32.hip (EPI_CONV, implicit 3x3 loader).  Its epilogue writes only the N real channels, so the channel padding
     // (196 -> 224) is cleared once up front; speed is not a goal of this path.
     if (f32 && hipMemsetAsync(q.ws, 0, pope_resnetfpn_workspace(q.n, q.H, q.W), stream) != hipSuccess) return POPE_ERR_LAUNCH;
-    // generic GEMM over pixel rows: out[rows, N] = act(A[rows, K] . W^T + bias)
-    auto gemm = [&](const void* a, int K, int wi, int N, int level, void* out_pl, float* out_f32, int out_pitch, float slope,
-                    const void* res_pl, int res_pitch, bool conv, int a_pitch, const float* up_src = nullptr, int up_lds = 0) -> int {
-        GemmParams g = {};
-        const int Wp = p.Wp[level];
-        const size_t shift = conv ? size_t(Wp) + 1 : 0;   // output (and shortcut) rows start at pixel Wp + 1
-        if (f32) {
-            g.A = static_cast<const float*>(a); g.W = q.wf[wi]; g.bias = q.b[wi];
-            g.lda = a_pitch; g.ldw = K; g.ldc = out_pitch;
-            g.M = int(p.rows[level] - (conv ? 2 * size_t(Wp) + 2 : 0)); g.N = N; g.K = K;
-            g.epilogue = EPI_CONV;
-            g.act_slope = slope;
-            g.C = (out_pl ? static_cast<float*>(out_pl) : out_f32) + shift * out_pitch;
-            if (res_pl) { g.res = static_cast<const float*>(res_pl) + shift * res_pitch; g.ldres = res_pitch; }
-            if (conv) g.conv_wp = Wp;
-            return pope_launch_gemm_nt_f32(g, stream);
-        }
-        g.a_pl = a; g.w_pl = q.w[wi]; g.bias = q.b[wi];
-        g.lda = a_pitch; g.ldw = K; g.ldc = out_pitch;
-        g.M = int(p.rows[level] - (conv ? 2 * size_t(Wp) + 2 : 0)); g.N = N; g.K = K;
-        g.epilogue = EPI_CONV;
-        g.act_slope = slope;
-        if (out_pl) g.c_pl = static_cast<char*>(out_pl) + shift * out_pitch * 4;
-        else g.C = out_f32 + shift * out_pitch;
-        if (res_pl) { g.res_pl = static_cast<const char*>(res_pl) + shift * res_pitch * 4; g.ldres_pl = res_pitch; }
-        if (conv) { g.conv_cch = a_pitch / 32; g.conv_wp = Wp; }
-        if (up_src) {
-            g.up_src = up_src; g.up_lds = up_lds; g.up_hp = p.Hp[level]; g.up_wp = Wp; g.up_n = q.n;
-            const int H = g.up_hp - 2, W = g.up_wp - 2, Hs = H / 2, Ws = W / 2;
-            g.up_sh = H > 1 ? float(Hs - 1) / float(H - 1) : 0.f;   // torch's area_pixel_compute_scale for align_corners
-            g.up_sw = W > 1 ? float(Ws - 1) / float(W - 1) : 0.f;
-            g.up_m_hw = unsigned((1ull << 32) / (unsigned long long)(g.up_hp) / (unsigned long long)(g.up_wp));
-            g.up_m_w = unsigned((1ull << 32) / (unsigned long long)(g.up_wp));
-        }
-        g.range_flag = q.range_flag; g.range_bit = POPE_RANGE_INPUT;
-        g.nbatch = 1;
-        return pope_launch_gemm_planes(g, stream);
-    };
-    auto zero_border = [&](void* b, int level, int pitch) -> int {
-        const long long total = (long long)q.n * (2 * p.Wp[level] + 2 * (p.Hp[level] - 2)) * (pitch / 4);
-        hipLaunchKernelGGL(zero_border_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, static_cast<u32x4*>(b), q.n,
-                           p.Hp[level], p.Wp[level], pitch / 4);
-        return pope_check_launch();
-    };
+    const int prec = q.precision;
+    unsigned* const flag = q.range_flag;
+    auto wt = [&](int wi) -> const void* { return f32 ? static_cast<const void*>(q.wf[wi]) : q.w[wi]; };
+    // the layer forms of conv_layer.h on the workspace buffers (one GEMM each, border rows zeroed after a planes output)
     auto conv3 = [&](Buf in, int wi, int N, int level, Buf out, float slope, int res /* Buf or -1 */) -> int {
-        const int ip = kBufs[in].pitch, op = kBufs[out].pitch;
-        int r = gemm(buf[in], 9 * ip, wi, N, level, buf[out], nullptr, op, slope, res >= 0 ? buf[res] : nullptr,
-                     res >= 0 ? kBufs[res].pitch : 0, true, ip);
-        return r ? r : zero_border(buf[out], level, op);
+        return pope_conv3_layer(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], N, p.grid(level), buf[out], nullptr, kBufs[out].pitch, slope,
+                                res >= 0 ? buf[res] : nullptr, res >= 0 ? kBufs[res].pitch : 0, true, flag, stream);
     };
-    auto gather = [&](Buf in, int level_in, Buf out, int taps) -> int {
-        const int cch = kBufs[in].pitch / 32;
-        const long long total = (long long)p.rows[level_in + 1] * taps * cch * 8;
-        hipLaunchKernelGGL(gather_s2_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(buf[in]),
-                           reinterpret_cast<u32x4*>(buf[out]), q.n, p.Hp[level_in], p.Wp[level_in], cch, taps);
-        return pope_check_launch();
+    // 3 x 3 or 1 x 1 -> an fp32 map (the FPN's outputs): no border pass
+    auto conv3_f32 = [&](Buf in, int wi, int N, int level, float* out, int out_pitch) -> int {
+        return pope_conv3_layer(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], N, p.grid(level), nullptr, out, out_pitch, 1.f, nullptr, 0,
+                                false, flag, stream);
+    };
+    auto conv1_f32 = [&](Buf in, int K, int wi, int N, int level, float* out, int out_pitch) -> int {
+        return launch_gemm(prec, pope_conv_gemm_params(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], K, N, p.grid(level), false, nullptr, out,
+                                                       out_pitch, 1.f, nullptr, 0, flag), stream);
     };
     // BasicBlock (resnet_fpn.py:15-40) with stride 1: x -> t -> y; returns with the block output in `y`
     auto block_s1 = [&](Buf x, Buf t, Buf y, int w0, int N, int level) -> int {
         int r = conv3(x, w0, N, level, t, 0.f, -1);
         return r ? r : conv3(t, w0 + 1, N, level, y, 0.f, x);
     };
-    // BasicBlock with stride 2: x (level L) -> gathered taps -> t; shortcut 1x1 stride 2 -> s; y = relu(conv2(t) + s)
-    // stride-2 convolution of x (level_in) -> out (level_in + 1) straight from x's planes (gemm_plain.hip, CONV = 2) where the call
-    // fills a round of the CUs; returns 1 when the shape is not served (the caller gathers the taps instead: the same bits)
-    auto conv_s2_implicit = [&](Buf x, int level_in, int taps, int wi, int N, Buf out, float slope) -> int {
-        if (f32) return 1;
-        const int lo = level_in + 1;
-        GemmParams g = {};
-        g.a_pl = buf[x]; g.w_pl = q.w[wi]; g.bias = q.b[wi];
-        g.lda = kBufs[x].pitch; g.ldw = taps * kBufs[x].pitch; g.ldc = kBufs[out].pitch;
-        g.M = int(p.rows[lo]); g.N = N; g.K = taps * kBufs[x].pitch;
-        g.epilogue = EPI_CONV; g.act_slope = slope; g.c_pl = buf[out];
-        g.conv_cch = kBufs[x].pitch / 32; g.conv_wp = p.Wp[level_in];
-        g.conv_s2_taps = taps; g.conv_s2_hpi = p.Hp[level_in]; g.conv_s2_hpo = p.Hp[lo]; g.conv_s2_wpo = p.Wp[lo];
-        g.conv_s2_in_rows = int(p.rows[level_in]);
-        g.range_flag = q.range_flag; g.range_bit = POPE_RANGE_INPUT; g.nbatch = 1;
-        if (!pope_wide_conv_s2_supported(g)) return 1;
-        return pope_launch_gemm_planes(g, stream);
-    };
+    // BasicBlock with stride 2: x (level L) -> t (3 x 3 stride 2, border rows zeroed); shortcut 1 x 1 stride 2 -> s;
+    // y = relu(conv2(t) + s).  g9 / g1 hold the gathered taps where the implicit route does not serve the call.
     auto block_s2 = [&](Buf x, int level_in, Buf g9, Buf g1, Buf t, Buf s, Buf y, int w0, int N) -> int {
         const int lo = level_in + 1;
-        int r = conv_s2_implicit(x, level_in, 9, w0, N, t, 0.f);
-        if (r == 1) {
-            r = gather(x, level_in, g9, 9);
-            if (!r) r = gemm(buf[g9], kBufs[g9].pitch, w0, N, lo, buf[t], nullptr, kBufs[t].pitch, 0.f, nullptr, 0, false, kBufs[g9].pitch);
-        }
-        if (!r) r = zero_border(buf[t], lo, kBufs[t].pitch);
+        int r = pope_conv_s2_layer(prec, buf[x], kBufs[x].pitch, p.grid(level_in), 9, wt(w0), q.b[w0], N, buf[g9], buf[t], kBufs[t].pitch, 0.f,
+                                   true, flag, stream);
         if (r) return r;
-        r = conv_s2_implicit(x, level_in, 1, w0 + 2, N, s, 1.f);
-        if (r == 1) {
-            r = gather(x, level_in, g1, 1);
-            if (!r) r = gemm(buf[g1], kBufs[g1].pitch, w0 + 2, N, lo, buf[s], nullptr, kBufs[s].pitch, 1.f, nullptr, 0, false, kBufs[g1].pitch);
-        }
+        r = pope_conv_s2_layer(prec, buf[x], kBufs[x].pitch, p.grid(level_in), 1, wt(w0 + 2), q.b[w0 + 2], N, buf[g1], buf[s], kBufs[s].pitch,
+                               1.f, false, flag, stream);
         return r ? r : conv3(t, w0 + 1, N, lo, y, 0.f, s);
+    };
+    // the fp32 mode's FPN merge: lateral map + bilinear x2 of the coarser map -> fp32 rows, border rows zeroed
+    auto upsample_add = [&](Buf lat, const float* src, int lds, Buf out, int C, int level) -> int {
+        const int pitch = kBufs[out].pitch;
+        const long long total = (long long)q.n * (p.Hp[level] - 2) * (p.Wp[level] - 2) * (pitch / 4);
+        hipLaunchKernelGGL(upsample_add_f32_kernel, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[lat]),
+                           kBufs[lat].pitch, src, lds, reinterpret_cast<float*>(buf[out]), pitch, C, q.n, p.Hp[level], p.Wp[level]);
+        int r = pope_check_launch();
+        return r ? r : pope_conv_zero_border(buf[out], p.grid(level), pitch, stream);
     };
 
     // stem (resnet_fpn.py:60-62,101)
-    {
-        const long long total = (long long)p.rows[1] * 8;
-        if (f32) hipLaunchKernelGGL(stem_gather_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.img,
-                                    reinterpret_cast<_Float16*>(buf[G0]), q.n, q.H, q.W, q.range_flag);
-        else hipLaunchKernelGGL(stem_gather_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, q.img,
-                                reinterpret_cast<_Float16*>(buf[G0]), q.n, q.H, q.W, q.range_flag);
-        if ((rc = pope_check_launch())) return rc;
-    }
-    if ((rc = gemm(buf[G0], 64, 0, 128, 1, buf[P1A], nullptr, 128, 0.f, nullptr, 0, false, 64))) return rc;
-    if ((rc = zero_border(buf[P1A], 1, 128))) return rc;
+    if ((rc = pope_conv_stem_layer(prec, q.img, q.n, q.H, q.W, buf[G0], wt(0), q.b[0], 128, buf[P1A], 128, 0.f, flag, stream))) return rc;
     // layer1 (1/2), layer2 (1/4), layer3 (1/8)
     if ((rc = block_s1(P1A, P1B, P1C, 1, 128, 1))) return rc;
     if ((rc = block_s1(P1C, P1A, P1B, 3, 128, 1))) return rc;             // x1 = P1B
@@ -333,44 +325,113 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if ((rc = block_s2(P2C, 2, G3, D3, P3A, P3C, P3B, 10, 256))) return rc;
     if ((rc = block_s1(P3B, P3A, P3C, 13, 256, 3))) return rc;            // x3 = P3C
     // FPN (resnet_fpn.py:107-117)
-    if ((rc = gemm(buf[P3C], 256, 15, 256, 3, nullptr, q.out_c, 256, 1.f, nullptr, 0, false, 256))) return rc;             // x3_out
+    if ((rc = conv1_f32(P3C, 256, 15, 256, 3, q.out_c, 256))) return rc;                                                   // x3_out
     // f16x3: the lateral 1 x 1 convolution's epilogue adds the bilinear x2 sample of the coarser map and writes the merged planes
     // (round 4: the fp32 lateral map and the upsample_add pass are gone — 1.9 GB of the call's fabric traffic at 48 images); the
     // fp32 mode keeps the two-step form
     if (!f32) {
-        if ((rc = gemm(buf[P2C], 224, 16, 256, 2, buf[T2A], nullptr, 256, 1.f, nullptr, 0, false, 224, q.out_c, 256))) return rc;
-        if ((rc = zero_border(buf[T2A], 2, 256))) return rc;
+        if ((rc = pope_conv1_up_layer(buf[P2C], 224, q.w[16], q.b[16], 256, p.grid(2), q.out_c, 256, buf[T2A], 256, 1.f, flag, stream))) return rc;
     } else {
-    if ((rc = gemm(buf[P2C], 224, 16, 256, 2, nullptr, reinterpret_cast<float*>(buf[F2]), 256, 1.f, nullptr, 0, false, 224))) return rc;
-    {
-        const long long total = (long long)q.n * (p.Hp[2] - 2) * (p.Wp[2] - 2) * (256 / 4);
-        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
-                                    256, q.out_c, 256, reinterpret_cast<_Float16*>(buf[T2A]), 256, 256, q.n, p.Hp[2], p.Wp[2], q.range_flag);
-        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F2]),
-                                256, q.out_c, 256, reinterpret_cast<_Float16*>(buf[T2A]), 256, 256, q.n, p.Hp[2], p.Wp[2], q.range_flag);
-        if ((rc = pope_check_launch())) return rc;
-        if ((rc = zero_border(buf[T2A], 2, 256))) return rc;
-    }
+        if ((rc = conv1_f32(P2C, 224, 16, 256, 2, reinterpret_cast<float*>(buf[F2]), 256))) return rc;
+        if ((rc = upsample_add(F2, q.out_c, 256, T2A, 256, 2))) return rc;
     }
     if ((rc = conv3(T2A, 17, 256, 2, T2B, 0.01f, -1))) return rc;
-    if ((rc = gemm(buf[T2B], 9 * 256, 18, 196, 2, nullptr, reinterpret_cast<float*>(buf[X2O]), 224, 1.f, nullptr, 0, true, 256))) return rc;
+    if ((rc = conv3_f32(T2B, 18, 196, 2, reinterpret_cast<float*>(buf[X2O]), 224))) return rc;
     if (!f32) {
-        if ((rc = gemm(buf[P1B], 128, 19, 196, 1, buf[T1A], nullptr, 224, 1.f, nullptr, 0, false, 128, reinterpret_cast<const float*>(buf[X2O]), 224))) return rc;
-        if ((rc = zero_border(buf[T1A], 1, 224))) return rc;
+        if ((rc = pope_conv1_up_layer(buf[P1B], 128, q.w[19], q.b[19], 196, p.grid(1), reinterpret_cast<const float*>(buf[X2O]), 224, buf[T1A],
+                                      224, 1.f, flag, stream)))
+            return rc;
     } else {
-    if ((rc = gemm(buf[P1B], 128, 19, 196, 1, nullptr, reinterpret_cast<float*>(buf[F1]), 224, 1.f, nullptr, 0, false, 128))) return rc;
-    {
-        const long long total = (long long)q.n * (p.Hp[1] - 2) * (p.Wp[1] - 2) * (224 / 4);
-        if (f32) hipLaunchKernelGGL(upsample_add_planes_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
-                                    224, reinterpret_cast<const float*>(buf[X2O]), 224, reinterpret_cast<_Float16*>(buf[T1A]), 224, 196, q.n,
-                                    p.Hp[1], p.Wp[1], q.range_flag);
-        else hipLaunchKernelGGL(upsample_add_planes_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, reinterpret_cast<const float*>(buf[F1]),
-                                224, reinterpret_cast<const float*>(buf[X2O]), 224, reinterpret_cast<_Float16*>(buf[T1A]), 224, 196, q.n,
-                                p.Hp[1], p.Wp[1], q.range_flag);
-        if ((rc = pope_check_launch())) return rc;
-        if ((rc = zero_border(buf[T1A], 1, 224))) return rc;
-    }
+        if ((rc = conv1_f32(P1B, 128, 19, 196, 1, reinterpret_cast<float*>(buf[F1]), 224))) return rc;
+        if ((rc = upsample_add(F1, reinterpret_cast<const float*>(buf[X2O]), 224, T1A, 196, 1))) return rc;
     }
     if ((rc = conv3(T1A, 20, 196, 1, T1B, 0.01f, -1))) return rc;
-    return gemm(buf[T1B], 9 * 224, 21, 128, 1, nullptr, q.out_f, 128, 1.f, nullptr, 0, true, 224);                         // x1_out
+    return conv3_f32(T1B, 21, 128, 1, q.out_f, 128);                                                                       // x1_out
+}
+
+// ---- pope_conv_layer_f32: one of the layer forms above on the caller's buffers ----------------------------------------------------
+namespace {
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// every kernel addresses its buffers through 32-bit byte offsets, a tile of rows past the end included
+inline bool fits32(size_t rows, size_t pitch) { return (rows + 256) * pitch * 4 < (size_t(1) << 32) - 512; }
+
+}  // namespace
+
+size_t pope_conv_layer_scratch(int form, int n, int H, int W, int cch, int taps) {
+    if (n <= 0 || H <= 0 || W <= 0 || cch < 0 || taps < 0) return 0;
+    const size_t out_rows = size_t(n) * (H / 2 + 2) * (W / 2 + 2);
+    if (form == POPE_CONV_S2) return out_rows * taps * cch * 128;   // the gathered taps
+    if (form == POPE_CONV_STEM) return out_rows * 256;              // 49 taps in two chunks
+    return 0;
+}
+
+int pope_conv_layer_check(const pope_conv_layer_args& a) {
+    const int form = a.form, prec = a.precision;
+    if (form != POPE_CONV3 && form != POPE_CONV_S2 && form != POPE_CONV1_UP && form != POPE_CONV_STEM) return POPE_ERR_ARG;
+    if (prec != POPE_PREC_F16X3) {
+        if (prec == POPE_PREC_F32_MFMA ? form != POPE_CONV3 && form != POPE_CONV_STEM : prec != POPE_PREC_F16 || form != POPE_CONV3)
+            return POPE_ERR_ARG;
+    }
+    const bool f32 = prec == POPE_PREC_F32_MFMA;
+    if (a.n < 1 || a.H < 1 || a.W < 1 || a.N < 4 || (a.N & 3) || a.N > 256) return POPE_ERR_ARG;
+    if (form != POPE_CONV3 && ((a.H | a.W) & 1)) return POPE_ERR_ARG;   // stride 2 halves the grid; CONV1_UP doubles one (and needs Wp >= 4)
+    const bool stem = form == POPE_CONV_STEM, s2 = form == POPE_CONV_S2;
+    if (stem ? a.cch != 0 || a.taps != 0 : a.cch < 1) return POPE_ERR_ARG;
+    if (s2 ? a.taps != 9 && a.taps != 1 : a.taps != 0) return POPE_ERR_ARG;
+    const int taps = form == POPE_CONV3 ? 9 : s2 ? a.taps : 1;
+    if (!stem && taps * a.cch < 2) return POPE_ERR_ARG;                  // the routers' minimum: two K-steps
+    if (!a.a || !a.w || !aligned16(a.a) || !aligned16(a.w) || (a.bias && !aligned16(a.bias))) return POPE_ERR_ARG;
+    const ConvGrid in = {a.n, a.H + 2, a.W + 2};
+    const ConvGrid out = form == POPE_CONV3 || form == POPE_CONV1_UP ? in : in.half();
+    const size_t pitch_in = stem ? 64 : size_t(32) * a.cch;
+    if (!stem && (a.a_rows < in.rows() || !fits32(in.rows(), pitch_in))) return POPE_ERR_ARG;
+    if (stem && size_t(a.n) * a.H * a.W * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
+    if (!fits32(256, size_t(taps) * pitch_in)) return POPE_ERR_ARG;      // the weight rows
+    // outputs
+    if ((a.out_planes == nullptr) == (a.out_f32 == nullptr)) return POPE_ERR_ARG;
+    if (a.out_planes) {
+        if (f32 || prec == POPE_PREC_F16 || a.ldc != ((a.N + 31) & ~31) || !aligned16(a.out_planes)) return POPE_ERR_ARG;
+    } else {
+        if (s2 || form == POPE_CONV1_UP || (stem && !f32)) return POPE_ERR_ARG;   // planes-only forms
+        if (a.ldc < a.N || (a.ldc & 3) || !aligned16(a.out_f32)) return POPE_ERR_ARG;
+    }
+    if (!a.zero_border && (stem || (a.out_planes && !s2))) return POPE_ERR_ARG;   // the next layer reads the border as its padding
+    if (!fits32(out.rows(), size_t(a.ldc))) return POPE_ERR_ARG;
+    // the shortcut and the FPN source
+    if (a.res) {
+        if (form != POPE_CONV3 || prec == POPE_PREC_F16 || a.ldres < a.N || (a.ldres & (f32 ? 3 : 31)) || !aligned16(a.res)) return POPE_ERR_ARG;
+        if (!fits32(out.rows(), size_t(a.ldres))) return POPE_ERR_ARG;
+    }
+    if (form == POPE_CONV1_UP) {
+        if (!a.up_src || a.up_lds < a.N || (a.up_lds & 3) || !aligned16(a.up_src) || in.Wp < 4) return POPE_ERR_ARG;
+        if (!fits32(in.half().rows(), size_t(a.up_lds))) return POPE_ERR_ARG;
+    } else if (a.up_src) {
+        return POPE_ERR_ARG;
+    }
+    if (s2 || stem) {
+        if (!a.scratch || !aligned16(a.scratch) || !fits32(out.rows(), size_t(taps) * pitch_in)) return POPE_ERR_ARG;
+        if (a.scratch_bytes < pope_conv_layer_scratch(form, a.n, a.H, a.W, a.cch, a.taps)) return POPE_ERR_WORKSPACE;
+    }
+    return POPE_OK;
+}
+
+int pope_launch_conv_layer(const pope_conv_layer_args& a, hipStream_t stream) {
+    POPE_TRY(pope_conv_layer_check(a));
+    const ConvGrid in = {a.n, a.H + 2, a.W + 2};
+    const int pitch = 32 * a.cch;
+    switch (a.form) {
+        case POPE_CONV3:
+            return pope_conv3_layer(a.precision, a.a, pitch, a.w, a.bias, a.N, in, a.out_planes, a.out_f32, a.ldc, a.slope, a.res, a.ldres,
+                                    a.zero_border != 0, a.range_flag, stream);
+        case POPE_CONV_S2:
+            return pope_conv_s2_layer(a.precision, a.a, pitch, in, a.taps, a.w, a.bias, a.N, a.scratch, a.out_planes, a.ldc, a.slope,
+                                      a.zero_border != 0, a.range_flag, stream);
+        case POPE_CONV1_UP:
+            return pope_conv1_up_layer(a.a, pitch, a.w, a.bias, a.N, in, a.up_src, a.up_lds, a.out_planes, a.ldc, a.slope, a.range_flag, stream);
+        case POPE_CONV_STEM:
+            return pope_conv_stem_layer(a.precision, static_cast<const float*>(a.a), a.n, a.H, a.W, a.scratch, a.w, a.bias, a.N,
+                                        a.out_planes ? a.out_planes : static_cast<void*>(a.out_f32), a.ldc, a.slope, a.range_flag, stream);
+    }
+    return POPE_ERR_ARG;
 }

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
 #pragma unroll
                     for (int e = 0; e < 4; ++e)   // conv.hip:upsample_add_planes_kernel's expression, term for term
                         res[i][e] = ly0 * (lx0 * v00[e] + lx1 * v01[e]) + ly1 * (lx0 * v10[e] + lx1 * v11[e]);
-                    pxp += 4u;                                        // Wp >= 10: at most one carry each
+                    pxp += 4u;                                        // Wp >= 4 (args_ok): at most one carry each
                     const bool cx = pxp >= unsigned(Wp);
                     pxp -= cx ? unsigned(Wp) : 0u;
                     pyp += cx ? 1u : 0u;
@@ -687,7 +687,8 @@ bool args_ok(const GemmParams& g) {
                    g.N == 3 * g.sam_dim;
         case EPI_CONV:
             if (g.conv_cch > 0) return g.K == 9 * 32 * g.conv_cch && g.lda == 32 * g.conv_cch && g.conv_wp >= 3;
-            return !g.up_src || (out_planes && !g.res_pl);
+            // up_src: the epilogue walks four pixel rows ahead with ONE carry (up_wp >= 4) on a grid that doubles the source's
+            return !g.up_src || (out_planes && !g.res_pl && g.up_wp >= 4 && g.up_hp >= 4 && g.up_n > 0 && g.up_lds >= g.N && !(g.up_lds & 3));
     }
     return false;
 }

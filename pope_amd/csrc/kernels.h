@@ -89,8 +89,8 @@ struct GemmParams {
     // EPI_CONV with up_src (gemm_planes.hip; round 4): the FPN merge of resnet_fpn.py:109-115 in the lateral 1 x 1 convolution's
     // epilogue — output row R is pixel R of this level's zero-bordered grid [up_n, up_hp, up_wp]; the bilinear x2
     // (align_corners) sample of the half-resolution fp32 map up_src [up_n, (up_hp - 2) / 2 + 2, (up_wp - 2) / 2 + 2, up_lds] at
-    // that pixel is added before the activation.  Replaces conv.hip's upsample_add pass (same arithmetic, same bits) and the
-    // fp32 round trip of the lateral map.  Not together with res_pl.
+    // that pixel is added before the activation.  The arithmetic of conv.hip's upsample_add_f32_kernel (the fp32 mode's two-step
+    // form), term for term, without the fp32 round trip of the lateral map.  Not together with res_pl; up_wp >= 4.
     const float* up_src;
     int up_lds, up_hp, up_wp, up_n;
     float up_sh, up_sw;          // bilinear scales (Hs - 1) / (H - 1), (Ws - 1) / (W - 1) (0 for a single output row / column)

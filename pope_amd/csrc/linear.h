@@ -1,5 +1,5 @@
 // The GemmParams of a dense Linear, C = epi(A . W^T + bias [, gamma, res]), built in one place (host only).  Everything that
-// is not a plain Linear keeps its own builder: the convolutions (conv.hip, the SAM necks), EPI_SIM (match.hip), EPI_SAM_QKV
+// is not a plain Linear keeps its own builder: the convolutions (conv_layer.h), EPI_SIM (match.hip), EPI_SAM_QKV
 // (sam_attention.hip) and the patch gather EPI_POSB.
 #pragma once
 #include "kernels.h"

@@ -9,6 +9,7 @@
 // residual stream in both; POPE_PREC_F32_MFMA = fp32 operands everywhere (kernels: sam_f32.hip), the range guard's re-run.
 // What is new in this encoder is the attention: sam_attention.hip.
 #include "attention_common.h"
+#include "conv_layer.h"
 #include "kernels.h"
 #include "linear.h"
 #include <algorithm>
@@ -278,25 +279,10 @@ int pope_launch_sam_encoder(const SamEncArgs& q, hipStream_t stream) {
     };
     // the 3x3 convolution as a GEMM over the bordered pixels (conv.hip): LayerNorm2d's bordered operand -> t2
     auto conv3x3 = [&] {
-        GemmParams c = {};
-        const int Wp = g + 2;
-        const size_t shift = size_t(Wp) + 1;   // output row R is pixel R + Wp + 1 (conv.hip)
         const int occ = plain ? oc / 2 : oc;   // plain: column pairs
-        c.lda = occ; c.ldw = 9 * occ; c.ldc = oc;
-        c.M = int(L.brows - (2 * size_t(Wp) + 2)); c.N = oc; c.K = 9 * occ;
-        c.epilogue = EPI_CONV; c.act_slope = 1.0f;   // identity
-        c.C = t2 + shift * oc;
-        c.conv_wp = Wp;
-        if (f32) {
-            c.A = reinterpret_cast<const float*>(base + L.t1b32); c.W = static_cast<const float*>(w.neck2_wp);
-            return pope_launch_gemm_nt_f32(c, stream);
-        }
-        c.a_pl = t1_pl; c.w_pl = w.neck2_wp;
-        c.plain = plain;
-        c.conv_cch = occ / 32;
-        c.range_flag = flag; c.range_bit = POPE_RANGE_INPUT;
-        c.nbatch = 1;
-        return pope_launch_gemm_planes(c, stream);
+        const void* a = f32 ? static_cast<const void*>(base + L.t1b32) : t1_pl;
+        return pope_conv3_layer(w.precision, a, occ, w.neck2_wp, nullptr, oc, ConvGrid{B, g + 2, g + 2}, nullptr, t2, oc, 1.0f /* identity */,
+                                nullptr, 0, false, flag, stream);
     };
     auto norm2d_out = [&] {
         if (f32) return pope_launch_sam32_ln2d(t2, w.neck3_w, w.neck3_b, q.out, B, g, oc, neck_eps, false, stream);
