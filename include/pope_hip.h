@@ -351,6 +351,22 @@ int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w_host, 
                                         const float* x_mask, const float* source_mask,
                                         int n, int L, int S, int C, int nhead, float ln_eps, int precision,
                                         void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* The same layer with FullAttention (linear_attention.py:50-81, the config's attention = 'full') in place of the linear body:
+ * message = softmax(Q K^T / sqrt(D), over the S source rows) V per head, D = C / nhead; everything around it, the weights
+ * struct and the workspace are those of pope_loftr_encoder_layer_f32.  No masks: a padded query row is NaN in the reference.
+ * The softmax runs in fp32 under both precisions (S > 64: flash-style on the fp32 MFMA, online softmax, nothing of size
+ * L x S is stored; S <= 64: fp32 FMAs, one workgroup per 32 queries of a sequence); POPE_PREC_F16X3 writes the message as
+ * the merge GEMM's operand planes and ORs POPE_RANGE_QKV into range_flag when a scaled value leaves the f16 range.  Every
+ * output row is bit-identical whatever n.  POPE_ERR_ARG before any launch: null pointers, C not 128 / 256, nhead != 8,
+ * non-positive sizes, an unknown precision. */
+int pope_loftr_encoder_layer_full_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
+                                      int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                                      void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* The attention core of that layer alone: q[n L, C], kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32, 16-byte aligned
+ * -> out[n L, C] fp32 rows.  precision is validated (F32_MFMA or F16X3; both run the fp32 kernels); range_flag is not
+ * touched.  Same argument checks. */
+int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L, int S, int C, int nhead, int precision,
+                                  float* out, unsigned* range_flag, void* stream);
 
 /* ResNetFPN_8_2.forward — src/matcher/backbone/resnet_fpn.py:100-118 (BasicBlock :15-40), eval mode: the LoFTR
  * matcher's local-feature CNN.  gray[n,1,H,W] in [0,1], H and W multiples of 8.  Every convolution is an f16x3 planes

@@ -348,16 +348,10 @@ size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead) {
     return pope_loftr_layer_workspace(n, L, S, C, nhead);
 }
 
-int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
-                                 int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
-                                 unsigned* range_flag, void* stream) {
-    return pope_loftr_encoder_layer_masked_f32(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace,
-                                               workspace_bytes, range_flag, stream);
-}
-
-int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
-                                        const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
-                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+// the three layer entries: one parameter block, the attention body chosen by `attention` (LOFTR_ATTN_*)
+static int loftr_layer_call(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
+                            const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                            void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream, int attention) {
     if (!w || !x || !source || !workspace || n <= 0 || L <= 0 || S <= 0) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
     LoftrLayerParams p = {};
@@ -372,7 +366,39 @@ int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float
     p.norm1_w = w->norm1_w; p.norm1_b = w->norm1_b; p.norm2_w = w->norm2_w; p.norm2_b = w->norm2_b;
     p.ln_eps = ln_eps; p.ws = workspace; p.ws_bytes = workspace_bytes; p.range_flag = range_flag;
     p.x_mask = x_mask; p.source_mask = source_mask;
+    p.attention = attention;
     return pope_launch_loftr_layer(p, static_cast<hipStream_t>(stream));
+}
+
+int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
+                                 int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
+                                 unsigned* range_flag, void* stream) {
+    return pope_loftr_encoder_layer_masked_f32(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace,
+                                               workspace_bytes, range_flag, stream);
+}
+
+int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
+                                        const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    return loftr_layer_call(w, x, source, x_mask, source_mask, n, L, S, C, nhead, ln_eps, precision, workspace, workspace_bytes,
+                            range_flag, stream, LOFTR_ATTN_LINEAR);
+}
+
+int pope_loftr_encoder_layer_full_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
+                                      int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
+                                      unsigned* range_flag, void* stream) {
+    if ((C != 256 && C != 128) || nhead != 8 || (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3)) return POPE_ERR_ARG;
+    return loftr_layer_call(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace, workspace_bytes, range_flag,
+                            stream, LOFTR_ATTN_FULL);
+}
+
+int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L, int S, int C, int nhead, int precision, float* out,
+                                  unsigned* range_flag, void* stream) {
+    if (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
+    POPE_TRY(pope_loftr_full_attention_check(q, kv, n, L, S, C, nhead, out));
+    StreamDevice on_device(stream);
+    // both precisions run the fp32-MFMA kernel (small sequences: fp32 FMAs); range_flag is not touched with fp32 rows out
+    return pope_launch_loftr_full_attention(q, kv, n, L, S, C, nhead, false, out, range_flag, static_cast<hipStream_t>(stream));
 }
 
 // one layer of the ResNet-FPN forward (or the SAM neck's 3 x 3) through the layer functions the models call (conv_layer.h);

@@ -285,7 +285,14 @@ struct LoftrLayerParams {
     // source_mask [n, S] padded source rows' K and V; null = no mask (the unmasked kernels)
     const float* x_mask;
     const float* source_mask;
+    int attention;         // LOFTR_ATTN_LINEAR (0: a zeroed struct is the linear layer) | LOFTR_ATTN_FULL (softmax; no masks)
 };
+enum { LOFTR_ATTN_LINEAR = 0, LOFTR_ATTN_FULL = 1 };
+// Full softmax attention of the layer (loftr_attention.hip): q [n L, C], kv [n S, 2C] (k | v) fp32 -> the message [n L, C] as fp32
+// rows, or (planes) as activation planes with POPE_RANGE_QKV on a value outside the f16 range.  C = 256 / 128, H = 8.
+int pope_loftr_full_attention_check(const void* q, const void* kv, int n, int L, int S, int C, int H, const void* out);   // no HIP call
+int pope_launch_loftr_full_attention(const float* q, const float* kv, int n, int L, int S, int C, int H, bool planes, float* msg,
+                                     unsigned* range_flag, hipStream_t stream);
 // ResNet-FPN local-feature CNN of the LoFTR matcher (conv.hip; resnet_fpn.py:43-118)
 struct ResnetFpnParams {
     const float* img;          // [n, 1, H, W] gray in [0, 1]

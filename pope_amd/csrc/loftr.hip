@@ -7,6 +7,8 @@
 //     msg = (Q . KV) * 1 / (Q . Ksum + 1e-6) * S
 //     msg = LayerNorm(msg Wm^T)  (eps 1e-5)
 //     x  <- x + LayerNorm(relu(cat[x, msg] W0^T) W1^T)
+// With LoftrLayerParams::attention = LOFTR_ATTN_FULL the second and third line are the softmax attention of
+// linear_attention.py:50-81 instead, msg = softmax(q k^T / sqrt(D)) v per head: one launch (loftr_attention.hip), no masks.
 // The five projections run on the f16x3 planes GEMM (gemm_planes.hip: fp32-equivalent arithmetic, bias-free, the MLP's
 // ReLU in the epilogue, its output straight to planes); everything around them is small and HBM / launch bound:
 // attention is O(L) — the per-head D x D state is reduced over the source rows in chunks (fixed order: deterministic),
@@ -232,6 +234,9 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     if (!p.norm1_w || !p.norm1_b || !p.norm2_w || !p.norm2_b) return POPE_ERR_ARG;
     if (f32 ? (!p.q_w || !p.kv_w || !p.merge_w || !p.mlp0_w || !p.mlp1_w) : (!p.q_wp || !p.kv_wp || !p.merge_wp || !p.mlp0_wp || !p.mlp1_wp))
         return POPE_ERR_ARG;
+    const bool full = p.attention == LOFTR_ATTN_FULL;
+    if (!full && p.attention != LOFTR_ATTN_LINEAR) return POPE_ERR_ARG;
+    if (full && (p.x_mask || p.source_mask)) return POPE_ERR_ARG;   // a padded query row is NaN in the reference's FullAttention
     if (p.ws_bytes < pope_loftr_layer_workspace(p.n, p.L, p.S, C, H)) return POPE_ERR_WORKSPACE;
     const size_t rx = size_t(p.n) * p.L, rs = size_t(p.n) * p.S;
     if (rx > 0x7fffffffull / (2 * C) || rs > 0x7fffffffull / (2 * C)) return POPE_ERR_ARG;
@@ -278,27 +283,33 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     // 2. q = x Wq^T ; [k | v] = source [Wk ; Wv]^T
     POPE_TRY(gemm(xp, Wq, q, nullptr, int(rx), C, C, EPI_BIAS));
     POPE_TRY(gemm(self ? xp : sp, Wkv, kv, nullptr, int(rs), 2 * C, C, EPI_BIAS));
-    // 3. per-head state, 4. message
-    // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
+    // 3.-4. full attention: softmax(q k^T / sqrt(D)) v in one launch (loftr_attention.hip), the message where step 4 writes it
+    if (full) {
+        if (f32) msgp = msg;
+        POPE_TRY(pope_launch_loftr_full_attention(q, kv, p.n, p.L, p.S, C, H, !f32, static_cast<float*>(msgp), p.range_flag, stream));
+    } else {
+        // 3. per-head state, 4. message
+        // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
 #define LA_REDUCE(DD, MK) hipLaunchKernelGGL((linattn_reduce_kernel<DD, MK>), dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, \
                                              part, chunks, p.source_mask)
-    if (p.source_mask) { if (D == 32) LA_REDUCE(32, true); else LA_REDUCE(16, true); }
-    else { if (D == 32) LA_REDUCE(32, false); else LA_REDUCE(16, false); }
+        if (p.source_mask) { if (D == 32) LA_REDUCE(32, true); else LA_REDUCE(16, true); }
+        else { if (D == 32) LA_REDUCE(32, false); else LA_REDUCE(16, false); }
 #undef LA_REDUCE
-    hipLaunchKernelGGL(linattn_finish_kernel, dim3(p.n * H, (per + 255) / 256), dim3(256), 0, stream, part, chunks, per, kvf);
-    const int rpb = 16;
-    // (f16x3: the message is written as planes straight away; fp32 mode: plain rows)
+        hipLaunchKernelGGL(linattn_finish_kernel, dim3(p.n * H, (per + 255) / 256), dim3(256), 0, stream, part, chunks, per, kvf);
+        const int rpb = 16;
+        // (f16x3: the message is written as planes straight away; fp32 mode: plain rows)
 #define LA_APPLY(DD, PL, MK, DST) hipLaunchKernelGGL((linattn_apply_kernel<DD, PL, MK>), dim3(p.n, (p.L + rpb - 1) / rpb), dim3(256), 0, stream, q, \
                                                      kvf, p.L, C, H, p.S, 1e-6f, DST, rpb, p.range_flag, p.x_mask)
 #define LA_APPLY_D(PL, MK, DST) do { if (D == 32) LA_APPLY(32, PL, MK, DST); else LA_APPLY(16, PL, MK, DST); } while (0)
-    if (f32) {
-        if (p.x_mask) LA_APPLY_D(false, true, msg); else LA_APPLY_D(false, false, msg);
-        msgp = msg;
-    } else {
-        if (p.x_mask) LA_APPLY_D(true, true, static_cast<float*>(msgp)); else LA_APPLY_D(true, false, static_cast<float*>(msgp));
-    }
+        if (f32) {
+            if (p.x_mask) LA_APPLY_D(false, true, msg); else LA_APPLY_D(false, false, msg);
+            msgp = msg;
+        } else {
+            if (p.x_mask) LA_APPLY_D(true, true, static_cast<float*>(msgp)); else LA_APPLY_D(true, false, static_cast<float*>(msgp));
+        }
 #undef LA_APPLY_D
 #undef LA_APPLY
+    }
     // 5. merge (-> q buffer), 6. cat[x, LN1(merge)] as planes
     POPE_TRY(gemm(msgp, Wm, q, nullptr, int(rx), C, C, EPI_BIAS));
     const dim3 rows4(unsigned((rx + 3) / 4));

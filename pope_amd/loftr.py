@@ -251,16 +251,28 @@ class PositionEncodingSine(nn.Module):
         return x + self.code(x.shape[2], x.shape[3], x.device)
 
 
-# -------------------------------------------------------------------------------- linear-attention transformer
+# -------------------------------------------------------------------------------- LoFTR transformer
+ATTENTIONS = ("linear", "full")
+FULL_MASK_MSG = ("pope_amd: padding masks are not supported with attention='full': in the reference's FullAttention a padded "
+                 "query row is an all -inf softmax row, i.e. NaN, and from the second layer on every row is NaN")
+
+
+def _refuse_full_masks(attention, *masks):
+    if attention == "full" and any(m is not None for m in masks):
+        raise NotImplementedError(FULL_MASK_MSG)
+
+
 class LoFTREncoderLayer(nn.Module):
-    """loftr_module/transformer.py:7-58 with the linear attention of linear_attention.py:20-47.  The layer update is ONE
-    call into the HIP library (pope_loftr_encoder_layer_f32: five GEMMs + the O(L) linear-attention kernels + both
+    """loftr_module/transformer.py:7-58 with the linear attention of linear_attention.py:20-47 (attention='linear') or the
+    softmax attention of :50-81 ('full'; same parameters, no padding masks).  The layer update is ONE call into the HIP
+    library (pope_loftr_encoder_layer_f32 / pope_loftr_encoder_layer_full_f32: five GEMMs + the attention kernels + both
     LayerNorms); this module holds the parameters."""
 
     def __init__(self, d_model, nhead, attention="linear"):
         super().__init__()
-        if attention != "linear":
-            raise NotImplementedError("pope_amd: only linear attention (cvpr_ds_config.py:27,49)")
+        if attention not in ATTENTIONS:   # (the reference treats every string but 'linear' as full)
+            raise ValueError(f"pope_amd: attention must be 'linear' or 'full', got {attention!r}")
+        self.attention = attention
         self.dim, self.nhead = d_model // nhead, nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
@@ -304,7 +316,8 @@ class LoFTREncoderLayer(nn.Module):
     def update_(self, x, source, workspace, precision="f16x3", x_mask=None, source_mask=None):
         """In-place layer update of `x` [n, L, C] (fp32, contiguous, CUDA) against `source` (may be `x`); returns the
         call's range-flag word (device).  x_mask [n, L] / source_mask [n, S]: optional fp32 0 / 1 padding masks
-        (`_lib.padding_mask`)."""
+        (`_lib.padding_mask`; linear attention only)."""
+        _refuse_full_masks(self.attention, x_mask, source_mask)
         w = self._weights(precision)
         n, L, Cd = x.shape
         S = source.shape[1]
@@ -316,18 +329,20 @@ class LoFTREncoderLayer(nn.Module):
                     n, L, S, Cd, self.nhead, float(self.norm1.eps), _lib.PRECISIONS[precision], C.c_void_p(workspace.data_ptr()),
                     workspace.numel(), C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), "pope_loftr_encoder_layer_masked_f32")
             return flag
+        name = "pope_loftr_encoder_layer_full_f32" if self.attention == "full" else "pope_loftr_encoder_layer_f32"
         with _lib.on_device_of(x):
-            _lib.check(_lib.lib().pope_loftr_encoder_layer_f32(
+            _lib.check(getattr(_lib.lib(), name)(
                 C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), n, L, S, Cd, self.nhead,
                 float(self.norm1.eps), _lib.PRECISIONS[precision], C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), "pope_loftr_encoder_layer_f32")
+                C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), name)
         return flag
 
     @torch.no_grad()
     def forward(self, x, source, x_mask=None, source_mask=None):
         """The reference's single-layer call (transformer.py:35-58): returns the updated copy of `x`.  x_mask [n, L] and
         source_mask [n, S] are the optional padding masks of the query and source rows (linear_attention.py:35-41; either
-        one alone is allowed)."""
+        one alone is allowed; attention='full' takes none: NotImplementedError)."""
+        _refuse_full_masks(self.attention, x_mask, source_mask)
         require_cuda(x, "LoFTREncoderLayer")
         require_cuda(source, "LoFTREncoderLayer")
         policy = ON_OVERFLOW
@@ -349,13 +364,15 @@ class LoFTREncoderLayer(nn.Module):
 
 class LocalFeatureTransformer(nn.Module):
     """loftr_module/transformer.py:61-106; 'cross' layers update feat0 first and feed the NEW feat0 into
-    the feat1 update (:101-102).  Every layer update is a HIP call; a range-guard event (weight or activation outside the
+    the feat1 update (:101-102).  config['attention'] = 'linear' | 'full' selects the layers' attention body (coarse and fine
+    may differ).  Every layer update is a HIP call; a range-guard event (weight or activation outside the
     f16x3 range) re-runs the whole transformer on the fp32 MFMA, with a warning."""
 
     def __init__(self, config):
         super().__init__()
         self.config = config
         self.d_model, self.nhead, self.layer_names = config["d_model"], config["nhead"], config["layer_names"]
+        self.attention = config["attention"]
         if self.d_model not in (128, 256) or self.nhead != 8:
             raise NotImplementedError("pope_amd: the HIP LoFTR layer is built for d_model 256 / 128 with 8 heads (cvpr_ds_config.py:21-49)")
         for name in self.layer_names:
@@ -405,7 +422,8 @@ class LocalFeatureTransformer(nn.Module):
     @torch.no_grad()
     def forward(self, feat0, feat1, mask0=None, mask1=None):
         """mask0 [n, L], mask1 [n, S]: optional padding masks of the two streams (transformer.py:85-106; either alone is
-        allowed)."""
+        allowed; attention='full' takes none: NotImplementedError)."""
+        _refuse_full_masks(self.attention, mask0, mask1)
         assert self.d_model == feat0.size(2), "the feature number of src and transformer must be equal"
         require_cuda(feat0, "LocalFeatureTransformer")
         require_cuda(feat1, "LocalFeatureTransformer")

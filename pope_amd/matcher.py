@@ -232,8 +232,9 @@ class Matcher(nn.Module):
         The f16x3 range flags of the captured launches are read after the replay (one synchronisation, where the eager
         path has two); a raised flag retires the graph and the eager path — with its warnings and fp32 re-runs — takes over."""
         from . import loftr
-        if not (self.use_graph and im0.size(0) > 0 and im0.dtype == torch.float32 and im1.dtype == torch.float32
-                and not torch.cuda.is_current_stream_capturing()):
+        # (full attention: always eager — its front end is not captured)
+        if not (self.use_graph and self.loftr_coarse.attention == "linear" and im0.size(0) > 0
+                and im0.dtype == torch.float32 and im1.dtype == torch.float32 and not torch.cuda.is_current_stream_capturing()):
             return self._features(im0, im1)
         # a captured graph has the device pointers of the weight planes / folded BatchNorm matrices baked in, and any edit of
         # a parameter or buffer makes the eager path rebuild (and free) them: the key carries every tensor's address and
@@ -280,6 +281,9 @@ class Matcher(nn.Module):
     @torch.no_grad()
     def forward(self, data, only_att_fea=False):
         im0, im1 = data["image0"], data["image1"]
+        if "mask0" in data and self.loftr_coarse.attention == "full":   # before the device check: no stage has run
+            from . import loftr
+            raise NotImplementedError(loftr.FULL_MASK_MSG)
         require_cuda(im0, "Matcher")
         require_cuda(im1, "Matcher")
         n = im0.size(0)

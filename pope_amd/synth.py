@@ -464,6 +464,50 @@ def masked_xfmr_case():
     return f0, f1, m0.flatten(1), m1.flatten(1)
 
 
+# ---- LoFTR layers with full (softmax) attention ---------------------------------------------------------------------
+# name: (stage, layer_names (None: ONE layer call, layers.0), n, L, S, seed, taps of the two outputs as (dim, step))
+LOFTR_FULL_CASES = {
+    "layer_self": ("coarse", None, 2, 200, 200, 41, ((1, 4), None)),
+    "layer_cross": ("coarse", None, 2, 80, 200, 42, ((1, 1), None)),
+    "coarse_xfmr": ("coarse", ["self", "cross"] * 2, 2, 80, 200, 43, ((1, 1), (1, 4))),
+    "fine_xfmr": ("fine", ["self", "cross"], 37, 25, 25, 44, ((0, 4), (0, 4))),
+}
+
+
+def loftr_full_case(name):
+    """Inputs of tests/golden/loftr_full.npz (scripts/gen_golden_loftr_full.py): dict(stage 'coarse' | 'fine', layer_names —
+    None for one call of layers.0 —, feat0 [n, L, C], feat1 [n, S, C] or None (the layer updates feat0 against itself), taps:
+    the (dim, step) stride with which each stored output is sampled).  Inputs are 3 * randn: under
+    `synthetic_matcher_state_dict(0)` the softmax scores then have a standard deviation of ~9 and the median largest
+    probability of a row is 0.84, so an online softmax really moves its running maximum."""
+    stage, names, n, L, S, seed, taps = LOFTR_FULL_CASES[name]
+    C = 256 if stage == "coarse" else 128
+    g = torch.Generator().manual_seed(seed)
+    f0 = 3.0 * torch.randn(n, L, C, generator=g)
+    f1 = None if names is None and name.endswith("self") else 3.0 * torch.randn(n, S, C, generator=g)
+    return {"stage": stage, "layer_names": names, "feat0": f0, "feat1": f1, "taps": taps}
+
+
+def loftr_full_tap(t, tap):
+    """The stored sample of an output of `loftr_full_case`: every step-th index along dim."""
+    dim, step = tap
+    return t[:, ::step] if dim == 1 else t[::step]
+
+
+def loftr_full_matcher_case(name):
+    """Image pairs of tests/golden/loftr_full_128.npz (Matcher with both transformers on full attention, thr 1e-3):
+    'pairs128' = synthetic_gray_pairs(2, 128, 128, seed=21); '96x128_vs_128x96' = one pair of different shapes, image1 a fresh
+    texture with a 96 x 96 region of image0 pasted 16 rows lower."""
+    if name == "pairs128":
+        return synthetic_gray_pairs(2, 128, 128, seed=21)
+    if name == "96x128_vs_128x96":
+        i0 = synthetic_gray_pairs(1, 96, 128, seed=21)[0]
+        i1 = synthetic_gray_pairs(1, 128, 96, seed=22)[0]
+        i1[:, :, 16:112, :] = i0[:, :, :, 16:112]
+        return i0, i1.contiguous()
+    raise KeyError(name)
+
+
 # ---- SAM prompt encoder + mask decoder ---------------------------------------------------------------------------------
 def synthetic_sam_decoder_state_dict(seed=0):
     """Seeded synthetic weights in the layout of a `Sam` checkpoint's `prompt_encoder.*` and `mask_decoder.*` keys
