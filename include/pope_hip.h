@@ -462,6 +462,21 @@ int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0_hos
                              int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
                              const float* merge_b, int precision, float* out, void* workspace, size_t workspace_bytes,
                              unsigned* range_flag, void* stream);
+/* The same with SHARED map-0 rows (one reference image matched against many crops): feat_f0 has n0 rows instead of one per
+ * pair, and the windows of match m in map 0 are read at row ref0_of_pair[b_ids[m]].  ref0_of_pair: int64[n] (DEVICE), n =
+ * the number of pairs; feat_c0 stays [n, L, Cc] and indexed by b_ids[m] (it is the per-pair transformer output), and so
+ * does everything of stream 1.  A pair outside [0, n) and a row outside [0, n0) are clamped on the device (a wrong window,
+ * never a read outside the map).  ref0_of_pair = NULL: pope_fine_preprocess_f32 (n, n0 unused); otherwise n, n0 >= 1.
+ * n < 0, n0 < 0 and null feature / id / weight / out / workspace pointers return POPE_ERR_ARG before any HIP call.  Same
+ * workspace query. */
+int pope_fine_preprocess_indexed_f32(const float* feat_f0, const long long* strides0_host, int H0, int W0, int wc0,
+                                     const float* feat_f1, const long long* strides1_host, int H1, int W1, int wc1,
+                                     const float* feat_c0, const float* feat_c1, int L, int S, int Cc, int Cf,
+                                     const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
+                                     int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
+                                     const float* merge_b, int precision, float* out, void* workspace,
+                                     size_t workspace_bytes, unsigned* range_flag, const long long* ref0_of_pair, int n,
+                                     int n0, void* stream);
 /* FineMatching.forward + get_fine_match — src/matcher/utils/fine_matching.py:15-74 for M > 0: correlation of the
  * centre of window 0 with window 1 (temperature 1/sqrt(C)), softmax, expectation over linspace(-1,1,Wn)^2 as (x, y)
  * and the summed standard deviation -> expec_f[M,3]; mkpts1_f[M,2] = mkpts1_c + expec_xy * (Wn/2) * scale_px

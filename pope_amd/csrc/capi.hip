@@ -441,9 +441,25 @@ int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0, in
                              int S, int Cc, int Cf, const long long* b_ids, const long long* i_ids, const long long* j_ids, int M, int Wn,
                              int stride, const void* down_wp, const float* down_b, const void* merge_wp, const float* merge_b,
                              int precision, float* out, void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    return pope_fine_preprocess_indexed_f32(feat_f0, strides0, H0, W0, wc0, feat_f1, strides1, H1, W1, wc1, feat_c0, feat_c1, L, S, Cc, Cf,
+                                            b_ids, i_ids, j_ids, M, Wn, stride, down_wp, down_b, merge_wp, merge_b, precision, out,
+                                            workspace, workspace_bytes, range_flag, nullptr, 0, 0, stream);
+}
+
+int pope_fine_preprocess_indexed_f32(const float* feat_f0, const long long* strides0, int H0, int W0, int wc0, const float* feat_f1,
+                                     const long long* strides1, int H1, int W1, int wc1, const float* feat_c0, const float* feat_c1, int L,
+                                     int S, int Cc, int Cf, const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
+                                     int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
+                                     const float* merge_b, int precision, float* out, void* workspace, size_t workspace_bytes,
+                                     unsigned* range_flag, const long long* ref0_of_pair, int n, int n0, void* stream) {
+    // the checks that need no device come first: a bad call returns before any HIP call
+    if (n < 0 || n0 < 0 || (ref0_of_pair && (n == 0 || n0 == 0))) return POPE_ERR_ARG;
+    if (!feat_f0 || !feat_f1 || !feat_c0 || !feat_c1 || !b_ids || !i_ids || !j_ids || !down_wp || !merge_wp || !out || !workspace)
+        return POPE_ERR_ARG;
     StreamDevice on_device(stream);
     if (!strides0 || !strides1 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0 || wc0 <= 0 || wc1 <= 0 || L <= 0 || S <= 0) return POPE_ERR_ARG;
     FinePreParams q = {};
+    q.ref0_of_pair = ref0_of_pair; q.n_pairs = n; q.n0 = n0;
     q.f0 = feat_f0; q.f1 = feat_f1;
     for (int i = 0; i < 4; ++i) { q.s0[i] = strides0[i]; q.s1[i] = strides1[i]; }
     q.H0 = H0; q.W0 = W0; q.H1 = H1; q.W1 = W1; q.wc0 = wc0; q.wc1 = wc1;

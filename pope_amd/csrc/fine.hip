@@ -50,13 +50,16 @@ __global__ __launch_bounds__(256) void fine_gather_coarse_kernel(const float* __
 
 // rows [2M * WW, 2 Cf] of the merge_feat input as planes: columns [0, Cf) = window position k of match m in the fine
 // map of its stream (zero outside the map), columns [Cf, 2 Cf) = the match's down-projected coarse feature.  The fine
-// maps are addressed through element strides (NCHW tensors and NHWC views alike).
+// maps are addressed through element strides (NCHW tensors and NHWC views alike).  ref0 != nullptr (shared references): map 0 has
+// n0 rows and pair b reads row ref0[b]; the pair and the row are clamped to [0, n_pairs) / [0, n0), so a bad index reads a wrong
+// window, never outside the map.
 struct FineMap { const float* p; long long sn, sc, sh, sw; int H, W, wc; };
 template <bool PLANES>
 __global__ __launch_bounds__(256) void fine_gather_windows_kernel(FineMap f0, FineMap f1, const float* __restrict__ c_win,
                                                                   const long long* __restrict__ b_ids, const long long* __restrict__ i_ids,
                                                                   const long long* __restrict__ j_ids, int M, int Wn, int stride, int Cf,
-                                                                  _Float16* __restrict__ out, unsigned* range_flag) {
+                                                                  _Float16* __restrict__ out, unsigned* range_flag,
+                                                                  const long long* __restrict__ ref0, int n_pairs, int n0) {
     const int WW = Wn * Wn, groups = 2 * Cf / 4, pad = Wn / 2;
     const long long total = 2ll * M * WW * groups;
     float amax = 0.f;
@@ -73,7 +76,13 @@ __global__ __launch_bounds__(256) void fine_gather_windows_kernel(FineMap f0, Fi
             const long long cell = r < M ? i_ids[m] : j_ids[m];
             const int y = int(cell / f.wc) * stride + k / Wn - pad, x = int(cell % f.wc) * stride + k % Wn - pad;
             if (y >= 0 && y < f.H && x >= 0 && x < f.W) {
-                const float* s = f.p + b_ids[m] * f.sn + y * f.sh + x * f.sw + c * f.sc;
+                long long b = b_ids[m];
+                if (ref0 && r < M) {
+                    const long long pair = b < 0 ? 0 : b >= n_pairs ? n_pairs - 1 : b;
+                    b = ref0[pair];
+                    b = b < 0 ? 0 : b >= n0 ? n0 - 1 : b;
+                }
+                const float* s = f.p + b * f.sn + y * f.sh + x * f.sw + c * f.sc;
                 if (f.sc == 1) v = *reinterpret_cast<const f32x4*>(s);
                 else v = f32x4{s[0], s[f.sc], s[2 * f.sc], s[3 * f.sc]};
             }
@@ -140,6 +149,7 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
     if (!f32 && q.precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
     if (!q.f0 || !q.f1 || !q.fc0 || !q.fc1 || !q.b_ids || !q.i_ids || !q.j_ids || !q.out || !q.ws) return POPE_ERR_ARG;
     if (f32 ? (!q.down_w || !q.merge_w) : (!q.down_wp || !q.merge_wp)) return POPE_ERR_ARG;
+    if (q.ref0_of_pair && (q.n_pairs <= 0 || q.n0 <= 0)) return POPE_ERR_ARG;
     const int WW = q.Wn * q.Wn;
     if (q.ws_bytes < pope_fine_preprocess_workspace(q.M, WW, q.Cc, q.Cf)) return POPE_ERR_WORKSPACE;
     pope_carver ws{static_cast<char*>(q.ws)};
@@ -164,9 +174,9 @@ int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream) {
     FineMap m0 = {q.f0, q.s0[0], q.s0[1], q.s0[2], q.s0[3], q.H0, q.W0, q.wc0};
     FineMap m1 = {q.f1, q.s1[0], q.s1[1], q.s1[2], q.s1[3], q.H1, q.W1, q.wc1};
     if (f32) hipLaunchKernelGGL(fine_gather_windows_kernel<false>, dim3(pope_grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
-                                c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag);
+                                c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag, q.ref0_of_pair, q.n_pairs, q.n0);
     else hipLaunchKernelGGL(fine_gather_windows_kernel<true>, dim3(pope_grid_for(2ll * q.M * WW * 2 * q.Cf / 4)), dim3(256), 0, stream, m0, m1,
-                            c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag);
+                            c_win, q.b_ids, q.i_ids, q.j_ids, q.M, q.Wn, q.stride, q.Cf, mpl, q.range_flag, q.ref0_of_pair, q.n_pairs, q.n0);
     POPE_TRY(pope_check_launch());
     return linear(mpl, q.merge_wp, q.merge_w, q.merge_b, q.out, 2 * q.M * WW, q.Cf, 2 * q.Cf);
 }

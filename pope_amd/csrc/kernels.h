@@ -325,6 +325,8 @@ struct FinePreParams {
     float* out;                    // [2 M, Wn * Wn, Cf]: windows of stream 0, then of stream 1
     void* ws; size_t ws_bytes;
     unsigned* range_flag;
+    const long long* ref0_of_pair; // [n_pairs] (device) or nullptr: map 0 has n0 rows and pair b reads row ref0_of_pair[b]; fc0 stays per pair
+    int n_pairs, n0;
 };
 size_t pope_fine_preprocess_workspace(int M, int WW, int Cc, int Cf);
 int pope_launch_fine_preprocess(const FinePreParams& q, hipStream_t stream);

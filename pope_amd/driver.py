@@ -13,6 +13,11 @@ frame: the SAM mask generator's proposals (sam_generator.py:propose_batch, boxes
 The `*_batch` functions take Q independent queries per call: one DINOv2 forward, the vote on the device (ops.vote_top3_batch),
 ONE Matcher call over 3 Q pairs, the per-slot tally and best-slot choice on the device (ops.slot_tally), one pose launch and a
 single download; each query's result is what the single-query function returns for it alone.
+
+Prompt once, query many frames: `encode_references` runs everything that depends on the reference images alone (their DINOv2
+CLS tokens, their gray images, the Matcher's `ReferenceEncoding`) and the `*_batch_u8` / `locate_pose_from_frame(s)` functions
+take the resulting `ReferenceSet` where they take `refs_bgr`, with `ref_index` (or `ReferenceSet.select`) naming each query's
+reference ("Reference encodings").
 """
 import numpy as np
 import torch
@@ -121,6 +126,94 @@ def _counts(proposals_per_query, Q, N, what):
     return counts
 
 
+class ReferenceSet:
+    """R reference images as the batched step needs them (`encode_references`): `cls` [R, 384] DINOv2 CLS tokens, `gray`
+    [R, 1, H0, W0] gray / 255, `encoding` the matcher's `ReferenceEncoding` of `gray`.  Built for one (dinov2_model, matcher)
+    pair; the encoding follows later weight changes of the matcher by itself, the CLS tokens are those of the ViT as it was."""
+
+    def __init__(self, cls, gray, encoding, index=None):
+        self.cls, self.gray, self.encoding, self.index = cls, gray, encoding, index
+
+    @property
+    def R(self):
+        return int(self.gray.shape[0])
+
+    def select(self, ref_index):
+        """The same references (nothing is copied) standing for len(ref_index) queries, query q using row ref_index[q]: what
+        the `ref_index` keyword says, for the calls that have no such keyword (`locate_pose_from_frames`, `locate_pose_from_frame`)."""
+        return ReferenceSet(self.cls, self.gray, self.encoding, _ref_index(ref_index, self.R, None, "ReferenceSet.select"))
+
+    def __len__(self):
+        """The number of queries this stands for: its rows, or the length of its selection."""
+        return self.R if self.index is None else len(self.index)
+
+
+@torch.no_grad()
+def encode_references(dinov2_model, matcher, refs_bgr):
+    """`refs_bgr` [R, H0, W0, 3] uint8 BGR (numpy or tensor; H0, W0 multiples of 8, >= 16) -> `ReferenceSet`: the reference side of
+    `locate_and_match_batch_u8`, computed once.  Pass it in place of `refs_bgr`, with `ref_index` naming each query's row."""
+    from .preprocess import gray_batch, set_torch_images
+    dev = next(dinov2_model.parameters()).device
+    refs = torch.as_tensor(refs_bgr).to(dev)
+    if refs.dim() != 4 or int(refs.shape[0]) == 0:
+        raise ValueError("encode_references: refs_bgr is [R >= 1, H0, W0, 3]")
+    cls = get_cls_token_torch(dinov2_model, set_torch_images(refs, center_crop=True))
+    gray = gray_batch(refs)
+    return ReferenceSet(cls, gray, matcher.encode_reference(gray))
+
+
+def _ref_index(ref_index, R, Q, what):
+    """The Q reference rows of the queries as ints: None is arange(Q) and needs R == Q; ValueError on a wrong count or a row
+    outside [0, R)."""
+    if ref_index is None:
+        if Q is not None and R != Q:
+            raise ValueError(f"{what}: {R} references for {Q} queries needs ref_index (one reference row per query)")
+        return list(range(R))
+    rows = np.asarray(ref_index.cpu() if torch.is_tensor(ref_index) else ref_index)
+    if rows.ndim != 1 or (rows.size and not np.issubdtype(rows.dtype, np.integer)):
+        raise ValueError(f"{what}: ref_index is a list of integers, one per query")
+    if Q is not None and rows.size != Q:
+        raise ValueError(f"{what}: {rows.size} ref_index entries for {Q} queries")
+    if rows.size and (rows.min() < 0 or rows.max() >= R):
+        raise ValueError(f"{what}: ref_index values must lie in [0, {R}), got [{int(rows.min())}, {int(rows.max())}]")
+    return [int(r) for r in rows]
+
+
+def _select_refs(refs, ref_index, Q, what):
+    """(references, rows): a `ReferenceSet` keeps its rows and is indexed on the device; images are selected here, so the
+    rest of the call sees one reference per query."""
+    if isinstance(refs, ReferenceSet):
+        if refs.index is not None:
+            if ref_index is not None:
+                raise ValueError(f"{what}: this ReferenceSet already carries a selection (ReferenceSet.select); give one of the two")
+            return refs, list(refs.index)
+        return refs, _ref_index(ref_index, refs.R, Q, what)
+    refs = torch.as_tensor(refs)
+    if ref_index is None:
+        return refs, None
+    rows = _ref_index(ref_index, int(refs.shape[0]), Q, what)
+    return refs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=refs.device)), None
+
+
+def _batch_refset_on_device(dinov2_model, matcher, refset, rows, crop_tensors, select_gray, counts, conf_thr):
+    """`_batch_on_device` with the reference side taken from a `ReferenceSet`: the ViT runs over the proposals only, the vote
+    reads the kept CLS tokens of rows `rows`, the Matcher gets the kept encoding and pair 3 q + s -> reference rows[q]."""
+    from .ops import slot_tally, vote_top3_batch
+    Q = len(counts)
+    fea = get_cls_token_torch(dinov2_model, crop_tensors)
+    rows_h = torch.as_tensor(rows, dtype=torch.int64)
+    dv = vote_top3_batch(refset.cls.index_select(0, rows_h.to(fea.device)), fea, counts, eps=1e-8)
+    live = dv["pair_live"].bool()[:, None, None, None]
+    sel = select_gray(dv["pair_row"])
+    batch = {"reference": refset.encoding, "image0_index": rows_h.repeat_interleave(3),
+             "image1": torch.where(live, sel, torch.zeros_like(sel[:1, :1, :1, :1]))}
+    matcher(batch)
+    dv.update(slot_tally(batch["m_bids"], batch["mconf"], batch["mkpts0_f"], batch["mkpts1_f"], dv["pair_live"], conf_thr))
+    dv.update(mkpts0=batch["mkpts0_f"], mkpts1=batch["mkpts1_f"], mconf=batch["mconf"])
+    dv["best_row"] = dv["pair_row"].view(Q, 3).gather(1, dv["best_slot"].long()[:, None])[:, 0]
+    return dv
+
+
 def _batch_on_device(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs, select_gray, counts, conf_thr):
     """Launch sequence of the batched step, nothing read back: one DINOv2 forward over the Q references and the N proposals
     -> `vote_top3_batch` -> ONE Matcher call over 3 Q pairs (pair 3 q + s: reference q against the crop in slot s of query q;
@@ -198,30 +291,40 @@ def locate_and_match_batch(dinov2_model, matcher, ref_tensors, crop_tensors, gra
     return _download(dv, counts)
 
 
-def _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr):
+def _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr, rows=None):
     from .preprocess import gray_batch, set_torch_images
+    if isinstance(refs, ReferenceSet):
+        return _batch_refset_on_device(dinov2_model, matcher, refs, rows, set_torch_images(crops, center_crop=True),
+                                       lambda r: gray_batch(crops.index_select(0, r)), counts, conf_thr)
     # gray conversion of the 3 Q voted crops only (a per-pixel op: bit-equal to converting all N and selecting)
     return _batch_on_device(dinov2_model, matcher, set_torch_images(refs, center_crop=True), set_torch_images(crops, center_crop=True),
                             gray_batch(refs), lambda rows: gray_batch(crops.index_select(0, rows)), counts, conf_thr)
 
 
 @torch.no_grad()
-def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, proposals_per_query, conf_thr=0.9):
+def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, proposals_per_query, conf_thr=0.9, ref_index=None):
     """`locate_and_match_u8` for Q queries: `refs_bgr` [Q, H0, W0, 3] and `crops_bgr` [N, 256, 256, 3] uint8 BGR (numpy or
     tensors), query q owning the next `proposals_per_query[q]` crops.  Preprocessing as there, except that only the 3 Q crops
-    the vote selected are converted to gray."""
-    refs, crops = torch.as_tensor(refs_bgr), torch.as_tensor(crops_bgr)
-    Q, N = int(refs.shape[0]), int(crops.shape[0])
+    the vote selected are converted to gray.
+
+    `refs_bgr` may be a `ReferenceSet` (`encode_references`); `ref_index` (Q integers, default arange(Q), which needs R == Q) names
+    the reference row of each query, for a set and for images alike.  Each query's result is, bit for bit, that of the call with
+    the images `refs_bgr[ref_index]`."""
+    crops = torch.as_tensor(crops_bgr)
+    refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_and_match_batch_u8")
+    Q, N = len(rows) if rows is not None else int(refs.shape[0]), int(crops.shape[0])
     counts = _counts(proposals_per_query, Q, N, "locate_and_match_batch_u8")
     dev = next(dinov2_model.parameters()).device
     if Q == 0 or N == 0:
         return [_empty_result(dev) for _ in range(Q)]
-    return _download(_batch_u8_on_device(dinov2_model, matcher, refs.to(dev), crops.to(dev), counts, conf_thr), counts)
+    if rows is None:
+        refs = refs.to(dev)
+    return _download(_batch_u8_on_device(dinov2_model, matcher, refs, crops.to(dev), counts, conf_thr, rows), counts)
 
 
 @torch.no_grad()
 def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bboxes_xywh, K0, K1, conf_thr=0.9, ransac_thr=0.5,
-                               ransac_conf=0.99, out_size=256):
+                               ransac_conf=0.99, out_size=256, ref_index=None):
     """`locate_match_pose_u8` for Q queries in one call: `refs_bgr` [Q, H0, W0, 3] uint8, `frames_bgr` [Q, H, W, 3] uint8 (an
     array, a tensor or Q frames of one size), `bboxes_xywh` a list of Q arrays [P_q, 4] (P_q = 0 allowed), `K0` / `K1` [3, 3]
     for all queries or [Q, 3, 3].  Returns a list of Q dicts, each what `locate_match_pose_u8` returns for that query alone.
@@ -229,11 +332,12 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     crop_proposals per frame (asynchronous launches) -> the batched vote + ONE Matcher call over 3 Q pairs + slot tally
     (`locate_and_match_batch_u8`) -> ONE `estimate_pose_batch` over the Q best slots, fed by the tally's compacted matches
     and the crop intrinsics gathered on the device by best proposal row -> one download.  `pose` is None under
-    `estimate_pose`'s conditions (fewer than five matches, no inliers) and when no slot was filled."""
+    `estimate_pose`'s conditions (fewer than five matches, no inliers) and when no slot was filled.
+    `refs_bgr` may be a `ReferenceSet`, and `ref_index` names each query's reference row, as in `locate_and_match_batch_u8`."""
     from .crops import crop_proposals
     from .pose import estimate_pose_batch
-    refs = torch.as_tensor(refs_bgr)
-    Q = int(refs.shape[0])
+    refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_match_pose_batch_u8")
+    Q = len(rows) if rows is not None else int(refs.shape[0])
     if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
         frames_bgr = [torch.as_tensor(f) for f in frames_bgr]
         if len({tuple(f.shape) for f in frames_bgr}) > 1:
@@ -264,7 +368,7 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     else:
         crops = torch.cat([p["crops"] for p in props], 0)
         K_crops = torch.from_numpy(np.ascontiguousarray(np.concatenate([p["K"] for p in props], 0))).to(dev)
-        dv = _batch_u8_on_device(dinov2_model, matcher, refs.to(dev), crops, counts, conf_thr)
+        dv = _batch_u8_on_device(dinov2_model, matcher, refs if rows is not None else refs.to(dev), crops, counts, conf_thr, rows)
         pose = estimate_pose_batch(dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], K0q, K_crops.index_select(0, dv["best_row"]),
                                    ransac_thr, ransac_conf)
         outs = _download(dv, counts)
@@ -300,7 +404,9 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
     keeps the first `max_proposals` boxes of each frame in record order (None: all of them, as the reference does).
 
     Returns `locate_match_pose_batch_u8`'s list of Q dicts, each with one more key: `proposals`, the int64 [P_q, 4] XYWH boxes
-    of that query.  A frame without a proposal yields the empty result (`best_proposal` -1, `pose` None)."""
+    of that query.  A frame without a proposal yields the empty result (`best_proposal` -1, `pose` None).
+    `refs_bgr` may be a `ReferenceSet` (`encode_references`): one row per frame, or `refs.select(ref_index)` naming each frame's
+    row — one reference and eight frames is `refs.select([0] * 8)`."""
     dev = next(dinov2_model.parameters()).device
     devices = {"mask_generator": torch.device(mask_generator.predictor.device), "dinov2_model": dev,
                "matcher": next(matcher.parameters()).device}
@@ -331,7 +437,10 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
 
 def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
                            ransac_conf=0.99, out_size=256, max_proposals=None):
-    """`locate_pose_from_frames` for one query: `ref_bgr` [H0, W0, 3], `frame_bgr` [H, W, 3], `K0` / `K1` [3, 3]; one dict."""
-    ref, frame = (a[None] if on_device(a) else np.asarray(a.cpu() if torch.is_tensor(a) else a)[None] for a in (ref_bgr, frame_bgr))
-    return locate_pose_from_frames(mask_generator, dinov2_model, matcher, ref, frame, K0, K1, conf_thr, ransac_thr, ransac_conf,
-                                   out_size, max_proposals)[0]
+    """`locate_pose_from_frames` for one query: `ref_bgr` [H0, W0, 3], `frame_bgr` [H, W, 3], `K0` / `K1` [3, 3]; one dict.
+    `ref_bgr` may be a `ReferenceSet` standing for one query: a set of one, or `refs.select([row])`."""
+    def batch_of_one(a):
+        return a[None] if on_device(a) else np.asarray(a.cpu() if torch.is_tensor(a) else a)[None]
+    ref = ref_bgr if isinstance(ref_bgr, ReferenceSet) else batch_of_one(ref_bgr)
+    return locate_pose_from_frames(mask_generator, dinov2_model, matcher, ref, batch_of_one(frame_bgr), K0, K1, conf_thr, ransac_thr,
+                                   ransac_conf, out_size, max_proposals)[0]

@@ -190,14 +190,18 @@ class ResNetFPN_8_2(nn.Module):
         # the reference's NCHW maps as views of the zero-bordered NHWC outputs
         return [out_c[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2), out_f[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2)], flag
 
-    @torch.no_grad()
-    def forward(self, x):
+    def checked_input(self, x):
+        """The input checks of `forward`; returns `x` as contiguous fp32."""
         if self.training:
             raise NotImplementedError("pope_amd: inference only (BatchNorm is folded; call .eval())")
         require_cuda(x, "ResNetFPN_8_2")
         if x.dim() != 4 or x.shape[0] == 0 or x.shape[1] != 1 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[2] < 16 or x.shape[3] < 16:
             raise PopeHipError(f"pope_amd: ResNetFPN_8_2 takes [n >= 1, 1, H, W] gray images with H, W multiples of 8 and >= 16, got {tuple(x.shape)}")
-        x = x.float().contiguous()
+        return x.float().contiguous()
+
+    @torch.no_grad()
+    def forward(self, x):
+        x = self.checked_input(x)
         policy = self.on_overflow or ON_OVERFLOW
         if self._weights("f16x3") is None:
             if policy == "raise":
@@ -419,6 +423,83 @@ class LocalFeatureTransformer(nn.Module):
                 flags.append(layer.update_(f1, f0, ws, precision, mask1, mask0))
         return (f0, f1), flags
 
+    # ---- shared references (Matcher.encode_reference): stream 0 enters after its leading 'self' layers ----
+    @property
+    def n_leading_self(self):
+        """Number of layers before the first 'cross': until there a stream sees only itself, so what they make of an image can
+        be computed once and kept (every layer, if there is no 'cross' at all)."""
+        names = list(self.layer_names)
+        return names.index("cross") if "cross" in names else len(names)
+
+    @torch.no_grad()
+    def encode_leading(self, feat, precision):
+        """The leading 'self' layers on one stream alone: feat [R, L, C] -> (the updated copy, the OR of the range-flag words).
+        No policy here: the caller folds the bits into the call that uses the result."""
+        f = feat.float().contiguous().clone()
+        R, L, Cd = f.shape
+        k = self.n_leading_self
+        if k == 0:
+            return f, 0
+        ws = torch.empty(_lib.lib().pope_loftr_layer_workspace_bytes(R, L, L, Cd, self.nhead), dtype=torch.uint8, device=f.device)
+        flags = [layer.update_(f, f, ws, precision) for layer in list(self.layers)[:k]]
+        return f, (_read_flags(flags) if precision == "f16x3" else 0)
+
+    def _run_indexed(self, lead0, feat1, precision):
+        """`_run` with stream 0 given AFTER its leading 'self' layers (lead0 [n, L, C], a fresh tensor): those layers update
+        stream 1 only; from the first 'cross' on this is `_run`, buffers, calls and order."""
+        n, L, Cd = lead0.shape
+        S = feat1.shape[1]
+        lib = _lib.lib()
+        if L == S:
+            both = torch.cat([lead0, feat1.float()], 0).contiguous()
+            f0, f1 = both[:n], both[n:]
+        else:
+            both = None
+            f0, f1 = lead0.contiguous(), feat1.float().contiguous().clone()
+        nbytes = max(lib.pope_loftr_layer_workspace_bytes(2 * n if both is not None else n, a, b, Cd, self.nhead)
+                     for a in (L, S) for b in (L, S))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f0.device)
+        flags = []
+        k = self.n_leading_self
+        for li, (layer, name) in enumerate(zip(self.layers, self.layer_names)):
+            if li < k:
+                flags.append(layer.update_(f1, f1, ws, precision))
+            elif name == "self":
+                if both is not None:
+                    flags.append(layer.update_(both, both, ws, precision))
+                else:
+                    flags.append(layer.update_(f0, f0, ws, precision))
+                    flags.append(layer.update_(f1, f1, ws, precision))
+            else:
+                flags.append(layer.update_(f0, f1, ws, precision))
+                flags.append(layer.update_(f1, f0, ws, precision))
+        return (f0, f1), flags
+
+    @torch.no_grad()
+    def forward_indexed(self, lead_of, feat1, index):
+        """`forward(feat0, feat1)` for feat0 = stream 0 rows selected by `index` (int64 [n], device), with the leading 'self'
+        layers of stream 0 taken from `lead_of(precision) -> ([R, L, C], range bits)`.  One range policy for the call, as in
+        `forward`: the reference's bits count like those of the layers run here, and a re-run takes both sides in fp32."""
+        require_cuda(feat1, "LocalFeatureTransformer")
+        assert self.d_model == feat1.size(2), "the feature number of src and transformer must be equal"
+        policy = self.on_overflow or ON_OVERFLOW
+
+        def run(precision):
+            lead, bits = lead_of(precision)
+            out, flags = self._run_indexed(lead.index_select(0, index), feat1, precision)
+            return out, bits, flags
+
+        if any(l._weights("f16x3") is None for l in self.layers):
+            if policy == "raise":
+                raise PopeRangeError("pope_amd: a LoFTR transformer weight is outside the f16x3 weight range (|w| < 255.9)")
+            return run("f32")[0]
+        out, bits, flags = run("f16x3")
+        bits |= _read_flags(flags)   # one synchronisation per transformer
+        if bits:
+            _overflow("LoFTR transformer", bits, policy)
+            out = run("f32")[0]
+        return out
+
     @torch.no_grad()
     def forward(self, feat0, feat1, mask0=None, mask1=None):
         """mask0 [n, L], mask1 [n, S]: optional padding masks of the two streams (transformer.py:85-106; either alone is
@@ -489,7 +570,7 @@ class FinePreprocess(nn.Module):
                 ent[precision] = ent["mats"] if precision == "f32" else [_lib.to_planes(m, _lib.PLANES_W_SCALE) for m in ent["mats"]]
         return ent[precision]
 
-    def _run(self, f0, f1, fc0, fc1, data, stride, precision):
+    def _run(self, f0, f1, fc0, fc1, data, stride, precision, ref0_of_pair=None):
         dwp, mwp = self._weights(precision)
         db, mb = self._hip["biases"]
         b, i, j = (t.contiguous() for t in (data["b_ids"], data["i_ids"], data["j_ids"]))
@@ -501,6 +582,18 @@ class FinePreprocess(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         s0, s1 = (C.c_longlong * 4)(*f0.stride()), (C.c_longlong * 4)(*f1.stride())
+        if ref0_of_pair is not None:   # shared references: f0 has one row per reference, pair b reads row ref0_of_pair[b]
+            with _lib.on_device_of(f0):
+                _lib.check(lib.pope_fine_preprocess_indexed_f32(
+                    C.c_void_p(f0.data_ptr()), s0, f0.shape[2], f0.shape[3], int(data["hw0_c"][1]),
+                    C.c_void_p(f1.data_ptr()), s1, f1.shape[2], f1.shape[3], int(data["hw1_c"][1]),
+                    C.c_void_p(fc0.data_ptr()), C.c_void_p(fc1.data_ptr()), fc0.shape[1], fc1.shape[1], fc0.shape[2], Cf,
+                    C.c_void_p(b.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(j.data_ptr()), M, W, int(stride),
+                    C.c_void_p(dwp.data_ptr()), C.c_void_p(db.data_ptr()), C.c_void_p(mwp.data_ptr()), C.c_void_p(mb.data_ptr()),
+                    _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
+                    C.c_void_p(flag.data_ptr()), C.c_void_p(ref0_of_pair.data_ptr()), int(ref0_of_pair.shape[0]), int(f0.shape[0]),
+                    _lib.stream_of(dev)), "pope_fine_preprocess_indexed_f32")
+            return (out[:M], out[M:]), flag
         with _lib.on_device_of(f0):
             _lib.check(lib.pope_fine_preprocess_f32(
                 C.c_void_p(f0.data_ptr()), s0, f0.shape[2], f0.shape[3], int(data["hw0_c"][1]),
@@ -513,7 +606,9 @@ class FinePreprocess(nn.Module):
         return (out[:M], out[M:]), flag
 
     @torch.no_grad()
-    def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data):
+    def forward(self, feat_f0, feat_f1, feat_c0, feat_c1, data, ref0_of_pair=None):
+        """ref0_of_pair (int64 [n], device; shared references): feat_f0 has one row per reference and pair b reads row
+        ref0_of_pair[b]; feat_c0 stays per pair."""
         W = self.W
         stride = data["hw0_f"][0] // data["hw0_c"][0]
         data.update({"W": W})
@@ -523,16 +618,21 @@ class FinePreprocess(nn.Module):
         require_cuda(feat_f0, "FinePreprocess")
         # NB the reference unfolds image 1 with image 0's stride and both with their own width (:44-47)
         args = (feat_f0.float(), feat_f1.float(), feat_c0.float().contiguous(), feat_c1.float().contiguous(), data, stride)
+        if ref0_of_pair is not None:
+            if ref0_of_pair.dtype != torch.int64 or ref0_of_pair.dim() != 1 or ref0_of_pair.shape[0] != feat_c0.shape[0]:
+                raise ValueError("FinePreprocess: ref0_of_pair is an int64 tensor with one entry per pair")
+            require_cuda(ref0_of_pair, "FinePreprocess")
+            ref0_of_pair = ref0_of_pair.contiguous()
         policy = self.on_overflow or ON_OVERFLOW
         if self._weights("f16x3") is None:
             if policy == "raise":
                 raise PopeRangeError("pope_amd: a LoFTR fine-preprocess weight is outside the f16x3 weight range (|w| < 255.9)")
-            return self._run(*args, "f32")[0]
-        out, flag = self._run(*args, "f16x3")
+            return self._run(*args, "f32", ref0_of_pair)[0]
+        out, flag = self._run(*args, "f16x3", ref0_of_pair)
         bits = int(flag.item())
         if bits:
             _overflow("LoFTR fine preprocess", bits, policy)
-            out = self._run(*args, "f32")[0]
+            out = self._run(*args, "f32", ref0_of_pair)[0]
         return out
 
 

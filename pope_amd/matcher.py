@@ -147,6 +147,11 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     }
 
 
+def _loftr():
+    from . import loftr
+    return loftr
+
+
 class CoarseMatching(nn.Module):
     """Drop-in for the reference module (eval, match_type='dual_softmax')."""
 
@@ -182,6 +187,79 @@ class CoarseMatching(nn.Module):
         data.update(out)
 
 
+def _image0_index(index, n, R):
+    """data['image0_index'] as a host int64 [n] tensor: pair b uses reference row index[b].  None: arange(n), which needs
+    R == n.  ValueError on a float dtype, a wrong length or a value outside [0, R) — on the host, before any launch."""
+    if index is None:
+        if R != n:
+            raise ValueError(f"Matcher: {R} reference images for {n} pairs needs data['image0_index'] (one reference row per pair)")
+        return torch.arange(n, dtype=torch.int64)
+    idx = torch.as_tensor(index).detach().cpu()
+    if idx.dtype in (torch.bool,) or idx.is_floating_point() or idx.is_complex():
+        raise ValueError(f"Matcher: image0_index holds integers (int64), got {idx.dtype}")
+    if idx.dim() != 1 or idx.shape[0] != n:
+        raise ValueError(f"Matcher: image0_index has one entry per pair ([{n}]), got {tuple(idx.shape)}")
+    idx = idx.to(torch.int64)
+    if n and (int(idx.min()) < 0 or int(idx.max()) >= R):
+        raise ValueError(f"Matcher: image0_index values must lie in [0, {R}), got [{int(idx.min())}, {int(idx.max())}]")
+    return idx.contiguous()
+
+
+class ReferenceEncoding:
+    """What the Matcher makes of R reference images before stream 0 meets a stream 1 (`Matcher.encode_reference`): the 1/2-
+    resolution fine map (the backbone's zero-bordered NHWC buffer, seen as NCHW) and the coarse map after the position code and
+    every leading 'self' layer of the coarse transformer ([R, L, 256]); the first 'cross' layer mixes the pair, so nothing
+    later can be kept.  The image itself is kept too: the fp32 forms the range guard asks for, and a re-encoding after the
+    matcher's weights changed or moved (the encoding carries `_lib.slots_key` of the matcher's parameters and buffers), are built
+    from it on the next use.  Forms are held per arithmetic mode ("f16x3" / "f32") of the backbone and of the transformer, each
+    with the range bits it raised; at 256 x 256 a form is ~8.7 MB fine map + 2 x 1 MB coarse map per reference."""
+
+    def __init__(self, matcher, image0):
+        if not isinstance(image0, torch.Tensor) or image0.dim() != 4:
+            raise ValueError("Matcher.encode_reference: image0 is a [R, 1, H0, W0] tensor")
+        self._matcher = matcher
+        self.image = matcher.backbone.checked_input(image0)
+        if self.image is image0:
+            self.image = image0.clone()   # the caller may overwrite theirs
+        self.key, self._bb, self._lead = None, {}, {}
+        self.mode = None   # the backbone arithmetic a call reads this encoding in ("f16x3" | "f32"), set when it is built
+        self._fresh()
+
+    R = property(lambda self: int(self.image.shape[0]))
+    hw_i = property(lambda self: self.image.shape[2:])
+
+    def _fresh(self):
+        """Drop every form built under other weights, or on another device, than the matcher has now."""
+        m = self._matcher
+        key = (m._moves, _lib.slots_key(m._ref_slots()))
+        if key != self.key:
+            self.key, self._bb, self._lead = key, {}, {}
+            dev = next(m.parameters()).device
+            if self.image.device != dev:
+                self.image = self.image.to(dev)
+
+    def _put_backbone(self, precision, maps, bits):
+        feat_c, feat_f = maps
+        m = self._matcher
+        self._bb[precision] = {"fine": feat_f, "hw_c": feat_c.shape[2:], "bits": bits,
+                               "cpos": None if bits else m.pos_encoding(feat_c).flatten(2).transpose(1, 2)}
+
+    def backbone(self, precision):
+        """{'fine' [R, 128, H/2, W/2], 'cpos' [R, L, 256] (position code added), 'hw_c', 'bits'} of one backbone mode; a form
+        whose bits are raised holds nothing usable ('cpos' None)."""
+        if precision not in self._bb:
+            maps, flag = self._matcher.backbone._run(self.image, precision)
+            self._put_backbone(precision, maps, int(flag.item()) if precision == "f16x3" else 0)
+        return self._bb[precision]
+
+    def leading(self, bb_precision, precision):
+        """([R, L, 256] after the leading 'self' layers, range bits) for one (backbone mode, transformer mode)."""
+        k = (bb_precision, precision)
+        if k not in self._lead:
+            self._lead[k] = self._matcher.loftr_coarse.encode_leading(self.backbone(bb_precision)["cpos"], precision)
+        return self._lead[k]
+
+
 class Matcher(nn.Module):
     """Drop-in for the reference `Matcher` (src/matcher/matcher.py:12-85): same constructor, same in-place
     `forward(data, only_att_fea=False)` protocol and published keys, same checkpoint layout (`matcher.`
@@ -210,6 +288,7 @@ class Matcher(nn.Module):
         # always runs eagerly: the masks are inputs the captured graph does not have.
         self.use_graph = False
         self._graphs, self._gsrc = {}, None
+        self._moves, self._rsrc = 0, None   # ReferenceEncoding keys: .to() count, parameter / buffer slots
 
     def _features(self, im0, im1, mask_c0=None, mask_c1=None):
         """matcher.py:46-60: (feat_c0, feat_c1) after the coarse transformer [n, L, 256] and the fine maps (feat_f0, feat_f1);
@@ -276,10 +355,130 @@ class Matcher(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._graphs, self._gsrc = {}, None
+        self._moves, self._rsrc = self._moves + 1, None   # every ReferenceEncoding re-encodes itself on its next use
         return super()._apply(fn, *a, **k)
+
+    # ---- one reference image, many crops ("Reference encodings") ----
+    def _ref_slots(self):
+        if self._rsrc is None:
+            self._rsrc = _lib.param_slots(self, buffers=True)
+        return self._rsrc
+
+    @torch.no_grad()
+    def encode_reference(self, image0):
+        """image0 [R, 1, H0, W0] fp32 gray in [0, 1] on the matcher's device (H0, W0 multiples of 8, >= 16) -> `ReferenceEncoding`
+        for `matcher({"reference": ref, "image0_index": idx, "image1": crops})`: pair b matches reference row idx[b] against
+        crops[b], every published key bit for bit that of the plain call with image0 = image0.index_select(0, idx).  The
+        backbone, the position code and the leading 'self' layers of the coarse transformer run here, once per reference."""
+        ref = ReferenceEncoding(self, image0)
+        self._reference_backbone(ref)   # built now, in the mode a call will read it in
+        return ref
+
+    def _reference_backbone(self, ref):
+        """The backbone mode a call reads `ref` in, by `ResNetFPN_8_2.forward`'s rules for the reference images alone (weights
+        outside the f16x3 range, or a raised flag: fp32), and its bits.  The leading 'self' layers are built with it."""
+        ref._fresh()
+        bb = self.backbone
+        bits = 0
+        if bb._weights("f16x3") is None:
+            mode = "f32"
+        else:
+            bits = ref.backbone("f16x3")["bits"]
+            mode = "f32" if bits else "f16x3"
+        ref.mode = mode
+        if all(l._weights("f16x3") is not None for l in self.loftr_coarse.layers):
+            if ref.leading(mode, "f16x3")[1]:
+                ref.leading(mode, "f32")
+        else:
+            ref.leading(mode, "f32")
+        return mode, bits
+
+    def _forward_indexed(self, data, only_att_fea):
+        """`forward` for data['reference'] (or data['image0'] [R, ...]) + data['image0_index']: stream 0 comes from R reference
+        rows, each encoded once.  Stage by stage this makes the decisions the plain call makes on the expanded batch: where the
+        plain call runs both images through one launch sequence (equal sizes) one range policy covers both, and the reference's
+        bits count; otherwise each side keeps its own."""
+        loftr = _loftr()
+        if "reference" in data and "image0" in data:
+            raise ValueError("Matcher: give data['reference'] or data['image0'], not both")
+        if "reference" not in data and "image0" not in data:
+            raise ValueError("Matcher: data['image0_index'] needs data['image0'] or data['reference']")
+        if "mask0" in data or "mask1" in data:   # before the device check: no stage has run
+            raise NotImplementedError("pope_amd: padding masks (data['mask0'] / data['mask1']) are not supported together with "
+                                      "data['reference'] / data['image0_index']: expand image0 and make the plain call")
+        ref, im1 = data.get("reference"), data["image1"]
+        if ref is not None and not (isinstance(ref, ReferenceEncoding) and ref._matcher is self):
+            raise ValueError("Matcher: data['reference'] is a ReferenceEncoding of this matcher (matcher.encode_reference)")
+        n = int(im1.shape[0])
+        R = ref.R if ref is not None else int(data["image0"].shape[0])
+        index = _image0_index(data.get("image0_index"), n, R)
+        require_cuda(im1, "Matcher")
+        if ref is None:
+            require_cuda(data["image0"], "Matcher")
+        for k in ("scale0", "scale1"):
+            if k in data:
+                _lib.pair_scale(data[k], n, im1.device, f"Matcher {k}")
+        bb = self.backbone
+        policy = bb.on_overflow or loftr.ON_OVERFLOW
+        x1 = bb.checked_input(im1)
+        fits = bb._weights("f16x3") is not None
+        if not fits and policy == "raise":
+            raise PopeRangeError("pope_amd: a folded LoFTR backbone filter is outside the f16x3 weight range (|w| < 255.9)")
+        crops = None
+        if ref is None:
+            ref = ReferenceEncoding(self, data["image0"])
+            if ref.hw_i == x1.shape[2:]:   # the encoding is built inside the call: one launch sequence for R + n images
+                both = torch.cat([ref.image, x1], 0)
+                mode = "f16x3" if fits else "f32"
+                maps, flag = bb._run(both, mode)
+                if fits:
+                    bits = loftr._read_flags([flag])
+                    if bits:
+                        loftr._overflow("LoFTR backbone", bits, policy)
+                        mode = "f32"
+                        maps, _ = bb._run(both, mode)
+                ref._put_backbone(mode, [t[:R] for t in maps], 0)
+                ref.mode = mode
+                crops = [t[R:] for t in maps]
+        same = ref.hw_i == x1.shape[2:]
+        if crops is None:
+            mode, rbits = self._reference_backbone(ref)
+            if same and mode == "f16x3":
+                crops, flag = bb._run(x1, "f16x3")
+                cbits = loftr._read_flags([flag])
+                if cbits:
+                    loftr._overflow("LoFTR backbone", cbits, policy)
+                    mode = "f32"
+                    crops = bb._run(x1, "f32")[0]
+            elif same:   # the reference is fp32 (its flag, or the weights): the plain call runs both images in fp32
+                if rbits:
+                    loftr._overflow("LoFTR backbone", rbits, policy)
+                crops = bb._run(x1, "f32")[0]
+            else:        # two launch sequences in the plain call: each image's own guard
+                if rbits:
+                    loftr._overflow("LoFTR backbone", rbits, policy)
+                crops = bb(x1)
+        rform = ref.backbone(mode)
+        feat_c1, feat_f1 = crops
+        feat_f0 = rform["fine"]
+        hw0_c, hw1_c = rform["hw_c"], feat_c1.shape[2:]
+        data.update({"bs": n, "hw0_i": ref.hw_i, "hw1_i": im1.shape[2:]})
+        feat_c1 = self.pos_encoding(feat_c1).flatten(2).transpose(1, 2)
+        dev_index = index.to(x1.device)
+        feat_c0, feat_c1 = self.loftr_coarse.forward_indexed(lambda precision: ref.leading(mode, precision), feat_c1, dev_index)
+        data.update({"hw0_c": hw0_c, "hw1_c": hw1_c, "hw0_f": feat_f0.shape[2:], "hw1_f": feat_f1.shape[2:]})
+        if only_att_fea:
+            return feat_c0.clone(), feat_c1.clone()
+        self.coarse_matching(feat_c0, feat_c1, data)
+        win0, win1 = self.fine_preprocess(feat_f0, feat_f1, feat_c0, feat_c1, data, ref0_of_pair=dev_index)
+        if win0.size(0) != 0:
+            win0, win1 = self.loftr_fine(win0, win1)
+        self.fine_matching(win0, win1, data)
 
     @torch.no_grad()
     def forward(self, data, only_att_fea=False):
+        if "reference" in data or "image0_index" in data:   # shared references: always eager (no graph is captured for them)
+            return self._forward_indexed(data, only_att_fea)
         im0, im1 = data["image0"], data["image1"]
         if "mask0" in data and self.loftr_coarse.attention == "full":   # before the device check: no stage has run
             from . import loftr

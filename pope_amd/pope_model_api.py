@@ -20,9 +20,10 @@ import torch.nn.functional as F  # noqa: F401
 
 from .crops import crop_proposals, expand_box, get_affine_transform, get_image_crop_resize, get_K_crop_resize  # noqa: F401
 from .dinov2_utils import get_cls_token_torch, load_dinov2_model, set_torch_image  # noqa: F401
-from .driver import (locate_and_match, locate_and_match_batch, locate_and_match_batch_u8, locate_match_pose_batch_u8,  # noqa: F401
-                     locate_match_pose_u8, locate_pose_from_frame, locate_pose_from_frames)
-from .matcher import CoarseMatching, Matcher, default_cfg, dense_match  # noqa: F401
+from .driver import (ReferenceSet, encode_references, locate_and_match, locate_and_match_batch,  # noqa: F401
+                     locate_and_match_batch_u8, locate_match_pose_batch_u8, locate_match_pose_u8, locate_pose_from_frame,
+                     locate_pose_from_frames)
+from .matcher import CoarseMatching, Matcher, ReferenceEncoding, default_cfg, dense_match  # noqa: F401
 from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch  # noqa: F401
 from .pipeline import PairPipeline, gather_counts, shard_range  # noqa: F401
 from .pose import estimate_pose, estimate_pose_batch, relative_pose_error  # noqa: F401
