@@ -801,6 +801,19 @@ int pope_vote_top3_batch_f32(const float* cls_ref, const float* cls_prop, const 
                              float* scores, float* slot_scores, long long* slot_index, int* pair_row, unsigned char* pair_live,
                              void* stream);
 
+/* The same vote for Q queries that SHARE proposal segments (several queries asked of one frame): cls_prop [N, D] holds every
+ * segment once and is read in place, no gathered copy is made.  seg [S + 1] int32 (DEVICE): segment s owns rows seg[s] ..
+ * seg[s + 1], clamped to [0, N] as above.  query_seg [Q] int32 (DEVICE): query q votes over segment query_seg[q]; a value
+ * outside [0, S) is an empty segment.  score_begin [Q + 1] int32 (DEVICE): query q's scores go to scores[score_begin[q] ..),
+ * in proposal order; at most score_begin[q + 1] - score_begin[q] of them are written and voted on (none when score_begin[q]
+ * is negative), so `scores` holds score_begin[Q] floats.  slot_scores / slot_index as above, slot_index local to the segment;
+ * pair_row [3 Q] is the GLOBAL row in N (two queries may name the same row), 0 for a dead slot.  A query with an empty
+ * segment still gets its three slots written as dead.  pope_vote_top3_batch_f32 is this entry with query_seg[q] = q and
+ * score_begin = seg: one device body serves both, bit for bit.  Q = 0: POPE_OK, nothing launched. */
+int pope_vote_top3_shared_f32(const float* cls_ref, const float* cls_prop, const int* seg, int S, const int* query_seg,
+                              const int* score_begin, int Q, int N, int D, float eps, float* scores, float* slot_scores,
+                              long long* slot_index, int* pair_row, unsigned char* pair_live, void* stream);
+
 /* The published matches of a Matcher call over 3 Q pairs (pair 3 q + s = slot s of query q) -> the pose solver's inputs.
  * m_bids [M] int64 sorted (matches pair-contiguous, pairs in order), mconf [M], mkpts0_f / mkpts1_f [M, 2] fp32, pair_live
  * [3 Q] bytes.  pair_begin / pair_count [3 Q] int32: each pair's rows in the match list; matching_score [Q, 3] int64 =

@@ -212,6 +212,8 @@ PROTOTYPES = {
     "pope_five_point_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_streaming_top3_host": (C.c_int, [c_float_p, C.c_int, c_float_p, c_ll_p]),
     "pope_vote_top3_batch_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5 + [C.c_void_p]),
+    "pope_vote_top3_shared_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float]
+                                  + [C.c_void_p] * 5 + [C.c_void_p]),
     "pope_slot_tally_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_float] + [C.c_void_p] * 7 + [C.c_void_p]),
 }
 

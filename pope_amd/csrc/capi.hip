@@ -692,6 +692,14 @@ int pope_vote_top3_batch_f32(const float* cls_ref, const float* cls_prop, const 
                                        static_cast<hipStream_t>(stream));
 }
 
+int pope_vote_top3_shared_f32(const float* cls_ref, const float* cls_prop, const int* seg, int S, const int* query_seg,
+                              const int* score_begin, int Q, int N, int D, float eps, float* scores, float* slot_scores,
+                              long long* slot_index, int* pair_row, unsigned char* pair_live, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_vote_top3_shared(cls_ref, cls_prop, seg, S, query_seg, score_begin, Q, N, D, eps, scores, slot_scores,
+                                        slot_index, pair_row, pair_live, static_cast<hipStream_t>(stream));
+}
+
 int pope_slot_tally_f32(const long long* m_bids, const float* mconf, const float* mkpts0_f, const float* mkpts1_f,
                         const unsigned char* pair_live, int Q, long long M, float conf_thr, int* pair_begin, int* pair_count,
                         long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,

@@ -406,6 +406,9 @@ int pope_launch_five_point(const double* x0, const double* x1, int S, double* E_
 int pope_launch_vote_top3_batch(const float* cls_ref, const float* cls_prop, const int* seg, int Q, int N, int D, float eps,
                                 float* scores, float* slot_scores, long long* slot_index, int* pair_row, unsigned char* pair_live,
                                 hipStream_t stream);
+int pope_launch_vote_top3_shared(const float* cls_ref, const float* cls_prop, const int* seg, int S, const int* query_seg,
+                                 const int* score_begin, int Q, int N, int D, float eps, float* scores, float* slot_scores,
+                                 long long* slot_index, int* pair_row, unsigned char* pair_live, hipStream_t stream);
 int pope_launch_slot_tally(const long long* m_bids, const float* mconf, const float* mkpts0, const float* mkpts1,
                            const unsigned char* pair_live, int Q, long long M, float conf_thr, int* pair_begin, int* pair_count,
                            long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,

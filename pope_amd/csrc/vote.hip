@@ -7,22 +7,19 @@
 
 namespace {
 
-// One workgroup per query.  Scores: the arithmetic of cls_cosine_kernel (capi.hip) — one wave per proposal, lane-strided
-// accumulation, wave_sum, each norm clamped by eps separately — so scores[] is bit-equal to pope_cls_cosine_f32 per query.
+// The vote of one query, run by one workgroup: reference row `ref` against proposal rows begin .. begin + count of cls_prop,
+// scores to out[0 .. count) in proposal order, the three slots to entry q of the slot arrays.
+// Scores: the arithmetic of cls_cosine_kernel (capi.hip) — one wave per proposal, lane-strided accumulation, wave_sum, each
+// norm clamped by eps separately — so out[] is bit-equal to pope_cls_cosine_f32 over those rows.
 // Vote: pope_streaming_top3_host's loop, run by one lane over the query's scores in proposal order (it is order-dependent
 // by definition: a score enters only if strictly greater than some slot and replaces the FIRST minimum).
-__global__ __launch_bounds__(256) void vote_top3_batch_kernel(const float* __restrict__ cls_ref, const float* __restrict__ cls_prop,
-                                                               const int* __restrict__ seg, int N, int D, float eps,
-                                                               float* scores, float* __restrict__ slot_scores,
-                                                               long long* __restrict__ slot_index, int* __restrict__ pair_row,
-                                                               unsigned char* __restrict__ pair_live) {
-    const int q = blockIdx.x;
+__device__ __forceinline__ void vote_top3_body(const float* __restrict__ ref, const float* __restrict__ cls_prop, int begin, int count,
+                                               int D, float eps, float* out, int q, float* __restrict__ slot_scores,
+                                               long long* __restrict__ slot_index, int* __restrict__ pair_row,
+                                               unsigned char* __restrict__ pair_live) {
     const int lane = threadIdx.x & 63;
-    const int begin = min(max(seg[q], 0), N);
-    const int end = min(max(seg[q + 1], begin), N);
-    const float* ref = cls_ref + size_t(q) * D;
-    for (int p = begin + (threadIdx.x >> 6); p < end; p += 4) {
-        const float* f = cls_prop + size_t(p) * D;
+    for (int p = threadIdx.x >> 6; p < count; p += 4) {
+        const float* f = cls_prop + size_t(begin + p) * D;
         float dot = 0.f, nr = 0.f, nf = 0.f;
         for (int i = lane; i < D; i += 64) {
             const float a = ref[i], b = f[i];
@@ -33,21 +30,21 @@ __global__ __launch_bounds__(256) void vote_top3_batch_kernel(const float* __res
         dot = wave_sum(dot);
         nr = wave_sum(nr);
         nf = wave_sum(nf);
-        if (lane == 0) scores[p] = dot / (fmaxf(sqrtf(nr), eps) * fmaxf(sqrtf(nf), eps));
+        if (lane == 0) out[p] = dot / (fmaxf(sqrtf(nr), eps) * fmaxf(sqrtf(nf), eps));
     }
     __threadfence_block();
     __syncthreads();
     if (threadIdx.x != 0) return;
     float s3[3] = {0.f, 0.f, 0.f};
     int i3[3] = {-1, -1, -1};
-    for (int p = begin; p < end; ++p) {
-        const float s = scores[p];
+    for (int p = 0; p < count; ++p) {
+        const float s = out[p];
         if (s > s3[0] || s > s3[1] || s > s3[2]) {
             int k = 0;  // np.argmin: first minimum
             if (s3[1] < s3[k]) k = 1;
             if (s3[2] < s3[k]) k = 2;
             s3[k] = s;
-            i3[k] = p - begin;
+            i3[k] = p;
         }
     }
     for (int k = 0; k < 3; ++k) {
@@ -56,6 +53,40 @@ __global__ __launch_bounds__(256) void vote_top3_batch_kernel(const float* __res
         pair_row[3 * q + k] = i3[k] >= 0 ? begin + i3[k] : 0;
         pair_live[3 * q + k] = i3[k] >= 0;
     }
+}
+
+// One workgroup per query; query q owns segment q and its scores lie at the segment's own rows.
+__global__ __launch_bounds__(256) void vote_top3_batch_kernel(const float* __restrict__ cls_ref, const float* __restrict__ cls_prop,
+                                                               const int* __restrict__ seg, int N, int D, float eps,
+                                                               float* scores, float* __restrict__ slot_scores,
+                                                               long long* __restrict__ slot_index, int* __restrict__ pair_row,
+                                                               unsigned char* __restrict__ pair_live) {
+    const int q = blockIdx.x;
+    const int begin = min(max(seg[q], 0), N);
+    const int end = min(max(seg[q + 1], begin), N);
+    vote_top3_body(cls_ref + size_t(q) * D, cls_prop, begin, end - begin, D, eps, scores + begin, q, slot_scores, slot_index,
+                   pair_row, pair_live);
+}
+
+// One workgroup per query; query q votes over segment query_seg[q] of the shared proposals, read in place (two queries may
+// name one segment), and its scores go to scores[score_begin[q] ..): as many as that range holds, the vote sees no more.
+__global__ __launch_bounds__(256) void vote_top3_shared_kernel(const float* __restrict__ cls_ref, const float* __restrict__ cls_prop,
+                                                                const int* __restrict__ seg, int S, const int* __restrict__ query_seg,
+                                                                const int* __restrict__ score_begin, int N, int D, float eps,
+                                                                float* scores, float* __restrict__ slot_scores,
+                                                                long long* __restrict__ slot_index, int* __restrict__ pair_row,
+                                                                unsigned char* __restrict__ pair_live) {
+    const int q = blockIdx.x;
+    const int s = query_seg[q];
+    int begin = 0, count = 0;
+    if (s >= 0 && s < S) {
+        begin = min(max(seg[s], 0), N);
+        count = min(max(seg[s + 1], begin), N) - begin;
+    }
+    const int first = score_begin[q];
+    count = first < 0 ? 0 : min(count, max(score_begin[q + 1] - first, 0));
+    vote_top3_body(cls_ref + size_t(q) * D, cls_prop, begin, count, D, eps, scores + max(first, 0), q, slot_scores, slot_index,
+                   pair_row, pair_live);
 }
 
 // Matches a slot hands on: a dead slot's are dropped whatever the Matcher found in its all-zero image.
@@ -151,6 +182,19 @@ int pope_launch_vote_top3_batch(const float* cls_ref, const float* cls_prop, con
         return POPE_ERR_ARG;
     hipLaunchKernelGGL(vote_top3_batch_kernel, dim3(Q), dim3(256), 0, stream, cls_ref, cls_prop, seg, N, D, eps, scores,
                        slot_scores, slot_index, pair_row, pair_live);
+    return pope_check_launch();
+}
+
+int pope_launch_vote_top3_shared(const float* cls_ref, const float* cls_prop, const int* seg, int S, const int* query_seg,
+                                 const int* score_begin, int Q, int N, int D, float eps, float* scores, float* slot_scores,
+                                 long long* slot_index, int* pair_row, unsigned char* pair_live, hipStream_t stream) {
+    if (Q < 0 || N < 0 || S < 0 || D <= 0) return POPE_ERR_ARG;
+    if (Q == 0) return POPE_OK;
+    if (!cls_ref || !seg || !query_seg || !score_begin || !slot_scores || !slot_index || !pair_row || !pair_live ||
+        (N > 0 && (!cls_prop || !scores)))
+        return POPE_ERR_ARG;
+    hipLaunchKernelGGL(vote_top3_shared_kernel, dim3(Q), dim3(256), 0, stream, cls_ref, cls_prop, seg, S, query_seg, score_begin, N,
+                       D, eps, scores, slot_scores, slot_index, pair_row, pair_live);
     return pope_check_launch();
 }
 

@@ -18,6 +18,12 @@ Prompt once, query many frames: `encode_references` runs everything that depends
 CLS tokens, their gray images, the Matcher's `ReferenceEncoding`) and the `*_batch_u8` / `locate_pose_from_frame(s)` functions
 take the resulting `ReferenceSet` where they take `refs_bgr`, with `ref_index` (or `ReferenceSet.select`) naming each query's
 reference ("Reference encodings").
+
+Queries that share a frame: `frame_index` on the `*_batch_u8` calls (`SharedFrames(frames, frame_index)` in place of the frames
+of `locate_pose_from_frames`) names each query's frame, the frames are given once, and everything
+that depends on the frame alone (the generator's proposals, the crops and their intrinsics, their DINOv2 forward) runs once per
+frame; the vote reads the shared CLS rows in place (ops.vote_top3_shared).  `locate_poses_in_frame` asks R references of one
+frame, `share_frames` groups a list of queries by frame ("Shared frames").
 """
 import numpy as np
 import torch
@@ -195,14 +201,61 @@ def _select_refs(refs, ref_index, Q, what):
     return refs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=refs.device)), None
 
 
-def _batch_refset_on_device(dinov2_model, matcher, refset, rows, crop_tensors, select_gray, counts, conf_thr):
+def _frame_index(frame_index, F, Q, what):
+    """The frames of the Q queries as ints; ValueError on a wrong count, a non-integer value or a frame outside [0, F)."""
+    rows = np.asarray(frame_index.cpu() if torch.is_tensor(frame_index) else frame_index)
+    if rows.ndim != 1 or (rows.size and not np.issubdtype(rows.dtype, np.integer)):
+        raise ValueError(f"{what}: frame_index is a list of integers, one per query")
+    if rows.size != Q:
+        raise ValueError(f"{what}: {rows.size} frame_index entries for {Q} queries")
+    if rows.size and (rows.min() < 0 or rows.max() >= F):
+        raise ValueError(f"{what}: frame_index values must lie in [0, {F}), got [{int(rows.min())}, {int(rows.max())}]")
+    return [int(r) for r in rows]
+
+
+class SharedFrames:
+    """F frames standing for len(frame_index) queries, query q asked of frame frame_index[q]: what the `frame_index` keyword of
+    the `*_batch_u8` calls says, for `locate_pose_from_frames`, whose signature is that of the reference's loop body and has no
+    such keyword.  `frames` is whatever that call takes as `frames_bgr`; nothing is copied, the index is checked by the call."""
+
+    def __init__(self, frames, frame_index):
+        self.frames, self.index = frames, frame_index
+
+    def __len__(self):
+        """The number of queries this stands for."""
+        return len(self.index)
+
+
+def share_frames(keys):
+    """Groups queries by frame for the `frame_index` calls: `keys` holds one hashable key per query (what names its frame, such
+    as (object, frame number)).  Returns `(positions, frame_index)`: `positions[f]` is the first query with the f-th distinct
+    key, in order of first appearance, and `keys[positions[frame_index[q]]] == keys[q]`.  A walker loads the frames of
+    `positions` and hands `frame_index` to the call."""
+    first, positions, frame_index = {}, [], []
+    for q, key in enumerate(keys):
+        if key not in first:
+            first[key] = len(positions)
+            positions.append(q)
+        frame_index.append(first[key])
+    return positions, frame_index
+
+
+def _vote(cls_ref, fea, counts, frame_rows):
+    """The vote of the batched step: query q over segment q, or with `frame_rows` over segment frame_rows[q] of shared segments."""
+    from .ops import vote_top3_batch, vote_top3_shared
+    if frame_rows is None:
+        return vote_top3_batch(cls_ref, fea, counts, eps=1e-8)
+    return vote_top3_shared(cls_ref, fea, counts, frame_rows, eps=1e-8)
+
+
+def _batch_refset_on_device(dinov2_model, matcher, refset, rows, crop_tensors, select_gray, counts, conf_thr, frame_rows=None):
     """`_batch_on_device` with the reference side taken from a `ReferenceSet`: the ViT runs over the proposals only, the vote
     reads the kept CLS tokens of rows `rows`, the Matcher gets the kept encoding and pair 3 q + s -> reference rows[q]."""
-    from .ops import slot_tally, vote_top3_batch
-    Q = len(counts)
+    from .ops import slot_tally
+    Q = len(rows)
     fea = get_cls_token_torch(dinov2_model, crop_tensors)
     rows_h = torch.as_tensor(rows, dtype=torch.int64)
-    dv = vote_top3_batch(refset.cls.index_select(0, rows_h.to(fea.device)), fea, counts, eps=1e-8)
+    dv = _vote(refset.cls.index_select(0, rows_h.to(fea.device)), fea, counts, frame_rows)
     live = dv["pair_live"].bool()[:, None, None, None]
     sel = select_gray(dv["pair_row"])
     batch = {"reference": refset.encoding, "image0_index": rows_h.repeat_interleave(3),
@@ -214,20 +267,22 @@ def _batch_refset_on_device(dinov2_model, matcher, refset, rows, crop_tensors, s
     return dv
 
 
-def _batch_on_device(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs, select_gray, counts, conf_thr):
+def _batch_on_device(dinov2_model, matcher, ref_tensors, crop_tensors, gray_refs, select_gray, counts, conf_thr, frame_rows=None):
     """Launch sequence of the batched step, nothing read back: one DINOv2 forward over the Q references and the N proposals
     -> `vote_top3_batch` -> ONE Matcher call over 3 Q pairs (pair 3 q + s: reference q against the crop in slot s of query q;
     a dead slot keeps its place with an all-zero image1, so the batch is sized without a host read) -> `slot_tally`.
-    `select_gray(pair_row)` -> [3 Q, 1, H1, W1] gray crops of the voted rows.  Returns the device tensors of both ops."""
-    from .ops import slot_tally, vote_top3_batch
-    Q = len(counts)
+    `select_gray(pair_row)` -> [3 Q, 1, H1, W1] gray crops of the voted rows.  Returns the device tensors of both ops.
+    With `frame_rows` (Q segment numbers) the N proposals are those of F shared frames, `counts` their F counts, and query q votes
+    over segment frame_rows[q] (`vote_top3_shared`): a frame's crops pass through the ViT once however many queries name it."""
+    from .ops import slot_tally
+    Q = int(ref_tensors.shape[0])
     if ref_tensors.shape[1:] == crop_tensors.shape[1:]:
         both = get_cls_token_torch(dinov2_model, torch.cat([ref_tensors, crop_tensors], 0))
         ref, fea = both[:Q], both[Q:]
     else:
         ref = get_cls_token_torch(dinov2_model, ref_tensors)
         fea = get_cls_token_torch(dinov2_model, crop_tensors)
-    dv = vote_top3_batch(ref, fea, counts, eps=1e-8)
+    dv = _vote(ref, fea, counts, frame_rows)
     live = dv["pair_live"].bool()[:, None, None, None]
     sel = select_gray(dv["pair_row"])
     batch = {"image0": gray_refs.repeat_interleave(3, dim=0), "image1": torch.where(live, sel, torch.zeros_like(sel[:1, :1, :1, :1]))}
@@ -247,7 +302,8 @@ def _empty_result(device):
 
 
 def _download(dv, counts):
-    """The one download of the batched step: Q dicts with the keys and types of `locate_and_match`."""
+    """The one download of the batched step: Q dicts with the keys and types of `locate_and_match`.  `counts` are the Q
+    per-query proposal counts: with shared frames too, query q's scores lie at the exclusive scan of its own counts."""
     Q = len(counts)
     keys = ("slot_scores", "slot_index", "pair_live", "pair_begin", "pair_count", "matching_score", "best_slot", "mkpts0", "mkpts1", "mconf")
     h = {k: dv[k].cpu().numpy() for k in keys}
@@ -291,40 +347,53 @@ def locate_and_match_batch(dinov2_model, matcher, ref_tensors, crop_tensors, gra
     return _download(dv, counts)
 
 
-def _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr, rows=None):
+def _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr, rows=None, frame_rows=None):
     from .preprocess import gray_batch, set_torch_images
     if isinstance(refs, ReferenceSet):
         return _batch_refset_on_device(dinov2_model, matcher, refs, rows, set_torch_images(crops, center_crop=True),
-                                       lambda r: gray_batch(crops.index_select(0, r)), counts, conf_thr)
+                                       lambda r: gray_batch(crops.index_select(0, r)), counts, conf_thr, frame_rows)
     # gray conversion of the 3 Q voted crops only (a per-pixel op: bit-equal to converting all N and selecting)
     return _batch_on_device(dinov2_model, matcher, set_torch_images(refs, center_crop=True), set_torch_images(crops, center_crop=True),
-                            gray_batch(refs), lambda rows: gray_batch(crops.index_select(0, rows)), counts, conf_thr)
+                            gray_batch(refs), lambda rows: gray_batch(crops.index_select(0, rows)), counts, conf_thr, frame_rows)
 
 
 @torch.no_grad()
-def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, proposals_per_query, conf_thr=0.9, ref_index=None):
+def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, proposals_per_query, conf_thr=0.9, ref_index=None,
+                              frame_index=None):
     """`locate_and_match_u8` for Q queries: `refs_bgr` [Q, H0, W0, 3] and `crops_bgr` [N, 256, 256, 3] uint8 BGR (numpy or
     tensors), query q owning the next `proposals_per_query[q]` crops.  Preprocessing as there, except that only the 3 Q crops
     the vote selected are converted to gray.
 
     `refs_bgr` may be a `ReferenceSet` (`encode_references`); `ref_index` (Q integers, default arange(Q), which needs R == Q) names
     the reference row of each query, for a set and for images alike.  Each query's result is, bit for bit, that of the call with
-    the images `refs_bgr[ref_index]`."""
+    the images `refs_bgr[ref_index]`.
+
+    `frame_index` (Q integers) lets queries share the crops of a frame: `crops_bgr` then holds the crops of F frames once each,
+    `proposals_per_query` their F counts (frame f owning the next count rows), and query q votes over the crops of frame
+    `frame_index[q]`.  The crops pass through the ViT once, not once per query that names them; a frame no query names is allowed.
+    Each query's result is, bit for bit, that of the call with every frame's crops repeated per query."""
     crops = torch.as_tensor(crops_bgr)
     refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_and_match_batch_u8")
     Q, N = len(rows) if rows is not None else int(refs.shape[0]), int(crops.shape[0])
-    counts = _counts(proposals_per_query, Q, N, "locate_and_match_batch_u8")
+    fidx = None
+    if frame_index is None:
+        counts = own = _counts(proposals_per_query, Q, N, "locate_and_match_batch_u8")
+    else:
+        counts = [int(p) for p in proposals_per_query]
+        counts = _counts(counts, len(counts), N, "locate_and_match_batch_u8")
+        fidx = _frame_index(frame_index, len(counts), Q, "locate_and_match_batch_u8")
+        own = [counts[f] for f in fidx]
     dev = next(dinov2_model.parameters()).device
-    if Q == 0 or N == 0:
+    if Q == 0 or sum(own) == 0:
         return [_empty_result(dev) for _ in range(Q)]
     if rows is None:
         refs = refs.to(dev)
-    return _download(_batch_u8_on_device(dinov2_model, matcher, refs, crops.to(dev), counts, conf_thr, rows), counts)
+    return _download(_batch_u8_on_device(dinov2_model, matcher, refs, crops.to(dev), counts, conf_thr, rows, fidx), own)
 
 
 @torch.no_grad()
 def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bboxes_xywh, K0, K1, conf_thr=0.9, ransac_thr=0.5,
-                               ransac_conf=0.99, out_size=256, ref_index=None):
+                               ransac_conf=0.99, out_size=256, ref_index=None, frame_index=None):
     """`locate_match_pose_u8` for Q queries in one call: `refs_bgr` [Q, H0, W0, 3] uint8, `frames_bgr` [Q, H, W, 3] uint8 (an
     array, a tensor or Q frames of one size), `bboxes_xywh` a list of Q arrays [P_q, 4] (P_q = 0 allowed), `K0` / `K1` [3, 3]
     for all queries or [Q, 3, 3].  Returns a list of Q dicts, each what `locate_match_pose_u8` returns for that query alone.
@@ -333,7 +402,14 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     (`locate_and_match_batch_u8`) -> ONE `estimate_pose_batch` over the Q best slots, fed by the tally's compacted matches
     and the crop intrinsics gathered on the device by best proposal row -> one download.  `pose` is None under
     `estimate_pose`'s conditions (fewer than five matches, no inliers) and when no slot was filled.
-    `refs_bgr` may be a `ReferenceSet`, and `ref_index` names each query's reference row, as in `locate_and_match_batch_u8`."""
+    `refs_bgr` may be a `ReferenceSet`, and `ref_index` names each query's reference row, as in `locate_and_match_batch_u8`.
+
+    `frame_index` (Q integers in [0, F)) lets queries share frames: `frames_bgr` is then [F, H, W, 3], `bboxes_xywh` F arrays and
+    `K1` [3, 3] or [F, 3, 3], all per FRAME, while `refs_bgr` / `ref_index` and `K0` ([3, 3] or [Q, 3, 3]) stay per query; query
+    q is asked of frame `frame_index[q]`.  The crops, their intrinsics, their preprocessing and their DINOv2 forward are done
+    once per frame; the vote (ops.vote_top3_shared), the 3 Q Matcher pairs, the tally and the pose stay per query.  A frame no
+    query names is allowed (its crops are computed and unused).  Each query's dict is, key by key and bit for bit, that of
+    the call with `frames_bgr[frame_index]` and the box lists repeated, and its `boxes` / `K_crops` are arrays of its own."""
     from .crops import crop_proposals
     from .pose import estimate_pose_batch
     refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_match_pose_batch_u8")
@@ -348,39 +424,45 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
         raise ValueError("locate_match_pose_batch_u8: frames_bgr is [Q, H, W, 3] (frames of one size)")
     boxes_in = [np.asarray(b).reshape(-1, 4) for b in bboxes_xywh]
 
-    def per_query(K, name):
+    def per_row(K, name, n):
         K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
-        if K.shape not in ((3, 3), (Q, 3, 3)):
-            raise ValueError(f"locate_match_pose_batch_u8: {name} is [3, 3] or [{Q}, 3, 3]")
-        return np.ascontiguousarray(np.broadcast_to(K, (Q, 3, 3)))
+        if K.shape not in ((3, 3), (n, 3, 3)):
+            raise ValueError(f"locate_match_pose_batch_u8: {name} is [3, 3] or [{n}, 3, 3]")
+        return np.ascontiguousarray(np.broadcast_to(K, (n, 3, 3)))
 
-    if int(frames.shape[0]) != Q or len(boxes_in) != Q:
-        raise ValueError(f"locate_match_pose_batch_u8: {Q} references, {int(frames.shape[0])} frames, {len(boxes_in)} box lists")
-    K0q, K1q = per_query(K0, "K0"), per_query(K1, "K1")
-    counts = [len(b) for b in boxes_in]
+    F = Q if frame_index is None else int(frames.shape[0])
+    fidx = None if frame_index is None else _frame_index(frame_index, F, Q, "locate_match_pose_batch_u8")
+    if int(frames.shape[0]) != F or len(boxes_in) != F:
+        raise ValueError(f"locate_match_pose_batch_u8: {Q} references, {int(frames.shape[0])} frames, {len(boxes_in)} box lists"
+                         + ("" if fidx is None else " (with frame_index: one box list per frame)"))
+    K0q, K1f = per_row(K0, "K0", Q), per_row(K1, "K1", F)
+    counts = [len(b) for b in boxes_in]                     # per frame; `own` per query
+    frame_of = list(range(Q)) if fidx is None else fidx
+    own = [counts[f] for f in frame_of]
     dev = next(dinov2_model.parameters()).device
     frames = frames.to(dev)
-    props = [crop_proposals(frames[q], boxes_in[q], K1q[q], out_size=out_size) for q in range(Q)]
-    N = sum(counts)
-    if Q == 0 or N == 0:
+    props = [crop_proposals(frames[f], boxes_in[f], K1f[f], out_size=out_size) for f in range(F)]
+    if Q == 0 or sum(own) == 0:
         outs = [_empty_result(dev) for _ in range(Q)]
         pose = None
     else:
         crops = torch.cat([p["crops"] for p in props], 0)
         K_crops = torch.from_numpy(np.ascontiguousarray(np.concatenate([p["K"] for p in props], 0))).to(dev)
-        dv = _batch_u8_on_device(dinov2_model, matcher, refs if rows is not None else refs.to(dev), crops, counts, conf_thr, rows)
+        dv = _batch_u8_on_device(dinov2_model, matcher, refs if rows is not None else refs.to(dev), crops, counts, conf_thr, rows, fidx)
         pose = estimate_pose_batch(dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], K0q, K_crops.index_select(0, dv["best_row"]),
                                    ransac_thr, ransac_conf)
-        outs = _download(dv, counts)
+        outs = _download(dv, own)
         R, t, inl, n_inl = (pose[k].cpu().numpy() for k in ("R", "t", "inliers", "n_inliers"))
         off = np.concatenate([[0], np.cumsum(dv["best_count"].cpu().numpy())])
     for q, out in enumerate(outs):
-        out["boxes"], out["K_crops"] = props[q]["boxes"], props[q]["K"]
+        prop = props[frame_of[q]]
+        # queries that share a frame each get arrays of their own
+        out["boxes"], out["K_crops"] = (prop["boxes"], prop["K"]) if fidx is None else (prop["boxes"].copy(), prop["K"].copy())
         best = out["best_proposal"]
         if best < 0:
             out["pre_bbox"], out["pre_K"], out["pose"] = None, None, None
             continue
-        out["pre_bbox"], out["pre_K"] = props[q]["boxes"][best], props[q]["K"][best]
+        out["pre_bbox"], out["pre_K"] = out["boxes"][best], out["K_crops"][best]
         n = int(off[q + 1] - off[q])
         out["pose"] = (R[q], t[q], inl[off[q]:off[q + 1]]) if n >= 5 and int(n_inl[q]) > 0 else None
     return outs
@@ -406,7 +488,25 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
     Returns `locate_match_pose_batch_u8`'s list of Q dicts, each with one more key: `proposals`, the int64 [P_q, 4] XYWH boxes
     of that query.  A frame without a proposal yields the empty result (`best_proposal` -1, `pose` None).
     `refs_bgr` may be a `ReferenceSet` (`encode_references`): one row per frame, or `refs.select(ref_index)` naming each frame's
-    row — one reference and eight frames is `refs.select([0] * 8)`."""
+    row — one reference and eight frames is `refs.select([0] * 8)`.
+
+    `frames_bgr` may be `SharedFrames(frames, frame_index)` (Q integers in [0, F)), which asks several queries of one frame, as
+    `ReferenceSet.select` does on the reference side: the frames are then [F, H, W, 3] and `K1` [3, 3] or [F, 3, 3], per frame; the
+    references (Q images, or a `ReferenceSet` whose rows or selection number Q) and `K0` stay per query, and `max_proposals`
+    applies per frame.  The generator, the crops and their DINOv2 forward run once per frame (a frame no query names is still
+    proposed for), the rest per query, and each query's dict is that of the call with `frames[frame_index]`, bit for bit, with a
+    `proposals` array of its own."""
+    frame_index = None
+    if isinstance(frames_bgr, SharedFrames):
+        frames_bgr, frame_index = frames_bgr.frames, frames_bgr.index
+    if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
+        frames_bgr = list(frames_bgr)
+    fidx = None
+    if frame_index is not None:            # checked before any model is touched
+        F = len(frames_bgr)
+        fidx = _frame_index(frame_index, F, len(refs_bgr), "locate_pose_from_frames")
+        if tuple(np.shape(K1.cpu() if torch.is_tensor(K1) else K1)) not in ((3, 3), (F, 3, 3)):
+            raise ValueError(f"locate_pose_from_frames: K1 is [3, 3] or [{F}, 3, 3], per frame")
     dev = next(dinov2_model.parameters()).device
     devices = {"mask_generator": torch.device(mask_generator.predictor.device), "dinov2_model": dev,
                "matcher": next(matcher.parameters()).device}
@@ -415,23 +515,21 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
                          + ", ".join(f"{k} on {v}" for k, v in devices.items()))
     if max_proposals is not None and int(max_proposals) < 0:
         raise ValueError(f"locate_pose_from_frames: max_proposals is None or a count, got {max_proposals}")
-    if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
-        frames_bgr = list(frames_bgr)
     frames = stack = frames_on_device(frames_bgr, "locate_pose_from_frames")   # frames in HBM stay there, for both calls below
     if stack is None:
         if isinstance(frames_bgr, torch.Tensor):
             frames_bgr = frames_bgr.cpu().numpy()
         frames = [np.asarray(f.cpu() if torch.is_tensor(f) else f) for f in frames_bgr]
         stack = np.stack(frames) if frames else frames
-    if len(frames) != len(refs_bgr):
+    if fidx is None and len(frames) != len(refs_bgr):
         raise ValueError(f"locate_pose_from_frames: {len(refs_bgr)} references, {len(frames)} frames")
     proposals = mask_generator.propose_batch(frames)            # mixed frame sizes raise there
     if max_proposals is not None:
         proposals = [p[:int(max_proposals)] for p in proposals]
     outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, stack, proposals, K0, K1, conf_thr, ransac_thr, ransac_conf,
-                                      out_size)
-    for out, p in zip(outs, proposals):
-        out["proposals"] = p
+                                      out_size, frame_index=fidx)
+    for q, out in enumerate(outs):
+        out["proposals"] = proposals[q] if fidx is None else proposals[fidx[q]].copy()
     return outs
 
 
@@ -444,3 +542,13 @@ def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame
     ref = ref_bgr if isinstance(ref_bgr, ReferenceSet) else batch_of_one(ref_bgr)
     return locate_pose_from_frames(mask_generator, dinov2_model, matcher, ref, batch_of_one(frame_bgr), K0, K1, conf_thr, ransac_thr,
                                    ransac_conf, out_size, max_proposals)[0]
+
+
+def locate_poses_in_frame(mask_generator, dinov2_model, matcher, refs_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
+                          ransac_conf=0.99, out_size=256, max_proposals=None):
+    """R references asked of ONE frame: `refs_bgr` [R, H0, W0, 3] uint8 or a `ReferenceSet` (its R rows, or its selection),
+    `frame_bgr` [H, W, 3], `K0` [3, 3] or [R, 3, 3], `K1` [3, 3].  `locate_pose_from_frames` with `SharedFrames([frame], [0] * R)`:
+    the frame passes through the mask generator once and its crops through DINOv2 once.  Returns a list of R dicts."""
+    frame = frame_bgr[None] if on_device(frame_bgr) else np.asarray(frame_bgr.cpu() if torch.is_tensor(frame_bgr) else frame_bgr)[None]
+    return locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, SharedFrames(frame, [0] * len(refs_bgr)), K0, K1,
+                                   conf_thr, ransac_thr, ransac_conf, out_size, max_proposals)

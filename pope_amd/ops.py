@@ -151,6 +151,51 @@ def vote_top3_batch(cls_ref, cls_prop, proposals_per_query, eps=1e-8):
     return out
 
 
+def vote_top3_shared(cls_ref, cls_prop, proposals_per_segment, segment_of_query, eps=1e-8):
+    """`vote_top3_batch` for Q queries that share proposal segments (pope_vote_top3_shared_f32): cls_ref [Q, D], cls_prop [N, D]
+    holding every segment once; `proposals_per_segment`: S counts summing to N (segment s owns the next P_s rows);
+    `segment_of_query`: Q integers in [0, S), the segment query q votes over (two queries may name one segment, a segment may
+    go unnamed).  The proposals are read in place, no copy per query is made.  Returns the dict of `vote_top3_batch` — scores
+    [sum of the queries' P] with query q's at score_begin[q] .. score_begin[q + 1], slot_index local to the segment, pair_row
+    the global row in N, `seg` the [S + 1] row offsets — plus `score_begin`, int32 [Q + 1].  ValueError on counts that are
+    negative or do not sum to N, and on a segment outside [0, S), before anything is launched."""
+    import numpy as np
+    cls_ref = _f32c(cls_ref, "vote_top3_shared")
+    cls_prop = _f32c(cls_prop, "vote_top3_shared")
+    dev = cls_ref.device
+    if cls_ref.dim() != 2 or cls_prop.dim() != 2:
+        raise ValueError("vote_top3_shared: cls_ref is [Q, D] and cls_prop [N, D]")
+    q, d = cls_ref.shape
+    n = int(cls_prop.shape[0])
+    counts = [int(p) for p in proposals_per_segment]
+    if min(counts, default=0) < 0 or sum(counts) != n:
+        raise ValueError("vote_top3_shared: proposals_per_segment must be non-negative and sum to the number of proposal rows")
+    which = np.asarray(segment_of_query.cpu() if torch.is_tensor(segment_of_query) else segment_of_query)
+    if which.ndim != 1 or (which.size and not np.issubdtype(which.dtype, np.integer)):
+        raise ValueError("vote_top3_shared: segment_of_query is a list of integers, one per query")
+    if which.size != q or (n and cls_prop.shape[1] != d):
+        raise ValueError("vote_top3_shared: one segment index per reference row, and one feature width")
+    if which.size and (which.min() < 0 or which.max() >= len(counts)):
+        raise ValueError(f"vote_top3_shared: segment_of_query values must lie in [0, {len(counts)}), got "
+                         f"[{int(which.min())}, {int(which.max())}]")
+    which = [int(s) for s in which]
+    total = sum(counts[s] for s in which)
+    if max(n, total) > 0x7fffffff:
+        raise ValueError("vote_top3_shared: the row and score offsets are int32")
+    offsets = lambda c: torch.tensor([0] + c, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)  # noqa: E731
+    seg, score_begin = offsets(counts), offsets([counts[s] for s in which])
+    query_seg = torch.tensor(which, dtype=torch.int32).to(dev)
+    out = {"scores": torch.empty(total, device=dev, dtype=torch.float32), "slot_scores": torch.empty(q, 3, device=dev, dtype=torch.float32),
+           "slot_index": torch.empty(q, 3, device=dev, dtype=torch.int64), "pair_row": torch.empty(3 * q, device=dev, dtype=torch.int32),
+           "pair_live": torch.empty(3 * q, device=dev, dtype=torch.uint8), "seg": seg, "score_begin": score_begin}
+    with on_device_of(cls_ref):
+        check(_lib.lib().pope_vote_top3_shared_f32(ptr(cls_ref), ptr(cls_prop), ptr(seg), len(counts), ptr(query_seg), ptr(score_begin),
+                                                   q, n, d, float(eps), ptr(out["scores"]), ptr(out["slot_scores"]),
+                                                   ptr(out["slot_index"]), ptr(out["pair_row"]), ptr(out["pair_live"]), stream_of(dev)),
+              "pope_vote_top3_shared_f32")
+    return out
+
+
 def slot_tally(m_bids, mconf, mkpts0_f, mkpts1_f, pair_live, conf_thr=0.9):
     """The matches a `Matcher` call over 3 Q pairs published (pair 3 q + s = slot s of query q) -> per-slot counts, the best
     slot of every query and its matches compacted for `estimate_pose_batch` (pope_slot_tally_f32), all on the device.

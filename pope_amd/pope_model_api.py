@@ -4,7 +4,9 @@ lies on the accelerated path, including the caller-side geometr
 and their intrinsics (`get_image_crop_resize`, `get_K_crop_resize`; batched: `crop_proposals`) and the pose solver
 (`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`), the SAM proposal generator the drivers build from it
 (`sam_model_registry`, the `build_sam_vit_*` builders, `SamPredictor`, `SamAutomaticMaskGenerator`, `get_model_info`) and the
-call that joins the two: `locate_pose_from_frames` / `locate_pose_from_frame`, reference crop and raw frame in, pose out.  Names
+call that joins the two: `locate_pose_from_frames` / `locate_pose_from_frame`, reference crop and raw frame in, pose out
+(`locate_poses_in_frame`: several references asked of one frame; `SharedFrames`: frames that several queries name;
+`share_frames` groups a list of queries by frame).  Names
 that belong to out-of-scope stages (dataset helpers) are not re-implemented here — the reference's own modules keep providing them.
 
 Unlike the reference façade, importing this module has no side effects (the reference builds the
@@ -20,11 +22,11 @@ import torch.nn.functional as F  # noqa: F401
 
 from .crops import crop_proposals, expand_box, get_affine_transform, get_image_crop_resize, get_K_crop_resize  # noqa: F401
 from .dinov2_utils import get_cls_token_torch, load_dinov2_model, set_torch_image  # noqa: F401
-from .driver import (ReferenceSet, encode_references, locate_and_match, locate_and_match_batch,  # noqa: F401
+from .driver import (ReferenceSet, SharedFrames, encode_references, locate_and_match, locate_and_match_batch,  # noqa: F401
                      locate_and_match_batch_u8, locate_match_pose_batch_u8, locate_match_pose_u8, locate_pose_from_frame,
-                     locate_pose_from_frames)
+                     locate_pose_from_frames, locate_poses_in_frame, share_frames)
 from .matcher import CoarseMatching, Matcher, ReferenceEncoding, default_cfg, dense_match  # noqa: F401
-from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch  # noqa: F401
+from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch, vote_top3_shared  # noqa: F401
 from .pipeline import PairPipeline, gather_counts, shard_range  # noqa: F401
 from .pose import estimate_pose, estimate_pose_batch, relative_pose_error  # noqa: F401
 from .sam_generator import (SamAutomaticMaskGenerator, SamPredictor, build_sam, build_sam_vit_b, build_sam_vit_h,  # noqa: F401
