@@ -316,6 +316,27 @@ int pope_dense_match_masked_f32(const float* feat0, long long stride0, const flo
                                 float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
                                 void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
                                 void* stream);
+/* match_type='sinkhorn' (coarse_matching.py:121-143): pope_dense_match_masked_f32 with the dual softmax replaced by log-domain
+ * optimal transport.  sim carries no temperature; Z [L+1, S+1] is sim (after the -1e9 fill) bordered by a dustbin row, column
+ * and corner that all hold *bin_score; norm = -log(L+S), log_mu = [norm]*L + [log(S)+norm], log_nu = [norm]*S + [log(L)+norm];
+ * from u = v = 0, skh_iters (>= 1) times u_i = log_mu_i - logsumexp_j(Z_ij + v_j), v_j = log_nu_j - logsumexp_i(Z_ij + u_i);
+ * conf = exp(Z + u + v - norm)[:L, :S].  skh_prefilter != 0 zeroes the rows of conf whose largest assignment over the S+1
+ * columns is the dustbin (strictly: a tie goes to the real cell) and the columns likewise (:136-140).  Threshold, border,
+ * mutual nearest neighbour, ordering and scaling then apply to conf exactly as in the dual-softmax entries.
+ *   bin_score: DEVICE pointer to one float, read by the kernels at run time (the learned parameter's own storage; the host
+ *     never reads it, an in-place update is seen by the next call).
+ *   The masks and scales are optional as above (NULL = none).  conf_matrix may be NULL: conf then lives in the workspace.
+ * Workspace: pope_dense_match_sinkhorn_workspace_bytes(...). */
+size_t pope_dense_match_sinkhorn_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks);
+int pope_dense_match_sinkhorn_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
+                                  int n, int L, int S, int C, int h0, int w0, int h1, int w1,
+                                  float thr, int border_rm, const float* bin_score, int skh_iters, int skh_prefilter, float scale,
+                                  const float* fill_mask0, const float* fill_mask1, const float* border_mask0,
+                                  const float* border_mask1, const float* scale0, const float* scale1,
+                                  float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids,
+                                  float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
+                                  void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
+                                  void* stream);
 /* Shorthands: POPE_PREC_F32_MFMA, conf_matrix published, no range flag. */
 size_t pope_dense_match_workspace_bytes(int n, int L, int S);
 int pope_dense_match_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,

@@ -150,6 +150,10 @@ PROTOTYPES = {
     "pope_dense_match_masked_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
                                     + [C.c_float, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.c_void_p] * 8
                                     + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_dense_match_sinkhorn_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "pope_dense_match_sinkhorn_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
+                                      + [C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 6
+                                      + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_loftr_layer_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "pope_loftr_encoder_layer_f32": (C.c_int, [C.POINTER(LoftrLayerWeights), C.c_void_p, C.c_void_p] + [C.c_int] * 5
                                      + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

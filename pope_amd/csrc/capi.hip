@@ -288,12 +288,26 @@ size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int p
     return MatchLayout(n, L, S, C, precision, publish_conf != 0).total + (has_border_masks ? pope_align256(size_t(n) * 4 * 4) : 0);
 }
 
-int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                                int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
-                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
-                                const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
-                                long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
-                                size_t workspace_bytes, int precision, unsigned* range_flag, void* stream) {
+namespace {
+// Sinkhorn scratch behind the dual-softmax layout: u [n, L + 1], v [n, S + 1], the last column step's maxima [n, S]
+struct SinkhornLayout {
+    size_t u, v, cmax, total;
+    SinkhornLayout(int n, int L, int S) {
+        u = pope_align256(size_t(n) * (L + 1) * 4);
+        v = pope_align256(size_t(n) * (S + 1) * 4);
+        cmax = pope_align256(size_t(n) * S * 4);
+        total = u + v + cmax;
+    }
+};
+
+// One body for both matchers: bin_score == nullptr is the dual softmax with `temperature`
+int dense_match_entry(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
+                      int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
+                      const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
+                      const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
+                      long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
+                      size_t workspace_bytes, int precision, unsigned* range_flag, void* stream, const float* bin_score,
+                      int skh_iters, int skh_prefilter) {
     if (!feat0 || !feat1 || !b_ids || !i_ids || !j_ids || !mconf || !mkpts0_c || !mkpts1_c || !counts || !workspace)
         return POPE_ERR_ARG;
     if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return POPE_ERR_ARG;
@@ -303,7 +317,8 @@ int pope_dense_match_masked_f32(const float* feat0, long long stride0, const flo
     const bool padded = border_mask0 || border_mask1;
     const MatchLayout lay(n, L, S, C, precision, publish);
     const size_t ext_bytes = padded ? pope_align256(size_t(n) * 4 * 4) : 0;
-    if (workspace_bytes < lay.total + ext_bytes) return POPE_ERR_WORKSPACE;
+    const SinkhornLayout skh(n, L, S);
+    if (workspace_bytes < lay.total + ext_bytes + (bin_score ? skh.total : 0)) return POPE_ERR_WORKSPACE;
     pope_carver ws{static_cast<char*>(workspace)};   // (every piece of the layout is a multiple of 256 bytes)
     MatchParams p = {};
     p.feat0 = feat0; p.feat1 = feat1;
@@ -340,7 +355,45 @@ int pope_dense_match_masked_f32(const float* feat0, long long stride0, const flo
     p.border0 = border_mask0; p.border1 = border_mask1;
     if (padded) p.extent = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.total);
     p.scale0 = scale0; p.scale1 = scale1;
-    return pope_launch_dense_match_f32(p, static_cast<hipStream_t>(stream));
+    if (!bin_score) return pope_launch_dense_match_f32(p, static_cast<hipStream_t>(stream));
+    pope_carver tail{static_cast<char*>(workspace) + lay.total + ext_bytes};
+    p.bin_score = bin_score; p.skh_iters = skh_iters; p.skh_prefilter = skh_prefilter;
+    p.skh_u = tail.take<float>(skh.u);
+    p.skh_v = tail.take<float>(skh.v);
+    p.skh_cmax = tail.take<float>(skh.cmax);
+    return pope_launch_dense_match_sinkhorn_f32(p, static_cast<hipStream_t>(stream));
+}
+}  // namespace
+
+int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
+                                int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
+                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
+                                const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
+                                long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
+                                size_t workspace_bytes, int precision, unsigned* range_flag, void* stream) {
+    return dense_match_entry(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, temperature, scale, fill_mask0,
+                             fill_mask1, border_mask0, border_mask1, scale0, scale1, conf_matrix, b_ids, i_ids, j_ids, mconf, mkpts0_c,
+                             mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream, nullptr, 0, 0);
+}
+
+size_t pope_dense_match_sinkhorn_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks) {
+    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
+    // the matrix holds conf after the confidence pass even when it is not published: it lives in the workspace then
+    return pope_dense_match_masked_workspace_bytes(n, L, S, C, precision, publish_conf, has_border_masks) + SinkhornLayout(n, L, S).total;
+}
+
+int pope_dense_match_sinkhorn_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
+                                  int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, const float* bin_score,
+                                  int skh_iters, int skh_prefilter, float scale, const float* fill_mask0, const float* fill_mask1,
+                                  const float* border_mask0, const float* border_mask1, const float* scale0, const float* scale1,
+                                  float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids, float* mconf,
+                                  float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace, size_t workspace_bytes,
+                                  int precision, unsigned* range_flag, void* stream) {
+    if (!bin_score || skh_iters < 1) return POPE_ERR_ARG;
+    return dense_match_entry(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, 1.0f, scale, fill_mask0,
+                             fill_mask1, border_mask0, border_mask1, scale0, scale1, conf_matrix, b_ids, i_ids, j_ids, mconf, mkpts0_c,
+                             mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream, bin_score, skh_iters,
+                             skh_prefilter);
 }
 
 size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead) {

@@ -229,9 +229,41 @@ struct MatchParams {
     const float* border0; const float* border1;
     int* extent;
     const float* scale0; const float* scale1;
+    // Sinkhorn matcher only (match_type='sinkhorn', sinkhorn.hip): the dustbin score is read on the device, from the
+    // parameter's own storage; u [n, L + 1] / v [n, S + 1] the dual potentials (last entry: the dustbin), skh_cmax [n, S] the
+    // column maxima of Z + u over the real rows after the last column step (the column prefilter's left-hand side)
+    const float* bin_score;
+    int skh_iters, skh_prefilter;
+    float* skh_u; float* skh_v; float* skh_cmax;
+    float skh_norm, skh_log_mu_bin, skh_log_nu_bin;   // -log(L + S), log(S) + norm, log(L) + norm (fp32, set by the launcher)
 };
 int pope_match_nrb2(int L);
 int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream);
+// match_type='sinkhorn': same contraction (temperature 1), then the passes of sinkhorn.hip in place of the dual softmax, then
+// the same selection / compaction kernels.  The matrix always ends up holding conf (in the workspace when not published).
+int pope_launch_dense_match_sinkhorn_f32(MatchParams p, hipStream_t stream);
+// sinkhorn.hip: p.sim holds Z's L x S block and p.row_max / p.row_sum its row softmax statistics; runs the iterations and the
+// confidence pass (conf in place; conf_rowmax / row_arg / row_cnt / colmax_part as conf_pass_kernel of match.hip leaves them)
+int pope_launch_sinkhorn_passes(const MatchParams& p, hipStream_t stream);
+
+#ifdef __HIPCC__
+struct RowBest {   // running (max, first argmax, number of argmax ties) of a row
+    float v;
+    int idx, cnt;
+    __device__ __forceinline__ void take(float c, int col) {
+        const bool gt = c > v, eq = c == v;
+        cnt = gt ? 1 : cnt + (eq ? 1 : 0);
+        idx = gt ? col : idx;   // columns arrive in ascending order per lane: a tie keeps the earlier column
+        v = gt ? c : v;
+    }
+    __device__ __forceinline__ void merge(float ov, int oidx, int ocnt) {
+        const bool gt = ov > v, eq = ov == v;
+        cnt = gt ? ocnt : cnt + (eq ? ocnt : 0);
+        idx = gt ? oidx : (eq && oidx < idx ? oidx : idx);
+        v = gt ? ov : v;
+    }
+};
+#endif
 
 // Batched PIL-exact preprocessing (preprocess.hip): resize (window / fixed-point weight tables from the host) ->
 // centre crop -> /255 -> normalise, uint8 HWC [P, Hin, Win, 3] -> fp32 NCHW [P, 3, ch, cw]

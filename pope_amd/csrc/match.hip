@@ -181,23 +181,6 @@ constexpr int CP_ROWS = 32;   // rows per workgroup: 8 per wave
 constexpr int CP_K = 16;      // column pairs per lane and chunk: a chunk is 64 * 2 * 16 = 2048 columns
 constexpr int CP_CHUNK = 64 * 2 * CP_K;
 
-struct RowBest {   // running (max, first argmax, number of argmax ties) of a row
-    float v;
-    int idx, cnt;
-    __device__ __forceinline__ void take(float c, int col) {
-        const bool gt = c > v, eq = c == v;
-        cnt = gt ? 1 : cnt + (eq ? 1 : 0);
-        idx = gt ? col : idx;   // columns arrive in ascending order per lane: a tie keeps the earlier column
-        v = gt ? c : v;
-    }
-    __device__ __forceinline__ void merge(float ov, int oidx, int ocnt) {
-        const bool gt = ov > v, eq = ov == v;
-        cnt = gt ? ocnt : cnt + (eq ? ocnt : 0);
-        idx = gt ? oidx : (eq && oidx < idx ? oidx : idx);
-        v = gt ? ov : v;
-    }
-};
-
 // Workgroup = 32 rows of one pair x all columns.  Lane l of every wave owns columns c0 + 128 k + 2 l (+1): it keeps
 // their column statistics and their running column maximum in registers while the wave walks its 8 rows, so a row is
 // read as 8-byte pieces that make whole 512-byte wave transactions.  VEC2 = false (odd S: rows are only 4-byte
@@ -603,13 +586,21 @@ void launch_conf_and_select(const MatchParams& p, hipStream_t stream) {
 
 int pope_match_nrb2(int L) { return (L + CP_ROWS - 1) / CP_ROWS; }
 
-int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
+namespace {
+
+int check_match_params(const MatchParams& p) {
     if (p.n <= 0 || p.L <= 0 || p.S <= 0 || p.C <= 0 || (p.C & 3) || p.n > 65535) return POPE_ERR_ARG;
     if (p.L != p.h0 * p.w0 || p.S != p.h1 * p.w1) return POPE_ERR_ARG;
     if (p.bs0 < (long long)p.L * p.C || p.bs1 < (long long)p.S * p.C || (p.bs0 & 3) || (p.bs1 & 3)) return POPE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(p.feat0) & 15) || (reinterpret_cast<uintptr_t>(p.feat1) & 15)) return POPE_ERR_ARG;
     if (!p.sim || !p.colmax_part || p.nrb2 != pope_match_nrb2(p.L) || p.ldp < p.S || (p.ldp & 3)) return POPE_ERR_ARG;
     if ((p.border0 || p.border1) && !p.extent) return POPE_ERR_ARG;
+    return POPE_OK;
+}
+
+// sim = (f0 / sqrt(C)) . (f1 / sqrt(C))^T / temperature with the padding fill, and its softmax statistics: row_max / row_sum
+// always, col_max / col_sum when `col_stats` (the Sinkhorn matcher's column steps run on u, not on sim alone)
+int launch_contraction(const MatchParams& p, bool col_stats, hipStream_t stream) {
     const bool fill = p.fill0 || p.fill1;
     bool sim_done = false;
     if (p.planes0 && p.planes1 && p.row_part && p.col_pmax && p.col_psum && (p.C & 31) == 0 && p.C >= 64) {
@@ -633,7 +624,7 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
         if (rc == 0) {
             sim_done = true;
             hipLaunchKernelGGL(combine_row_stats_kernel, dim3(unsigned((size_t(p.n) * p.L + 255) / 256)), dim3(256), 0, stream, p);
-            hipLaunchKernelGGL(combine_col_stats_kernel, dim3((p.S + 255) / 256, p.n), dim3(256), 0, stream, p);
+            if (col_stats) hipLaunchKernelGGL(combine_col_stats_kernel, dim3((p.S + 255) / 256, p.n), dim3(256), 0, stream, p);
         } else if (rc != POPE_ERR_ARG) {
             return rc;  // shapes beyond the 32-bit offsets: the fp32 kernels below
         }
@@ -643,13 +634,43 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
         if (fill) hipLaunchKernelGGL(sim_kernel<true>, dim3(tiles, p.n), dim3(THREADS), LDS_BYTES, stream, p, 0.f);
         else hipLaunchKernelGGL(sim_kernel<false>, dim3(tiles, p.n), dim3(THREADS), LDS_BYTES, stream, p, 0.f);
         hipLaunchKernelGGL(row_stats_kernel, dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(col_stats_kernel, dim3((p.S + 63) / 64, p.n), dim3(256), 0, stream, p);
+        if (col_stats) hipLaunchKernelGGL(col_stats_kernel, dim3((p.S + 63) / 64, p.n), dim3(256), 0, stream, p);
     }
-    if (p.extent) hipLaunchKernelGGL(border_extent_kernel, dim3(p.n, 2), dim3(256), 0, stream, p);
-    if (p.publish_conf) launch_conf_and_select<true>(p, stream);
-    else launch_conf_and_select<false>(p, stream);
+    return POPE_OK;
+}
+
+void launch_compaction(const MatchParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(count_kernel, dim3(p.n), dim3(256), 0, stream, p);
     if (p.scale0 || p.scale1) hipLaunchKernelGGL(scatter_kernel<true>, dim3(p.n), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(scatter_kernel<false>, dim3(p.n), dim3(256), 0, stream, p);
+}
+
+}  // namespace
+
+int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
+    POPE_TRY(check_match_params(p));
+    POPE_TRY(launch_contraction(p, true, stream));
+    if (p.extent) hipLaunchKernelGGL(border_extent_kernel, dim3(p.n, 2), dim3(256), 0, stream, p);
+    if (p.publish_conf) launch_conf_and_select<true>(p, stream);
+    else launch_conf_and_select<false>(p, stream);
+    launch_compaction(p, stream);
+    return pope_check_launch();
+}
+
+int pope_launch_dense_match_sinkhorn_f32(MatchParams p, hipStream_t stream) {
+    POPE_TRY(check_match_params(p));
+    if (!p.bin_score || p.skh_iters < 1 || !p.skh_u || !p.skh_v || !p.skh_cmax) return POPE_ERR_ARG;
+    p.temperature = 1.0f;   // coarse_matching.py:122: the similarity of the transport problem has no temperature
+    p.skh_norm = -logf(float(p.L + p.S));
+    p.skh_log_mu_bin = logf(float(p.S)) + p.skh_norm;
+    p.skh_log_nu_bin = logf(float(p.L)) + p.skh_norm;
+    POPE_TRY(launch_contraction(p, false, stream));
+    if (p.extent) hipLaunchKernelGGL(border_extent_kernel, dim3(p.n, 2), dim3(256), 0, stream, p);
+    POPE_TRY(pope_launch_sinkhorn_passes(p, stream));
+    // the matrix holds conf whether or not the caller keeps it: the tie re-scan of select_kernel reads it
+    hipLaunchKernelGGL(combine_colmax_kernel, dim3((p.S + 255) / 256, p.n), dim3(256), 0, stream, p);
+    if (p.extent) hipLaunchKernelGGL((select_kernel<true, true>), dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((select_kernel<true, false>), dim3((p.L + 3) / 4, p.n), dim3(256), 0, stream, p);
+    launch_compaction(p, stream);
     return pope_check_launch();
 }

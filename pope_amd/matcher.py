@@ -1,6 +1,7 @@
 """Dense cross-image matcher on the HIP kernels: mirror of the reference ``CoarseMatching``
-(src/matcher/utils/coarse_matching.py:60-261) for the eval / dual-softmax path, plus a functional
-``dense_match`` used directly on DINOv2 patch tokens (BASELINE config 3).
+(src/matcher/utils/coarse_matching.py:60-261) for the eval path with both of its matchers, ``match_type='dual_softmax'`` and
+``match_type='sinkhorn'`` (log-domain optimal transport with the learned dustbin score ``bin_score``, csrc/sinkhorn.hip), plus
+a functional ``dense_match`` used directly on DINOv2 patch tokens (BASELINE config 3).
 """
 import ctypes as C
 import warnings
@@ -41,8 +42,8 @@ DEFAULT_PRECISION = "f16x3"   # arithmetic of the L x S x C contraction ("f32": 
 @torch.no_grad()
 def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, temperature=0.1, precision=None,
                 on_overflow="rerun_f32", want_conf=True, mask0=None, mask1=None, border_mask0=None, border_mask1=None,
-                scale0=None, scale1=None):
-    """All-pairs similarity -> dual softmax -> threshold/border/mutual-NN -> ordered matches.
+                scale0=None, scale1=None, match_type="dual_softmax", bin_score=None, skh_iters=3, skh_prefilter=True):
+    """All-pairs similarity -> dual softmax (or Sinkhorn) -> threshold/border/mutual-NN -> ordered matches.
 
     feat0 [n,L,C], feat1 [n,S,C] fp32 on the GPU.  Returns the dict CoarseMatching publishes
     (coarse_matching.py:145-148,239-259): conf_matrix, b_ids, i_ids, j_ids, gt_mask, m_bids,
@@ -56,7 +57,25 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     Padded batches and rescaling (coarse_matching.py:115-118,178-184,242-250), all optional and independent of each other:
     mask0 [n, L] / mask1 [n, S] (or [n, h, w]) fill sim with -1e9 where mask0[i] * mask1[j] == 0 (a missing one counts as
     ones); border_mask0 / border_mask1 [n, h, w] put the bottom / right border at each pair's valid extent; scale0 / scale1
-    [n, 2] (x, y) rescale mkpts0_c / mkpts1_c.  Masks are bool or 0 / 1; the kernels apply them, torch only converts."""
+    [n, 2] (x, y) rescale mkpts0_c / mkpts1_c.  Masks are bool or 0 / 1; the kernels apply them, torch only converts.
+
+    match_type="sinkhorn" (coarse_matching.py:121-143) replaces the dual softmax by `skh_iters` (>= 1) iterations of log-domain
+    optimal transport over the similarity without temperature, bordered by a dustbin row and column of score `bin_score`;
+    conf_matrix is the assignment without its dustbins, and `skh_prefilter` zeroes the rows and columns whose largest
+    assignment is their dustbin.  `bin_score` is a 0-d or one-element fp32 tensor (the learned parameter): the kernels read it
+    from its own storage, the host never does; a tensor on another device is copied over.  `temperature` is not used."""
+    if match_type not in ("dual_softmax", "sinkhorn"):
+        raise ValueError(f"dense_match: match_type is 'dual_softmax' or 'sinkhorn', got {match_type!r}")
+    sinkhorn = match_type == "sinkhorn"
+    if sinkhorn:
+        if not isinstance(bin_score, torch.Tensor):
+            raise TypeError("dense_match: match_type='sinkhorn' needs bin_score as a float32 tensor (0-d or one element)")
+        if bin_score.dtype != torch.float32:
+            raise TypeError(f"dense_match: bin_score is float32, got {bin_score.dtype}")
+        if bin_score.numel() != 1:
+            raise ValueError(f"dense_match: bin_score holds one value, got shape {tuple(bin_score.shape)}")
+        if int(skh_iters) < 1:
+            raise ValueError(f"dense_match: skh_iters >= 1, got {skh_iters}")
     require_cuda(feat0, "dense_match")
     require_cuda(feat1, "dense_match")
     if feat0.dtype != torch.float32 or feat1.dtype != torch.float32:
@@ -92,7 +111,13 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     if Cc % 32 or Cc < 64:
         precision = "f32"   # the planes layout needs whole 32-column chunks
     prec = _lib.PRECISIONS[precision]
-    if masked:
+    if sinkhorn:
+        bin_score = bin_score.detach()
+        if bin_score.device != dev:
+            bin_score = bin_score.to(dev)
+        ws_bytes = lib.pope_dense_match_sinkhorn_workspace_bytes(n, L, S, Cc, prec, 1 if want_conf else 0,
+                                                                 int(bord0 is not None or bord1 is not None))
+    elif masked:
         ws_bytes = lib.pope_dense_match_masked_workspace_bytes(n, L, S, Cc, prec, 1 if want_conf else 0,
                                                                int(bord0 is not None or bord1 is not None))
     else:
@@ -113,7 +138,15 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     bs0 = feat0.stride(0) if n > 1 else L * Cc
     bs1 = feat1.stride(0) if n > 1 else S * Cc
     with on_device_of(feat0):
-        if masked:
+        if sinkhorn:
+            check(lib.pope_dense_match_sinkhorn_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
+                                                    bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
+                                                    C.c_void_p(bin_score.data_ptr()), int(skh_iters), int(bool(skh_prefilter)),
+                                                    float(scale), *[ptr(t) for t in extra], ptr(conf), ptr(b_ids),
+                                                    ptr(i_ids), ptr(j_ids), ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts),
+                                                    C.c_void_p(ws.data_ptr()), ws_bytes, prec, flag_ptr, stream_of(dev)),
+                  "pope_dense_match_sinkhorn_f32")
+        elif masked:
             check(lib.pope_dense_match_masked_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
                                                   bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
                                                   float(temperature), float(scale), *[ptr(t) for t in extra], ptr(conf), ptr(b_ids),
@@ -135,7 +168,7 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
         warnings.warn(msg + "; re-running with the fp32-MFMA contraction")
         del conf, ws, b_ids, i_ids, j_ids, mconf, mk0, mk1
         return dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr, border_rm, temperature, "f32", on_overflow, want_conf,
-                           *extra)
+                           *extra, match_type=match_type, bin_score=bin_score, skh_iters=skh_iters, skh_prefilter=skh_prefilter)
     m = int(counts_h[n])
     b_ids, i_ids, j_ids, mconf = b_ids[:m], i_ids[:m], j_ids[:m], mconf[:m]
     return {
@@ -153,7 +186,10 @@ def _loftr():
 
 
 class CoarseMatching(nn.Module):
-    """Drop-in for the reference module (eval, match_type='dual_softmax')."""
+    """Drop-in for the reference module (eval), match_type 'dual_softmax' or 'sinkhorn'.  The Sinkhorn matcher owns the learned
+    dustbin score as the parameter `bin_score` (initialised to config['skh_init_bin_score']; the `coarse_matching.bin_score` of
+    the released `*_ot` checkpoints) and hands the parameter itself to the kernels.  config['sparse_spvs'] is accepted and
+    ignored: the `conf_matrix_with_bin` it asks for is consumed only by the training loss."""
 
     def __init__(self, config):
         super().__init__()
@@ -165,9 +201,12 @@ class CoarseMatching(nn.Module):
         self.match_type = config["match_type"]
         if self.match_type == "dual_softmax":
             self.temperature = config["dsmax_temperature"]
+        elif self.match_type == "sinkhorn":
+            self.bin_score = nn.Parameter(torch.tensor(config["skh_init_bin_score"], dtype=torch.float32))
+            self.skh_iters = config["skh_iters"]
+            self.skh_prefilter = config["skh_prefilter"]
         else:
-            raise NotImplementedError("pope_amd: only the dual_softmax matcher is on the hot path "
-                                      "(default_cfg; sinkhorn needs the absent superglue.py in the reference too)")
+            raise NotImplementedError(f"pope_amd: match_type is 'dual_softmax' or 'sinkhorn', got {self.match_type!r}")
 
     def forward(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None):
         """mask_c0 [n, L] / mask_c1 [n, S]: the similarity fill (coarse_matching.py:115-118, applied when mask_c0 is given);
@@ -180,9 +219,14 @@ class CoarseMatching(nn.Module):
             raise ValueError("CoarseMatching: mask_c0 needs mask_c1 (the fill is mask_c0[i] * mask_c1[j])")
         fill0, fill1 = (mask_c0, mask_c1) if mask_c0 is not None else (None, None)
         bord0, bord1 = (data["mask0"], data["mask1"]) if "mask0" in data else (None, None)
+        if self.match_type == "sinkhorn":
+            how = {"match_type": "sinkhorn", "bin_score": self.bin_score, "skh_iters": self.skh_iters,
+                   "skh_prefilter": self.skh_prefilter}
+        else:
+            how = {"temperature": self.temperature}
         out = dense_match(feat_c0, feat_c1, data["hw0_c"], data["hw1_c"], data["hw0_i"], self.thr, self.border_rm,
-                          self.temperature, mask0=fill0, mask1=fill1, border_mask0=bord0, border_mask1=bord1,
-                          scale0=data.get("scale0"), scale1=data.get("scale1"))
+                          mask0=fill0, mask1=fill1, border_mask0=bord0, border_mask1=bord1,
+                          scale0=data.get("scale0"), scale1=data.get("scale1"), **how)
         out.pop("counts")
         data.update(out)
 

@@ -464,6 +464,53 @@ def masked_xfmr_case():
     return f0, f1, m0.flatten(1), m1.flatten(1)
 
 
+# ---- Sinkhorn coarse matching (match_type='sinkhorn'; tests/golden/sinkhorn.npz) --------------------------------------------
+# name: (pairs, grid 0, grid 1, seed).  "masked_16x16" also carries padding masks and scales; "unrelated" has nothing planted.
+SINKHORN_CASES = {
+    # L = 192, S = 140: L != S, neither a multiple of a tile.  (Seed searched: under every SINKHORN_SETTINGS entry each row's and
+    # column's dustbin stays > 1e-3 relative away from its best real entry; a typical seed leaves ~1e-4 over the ~4000 decisions.)
+    "12x16_vs_10x14": (2, (12, 16), (10, 14), 123),
+    "32x32": (3, (32, 32), (32, 32), 42),              # the drivers' grid
+    "16x16_vs_12x16": (1, (16, 16), (12, 16), 43),
+    "masked_16x16": (2, (16, 16), (16, 16), 44),
+    "unrelated": (2, (12, 16), (10, 14), 45),
+}
+# (skh_iters, bin_score, skh_prefilter) run on "12x16_vs_10x14" beside the default (3, 1.0, True)
+SINKHORN_SETTINGS = [(it, b, pre) for it in (1, 3) for b in (1.0, 2.5, -0.5) for pre in (True, False)]
+
+
+def sinkhorn_case(name):
+    """CoarseMatching inputs for the Sinkhorn matcher, C = 256: dict(feat0 [n, L, C], feat1 [n, S, C], hw0, hw1, hw0_i) and,
+    for "masked_16x16", mask0 / mask1 [n, h, w] bool and scale0 / scale1 [n, 2].  Both sides are N(0, 1); 60 % (masked: 90 %) of the cells of
+    the smaller side (of its valid cells, under masks) are copied across under a random permutation with noise 0.3 (a true pair
+    then scores ~12 in sim, an unrelated one ~N(0, 0.75)), and everything is scaled by sqrt(12).  "masked_16x16": pair 0 unpadded, pair 1 padded to the
+    valid extents 12 x 10 (image 0) and 14 x 16 (image 1)."""
+    n, hw0, hw1, seed = SINKHORN_CASES[name]
+    g = torch.Generator().manual_seed(seed)
+    L, S, c = hw0[0] * hw0[1], hw1[0] * hw1[1], 256
+    f0 = torch.randn(n, L, c, generator=g)
+    f1 = torch.randn(n, S, c, generator=g)
+    m0 = torch.ones(n, *hw0, dtype=torch.bool)
+    m1 = torch.ones(n, *hw1, dtype=torch.bool)
+    if name == "masked_16x16":
+        m0[1, 12:] = False
+        m0[1, :, 10:] = False
+        m1[1, 14:] = False
+    frac = 0.9 if name == "masked_16x16" else 0.6   # (a padded pair keeps an 8 x 6 interior: plant more to keep 16 matches)
+    if name != "unrelated":
+        for b in range(n):   # planted among the valid cells
+            v0, v1 = m0[b].flatten().nonzero().flatten(), m1[b].flatten().nonzero().flatten()
+            k = int(frac * min(len(v0), len(v1)))
+            src = v0[torch.randperm(len(v0), generator=g)[:k]]
+            dst = v1[torch.randperm(len(v1), generator=g)[:k]]
+            f1[b, dst] = f0[b, src] + 0.3 * torch.randn(k, c, generator=g)
+    out = {"feat0": (f0 * math.sqrt(12.0)).contiguous(), "feat1": (f1 * math.sqrt(12.0)).contiguous(), "hw0": hw0, "hw1": hw1,
+           "hw0_i": (8 * hw0[0], 8 * hw0[1])}
+    if name == "masked_16x16":
+        out.update(mask0=m0, mask1=m1, scale0=torch.tensor([[1.5, 0.75], [0.3, 2.5]]), scale1=torch.tensor([[0.6, 1.7], [2.0, 0.5]]))
+    return out
+
+
 # ---- LoFTR layers with full (softmax) attention ---------------------------------------------------------------------
 # name: (stage, layer_names (None: ONE layer call, layers.0), n, L, S, seed, taps of the two outputs as (dim, step))
 LOFTR_FULL_CASES = {
