@@ -848,6 +848,59 @@ int pope_slot_tally_f32(const long long* m_bids, const float* mconf, const float
                         long long* matching_score, int* best_slot, int* best_count, float* best_kpts0, float* best_kpts1,
                         void* stream);
 
+/* ---- learned pose regressor (pose/model.py:Mkpts_Reg_Model) ------------------------------------------------------ */
+
+/* One nn.TransformerEncoderLayer(d_model=76, nhead=2) in torch's own layouts (device pointers, fp32): in_proj [228, 76] /
+ * [228], out_proj [76, 76] / [76], linear1 [2048, 76] / [2048], linear2 [76, 2048] / [76], norm1 / norm2 [76] each. */
+typedef struct pope_pose_regressor_layer {
+    const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} pope_pose_regressor_layer;
+
+/* mode: POPE_ROT_MATRIX (rotation_head 32 -> 9, view(3, 3)), POPE_ROT_QUAT (32 -> 4, qua2mat, w x y z) or POPE_ROT_6D
+ * (32 -> 6, o6d2mat, x y z as columns).  mlp_w[i] / mlp_b[i] = mlp.{0,3,6,9,12,15,18}: [19S, 76S], [S, 19S], [256, S],
+ * [128, 256], [64, 128], [32, 64], [32, 32].  The pointers are read on every call: no derived copy exists. */
+#define POPE_ROT_MATRIX 0
+#define POPE_ROT_QUAT 1
+#define POPE_ROT_6D 2
+typedef struct pope_pose_regressor_weights {
+    int num_sample, mode;
+    pope_pose_regressor_layer layers[4];
+    const float* mlp_w[7];
+    const float* mlp_b[7];
+    const float *trans_w, *trans_b, *rot_w, *rot_b;
+} pope_pose_regressor_weights;
+
+/* Mkpts_Reg_Model.forward (pose/model.py:106-114) for B pairs of S = num_sample sample slots, fp32 throughout:
+ * embedding [x, sin(f x), cos(f x)] with f = linspace(1, 256, 9) and the fp32-rounded product f * x as the argument ->
+ * four post-norm encoder layers (ReLU, eps 1e-5) -> mlp -> translation / rotation heads -> convert2matrix.
+ * The B pairs form B / G attention groups of G consecutive pairs (1 <= G <= 64, B % G == 0): attention runs across the G
+ * members of a group, separately per sample slot — the reference's batch_first=False reading of [B, S, 76] is G = B; every
+ * pair on its own (the notebooks' unsqueeze(0)) is G = 1.
+ * Input, one of:  dense0 / dense1 [B, S, 2] (kpts0 / kpts1 / counts NULL), or the matcher's compacted buffers kpts0 / kpts1
+ * [M, 2] with pairs contiguous and counts [B] int32 on the DEVICE (dense0 / dense1 NULL; the contract of
+ * pope_estimate_pose_f64).  A pair with count <= S is zero-padded to S rows; with count > S it is sampled: by sample_index
+ * [B, S] int32 when given (an entry outside [0, count) sets status -2 for that pair and is not read), else by the device
+ * sampler: key(i) = splitmix64(seed_b ^ (i + 1) * 0xD1B54A32D192ED03) (splitmix64 as in pose_math.h), slot j takes the match
+ * with the j-th smallest (key, i).  seeds [B] uint64 on the device (NULL: all 0).
+ * Outputs (device): trans [B, 3], rot [B, 9] row-major, status [B] int32 (0 ok; -1 refused: negative count here or before,
+ * or counts exceed M; -2 sample_index out of range) — a pair whose status is not 0 gets zeros.
+ * The *_embedding / *_encoder entries stop early for tests: x_out [B, S, 76] after the embedding / after layer 4, index_out
+ * [B, S] int32 the chosen match per slot (-1: padding).  Workspace >= pope_pose_regressor_workspace_bytes(B, S), 256-byte
+ * aligned.  Bad arguments (null pointers, S != weights->num_sample, G, B, workspace) return a negative code before any launch. */
+size_t pope_pose_regressor_workspace_bytes(int B, int S);
+int pope_pose_regressor_forward_f32(const pope_pose_regressor_weights* w, const float* dense0, const float* dense1,
+                                    const float* kpts0, const float* kpts1, const int* counts, const int* sample_index,
+                                    const unsigned long long* seeds, int B, int S, int G, long long M, float* trans, float* rot,
+                                    int* status, void* workspace, size_t workspace_bytes, void* stream);
+int pope_pose_regressor_embedding_f32(const float* dense0, const float* dense1, const float* kpts0, const float* kpts1,
+                                      const int* counts, const int* sample_index, const unsigned long long* seeds, int B, int S,
+                                      long long M, float* x_out, int* index_out, int* status, void* stream);
+int pope_pose_regressor_encoder_f32(const pope_pose_regressor_weights* w, const float* dense0, const float* dense1,
+                                    const float* kpts0, const float* kpts1, const int* counts, const int* sample_index,
+                                    const unsigned long long* seeds, int B, int S, int G, long long M, float* x_out,
+                                    int* index_out, int* status, void* stream);
+
 /* ---- host-side helper ------------------------------------------------------------------------ */
 
 /* Streaming top-3 proposal vote — eval_linemod_json.py:71,95-101 (HOST pointers): slots start at

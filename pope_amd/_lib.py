@@ -80,6 +80,16 @@ class SamMaskEmbedWeights(C.Structure):
         (n, C.c_void_p) for n in ("conv1_w", "conv1_b", "ln1_w", "ln1_b", "conv2_w", "conv2_b", "ln2_w", "ln2_b", "conv3_w", "conv3_b")]
 
 
+class PoseRegressorLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b", "linear2_w",
+                                           "linear2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
+
+
+class PoseRegressorWeights(C.Structure):
+    _fields_ = [("num_sample", C.c_int), ("mode", C.c_int), ("layers", PoseRegressorLayer * 4), ("mlp_w", C.c_void_p * 7),
+                ("mlp_b", C.c_void_p * 7)] + [(n, C.c_void_p) for n in ("trans_w", "trans_b", "rot_w", "rot_b")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pope_hip.h
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
@@ -213,6 +223,12 @@ PROTOTYPES = {
     "pope_estimate_pose_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
     "pope_estimate_pose_f64": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_double, C.c_double, C.c_int, C.c_ulonglong]
                                + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pope_pose_regressor_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pope_pose_regressor_forward_f32": (C.c_int, [C.POINTER(PoseRegressorWeights)] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_longlong]
+                                        + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "pope_pose_regressor_embedding_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4),
+    "pope_pose_regressor_encoder_f32": (C.c_int, [C.POINTER(PoseRegressorWeights)] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_longlong]
+                                        + [C.c_void_p] * 4),
     "pope_five_point_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_streaming_top3_host": (C.c_int, [c_float_p, C.c_int, c_float_p, c_ll_p]),
     "pope_vote_top3_batch_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5 + [C.c_void_p]),

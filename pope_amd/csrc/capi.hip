@@ -777,6 +777,98 @@ int pope_estimate_pose_f64(const float* kpts0, const float* kpts1, const int* co
     return pope_launch_estimate_pose(q, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+// ---- learned pose regressor (pose_regressor.hip) ---------------------------------------------------------------------------
+
+namespace {
+
+struct PoseRegWorkspace { size_t x, index, y1, y2, total; };
+PoseRegWorkspace posereg_layout(int B, int S) {
+    PoseRegWorkspace l;
+    const size_t b = size_t(B), s = size_t(S);
+    l.x = pope_align256(b * s * 76 * sizeof(float));
+    l.index = pope_align256(b * s * sizeof(int));
+    l.y1 = pope_align256(b * s * 19 * sizeof(float));
+    l.y2 = pope_align256(b * s * sizeof(float));
+    l.total = l.x + l.index + l.y1 + l.y2;
+    return l;
+}
+
+bool posereg_weights_ok(const pope_pose_regressor_weights* w, int S) {
+    if (!w || w->num_sample != S || w->mode < POPE_ROT_MATRIX || w->mode > POPE_ROT_6D) return false;
+    uintptr_t bits = 0;
+    bool all = true;
+    auto see = [&](const float* p) { all = all && p; bits |= reinterpret_cast<uintptr_t>(p); };
+    for (const pope_pose_regressor_layer& l : w->layers)
+        for (const float* p : {l.in_proj_w, l.in_proj_b, l.out_proj_w, l.out_proj_b, l.linear1_w, l.linear1_b, l.linear2_w, l.linear2_b,
+                               l.norm1_w, l.norm1_b, l.norm2_w, l.norm2_b}) see(p);
+    for (int i = 0; i < 7; ++i) { see(w->mlp_w[i]); see(w->mlp_b[i]); }
+    for (const float* p : {w->trans_w, w->trans_b, w->rot_w, w->rot_b}) see(p);
+    return all && !(bits & 15);
+}
+
+PoseRegInput posereg_input(const float* dense0, const float* dense1, const float* kpts0, const float* kpts1, const int* counts,
+                           const int* sample_index, const unsigned long long* seeds, int B, int S, long long M) {
+    PoseRegInput in = {};
+    in.dense0 = dense0; in.dense1 = dense1; in.kpts0 = kpts0; in.kpts1 = kpts1; in.counts = counts; in.sample_index = sample_index;
+    in.seeds = seeds; in.B = B; in.S = S; in.M = M;
+    return in;
+}
+
+int posereg_encoder(const pope_pose_regressor_weights* w, const PoseRegInput& in, int G, float* X, int* index, int* status,
+                    hipStream_t stream) {
+    POPE_TRY(pope_launch_posereg_embed(in, X, index, status, stream));
+    for (const pope_pose_regressor_layer& l : w->layers) POPE_TRY(pope_launch_posereg_layer(l, X, in.B, in.S, G, stream));
+    return POPE_OK;
+}
+
+}  // namespace
+
+size_t pope_pose_regressor_workspace_bytes(int B, int S) { return B > 0 && S > 0 ? posereg_layout(B, S).total : 0; }
+
+int pope_pose_regressor_embedding_f32(const float* dense0, const float* dense1, const float* kpts0, const float* kpts1,
+                                      const int* counts, const int* sample_index, const unsigned long long* seeds, int B, int S,
+                                      long long M, float* x_out, int* index_out, int* status, void* stream) {
+    const PoseRegInput in = posereg_input(dense0, dense1, kpts0, kpts1, counts, sample_index, seeds, B, S, M);
+    POPE_TRY(pope_posereg_input_check(in));
+    if (!x_out || !index_out || !status) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_posereg_embed(in, x_out, index_out, status, static_cast<hipStream_t>(stream));
+}
+
+int pope_pose_regressor_encoder_f32(const pope_pose_regressor_weights* w, const float* dense0, const float* dense1,
+                                    const float* kpts0, const float* kpts1, const int* counts, const int* sample_index,
+                                    const unsigned long long* seeds, int B, int S, int G, long long M, float* x_out,
+                                    int* index_out, int* status, void* stream) {
+    const PoseRegInput in = posereg_input(dense0, dense1, kpts0, kpts1, counts, sample_index, seeds, B, S, M);
+    POPE_TRY(pope_posereg_input_check(in));
+    if (!posereg_weights_ok(w, S) || !x_out || !index_out || !status || G < 1 || G > 64 || B % G) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return posereg_encoder(w, in, G, x_out, index_out, status, static_cast<hipStream_t>(stream));
+}
+
+int pope_pose_regressor_forward_f32(const pope_pose_regressor_weights* w, const float* dense0, const float* dense1,
+                                    const float* kpts0, const float* kpts1, const int* counts, const int* sample_index,
+                                    const unsigned long long* seeds, int B, int S, int G, long long M, float* trans, float* rot,
+                                    int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const PoseRegInput in = posereg_input(dense0, dense1, kpts0, kpts1, counts, sample_index, seeds, B, S, M);
+    POPE_TRY(pope_posereg_input_check(in));
+    if (!posereg_weights_ok(w, S) || !trans || !rot || !status || G < 1 || G > 64 || B % G) return POPE_ERR_ARG;
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return POPE_ERR_ARG;
+    const PoseRegWorkspace lay = posereg_layout(B, S);
+    if (workspace_bytes < lay.total) return POPE_ERR_WORKSPACE;
+    StreamDevice on_device(stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    pope_carver ws{static_cast<char*>(workspace)};
+    float* X = ws.take<float>(lay.x);
+    int* index = ws.take<int>(lay.index);
+    float* y1 = ws.take<float>(lay.y1);
+    float* y2 = ws.take<float>(lay.y2);
+    POPE_TRY(posereg_encoder(w, in, G, X, index, status, st));
+    POPE_TRY(pope_launch_posereg_stream_linear(X, w->mlp_w[0], w->mlp_b[0], y1, B, 76ll * S, 19 * S, st));
+    POPE_TRY(pope_launch_posereg_stream_linear(y1, w->mlp_w[1], w->mlp_b[1], y2, B, 19ll * S, S, st));
+    return pope_launch_posereg_tail(*w, y2, status, B, trans, rot, st);
+}
+
 int pope_five_point_f64(const double* x0, const double* x1, int S, double* E_out, int* n_out, void* stream) {
     StreamDevice on_device(stream);
     return pope_launch_five_point(x0, x1, S, E_out, n_out, static_cast<hipStream_t>(stream));

@@ -513,3 +513,22 @@ struct SamRleArgs {
 };
 int pope_sam_rle_check(const SamRleArgs& a);   // no HIP call
 int pope_launch_sam_rle(const SamRleArgs& a, hipStream_t stream);
+
+// Learned pose regressor (pose_regressor.hip; pose/model.py:Mkpts_Reg_Model): the inputs of pope_pose_regressor_forward_f32
+struct PoseRegInput {
+    const float *dense0, *dense1;             // [B, S, 2], or
+    const float *kpts0, *kpts1;               // [M, 2] compacted, with
+    const int* counts;                        // [B] (device)
+    const int* sample_index;                  // [B, S] or null
+    const unsigned long long* seeds;          // [B] or null
+    int B, S;
+    long long M;
+};
+int pope_posereg_input_check(const PoseRegInput& in);   // no HIP call
+int pope_launch_posereg_embed(const PoseRegInput& in, float* X, int* index, int* status, hipStream_t stream);
+int pope_launch_posereg_layer(const pope_pose_regressor_layer& w, float* X, int B, int S, int G, hipStream_t stream);
+// Y[B, N] = leaky_relu(A[B, K] . W[N, K]^T + bias, 0.01), W read once per chunk of pairs (mlp.0 and mlp.3)
+int pope_launch_posereg_stream_linear(const float* A, const float* W, const float* bias, float* Y, int B, long long K, int N,
+                                      hipStream_t stream);
+int pope_launch_posereg_tail(const pope_pose_regressor_weights& w, const float* Y2, const int* status, int B, float* trans,
+                             float* rot, hipStream_t stream);

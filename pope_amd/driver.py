@@ -393,7 +393,8 @@ def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, propos
 
 @torch.no_grad()
 def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bboxes_xywh, K0, K1, conf_thr=0.9, ransac_thr=0.5,
-                               ransac_conf=0.99, out_size=256, ref_index=None, frame_index=None):
+                               ransac_conf=0.99, out_size=256, ref_index=None, frame_index=None, pose_regressor=None,
+                               regressor_seed=0):
     """`locate_match_pose_u8` for Q queries in one call: `refs_bgr` [Q, H0, W0, 3] uint8, `frames_bgr` [Q, H, W, 3] uint8 (an
     array, a tensor or Q frames of one size), `bboxes_xywh` a list of Q arrays [P_q, 4] (P_q = 0 allowed), `K0` / `K1` [3, 3]
     for all queries or [Q, 3, 3].  Returns a list of Q dicts, each what `locate_match_pose_u8` returns for that query alone.
@@ -409,9 +410,15 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     q is asked of frame `frame_index[q]`.  The crops, their intrinsics, their preprocessing and their DINOv2 forward are done
     once per frame; the vote (ops.vote_top3_shared), the 3 Q Matcher pairs, the tally and the pose stay per query.  A frame no
     query names is allowed (its crops are computed and unused).  Each query's dict is, key by key and bit for bit, that of
-    the call with `frames_bgr[frame_index]` and the box lists repeated, and its `boxes` / `K_crops` are arrays of its own."""
+    the call with `frames_bgr[frame_index]` and the box lists repeated, and its `boxes` / `K_crops` are arrays of its own.
+
+    `pose_regressor` (a `pose_regressor.Mkpts_Reg_Model` on the models' device; default None: nothing changes) sends the same
+    best-slot matches through `regress_pose_batch` in this call, every query on its own, the device sampler seeded with
+    `regressor_seed`: each dict gains `pose_regressed` = (R [3, 3], t [3]) fp32, or None where the best slot has fewer than five
+    matches (the pairs `points_io.save_pair_points` skips) or no slot was filled.  Every other key stays what it was."""
     from .crops import crop_proposals
     from .pose import estimate_pose_batch
+    from .pose_regressor import MIN_MATCHES, regress_pose_batch
     refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_match_pose_batch_u8")
     Q = len(rows) if rows is not None else int(refs.shape[0])
     if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
@@ -451,7 +458,11 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
         dv = _batch_u8_on_device(dinov2_model, matcher, refs if rows is not None else refs.to(dev), crops, counts, conf_thr, rows, fidx)
         pose = estimate_pose_batch(dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], K0q, K_crops.index_select(0, dv["best_row"]),
                                    ransac_thr, ransac_conf)
+        if pose_regressor is not None:
+            reg = regress_pose_batch(pose_regressor, dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], seed=regressor_seed)
         outs = _download(dv, own)
+        if pose_regressor is not None:
+            reg_R, reg_t, reg_ok = reg["R"].cpu().numpy(), reg["t"].cpu().numpy(), reg["status"].cpu().numpy() == 0
         R, t, inl, n_inl = (pose[k].cpu().numpy() for k in ("R", "t", "inliers", "n_inliers"))
         off = np.concatenate([[0], np.cumsum(dv["best_count"].cpu().numpy())])
     for q, out in enumerate(outs):
@@ -459,12 +470,16 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
         # queries that share a frame each get arrays of their own
         out["boxes"], out["K_crops"] = (prop["boxes"], prop["K"]) if fidx is None else (prop["boxes"].copy(), prop["K"].copy())
         best = out["best_proposal"]
+        if pose_regressor is not None:
+            out["pose_regressed"] = None
         if best < 0:
             out["pre_bbox"], out["pre_K"], out["pose"] = None, None, None
             continue
         out["pre_bbox"], out["pre_K"] = out["boxes"][best], out["K_crops"][best]
         n = int(off[q + 1] - off[q])
         out["pose"] = (R[q], t[q], inl[off[q]:off[q + 1]]) if n >= 5 and int(n_inl[q]) > 0 else None
+        if pose_regressor is not None and n >= MIN_MATCHES and reg_ok[q]:
+            out["pose_regressed"] = (reg_R[q], reg_t[q])
     return outs
 
 
@@ -496,6 +511,13 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
     applies per frame.  The generator, the crops and their DINOv2 forward run once per frame (a frame no query names is still
     proposed for), the rest per query, and each query's dict is that of the call with `frames[frame_index]`, bit for bit, with a
     `proposals` array of its own."""
+    return _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bgr, K0, K1, conf_thr, ransac_thr, ransac_conf,
+                             out_size, max_proposals, None, 0)
+
+
+def _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bgr, K0, K1, conf_thr, ransac_thr, ransac_conf, out_size,
+                      max_proposals, pose_regressor, regressor_seed):
+    """`locate_pose_from_frames`, with `locate_match_pose_batch_u8`'s `pose_regressor` / `regressor_seed` handed through."""
     frame_index = None
     if isinstance(frames_bgr, SharedFrames):
         frames_bgr, frame_index = frames_bgr.frames, frames_bgr.index
@@ -527,7 +549,7 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
     if max_proposals is not None:
         proposals = [p[:int(max_proposals)] for p in proposals]
     outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, stack, proposals, K0, K1, conf_thr, ransac_thr, ransac_conf,
-                                      out_size, frame_index=fidx)
+                                      out_size, frame_index=fidx, pose_regressor=pose_regressor, regressor_seed=regressor_seed)
     for q, out in enumerate(outs):
         out["proposals"] = proposals[q] if fidx is None else proposals[fidx[q]].copy()
     return outs
@@ -545,10 +567,11 @@ def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame
 
 
 def locate_poses_in_frame(mask_generator, dinov2_model, matcher, refs_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
-                          ransac_conf=0.99, out_size=256, max_proposals=None):
+                          ransac_conf=0.99, out_size=256, max_proposals=None, pose_regressor=None, regressor_seed=0):
     """R references asked of ONE frame: `refs_bgr` [R, H0, W0, 3] uint8 or a `ReferenceSet` (its R rows, or its selection),
     `frame_bgr` [H, W, 3], `K0` [3, 3] or [R, 3, 3], `K1` [3, 3].  `locate_pose_from_frames` with `SharedFrames([frame], [0] * R)`:
-    the frame passes through the mask generator once and its crops through DINOv2 once.  Returns a list of R dicts."""
+    the frame passes through the mask generator once and its crops through DINOv2 once.  Returns a list of R dicts.
+    `pose_regressor` / `regressor_seed`: as in `locate_match_pose_batch_u8` (each dict gains `pose_regressed`)."""
     frame = frame_bgr[None] if on_device(frame_bgr) else np.asarray(frame_bgr.cpu() if torch.is_tensor(frame_bgr) else frame_bgr)[None]
-    return locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, SharedFrames(frame, [0] * len(refs_bgr)), K0, K1,
-                                   conf_thr, ransac_thr, ransac_conf, out_size, max_proposals)
+    return _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, SharedFrames(frame, [0] * len(refs_bgr)), K0, K1,
+                             conf_thr, ransac_thr, ransac_conf, out_size, max_proposals, pose_regressor, regressor_seed)

@@ -2,7 +2,8 @@
 eval_linemod_json.py:1).  Exports, under the reference's names, everything of that namespace that
 lies on the accelerated path, including the caller-side geometry either side of it: the proposal crops
 and their intrinsics (`get_image_crop_resize`, `get_K_crop_resize`; batched: `crop_proposals`) and the pose solver
-(`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`), the SAM proposal generator the drivers build from it
+(`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`), the fork's learned pose head (`Mkpts_Reg_Model`
+of `pose/model.py`; batched from the matcher's buffers: `regress_pose_batch`), the SAM proposal generator the drivers build from it
 (`sam_model_registry`, the `build_sam_vit_*` builders, `SamPredictor`, `SamAutomaticMaskGenerator`, `get_model_info`) and the
 call that joins the two: `locate_pose_from_frames` / `locate_pose_from_frame`, reference crop and raw frame in, pose out
 (`locate_poses_in_frame`: several references asked of one frame; `SharedFrames`: frames that several queries name;
@@ -29,6 +30,7 @@ from .matcher import CoarseMatching, Matcher, ReferenceEncoding, default_cfg, de
 from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch, vote_top3_shared  # noqa: F401
 from .pipeline import PairPipeline, gather_counts, shard_range  # noqa: F401
 from .pose import estimate_pose, estimate_pose_batch, relative_pose_error  # noqa: F401
+from .pose_regressor import Mkpts_Reg_Model, reference_sample_indices, regress_pose_batch  # noqa: F401
 from .sam_generator import (SamAutomaticMaskGenerator, SamPredictor, build_sam, build_sam_vit_b, build_sam_vit_h,  # noqa: F401
                             build_sam_vit_l, sam_model_registry)
 

@@ -733,3 +733,86 @@ def sam_generator_case(name, M=None):
     iou = (0.9 + 0.05 * torch.randn(M, generator=g)).float()
     assert iou.unique().numel() == M
     return low.contiguous(), iou.contiguous(), (ih, iw), (H, W)
+
+
+# ---- learned pose regressor (pose/model.py:Mkpts_Reg_Model) -------------------------------------------------------------------
+
+POSE_REGRESSOR_MODES = {"matrix": 9, "quat": 4, "6d": 6}
+# (num_sample, pairs per call) of tests/golden/pose_regressor.npz; every mode at each; the last pair of a call with more than
+# one pair has zero-padded rows.  The (300, 2) case is there for the real mlp.0 width and its 64-bit indexing (mode 'matrix' only)
+POSE_REGRESSOR_CASES = [(S, B) for S in (5, 37, 70) for B in (1, 3, 5)]
+POSE_REGRESSOR_LARGE = (300, 2)
+
+
+def pose_regressor_keys(num_sample, mode="matrix"):
+    """The 78 state-dict keys of `Mkpts_Reg_Model(num_sample, mode)` with their shapes, in the reference's order."""
+    S, d, hid = int(num_sample), 76, 2048
+    layer = [("self_attn.in_proj_weight", (3 * d, d)), ("self_attn.in_proj_bias", (3 * d,)), ("self_attn.out_proj.weight", (d, d)),
+             ("self_attn.out_proj.bias", (d,)), ("linear1.weight", (hid, d)), ("linear1.bias", (hid,)), ("linear2.weight", (d, hid)),
+             ("linear2.bias", (d,)), ("norm1.weight", (d,)), ("norm1.bias", (d,)), ("norm2.weight", (d,)), ("norm2.bias", (d,))]
+    keys = [("transformerlayer." + k, s) for k, s in layer]
+    for i in range(4):
+        keys += [(f"transformer.layers.{i}.{k}", s) for k, s in layer]
+    keys += [("translation_head.weight", (3, 32)), ("translation_head.bias", (3,))]
+    r = POSE_REGRESSOR_MODES[mode]
+    keys += [("rotation_head.weight", (r, 32)), ("rotation_head.bias", (r,))]
+    widths = [76 * S, 19 * S, S, 256, 128, 64, 32, 32]
+    for i in range(7):
+        keys += [(f"mlp.{3 * i}.weight", (widths[i + 1], widths[i])), (f"mlp.{3 * i}.bias", (widths[i + 1],))]
+    return keys
+
+
+def pose_regressor_state_dict(num_sample, mode="matrix", seed=0):
+    """Seeded weights that keep every branch O(1): matrices N(0, 2 / fan_in), biases and LayerNorm offsets N(0, 0.3^2), LayerNorm
+    gains 1 + N(0, 0.3^2).  (With torch's default init the outputs barely react to the inputs.)  The rotation head is drawn from
+    a generator of its own, so the three modes share every other tensor."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    gr = torch.Generator().manual_seed(2000 + seed)
+    sd = {}
+    for k, shape in pose_regressor_keys(num_sample, mode):
+        gen = gr if k.startswith("rotation_head") else g
+        if len(shape) == 2:
+            sd[k] = torch.randn(shape, generator=gen) * (2.0 / shape[1]) ** 0.5
+        elif "norm" in k and k.endswith("weight"):
+            sd[k] = 1.0 + 0.3 * torch.randn(shape, generator=gen)
+        else:
+            sd[k] = 0.3 * torch.randn(shape, generator=gen)
+    return sd
+
+
+def pose_regressor_matches(counts, seed=0, hw=(480, 640)):
+    """Seeded matches of len(counts) pairs in the matcher's compacted layout: (kpts0, kpts1) [sum(counts), 2] fp32 pixel
+    coordinates on a quarter-pixel grid (x < hw[1], y < hw[0]), kpts1 = kpts0 moved by a per-pair shift plus jitter."""
+    g = torch.Generator().manual_seed(3000 + seed)
+    k0, k1 = [], []
+    for c in counts:
+        c = max(int(c), 0)
+        p = torch.rand(c, 2, generator=g) * torch.tensor([hw[1] - 1.0, hw[0] - 1.0])
+        shift = (torch.rand(1, 2, generator=g) - 0.5) * 80.0
+        q = (p + shift + torch.randn(c, 2, generator=g)).clamp_(min=0.0)
+        q = torch.minimum(q, torch.tensor([hw[1] - 1.0, hw[0] - 1.0]))
+        k0.append(torch.round(p * 4) / 4)
+        k1.append(torch.round(q * 4) / 4)
+    return torch.cat(k0).float(), torch.cat(k1).float()
+
+
+def pose_regressor_case(num_sample, n_pairs, seed=None):
+    """Dense inputs of one fixture case: (mkpts0, mkpts1) [B, S, 2]; the last pair of a call of several keeps 2 S / 3 rows, the rest
+    of its rows are zero padding."""
+    S, B = int(num_sample), int(n_pairs)
+    counts = [S] * B
+    if B > 1:
+        counts[-1] = max(1, 2 * S // 3)
+    k0, k1 = pose_regressor_matches(counts, seed=100 * S + B if seed is None else seed)
+    d0, d1 = torch.zeros(B, S, 2), torch.zeros(B, S, 2)
+    off = 0
+    for b, c in enumerate(counts):
+        d0[b, :c], d1[b, :c] = k0[off:off + c], k1[off:off + c]
+        off += c
+    return d0, d1
+
+
+def pose_regressor_tap_slots(num_sample):
+    """Sample slots of the embedding / encoder taps the fixture keeps (all pairs of the call at each)."""
+    S = int(num_sample)
+    return sorted({s for s in (0, 1, S // 2, 31, 32, 33, 63, 64, 65, 2 * S // 3 - 1, 2 * S // 3, S - 1) if 0 <= s < S})
