@@ -178,17 +178,16 @@ __device__ __forceinline__ f32x2 conf_value2(f32x2 v, f32x2 cmx, f32x2 cinv, flo
 }
 
 constexpr int CP_ROWS = 32;   // rows per workgroup: 8 per wave
-constexpr int CP_K = 16;      // column pairs per lane and chunk: a chunk is 64 * 2 * 16 = 2048 columns
-constexpr int CP_CHUNK = 64 * 2 * CP_K;
+constexpr int CP_K = 16;      // columns per lane and chunk of conf_pass_kernel: a chunk is 64 * 16 = 1024 columns
 
-// Workgroup = 32 rows of one pair x all columns.  Lane l of every wave owns columns c0 + 128 k + 2 l (+1): it keeps
-// their column statistics and their running column maximum in registers while the wave walks its 8 rows, so a row is
-// read as 8-byte pieces that make whole 512-byte wave transactions.  VEC2 = false (odd S: rows are only 4-byte
-// aligned): the same with single columns c0 + 64 k + l and half the chunk.
-template <bool PUBLISH, bool VEC2>
+// Odd S (rows are only 4-byte aligned).  Workgroup = 32 rows of one pair x all columns.  Lane l of every wave owns the single
+// columns c0 + 64 k + l of a chunk of 64 * CP_K = 1024 columns: it keeps their column statistics and their running column
+// maximum in registers while the wave walks its 8 rows, so a row is read as whole 256-byte wave transactions.  A row's best
+// (RowBest) lives in registers across the chunks.  Even S: conf_pass_fast_kernel below.
+template <bool PUBLISH>
 __global__ __launch_bounds__(256) void conf_pass_kernel(const MatchParams p) {
-    __shared__ float cmax_s[4][CP_CHUNK];
-    constexpr int W = VEC2 ? 2 : 1;
+    constexpr int CHUNK = 64 * CP_K;
+    __shared__ float cmax_s[4][CHUNK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = blockIdx.y, blk = blockIdx.x;
     const int row0 = blk * CP_ROWS + wave * (CP_ROWS / 4);
@@ -199,18 +198,16 @@ __global__ __launch_bounds__(256) void conf_pass_kernel(const MatchParams p) {
 #pragma unroll
     for (int r = 0; r < CP_ROWS / 4; ++r) best[r] = RowBest{-1.f, 0, 0};   // conf >= 0
 
-    for (int c0 = 0; c0 < p.S; c0 += 64 * W * CP_K) {
-        float cmx[CP_K][W], cinv[CP_K][W], cbest[CP_K][W];
+    for (int c0 = 0; c0 < p.S; c0 += CHUNK) {
+        float cmx[CP_K], cinv[CP_K], cbest[CP_K];
 #pragma unroll
-        for (int k = 0; k < CP_K; ++k)
-#pragma unroll
-            for (int e = 0; e < W; ++e) {
-                const int col = c0 + 64 * W * k + W * lane + e;
-                const bool ok = col < p.S;
-                cmx[k][e] = ok ? cmx_g[col] : 0.f;
-                cinv[k][e] = ok ? 1.0f / csum_g[col] : 0.f;
-                cbest[k][e] = 0.f;
-            }
+        for (int k = 0; k < CP_K; ++k) {
+            const int col = c0 + 64 * k + lane;
+            const bool ok = col < p.S;
+            cmx[k] = ok ? cmx_g[col] : 0.f;
+            cinv[k] = ok ? 1.0f / csum_g[col] : 0.f;
+            cbest[k] = 0.f;
+        }
 #pragma unroll
         for (int r = 0; r < CP_ROWS / 4; ++r) {
             const int row = row0 + r;
@@ -219,41 +216,23 @@ __global__ __launch_bounds__(256) void conf_pass_kernel(const MatchParams p) {
             float* x = p.sim + (prow + row) * p.S;
 #pragma unroll
             for (int k = 0; k < CP_K; ++k) {
-                const int col = c0 + 64 * W * k + W * lane;
-                if (c0 + 64 * W * k >= p.S) break;   // wave-uniform
-                if constexpr (VEC2) {
-                    if (col + 1 < p.S) {
-                        const f32x2 v = *reinterpret_cast<const f32x2*>(x + col);
-                        const f32x2 c = {conf_value(v[0], cmx[k][0], cinv[k][0], rmx, rinv),
-                                         conf_value(v[1], cmx[k][1], cinv[k][1], rmx, rinv)};
-                        if constexpr (PUBLISH) *reinterpret_cast<f32x2*>(x + col) = c;
-                        best[r].take(c[0], col);
-                        best[r].take(c[1], col + 1);
-                        cbest[k][0] = fmaxf(cbest[k][0], c[0]);
-                        cbest[k][1] = fmaxf(cbest[k][1], c[1]);
-                    } else if (col < p.S) {
-                        const float c = conf_value(x[col], cmx[k][0], cinv[k][0], rmx, rinv);
-                        if constexpr (PUBLISH) x[col] = c;
-                        best[r].take(c, col);
-                        cbest[k][0] = fmaxf(cbest[k][0], c);
-                    }
-                } else if (col < p.S) {
-                    const float c = conf_value(x[col], cmx[k][0], cinv[k][0], rmx, rinv);
+                const int col = c0 + 64 * k + lane;
+                if (c0 + 64 * k >= p.S) break;   // wave-uniform
+                if (col < p.S) {
+                    const float c = conf_value(x[col], cmx[k], cinv[k], rmx, rinv);
                     if constexpr (PUBLISH) x[col] = c;
                     best[r].take(c, col);
-                    cbest[k][0] = fmaxf(cbest[k][0], c);
+                    cbest[k] = fmaxf(cbest[k], c);
                 }
             }
         }
         // column maxima of this 32-row block: the four waves' registers meet in LDS
         if (c0) __syncthreads();
 #pragma unroll
-        for (int k = 0; k < CP_K; ++k)
-#pragma unroll
-            for (int e = 0; e < W; ++e) cmax_s[wave][64 * W * k + W * lane + e] = cbest[k][e];
+        for (int k = 0; k < CP_K; ++k) cmax_s[wave][64 * k + lane] = cbest[k];
         __syncthreads();
         float* out = p.colmax_part + (size_t(pair) * p.nrb2 + blk) * p.ldp;
-        for (int c = threadIdx.x; c < 64 * W * CP_K && c0 + c < p.S; c += 256)
+        for (int c = threadIdx.x; c < CHUNK && c0 + c < p.S; c += 256)
             out[c0 + c] = fmaxf(fmaxf(cmax_s[0][c], cmax_s[1][c]), fmaxf(cmax_s[2][c], cmax_s[3][c]));
     }
     // per row: reduce the lanes' candidates (first argmax = smallest column among the maxima)
@@ -564,7 +543,7 @@ template <bool PUBLISH>
 void launch_conf_pass(const MatchParams& p, hipStream_t stream) {
     const dim3 blocks((p.L + CP_ROWS - 1) / CP_ROWS, p.n);
     if (p.S & 1) {   // odd S: rows are only 4-byte aligned
-        hipLaunchKernelGGL((conf_pass_kernel<PUBLISH, false>), blocks, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((conf_pass_kernel<PUBLISH>), blocks, dim3(256), 0, stream, p);
         return;
     }
     const int nk = (p.S + 127) / 128;
