@@ -901,6 +901,68 @@ int pope_pose_regressor_encoder_f32(const pope_pose_regressor_weights* w, const 
                                     const unsigned long long* seeds, int B, int S, int G, long long M, float* x_out,
                                     int* index_out, int* status, void* stream);
 
+/* ---- ConvNeXtV2 image backbone and the image pose head (pose/convnextv2/convnextv2.py, pose/model_cnn.py) -------- */
+
+/* One Block: dwconv 7 x 7 (groups = C) -> LayerNorm(C, 1e-6) -> pwconv1 + GELU -> GRN(4C) -> pwconv2 -> + input.
+ * dw_w is the depthwise weight [C, 1, 7, 7] RE-LAID [49, C] (tap-major, channel fastest); grn_gamma / grn_beta [4C];
+ * pw1_w [4C, C], pw2_w [C, 4C] fp32 in nn.Linear's layout; pw1_wp / pw2_wp the same matrices as weight planes
+ * (pope_split_planes_f32, scale POPE_PLANES_W_SCALE), read by POPE_PREC_F16X3 only and only where K % 32 == 0 (pw1_wp may be
+ * NULL when C % 32 != 0, both may be NULL for POPE_PREC_F32_MFMA). */
+typedef struct pope_convnext_block_weights {
+    const float *dw_w, *dw_b, *norm_w, *norm_b;
+    const float *pw1_w, *pw1_b, *grn_gamma, *grn_beta, *pw2_w, *pw2_b;
+    const void *pw1_wp, *pw2_wp;
+} pope_convnext_block_weights;
+
+/* stem_w: Conv2d(3, C0, 4, 4) weight flattened [C0, 48] (columns (channel, kh, kw), its own memory order); ds_w[i]: the
+ * downsample Conv2d(C_i, C_{i+1}, 2, 2) weight RE-LAID [C_{i+1}, (kh, kw, C_i)], ds_wp[i] its weight planes (POPE_PREC_F16X3);
+ * ds_ln_*: the channels-first LayerNorm(C_i) in front of it.  blocks_host: HOST array of depths[0] + .. + depths[3] blocks in
+ * stage order.  ones: max(dims) floats of 1.0f (the LayerScale slot of the residual epilogue).  dims[i] % 8 == 0.
+ * head_w [num_classes, C3]; num_classes % 4 == 0 when logits are asked for. */
+typedef struct pope_convnext_weights {
+    int depths[4], dims[4];
+    int num_classes;
+    const float *stem_w, *stem_b, *stem_ln_w, *stem_ln_b;
+    const float *ds_ln_w[3], *ds_ln_b[3], *ds_w[3], *ds_b[3];
+    const void* ds_wp[3];
+    const pope_convnext_block_weights* blocks_host;
+    const float *norm_w, *norm_b, *head_w, *head_b, *ones;
+} pope_convnext_weights;
+
+/* ConvNeXtV2.forward_features / forward for image [B, 3, H, W] fp32 (H % 32 == 0, W % 32 == 0: the reference would silently
+ * truncate other sizes; here they are POPE_ERR_ARG).  Activations are channels-last [B, h, w, C] fp32 between launches.
+ * precision: POPE_PREC_F32_MFMA, or POPE_PREC_F16X3: every Linear / 2 x 2 convolution whose K is a multiple of 32 runs on
+ * f16x3 planes (its operand written as planes by the producer in front of it: the block LayerNorm, the GRN apply step, the
+ * downsample LayerNorm), the others (stem K = 48, C = 40 / 48 / 80 ..) on the fp32 MFMA; the head Linear splits its operands
+ * in its K loop.  range_flag (device word, may be NULL) collects POPE_RANGE_LAYERNORM (LayerNorm producers), POPE_RANGE_GELU
+ * (GRN apply) and POPE_RANGE_INPUT (head operands); the caller re-runs the call with POPE_PREC_F32_MFMA when it is set.
+ * GRN statistics: a fixed-order column reduction per image (64-row chunks in row order, then the chunks in order), no
+ * atomics — an image's result does not depend on the other images of the call.
+ * features_out [B, C3] (the pooled, normalised features) and logits_out [B, num_classes] are each optional; taps: NULL or a
+ * HOST array of 5 device pointers (each may be NULL): the stem output and the four stage outputs, channels-last
+ * [B, H / 4 >> i, W / 4 >> i, dims[i]].  Workspace >= pope_convnext_workspace_bytes(w, B, H, W) (0: bad arguments), 256-byte
+ * aligned.  Every bad argument — null pointers, sizes, an unknown precision, a short workspace — is POPE_ERR_ARG, returned
+ * before the device is touched. */
+size_t pope_convnext_workspace_bytes(const pope_convnext_weights* w, int B, int H, int W);
+int pope_convnext_forward_f32(const pope_convnext_weights* w, const float* image, int B, int H, int W, int precision,
+                              float* features_out, float* logits_out, float* const* taps, void* workspace,
+                              size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* Depthwise Conv2d(C, C, 7, padding = 3, groups = C) + bias on channels-last x [B, H, W, C] -> y (y != x); w49 [49, C].
+ * Any H, W >= 1 (maps smaller than the kernel included), C >= 1. */
+int pope_convnext_dwconv_f32(const float* x, const float* w49, const float* bias, float* y, int B, int H, int W, int C,
+                             void* stream);
+/* GRN over x [B, HW, C] (C % 32 == 0): y = gamma * (x * Nx) + beta + x, Nx = Gx / (mean_c Gx + 1e-6), Gx = the L2 norm of a
+ * column over the HW rows of its image.  Exactly one of y_f32 (may be x itself) and y_planes (activation planes [B HW, C],
+ * POPE_RANGE_GELU into range_flag).  Workspace >= pope_convnext_grn_workspace_bytes(B, HW, C). */
+size_t pope_convnext_grn_workspace_bytes(int B, int HW, int C);
+int pope_convnext_grn_f32(const float* x, const float* gamma, const float* beta, int B, int HW, int C, float* y_f32,
+                          void* y_planes, void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+/* The image pose head (pose/model_cnn.py:179-180): trans [B, 3] = translation_head_rot(feat), rot [B, 9] =
+ * convert2matrix(rotation_head_rot(feat)) for feat [B, inner] (inner <= 256), mode POPE_ROT_*: the conversion code of the
+ * key-point regressor. */
+int pope_convnext_pose_heads_f32(const float* feat, const float* trans_w, const float* trans_b, const float* rot_w,
+                                 const float* rot_b, int mode, int B, int inner, float* trans, float* rot, void* stream);
+
 /* ---- host-side helper ------------------------------------------------------------------------ */
 
 /* Streaming top-3 proposal vote — eval_linemod_json.py:71,95-101 (HOST pointers): slots start at

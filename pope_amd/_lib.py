@@ -90,6 +90,18 @@ class PoseRegressorWeights(C.Structure):
                 ("mlp_b", C.c_void_p * 7)] + [(n, C.c_void_p) for n in ("trans_w", "trans_b", "rot_w", "rot_b")]
 
 
+class ConvNextBlockWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dw_w", "dw_b", "norm_w", "norm_b", "pw1_w", "pw1_b", "grn_gamma", "grn_beta", "pw2_w",
+                                           "pw2_b", "pw1_wp", "pw2_wp")]
+
+
+class ConvNextWeights(C.Structure):
+    _fields_ = [("depths", C.c_int * 4), ("dims", C.c_int * 4), ("num_classes", C.c_int)] + [
+        (n, C.c_void_p) for n in ("stem_w", "stem_b", "stem_ln_w", "stem_ln_b")] + [
+        (n, C.c_void_p * 3) for n in ("ds_ln_w", "ds_ln_b", "ds_w", "ds_b", "ds_wp")] + [
+        ("blocks_host", C.POINTER(ConvNextBlockWeights))] + [(n, C.c_void_p) for n in ("norm_w", "norm_b", "head_w", "head_b", "ones")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pope_hip.h
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
@@ -229,6 +241,14 @@ PROTOTYPES = {
     "pope_pose_regressor_embedding_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4),
     "pope_pose_regressor_encoder_f32": (C.c_int, [C.POINTER(PoseRegressorWeights)] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_longlong]
                                         + [C.c_void_p] * 4),
+    "pope_convnext_workspace_bytes": (C.c_size_t, [C.POINTER(ConvNextWeights), C.c_int, C.c_int, C.c_int]),
+    "pope_convnext_forward_f32": (C.c_int, [C.POINTER(ConvNextWeights), C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p,
+                                                                                                     C.POINTER(C.c_void_p), C.c_void_p,
+                                                                                                     C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_convnext_dwconv_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "pope_convnext_grn_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "pope_convnext_grn_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_convnext_pose_heads_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "pope_five_point_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_streaming_top3_host": (C.c_int, [c_float_p, C.c_int, c_float_p, c_ll_p]),
     "pope_vote_top3_batch_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5 + [C.c_void_p]),

@@ -869,6 +869,46 @@ int pope_pose_regressor_forward_f32(const pope_pose_regressor_weights* w, const 
     return pope_launch_posereg_tail(*w, y2, status, B, trans, rot, st);
 }
 
+// ---- ConvNeXtV2 backbone and the image pose head (convnext.hip) ------------------------------------------------------------
+
+size_t pope_convnext_workspace_bytes(const pope_convnext_weights* w, int B, int H, int W) { return pope_convnext_workspace(w, B, H, W); }
+
+int pope_convnext_forward_f32(const pope_convnext_weights* w, const float* image, int B, int H, int W, int precision,
+                              float* features_out, float* logits_out, float* const* taps, void* workspace,
+                              size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    ConvNextArgs a = {};
+    a.w = w; a.image = image; a.B = B; a.H = H; a.W = W; a.precision = precision; a.features = features_out; a.logits = logits_out;
+    a.taps = taps; a.ws = workspace; a.ws_bytes = workspace_bytes; a.range_flag = range_flag;
+    POPE_TRY(pope_convnext_check(a));
+    StreamDevice on_device(stream);
+    return pope_launch_convnext(a, static_cast<hipStream_t>(stream));
+}
+
+int pope_convnext_dwconv_f32(const float* x, const float* w49, const float* bias, float* y, int B, int H, int W, int C,
+                             void* stream) {
+    if (!x || !w49 || !bias || !y || x == y || B <= 0 || H <= 0 || W <= 0 || C <= 0) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_convnext_dwconv(x, w49, bias, y, B, H, W, C, static_cast<hipStream_t>(stream));
+}
+
+size_t pope_convnext_grn_workspace_bytes(int B, int HW, int C) { return pope_convnext_grn_workspace(B, HW, C); }
+
+int pope_convnext_grn_f32(const float* x, const float* gamma, const float* beta, int B, int HW, int C, float* y_f32,
+                          void* y_planes, void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    POPE_TRY(pope_convnext_grn_check(x, gamma, beta, B, HW, C, y_f32, y_planes, workspace, workspace_bytes));
+    StreamDevice on_device(stream);
+    return pope_launch_convnext_grn(x, gamma, beta, B, HW, C, y_f32, y_planes, workspace, range_flag, static_cast<hipStream_t>(stream));
+}
+
+int pope_convnext_pose_heads_f32(const float* feat, const float* trans_w, const float* trans_b, const float* rot_w,
+                                 const float* rot_b, int mode, int B, int inner, float* trans, float* rot, void* stream) {
+    if (!feat || !trans_w || !trans_b || !rot_w || !rot_b || !trans || !rot || B <= 0 || inner <= 0 || inner > 256 ||
+        mode < POPE_ROT_MATRIX || mode > POPE_ROT_6D)
+        return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_convnext_pose_heads(feat, trans_w, trans_b, rot_w, rot_b, mode, B, inner, trans, rot, static_cast<hipStream_t>(stream));
+}
+
 int pope_five_point_f64(const double* x0, const double* x1, int S, double* E_out, int* n_out, void* stream) {
     StreamDevice on_device(stream);
     return pope_launch_five_point(x0, x1, S, E_out, n_out, static_cast<hipStream_t>(stream));

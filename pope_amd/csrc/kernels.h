@@ -532,3 +532,27 @@ int pope_launch_posereg_stream_linear(const float* A, const float* W, const floa
                                       hipStream_t stream);
 int pope_launch_posereg_tail(const pope_pose_regressor_weights& w, const float* Y2, const int* status, int B, float* trans,
                              float* rot, hipStream_t stream);
+
+// ConvNeXtV2 backbone and the image pose head (convnext.hip; pose/convnextv2/convnextv2.py, pose/model_cnn.py): the arguments of
+// pope_convnext_forward_f32 and of the op-level entries.  The *_check functions make no HIP call.
+struct ConvNextArgs {
+    const pope_convnext_weights* w;
+    const float* image;
+    int B, H, W, precision;
+    float *features, *logits;
+    float* const* taps;
+    void* ws; size_t ws_bytes;
+    unsigned* range_flag;
+};
+size_t pope_convnext_workspace(const pope_convnext_weights* w, int B, int H, int W);   // 0: bad weights or geometry
+int pope_convnext_check(const ConvNextArgs& a);
+int pope_launch_convnext(const ConvNextArgs& a, hipStream_t stream);
+int pope_launch_convnext_dwconv(const float* x, const float* w49, const float* bias, float* y, int B, int H, int W, int C,
+                                hipStream_t stream);
+size_t pope_convnext_grn_workspace(int B, int HW, int C);
+int pope_convnext_grn_check(const float* x, const float* gamma, const float* beta, int B, int HW, int C, const float* y_f32,
+                            const void* y_planes, const void* ws, size_t ws_bytes);
+int pope_launch_convnext_grn(const float* x, const float* gamma, const float* beta, int B, int HW, int C, float* y_f32, void* y_planes,
+                             void* ws, unsigned* range_flag, hipStream_t stream);
+int pope_launch_convnext_pose_heads(const float* feat, const float* trans_w, const float* trans_b, const float* rot_w,
+                                    const float* rot_b, int mode, int B, int inner, float* trans, float* rot, hipStream_t stream);

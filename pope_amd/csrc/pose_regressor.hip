@@ -23,6 +23,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "pose_math.h"
+#include "rot_convert.h"
 
 namespace {
 
@@ -467,13 +468,6 @@ __device__ __forceinline__ void dense_layer(const float* in, int K, const float*
     __syncthreads();
 }
 
-__device__ __forceinline__ void normalize3(const float* v, int n, float* o) {   // pose/utils.py:normalize_vector (norm clamped at 1e-8)
-    float ss = 0.f;
-    for (int i = 0; i < n; ++i) ss += v[i] * v[i];
-    const float mag = fmaxf(sqrtf(ss), 1e-8f);
-    for (int i = 0; i < n; ++i) o[i] = v[i] / mag;
-}
-
 __global__ __launch_bounds__(256) void posereg_tail_kernel(pope_pose_regressor_weights w, const float* __restrict__ Y2,
                                                            const int* __restrict__ status, float* __restrict__ trans, float* __restrict__ rot) {
     __shared__ float a[256], c[128], head[12];
@@ -495,26 +489,7 @@ __global__ __launch_bounds__(256) void posereg_tail_kernel(pope_pose_regressor_w
     dense_layer(a, 32, w.rot_w, w.rot_b, rdim, head + 3, false);
     if (tid != 0) return;
     for (int i = 0; i < 3; ++i) t_out[i] = head[i];
-    const float* r = head + 3;
-    if (w.mode == POPE_ROT_MATRIX) {
-        for (int i = 0; i < 9; ++i) r_out[i] = r[i];
-    } else if (w.mode == POPE_ROT_QUAT) {     // pose/utils.py:qua2mat, (w, x, y, z)
-        float q[4];
-        normalize3(r, 4, q);
-        const float qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-        const float xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, xw = qx * qw, yw = qy * qw, zw = qz * qw;
-        r_out[0] = 1 - 2 * yy - 2 * zz; r_out[1] = 2 * xy - 2 * zw;     r_out[2] = 2 * xz + 2 * yw;
-        r_out[3] = 2 * xy + 2 * zw;     r_out[4] = 1 - 2 * xx - 2 * zz; r_out[5] = 2 * yz - 2 * xw;
-        r_out[6] = 2 * xz - 2 * yw;     r_out[7] = 2 * yz + 2 * xw;     r_out[8] = 1 - 2 * xx - 2 * yy;
-    } else {                                   // pose/utils.py:o6d2mat: x, y, z are the COLUMNS
-        float x[3], y[3], z[3], zr[3];
-        normalize3(r, 3, x);
-        const float* yr = r + 3;
-        zr[0] = x[1] * yr[2] - x[2] * yr[1]; zr[1] = x[2] * yr[0] - x[0] * yr[2]; zr[2] = x[0] * yr[1] - x[1] * yr[0];
-        normalize3(zr, 3, z);
-        y[0] = z[1] * x[2] - z[2] * x[1]; y[1] = z[2] * x[0] - z[0] * x[2]; y[2] = z[0] * x[1] - z[1] * x[0];
-        for (int i = 0; i < 3; ++i) { r_out[3 * i] = x[i]; r_out[3 * i + 1] = y[i]; r_out[3 * i + 2] = z[i]; }
-    }
+    pope_rot_to_matrix(w.mode, head + 3, r_out);
 }
 
 }  // namespace

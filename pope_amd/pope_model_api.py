@@ -3,7 +3,8 @@ eval_linemod_json.py:1).  Exports, under the reference's names, everything of th
 lies on the accelerated path, including the caller-side geometry either side of it: the proposal crops
 and their intrinsics (`get_image_crop_resize`, `get_K_crop_resize`; batched: `crop_proposals`) and the pose solver
 (`estimate_pose`, `relative_pose_error`; batched: `estimate_pose_batch`), the fork's learned pose head (`Mkpts_Reg_Model`
-of `pose/model.py`; batched from the matcher's buffers: `regress_pose_batch`), the SAM proposal generator the drivers build from it
+of `pose/model.py`; batched from the matcher's buffers: `regress_pose_batch`), the image pose head of `pose/model_cnn.py` with its
+ConvNeXtV2 backbone (`Mkpts_Reg_Model_CNN` = `pose_regressor_cnn.Mkpts_Reg_Model`, `ConvNeXtV2`, the `convnextv2_*` factories), the SAM proposal generator the drivers build from it
 (`sam_model_registry`, the `build_sam_vit_*` builders, `SamPredictor`, `SamAutomaticMaskGenerator`, `get_model_info`) and the
 call that joins the two: `locate_pose_from_frames` / `locate_pose_from_frame`, reference crop and raw frame in, pose out
 (`locate_poses_in_frame`: several references asked of one frame; `SharedFrames`: frames that several queries name;
@@ -31,6 +32,10 @@ from .ops import cls_cosine, slot_tally, streaming_top3, vote_top3_batch, vote_t
 from .pipeline import PairPipeline, gather_counts, shard_range  # noqa: F401
 from .pose import estimate_pose, estimate_pose_batch, relative_pose_error  # noqa: F401
 from .pose_regressor import Mkpts_Reg_Model, reference_sample_indices, regress_pose_batch  # noqa: F401
+from . import pose_regressor_cnn  # noqa: F401  (pose/model_cnn.py: its Mkpts_Reg_Model shares the key-point model's name)
+from .convnextv2 import (ConvNeXtV2, convnext_pico, convnextv2_atto, convnextv2_base, convnextv2_femto, convnextv2_huge,  # noqa: F401
+                         convnextv2_large, convnextv2_nano, convnextv2_tiny, remap_checkpoint_keys)
+from .pose_regressor_cnn import Mkpts_Reg_Model as Mkpts_Reg_Model_CNN  # noqa: F401
 from .sam_generator import (SamAutomaticMaskGenerator, SamPredictor, build_sam, build_sam_vit_b, build_sam_vit_h,  # noqa: F401
                             build_sam_vit_l, sam_model_registry)
 

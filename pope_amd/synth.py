@@ -816,3 +816,104 @@ def pose_regressor_tap_slots(num_sample):
     """Sample slots of the embedding / encoder taps the fixture keeps (all pairs of the call at each)."""
     S = int(num_sample)
     return sorted({s for s in (0, 1, S // 2, 31, 32, 33, 63, 64, 65, 2 * S // 3 - 1, 2 * S // 3, S - 1) if 0 <= s < S})
+
+
+# ---- ConvNeXtV2 backbone and the image pose head (pose/convnextv2/convnextv2.py, pose/model_cnn.py) ---------------------------
+
+CONVNEXT_SMALL = dict(depths=[1, 1, 2, 1], dims=[64, 80, 160, 320], num_classes=32)
+CONVNEXT_TINY = dict(depths=[3, 3, 9, 3], dims=[96, 192, 384, 768], num_classes=1000)
+# tests/golden/convnext.npz.  small: a non-square last map of 3 x 5, smaller than the 7 x 7 kernel, and the K % 32 != 0 route (80);
+# tiny_full: convnextv2_tiny at full depth on two 64 x 64 images side by side; pose_*: the small trunk under the two pose heads
+CONVNEXT_CASES = {"small": (CONVNEXT_SMALL, 3, (96, 160), 0), "tiny_full": (CONVNEXT_TINY, 2, (64, 128), 1)}
+CONVNEXT_POSE_CASES = {f"pose_{m}": (m, 2, (96, 80), 2) for m in POSE_REGRESSOR_MODES}
+CONVNEXT_TAP_SAMPLES = 4096     # entries kept of a tap wider than that, at seeded flat positions
+
+
+def convnext_keys(depths, dims, num_classes):
+    """State-dict keys of `ConvNeXtV2(depths=, dims=, num_classes=)` with their shapes, in the reference's order."""
+    keys = [("downsample_layers.0.0.weight", (dims[0], 3, 4, 4)), ("downsample_layers.0.0.bias", (dims[0],)),
+            ("downsample_layers.0.1.weight", (dims[0],)), ("downsample_layers.0.1.bias", (dims[0],))]
+    for i in range(3):
+        keys += [(f"downsample_layers.{i + 1}.0.weight", (dims[i],)), (f"downsample_layers.{i + 1}.0.bias", (dims[i],)),
+                 (f"downsample_layers.{i + 1}.1.weight", (dims[i + 1], dims[i], 2, 2)), (f"downsample_layers.{i + 1}.1.bias", (dims[i + 1],))]
+    for i in range(4):
+        c = dims[i]
+        for j in range(depths[i]):
+            p = f"stages.{i}.{j}."
+            keys += [(p + "dwconv.weight", (c, 1, 7, 7)), (p + "dwconv.bias", (c,)), (p + "norm.weight", (c,)), (p + "norm.bias", (c,)),
+                     (p + "pwconv1.weight", (4 * c, c)), (p + "pwconv1.bias", (4 * c,)), (p + "grn.gamma", (1, 1, 1, 4 * c)),
+                     (p + "grn.beta", (1, 1, 1, 4 * c)), (p + "pwconv2.weight", (c, 4 * c)), (p + "pwconv2.bias", (c,))]
+    keys += [("norm.weight", (dims[3],)), ("norm.bias", (dims[3],)), ("head.weight", (num_classes, dims[3])), ("head.bias", (num_classes,))]
+    return keys
+
+
+def _convnext_tensor(k, shape, gen):
+    if k.endswith("grn.gamma"):
+        return 0.5 + torch.rand(shape, generator=gen)
+    if k.endswith("grn.beta"):
+        return 0.3 * torch.randn(shape, generator=gen)
+    if len(shape) >= 2:                                   # matrices and convolution kernels: 1.5 / sqrt(fan_in)
+        return torch.randn(shape, generator=gen) * (1.5 / math.prod(shape[1:]) ** 0.5)
+    if k.endswith("bias"):
+        return 0.2 * torch.randn(shape, generator=gen)
+    return 1.0 + 0.3 * torch.randn(shape, generator=gen)  # LayerNorm gains
+
+
+def convnext_state_dict(depths, dims, num_classes, seed=0):
+    """Seeded weights with every term alive (torch's default init leaves GRN at zero and the branches at 0.02): GRN gamma in
+    [0.5, 1.5], beta 0.3 N; biases 0.2 N; LayerNorm gains 1 + 0.3 N; matrices and kernels 1.5 / sqrt(fan_in) N."""
+    g = torch.Generator().manual_seed(4000 + seed)
+    return {k: _convnext_tensor(k, s, g) for k, s in convnext_keys(depths, dims, num_classes)}
+
+
+def convnext_pose_state_dict(mode, seed=0):
+    """`pose/model_cnn.py:Mkpts_Reg_Model` over the small trunk: `convnextv2.model.*` and the two heads; the rotation head from a
+    generator of its own, so the modes share every other tensor."""
+    sd = {"convnextv2.model." + k: v for k, v in convnext_state_dict(seed=seed, **CONVNEXT_SMALL).items()}
+    g, gr = torch.Generator().manual_seed(5000 + seed), torch.Generator().manual_seed(6000 + seed)
+    r = POSE_REGRESSOR_MODES[mode]
+    for k, shape, gen in (("translation_head_rot.weight", (3, 32), g), ("translation_head_rot.bias", (3,), g),
+                          ("rotation_head_rot.weight", (r, 32), gr), ("rotation_head_rot.bias", (r,), gr)):
+        sd[k] = _convnext_tensor(k, shape, gen)
+    return sd
+
+
+def convnext_case(name):
+    """One case of tests/golden/convnext.npz: dict(cfg, state_dict, x [B, 3, H, W]) for the backbone cases, dict(mode, state_dict,
+    img0, img1 [B, 3, H, W / 2 each], cfg) for the pose cases."""
+    if name in CONVNEXT_CASES:
+        cfg, B, (H, W), seed = CONVNEXT_CASES[name]
+        g = torch.Generator().manual_seed(7000 + seed)
+        return {"cfg": cfg, "state_dict": convnext_state_dict(seed=seed, **cfg), "x": torch.randn(B, 3, H, W, generator=g)}
+    mode, B, (H, W), seed = CONVNEXT_POSE_CASES[name]
+    g = torch.Generator().manual_seed(7000 + seed)
+    return {"cfg": CONVNEXT_SMALL, "mode": mode, "state_dict": convnext_pose_state_dict(mode, seed=seed),
+            "img0": torch.randn(B, 3, H, W, generator=g), "img1": torch.randn(B, 3, H, W, generator=g)}
+
+
+def convnext_tap_index(name, tap, numel):
+    """Flat positions of a tap the fixture keeps: all of it up to CONVNEXT_TAP_SAMPLES entries, else that many seeded positions."""
+    if numel <= CONVNEXT_TAP_SAMPLES:
+        return torch.arange(numel)
+    g = torch.Generator().manual_seed(8000 + sum(map(ord, name + tap)))
+    return torch.randperm(numel, generator=g)[:CONVNEXT_TAP_SAMPLES].sort().values
+
+
+CONVNEXT_TAPS = ("stem", "stage0", "stage1", "stage2", "stage3", "features", "logits")
+
+
+def fcmae_checkpoint(seed=0):
+    """A seeded FCMAE-style (sparse pre-training) checkpoint dict of a two-block toy encoder, for `remap_checkpoint_keys`."""
+    g = torch.Generator().manual_seed(9000 + seed)
+    r = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    ck = {"encoder.downsample_layers.0.0.weight": r(8, 3, 4, 4), "encoder.downsample_layers.0.0.bias": r(8),
+          "encoder.downsample_layers.0.1.weight": r(8), "encoder.downsample_layers.0.1.bias": r(8),
+          "encoder.downsample_layers.1.0.ln.weight": r(8), "encoder.downsample_layers.1.0.ln.bias": r(8),
+          "encoder.downsample_layers.1.1.kernel": r(4, 8, 16), "encoder.downsample_layers.1.1.bias": r(1, 16)}
+    for i, c in ((0, 8), (1, 16)):
+        p = f"encoder.stages.{i}.0."
+        ck.update({p + "dwconv.kernel": r(49, c), p + "dwconv.bias": r(1, c), p + "norm.ln.weight": r(c), p + "norm.ln.bias": r(c),
+                   p + "pwconv1.linear.weight": r(4 * c, c), p + "pwconv1.linear.bias": r(4 * c), p + "grn.gamma": r(1, 4 * c),
+                   p + "grn.beta": r(1, 4 * c), p + "pwconv2.linear.weight": r(c, 4 * c), p + "pwconv2.linear.bias": r(c)})
+    ck["norm.weight"], ck["norm.bias"] = r(16), r(16)
+    return ck
