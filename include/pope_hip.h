@@ -963,6 +963,84 @@ int pope_convnext_grn_f32(const float* x, const float* gamma, const float* beta,
 int pope_convnext_pose_heads_f32(const float* feat, const float* trans_w, const float* trans_b, const float* rot_w,
                                  const float* rot_b, int mode, int B, int inner, float* trans, float* rot, void* stream);
 
+/* ---- MoCoPE fusion pose model (pose/model0604.py:MoCoPE) --------------------------------------------------------- */
+
+/* One layer of nn.TransformerEncoder / nn.TransformerDecoder (post-norm, ReLU, 2048 hidden, nhead = 1, eps 1e-5) in torch's own
+ * layouts (device pointers, fp32, 16-byte aligned): in_proj [3d, d] / [3d], out_proj [d, d] / [d], linear1 [2048, d] / [2048],
+ * linear2 [d, 2048] / [d], norms [d].  The decoder layer's cross_* are its multihead_attn (q from the target rows, k | v from
+ * the memory rows); its norm2 follows the cross-attention, norm3 the FFN. */
+typedef struct pope_mocope_encoder_layer {
+    const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} pope_mocope_encoder_layer;
+typedef struct pope_mocope_decoder_layer {
+    const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *cross_in_proj_w, *cross_in_proj_b, *cross_out_proj_w,
+        *cross_out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b, *norm3_w, *norm3_b;
+} pope_mocope_decoder_layer;
+/* nn.Transformer(d_model, nhead = 1): 6 encoder layers + encoder.norm, 6 decoder layers + decoder.norm */
+typedef struct pope_mocope_transformer {
+    pope_mocope_encoder_layer enc[6];
+    const float *enc_norm_w, *enc_norm_b;
+    pope_mocope_decoder_layer dec[6];
+    const float *dec_norm_w, *dec_norm_b;
+} pope_mocope_transformer;
+/* mode: POPE_ROT_*.  transformer_mkpts has d_model 76, mkpts_as_q / cnn_as_q 512.  mlp1_w[i] = mlp1.{0,3}: [38S, 76S],
+ * [1024, 38S]; mlp_img: [512, 1000]; mlp2_w[i] = mlp2.{0,3,..,18}: [1024, 2048], [512, 1024], [256, 512], [128, 256], [64, 128],
+ * [32, 64], [32, 32]; heads [3, 32] and [9 | 4 | 6, 32].  The pointers are read on every call: no derived copy exists. */
+typedef struct pope_mocope_weights {
+    int num_sample, mode;
+    pope_mocope_transformer transformer_mkpts, mkpts_as_q, cnn_as_q;
+    const float* mlp1_w[2];
+    const float* mlp1_b[2];
+    const float *mlp_img_w, *mlp_img_b;
+    const float* mlp2_w[7];
+    const float* mlp2_b[7];
+    const float *trans_w, *trans_b, *rot_w, *rot_b;
+} pope_mocope_weights;
+
+/* train_type of MoCoPE: the full fusion, or the reference's own reduced routes (mkpts_as_q(x_mkpts, x_mkpts) / cnn_as_q(x_img,
+ * x_img), each concatenated with itself) */
+#define POPE_MOCOPE_FUSION 0
+#define POPE_MOCOPE_MKPTS 1
+#define POPE_MOCOPE_CNN 2
+/* stages pope_mocope_tap_f32 stops after; tap_out is [B, S, 76] for the first three, [B, 2, 512] for the others */
+#define POPE_MOCOPE_TAP_EMBEDDING 0   /* Embedding(2, 9, logscale=False) of cat(mkpts0, mkpts1) */
+#define POPE_MOCOPE_TAP_MEMORY 1      /* transformer_mkpts: the encoder output after encoder.norm */
+#define POPE_MOCOPE_TAP_MKPTS_T 2     /* transformer_mkpts(x, x) */
+#define POPE_MOCOPE_TAP_X_MKPTS 3     /* mlp1 output */
+#define POPE_MOCOPE_TAP_X_IMG 4       /* stacked mlp_img outputs */
+#define POPE_MOCOPE_TAP_QMKPTS 5      /* mkpts_as_q output */
+#define POPE_MOCOPE_TAP_QIMG 6        /* cnn_as_q output */
+
+/* MoCoPE.forward (pose/model0604.py:248-300) after the backbone, fp32 throughout, for B pairs of S = num_sample sample slots.
+ * Key-point input, sampling, padding, seeds, status codes and the group size G are those of pope_pose_regressor_forward_f32:
+ * the B pairs form B / G attention groups of G consecutive pairs (1 <= G <= 64, B % G == 0) — torch reads [B, S, 76] and
+ * [B, 2, 512] with batch_first=False, so all three transformers attend ACROSS the pairs of a call (G = B); G = 1 is every pair
+ * on its own.  feat0 / feat1 [B, 1000]: the backbone's logits of the two images (not read by POPE_MOCOPE_MKPTS; the key points
+ * still give the status of a pair under POPE_MOCOPE_CNN).
+ * Launch sequence: select, embed | per transformer layer: in_proj (q | k | v of one streamed Linear, or v alone for G = 1),
+ * attention over the group, out_proj, residual + LayerNorm, (decoder: the same again against the memory rows), then the FFN: at
+ * d = 76 one launch on the fp32 MFMA (linear1 + ReLU + linear2 + residual + LayerNorm, hidden activation in registers), at d = 512
+ * linear1 + ReLU, linear2, residual + LayerNorm (the closing encoder.norm / decoder.norm ride the last layer's launch) | streamed Linears +
+ * LeakyReLU for mlp1, mlp_img, mlp2.0, mlp2.3 | one tail launch per call for mlp2.6 .. 18, the heads and convert2matrix.
+ * Every Linear output element is a lane-strided sum over K (lane l takes the 16-byte groups l, l + 64, ..) followed by a xor
+ * butterfly: its order depends on K alone, not on B, G, the row or the CU.  Plain launches only.
+ * Outputs (device): trans [B, 3], rot [B, 9] row-major, status [B] int32; a pair whose status is not 0 gets zeros.
+ * Workspace >= pope_mocope_workspace_bytes(B, S), 256-byte aligned.  Bad arguments (null pointers, S != weights->num_sample, B,
+ * G, train_type, stage, workspace) return a negative code before any HIP call. */
+size_t pope_mocope_workspace_bytes(int B, int S);
+int pope_mocope_forward_f32(const pope_mocope_weights* w, const float* dense0, const float* dense1, const float* kpts0,
+                            const float* kpts1, const int* counts, const int* sample_index, const unsigned long long* seeds,
+                            const float* feat0, const float* feat1, int B, int S, int G, long long M, int train_type,
+                            float* trans, float* rot, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The same call stopped after `stage` (POPE_MOCOPE_TAP_*, tests): tap_out receives that stage's tensor; a stage the
+ * train_type does not compute is POPE_ERR_ARG. */
+int pope_mocope_tap_f32(const pope_mocope_weights* w, const float* dense0, const float* dense1, const float* kpts0,
+                        const float* kpts1, const int* counts, const int* sample_index, const unsigned long long* seeds,
+                        const float* feat0, const float* feat1, int B, int S, int G, long long M, int train_type, int stage,
+                        float* tap_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- host-side helper ------------------------------------------------------------------------ */
 
 /* Streaming top-3 proposal vote — eval_linemod_json.py:71,95-101 (HOST pointers): slots start at

@@ -90,6 +90,29 @@ class PoseRegressorWeights(C.Structure):
                 ("mlp_b", C.c_void_p * 7)] + [(n, C.c_void_p) for n in ("trans_w", "trans_b", "rot_w", "rot_b")]
 
 
+class MocopeEncoderLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b", "linear2_w",
+                                           "linear2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
+
+
+class MocopeDecoderLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "cross_in_proj_w", "cross_in_proj_b",
+                                           "cross_out_proj_w", "cross_out_proj_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b",
+                                           "norm1_w", "norm1_b", "norm2_w", "norm2_b", "norm3_w", "norm3_b")]
+
+
+class MocopeTransformer(C.Structure):
+    _fields_ = [("enc", MocopeEncoderLayer * 6), ("enc_norm_w", C.c_void_p), ("enc_norm_b", C.c_void_p),
+                ("dec", MocopeDecoderLayer * 6), ("dec_norm_w", C.c_void_p), ("dec_norm_b", C.c_void_p)]
+
+
+class MocopeWeights(C.Structure):
+    _fields_ = [("num_sample", C.c_int), ("mode", C.c_int), ("transformer_mkpts", MocopeTransformer), ("mkpts_as_q", MocopeTransformer),
+                ("cnn_as_q", MocopeTransformer), ("mlp1_w", C.c_void_p * 2), ("mlp1_b", C.c_void_p * 2), ("mlp_img_w", C.c_void_p),
+                ("mlp_img_b", C.c_void_p), ("mlp2_w", C.c_void_p * 7), ("mlp2_b", C.c_void_p * 7)] + [
+        (n, C.c_void_p) for n in ("trans_w", "trans_b", "rot_w", "rot_b")]
+
+
 class ConvNextBlockWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dw_w", "dw_b", "norm_w", "norm_b", "pw1_w", "pw1_b", "grn_gamma", "grn_beta", "pw2_w",
                                            "pw2_b", "pw1_wp", "pw2_wp")]
@@ -241,6 +264,11 @@ PROTOTYPES = {
     "pope_pose_regressor_embedding_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4),
     "pope_pose_regressor_encoder_f32": (C.c_int, [C.POINTER(PoseRegressorWeights)] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_longlong]
                                         + [C.c_void_p] * 4),
+    "pope_mocope_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pope_mocope_forward_f32": (C.c_int, [C.POINTER(MocopeWeights)] + [C.c_void_p] * 9 + [C.c_int] * 3 + [C.c_longlong, C.c_int]
+                                + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "pope_mocope_tap_f32": (C.c_int, [C.POINTER(MocopeWeights)] + [C.c_void_p] * 9 + [C.c_int] * 3 + [C.c_longlong, C.c_int, C.c_int]
+                            + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "pope_convnext_workspace_bytes": (C.c_size_t, [C.POINTER(ConvNextWeights), C.c_int, C.c_int, C.c_int]),
     "pope_convnext_forward_f32": (C.c_int, [C.POINTER(ConvNextWeights), C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p,
                                                                                                      C.POINTER(C.c_void_p), C.c_void_p,

@@ -913,3 +913,34 @@ int pope_five_point_f64(const double* x0, const double* x1, int S, double* E_out
     StreamDevice on_device(stream);
     return pope_launch_five_point(x0, x1, S, E_out, n_out, static_cast<hipStream_t>(stream));
 }
+
+// ---- MoCoPE fusion pose model (mocope.hip) ------------------------------------------------------------------------------------
+
+size_t pope_mocope_workspace_bytes(int B, int S) { return pope_mocope_workspace(B, S); }
+
+int pope_mocope_forward_f32(const pope_mocope_weights* w, const float* dense0, const float* dense1, const float* kpts0,
+                            const float* kpts1, const int* counts, const int* sample_index, const unsigned long long* seeds,
+                            const float* feat0, const float* feat1, int B, int S, int G, long long M, int train_type,
+                            float* trans, float* rot, int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    MocopeArgs a = {};
+    a.w = w; a.in = posereg_input(dense0, dense1, kpts0, kpts1, counts, sample_index, seeds, B, S, M);
+    a.feat0 = feat0; a.feat1 = feat1; a.G = G; a.train_type = train_type; a.stage = MOCOPE_STAGE_FULL;
+    a.trans = trans; a.rot = rot; a.status = status; a.ws = workspace; a.ws_bytes = workspace_bytes;
+    POPE_TRY(pope_mocope_check(a));
+    StreamDevice on_device(stream);
+    return pope_launch_mocope(a, static_cast<hipStream_t>(stream));
+}
+
+int pope_mocope_tap_f32(const pope_mocope_weights* w, const float* dense0, const float* dense1, const float* kpts0,
+                        const float* kpts1, const int* counts, const int* sample_index, const unsigned long long* seeds,
+                        const float* feat0, const float* feat1, int B, int S, int G, long long M, int train_type, int stage,
+                        float* tap_out, int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    if (stage == MOCOPE_STAGE_FULL) return POPE_ERR_ARG;
+    MocopeArgs a = {};
+    a.w = w; a.in = posereg_input(dense0, dense1, kpts0, kpts1, counts, sample_index, seeds, B, S, M);
+    a.feat0 = feat0; a.feat1 = feat1; a.G = G; a.train_type = train_type; a.stage = stage;
+    a.tap_out = tap_out; a.status = status; a.ws = workspace; a.ws_bytes = workspace_bytes;
+    POPE_TRY(pope_mocope_check(a));
+    StreamDevice on_device(stream);
+    return pope_launch_mocope(a, static_cast<hipStream_t>(stream));
+}

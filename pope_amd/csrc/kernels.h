@@ -533,6 +533,22 @@ int pope_launch_posereg_stream_linear(const float* A, const float* W, const floa
 int pope_launch_posereg_tail(const pope_pose_regressor_weights& w, const float* Y2, const int* status, int B, float* trans,
                              float* rot, hipStream_t stream);
 
+// MoCoPE fusion pose model (mocope.hip; pose/model0604.py:MoCoPE): the arguments of pope_mocope_forward_f32 / pope_mocope_tap_f32
+struct MocopeArgs {
+    const pope_mocope_weights* w;
+    PoseRegInput in;
+    const float *feat0, *feat1;     // [B, 1000]
+    int G, train_type;
+    int stage;                      // POPE_MOCOPE_TAP_*, or MOCOPE_STAGE_FULL: trans / rot are written
+    float *trans, *rot, *tap_out;
+    int* status;
+    void* ws; size_t ws_bytes;
+};
+constexpr int MOCOPE_STAGE_FULL = -1;
+size_t pope_mocope_workspace(int B, int S);
+int pope_mocope_check(const MocopeArgs& a);   // no HIP call
+int pope_launch_mocope(const MocopeArgs& a, hipStream_t stream);
+
 // ConvNeXtV2 backbone and the image pose head (convnext.hip; pose/convnextv2/convnextv2.py, pose/model_cnn.py): the arguments of
 // pope_convnext_forward_f32 and of the op-level entries.  The *_check functions make no HIP call.
 struct ConvNextArgs {

@@ -163,6 +163,39 @@ def _run(model, stage, B, G, dense=None, compact=None, sample_index=None, seeds=
     return {"R": R, "t": t, "status": status}
 
 
+def compact_inputs(who, S, kpts0, kpts1, counts, seed, sample_index):
+    """The checked device form of the pipeline inputs (see `regress_pose_batch`): kpts0, kpts1 [M, 2] fp32, counts [B] int32,
+    sample_index [B, S] int32 or None, seeds [B] int64."""
+    for t in (kpts0, kpts1):
+        require_cuda(t, who)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who} expects float32 match coordinates")
+    dev = kpts0.device
+    kpts0, kpts1 = kpts0.contiguous(), kpts1.contiguous()
+    M = int(kpts0.shape[0])
+    if kpts0.shape != (M, 2) or kpts1.shape != (M, 2):
+        raise ValueError("kpts0 / kpts1 must both be [M, 2]")
+    counts = torch.as_tensor(counts)
+    if not counts.is_cuda and counts.numel() and int(counts.min()) < 0:     # host counts are checked for free; device counts by the
+        raise ValueError(f"{who}: negative match count")                  # kernel (status -1)
+    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
+    B = int(counts.numel())
+    if B == 0:
+        raise ValueError(f"{who}: no pairs")
+    if sample_index is not None:
+        sample_index = torch.as_tensor(sample_index).to(device=dev, dtype=torch.int32).contiguous()
+        if sample_index.shape != (B, S):
+            raise ValueError(f"sample_index must be [B, num_sample] = [{B}, {S}]")
+    if torch.is_tensor(seed):
+        seeds = seed.to(device=dev, dtype=torch.int64).contiguous()
+        if seeds.shape != (B,):
+            raise ValueError("seed must be one integer or a [B] tensor")
+    else:
+        s = int(seed) & _M64
+        seeds = torch.full((B,), s - (1 << 64) if s >> 63 else s, dtype=torch.int64, device=dev)
+    return kpts0, kpts1, counts, sample_index, seeds
+
+
 @torch.no_grad()
 def regress_pose_batch(model, kpts0, kpts1, counts, seed=0, sample_index=None, stage="forward"):
     """The pipeline form: every pair on its own (an attention group of one), from the matcher's compacted device buffers.
@@ -177,33 +210,9 @@ def regress_pose_batch(model, kpts0, kpts1, counts, seed=0, sample_index=None, s
         raise TypeError("regress_pose_batch expects a pope_amd Mkpts_Reg_Model")
     if model.training:
         raise NotImplementedError("Mkpts_Reg_Model runs inference only")
-    for t in (kpts0, kpts1):
-        require_cuda(t, "regress_pose_batch")
-        if t.dtype != torch.float32:
-            raise TypeError("regress_pose_batch expects float32 match coordinates")
-    dev = kpts0.device
-    kpts0, kpts1 = kpts0.contiguous(), kpts1.contiguous()
-    M = int(kpts0.shape[0])
-    if kpts0.shape != (M, 2) or kpts1.shape != (M, 2):
-        raise ValueError("kpts0 / kpts1 must both be [M, 2]")
-    counts = torch.as_tensor(counts)
-    if not counts.is_cuda and counts.numel() and int(counts.min()) < 0:     # host counts are checked for free; device counts by the
-        raise ValueError("regress_pose_batch: negative match count")      # kernel (status -1)
-    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
-    B, S = int(counts.numel()), model.num_sample
-    if B == 0:
-        raise ValueError("regress_pose_batch: no pairs")
-    if sample_index is not None:
-        sample_index = torch.as_tensor(sample_index).to(device=dev, dtype=torch.int32).contiguous()
-        if sample_index.shape != (B, S):
-            raise ValueError(f"sample_index must be [B, num_sample] = [{B}, {S}]")
-    if torch.is_tensor(seed):
-        seeds = seed.to(device=dev, dtype=torch.int64).contiguous()
-        if seeds.shape != (B,):
-            raise ValueError("seed must be one integer or a [B] tensor")
-    else:
-        s = int(seed) & _M64
-        seeds = torch.full((B,), s - (1 << 64) if s >> 63 else s, dtype=torch.int64, device=dev)
+    kpts0, kpts1, counts, sample_index, seeds = compact_inputs("regress_pose_batch", model.num_sample, kpts0, kpts1, counts, seed,
+                                                               sample_index)
+    B = int(counts.numel())
     return _run(model, stage, B, 1, compact=(kpts0, kpts1, counts), sample_index=sample_index, seeds=seeds)
 
 

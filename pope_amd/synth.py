@@ -917,3 +917,84 @@ def fcmae_checkpoint(seed=0):
                    p + "grn.beta": r(1, 4 * c), p + "pwconv2.linear.weight": r(c, 4 * c), p + "pwconv2.linear.bias": r(c)})
     ck["norm.weight"], ck["norm.bias"] = r(16), r(16)
     return ck
+
+
+# ---- MoCoPE fusion pose model (pose/model0604.py:MoCoPE) ----------------------------------------------------------------------
+
+MOCOPE_TRAIN_TYPES = ("mkpts+cnn", "mkpts", "cnn")
+# tests/golden/mocope.npz: (num_sample, pairs per call); every mode at MOCOPE_MODES_AT, '6d' elsewhere; the reduced train types at
+# MOCOPE_REDUCED; MOCOPE_WIDE for mlp1.0 = [8360, 16720] (flat index past 2^27).  Images are MOCOPE_IMAGE x MOCOPE_IMAGE, the trunk
+# is CONVNEXT_SMALL with the 1000-class head MoCoPE reads.
+MOCOPE_CASES = [(S, B) for S in (5, 37, 70) for B in (1, 2, 3, 5)]
+MOCOPE_MODES_AT = 37
+MOCOPE_REDUCED = (37, 3)
+MOCOPE_WIDE = (220, 2)
+MOCOPE_IMAGE = 64
+MOCOPE_TRUNK = dict(CONVNEXT_SMALL, num_classes=1000)
+MOCOPE_TAPS = ("embedding", "memory", "transformer_mkpts", "x_mkpts", "x_img", "qmkpts", "qimg")
+MOCOPE_TAP_COLUMNS = list(range(0, 512, 9))       # columns the fixture keeps of the [B, 2, 512] taps (all rows)
+MOCOPE_TAPS_OF = {"mkpts+cnn": MOCOPE_TAPS, "mkpts": ("embedding", "memory", "transformer_mkpts", "x_mkpts", "qmkpts"),
+                  "cnn": ("x_img", "qimg")}
+
+
+def _transformer_keys(prefix, d, hid=2048):
+    attn = lambda a: [(f"{a}.in_proj_weight", (3 * d, d)), (f"{a}.in_proj_bias", (3 * d,)), (f"{a}.out_proj.weight", (d, d)),  # noqa: E731
+                      (f"{a}.out_proj.bias", (d,))]
+    ffn = [("linear1.weight", (hid, d)), ("linear1.bias", (hid,)), ("linear2.weight", (d, hid)), ("linear2.bias", (d,))]
+    norms = lambda n: [(f"norm{i + 1}.{k}", (d,)) for i in range(n) for k in ("weight", "bias")]  # noqa: E731
+    keys = []
+    for i in range(6):
+        keys += [(f"{prefix}.encoder.layers.{i}.{k}", s) for k, s in attn("self_attn") + ffn + norms(2)]
+    keys += [(f"{prefix}.encoder.norm.weight", (d,)), (f"{prefix}.encoder.norm.bias", (d,))]
+    for i in range(6):
+        keys += [(f"{prefix}.decoder.layers.{i}.{k}", s) for k, s in attn("self_attn") + attn("multihead_attn") + ffn + norms(3)]
+    keys += [(f"{prefix}.decoder.norm.weight", (d,)), (f"{prefix}.decoder.norm.bias", (d,))]
+    return keys
+
+
+def mocope_keys(num_sample, mode="6d"):
+    """The state-dict keys of `MoCoPE(num_sample, mode)` outside `convnextv2.model.*`, with their shapes, in the reference's order."""
+    S = int(num_sample)
+    keys = _transformer_keys("transformer_mkpts", 76)
+    keys += [("mlp1.0.weight", (38 * S, 76 * S)), ("mlp1.0.bias", (38 * S,)), ("mlp1.3.weight", (1024, 38 * S)), ("mlp1.3.bias", (1024,))]
+    keys += [("mlp_img.0.weight", (512, 1000)), ("mlp_img.0.bias", (512,))]
+    keys += _transformer_keys("mkpts_as_q", 512) + _transformer_keys("cnn_as_q", 512)
+    widths = [2048, 1024, 512, 256, 128, 64, 32, 32]
+    for i in range(7):
+        keys += [(f"mlp2.{3 * i}.weight", (widths[i + 1], widths[i])), (f"mlp2.{3 * i}.bias", (widths[i + 1],))]
+    r = POSE_REGRESSOR_MODES[mode]
+    keys += [("translation_head.weight", (3, 32)), ("translation_head.bias", (3,)), ("rotation_head.weight", (r, 32)),
+             ("rotation_head.bias", (r,))]
+    return keys
+
+
+def mocope_state_dict(num_sample, mode="6d", seed=0):
+    """Seeded weights of the whole model, `convnextv2.model.*` (the MOCOPE_TRUNK) included, that keep every branch O(1): the rule of
+    `pose_regressor_state_dict`.  Every tensor outside the rotation head and mlp1 has a generator of its own group, so neither the
+    mode nor num_sample changes the others."""
+    gens = {}
+
+    def gen(k):
+        group = "rotation_head" if k.startswith("rotation_head") else "mlp1" if k.startswith("mlp1") else "rest"
+        if group not in gens:
+            gens[group] = torch.Generator().manual_seed(10000 + 1000 * ("rotation_head", "mlp1", "rest").index(group) + seed)
+        return gens[group]
+
+    sd = {}
+    for k, shape in mocope_keys(num_sample, mode):
+        if len(shape) == 2:
+            sd[k] = torch.randn(shape, generator=gen(k)) * (2.0 / shape[1]) ** 0.5
+        elif "norm" in k and k.endswith("weight"):
+            sd[k] = 1.0 + 0.3 * torch.randn(shape, generator=gen(k))
+        else:
+            sd[k] = 0.3 * torch.randn(shape, generator=gen(k))
+    sd.update({"convnextv2.model." + k: v for k, v in convnext_state_dict(seed=seed, **MOCOPE_TRUNK).items()})
+    return sd
+
+
+def mocope_case(num_sample, n_pairs):
+    """Inputs of one fixture case: (mkpts0, mkpts1 [B, S, 2] as `pose_regressor_case`, img0, img1 [B, 3, 64, 64])."""
+    d0, d1 = pose_regressor_case(num_sample, n_pairs)
+    g = torch.Generator().manual_seed(11000 + 100 * int(num_sample) + int(n_pairs))
+    shape = (int(n_pairs), 3, MOCOPE_IMAGE, MOCOPE_IMAGE)
+    return d0, d1, torch.randn(shape, generator=g), torch.randn(shape, generator=g)
