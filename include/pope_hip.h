@@ -766,6 +766,27 @@ int pope_crop_normalize_u8_f32(const unsigned char* img_hwc, int P, int Hin, int
 /* cv2.cvtColor(BGR2GRAY) (8-bit fixed point) followed by / 255. — eval_linemod_json.py:103-111:
  * bgr_hwc[P,H,W,3] uint8 -> out[P,1,H,W] fp32 in [0,1] (the Matcher's input). */
 int pope_gray_u8_f32(const unsigned char* bgr_hwc, int P, int H, int W, float* out, void* stream);
+/* The image pair of the image-conditioned pose heads (pose/model_cnn.py, pose/model0604.py), built on the device —
+ * linemod.py:107,129-130 and pose/dataset.py:102-106 (`cv2.resize(img, (224, 224))`, INTER_LINEAR on uint8), then
+ * train0604.py:148-151 (`.float()`, `.permute(0, 3, 2, 1)`): src_hwc[P, Hin, Win, 3] uint8 ->
+ *   transposed != 0: out[Q, 3, OW, OH] fp32, out[q, c, x, y] = (float)resized[q][y][x][c]   (the reference's layout)
+ *   transposed == 0: out[Q, 3, OH, OW] fp32, out[q, c, y, x]
+ * raw 0..255 values, channels in the stored order.  Output image q is the resize of src[rows[q]]: rows[Q] is a DEVICE int32
+ * array, or NULL for the identity (which needs Q == P); a row outside [0, P) gives an all-zero image and is never read.
+ * The resize is OpenCV's generic 8-bit INTER_LINEAR path, restated from its public algorithm and unpinned against cv2 (absent):
+ * per axis DEVICE int32 tables built on the host (pope_amd/preprocess.py:resize_linear_cv_tables): xstart[OW] / ystart[OH] the
+ * first tap (the second is min(first + 1, n_in - 1)), xcoef[OW, 2] / ycoef[OH, 2] the two coefficients with 11 fractional bits.
+ * With h(y) = src[y][sx] * ax0 + src[y][sx1] * ax1 in int32, a pixel is
+ *   (((ay0 * (h(sy) >> 4)) >> 16) + ((ay1 * (h(sy1) >> 4)) >> 16) + 2) >> 2.
+ * Equal sizes are thereby a copy; when BOTH axes shrink exactly 2 x (Hin == 2 OH and Win == 2 OW) the tables are not read and a
+ * pixel is (a + b + c + d + 2) >> 2 over its 2 x 2 block, as OpenCV's area path gives for that case.  Taps are clamped to the
+ * image whatever the tables say.  Integer arithmetic only: a pixel depends on nothing but its source image and the tables, so an
+ * image's result does not depend on Q or on its place in the batch.  One launch covers all Q; Q == 0 is a no-op.  Null pointers
+ * (other than rows), non-positive sizes, Q < 0, rows == NULL with Q != P and an `out` that is not 4-byte aligned return
+ * POPE_ERR_ARG before any HIP call. */
+int pope_pose_images_u8_f32(const unsigned char* src_hwc, int P, int Hin, int Win, const int* rows, int Q,
+                            const int* xstart, const int* xcoef, const int* ystart, const int* ycoef,
+                            int OH, int OW, int transposed, float* out, void* stream);
 
 /* Proposal crops — get_image_crop_resize (utils/data_utils.py:239-255 = cv2.warpAffine(image, M, (w, h), INTER_LINEAR), border
  * constant 0) as the drivers use it twice per SAM proposal (eval_linemod_json.py:83-90: crop at the expanded box's own size,

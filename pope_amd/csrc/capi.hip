@@ -715,6 +715,19 @@ int pope_gray_u8_f32(const unsigned char* bgr_hwc, int P, int H, int W, float* o
     return pope_launch_gray(bgr_hwc, size_t(P) * H * W, out, static_cast<hipStream_t>(stream));
 }
 
+int pope_pose_images_u8_f32(const unsigned char* src_hwc, int P, int Hin, int Win, const int* rows, int Q, const int* xstart,
+                            const int* xcoef, const int* ystart, const int* ycoef, int OH, int OW, int transposed, float* out,
+                            void* stream) {
+    PoseImagesParams p = {};
+    p.src = src_hwc; p.P = P; p.Hin = Hin; p.Win = Win; p.rows = rows; p.Q = Q;
+    p.xstart = xstart; p.xcoef = xcoef; p.ystart = ystart; p.ycoef = ycoef;
+    p.OH = OH; p.OW = OW; p.transposed = transposed; p.out = out;
+    if (const int rc = pope_pose_images_check(p)) return rc;   // before any HIP call
+    if (Q == 0) return POPE_OK;
+    StreamDevice on_device(stream);
+    return pope_launch_pose_images(p, static_cast<hipStream_t>(stream));
+}
+
 int pope_crop_warp_u8(const unsigned char* img_hwc, int H, int W, int C, const double* minv, const int* win, int P, int oh, int ow,
                       unsigned char* out, void* stream) {
     StreamDevice on_device(stream);

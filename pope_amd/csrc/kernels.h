@@ -300,6 +300,19 @@ int pope_launch_crop_warp(const unsigned char* img, int H, int W, int C, const d
                           unsigned char* out, hipStream_t stream);
 int pope_launch_crop_norm(const unsigned char* img, int P, int Hin, int Win, int top, int left, int ch, int cw, const float* mean,
                           const float* std, float* out, hipStream_t stream);
+// The image pair of the image-conditioned pose heads (preprocess.hip): OpenCV's 8-bit INTER_LINEAR resize of src[rows[q]] as
+// fp32 planes, uint8 HWC [P, Hin, Win, 3] -> [Q, 3, OW, OH] (transposed) or [Q, 3, OH, OW]
+struct PoseImagesParams {
+    const unsigned char* src;
+    int P, Hin, Win;
+    const int* rows; int Q;                    // device; NULL: the identity (Q == P)
+    const int *xstart, *xcoef;                 // [OW], [OW, 2]: first tap and the two 11-bit coefficients of every output column
+    const int *ystart, *ycoef;                 // [OH], [OH, 2]
+    int OH, OW, transposed;
+    float* out;
+};
+int pope_pose_images_check(const PoseImagesParams& p);   // no HIP call
+int pope_launch_pose_images(const PoseImagesParams& p, hipStream_t stream);
 
 // One LoFTR encoder layer update (loftr.hip): x <- layer(x, source); weights as f16x3 planes (bias-free Linears)
 struct LoftrLayerParams {

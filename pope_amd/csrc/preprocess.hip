@@ -242,6 +242,90 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const unsigned char* __r
     }
 }
 
+// The image pair of the image-conditioned pose heads (pose/dataset.py:102-106 -> train0604.py:148-151): cv2.resize(img, (OW, OH))
+// of uint8 images (OpenCV's generic 8-bit INTER_LINEAR path: per axis a first tap and two coefficients with 11 fractional bits
+// from the host, pope_amd/preprocess.py:resize_linear_cv_tables; horizontal pass in int32, vertical pass on the row sums >> 4 with
+// two 16-bit shifts and a rounding >> 2), `.float()`, and the layout the heads are fed: out[q][c][x][y] (transposed: the
+// reference's permute(0, 3, 2, 1)) or out[q][c][y][x], raw 0..255 values, channels as stored.  Image q is the resize of
+// src[rows[q]] (rows == NULL: src[q]); a row outside [0, P) gives zeros and reads nothing.  `area`: both axes shrink exactly
+// 2 x, where OpenCV averages the 2 x 2 block instead.  Integer arithmetic only.
+// A workgroup owns a 32 x 32 tile of one output image: it computes the tile with x along the lanes (the source is contiguous along
+// x), parks the three planes in LDS (rows padded to 33 words) and stores them with the output's fast axis along the lanes.
+// Taps are clamped to the image whatever the tables say.
+constexpr int PI_TILE = 32;
+
+__global__ __launch_bounds__(256) void pose_images_kernel(const unsigned char* __restrict__ src, int P, int Hin, int Win,
+                                                           const int* __restrict__ rows, const int* __restrict__ xstart,
+                                                           const int* __restrict__ xcoef, const int* __restrict__ ystart,
+                                                           const int* __restrict__ ycoef, int OH, int OW, int tiles_x, int tiles_y,
+                                                           int transposed, int area, float* __restrict__ out) {
+    __shared__ float tile[3][PI_TILE][PI_TILE + 1];
+    const int per_image = tiles_x * tiles_y;
+    const int q = int(blockIdx.x) / per_image, t = int(blockIdx.x) % per_image;
+    const int oy0 = (t / tiles_x) * PI_TILE, ox0 = (t % tiles_x) * PI_TILE;
+    const int r = rows ? rows[q] : q;
+    const bool live = r >= 0 && r < P;
+    const unsigned char* img = src + (live ? size_t(r) : size_t(0)) * Hin * Win * 3;
+    const int lane = int(threadIdx.x) & 31, group = int(threadIdx.x) >> 5;
+
+    const int ox = ox0 + lane;
+    int sx = 0, sx1 = 0, ax0 = 0, ax1 = 0;
+    if (live && ox < OW) {
+        if (area) {
+            sx = 2 * ox; sx1 = sx + 1;
+        } else {
+            sx = xstart[ox];
+            sx = sx < 0 ? 0 : (sx > Win - 1 ? Win - 1 : sx);
+            sx1 = sx + 1 > Win - 1 ? Win - 1 : sx + 1;
+            ax0 = xcoef[2 * ox]; ax1 = xcoef[2 * ox + 1];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PI_TILE / 8; ++k) {
+        const int ly = group + 8 * k, oy = oy0 + ly;
+        int v[3] = {0, 0, 0};
+        if (live && ox < OW && oy < OH) {
+            if (area) {
+                const unsigned char* r0 = img + size_t(2 * oy) * Win * 3;
+                const unsigned char* r1 = r0 + size_t(Win) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    v[c] = (int(r0[3 * sx + c]) + int(r0[3 * sx1 + c]) + int(r1[3 * sx + c]) + int(r1[3 * sx1 + c]) + 2) >> 2;
+            } else {
+                int sy = ystart[oy];
+                sy = sy < 0 ? 0 : (sy > Hin - 1 ? Hin - 1 : sy);
+                const int sy1 = sy + 1 > Hin - 1 ? Hin - 1 : sy + 1;
+                const int ay0 = ycoef[2 * oy], ay1 = ycoef[2 * oy + 1];
+                const unsigned char* r0 = img + size_t(sy) * Win * 3;
+                const unsigned char* r1 = img + size_t(sy1) * Win * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int h0 = int(r0[3 * sx + c]) * ax0 + int(r0[3 * sx1 + c]) * ax1;
+                    const int h1 = int(r1[3 * sx + c]) * ax0 + int(r1[3 * sx1 + c]) * ax1;
+                    v[c] = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tile[c][ly][lane] = float(v[c]);
+    }
+    __syncthreads();
+    const size_t plane = size_t(OH) * OW;
+    float* o = out + size_t(q) * 3 * plane;
+#pragma unroll
+    for (int k = 0; k < PI_TILE / 8; ++k) {
+        const int far = group + 8 * k;
+        // transposed: lanes run along y, the output's fast axis; else along x
+        const int ly = transposed ? lane : far, lx = transposed ? far : lane;
+        const int y = oy0 + ly, x = ox0 + lx;
+        if (y < OH && x < OW) {
+            const size_t at = transposed ? size_t(x) * OH + y : size_t(y) * OW + x;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c * plane + at] = tile[c][ly][lx];
+        }
+    }
+}
+
 inline unsigned grid_for(size_t n) { return unsigned(n / 256 + 1 < 16384 ? n / 256 + 1 : 16384); }
 
 }  // namespace
@@ -289,6 +373,26 @@ int pope_launch_crop_norm(const unsigned char* img, int P, int Hin, int Win, int
     if (reinterpret_cast<uintptr_t>(out) & 15) return POPE_ERR_ARG;
     hipLaunchKernelGGL(crop_norm_kernel, dim3(grid_for(size_t(P) * ch * ((cw + 3) / 4))), dim3(256), 0, stream, img, P, Hin, Win, top,
                        left, ch, cw, mean[0], mean[1], mean[2], std[0], std[1], std[2], out);
+    return pope_check_launch();
+}
+
+int pope_pose_images_check(const PoseImagesParams& p) {
+    if (!p.src || !p.out || !p.xstart || !p.xcoef || !p.ystart || !p.ycoef) return POPE_ERR_ARG;
+    if (p.P <= 0 || p.Hin <= 0 || p.Win <= 0 || p.OH <= 0 || p.OW <= 0 || p.Q < 0) return POPE_ERR_ARG;
+    if (!p.rows && p.Q != p.P) return POPE_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(p.out) & 3) return POPE_ERR_ARG;
+    const size_t tiles = size_t((p.OW + PI_TILE - 1) / PI_TILE) * size_t((p.OH + PI_TILE - 1) / PI_TILE);
+    if (tiles > 0x7fffffffu || tiles * size_t(p.Q) > 0x7fffffffu) return POPE_ERR_ARG;   // one workgroup per tile, a flat grid
+    return POPE_OK;
+}
+
+int pope_launch_pose_images(const PoseImagesParams& p, hipStream_t stream) {
+    POPE_TRY(pope_pose_images_check(p));
+    if (p.Q == 0) return POPE_OK;
+    const int tiles_x = (p.OW + PI_TILE - 1) / PI_TILE, tiles_y = (p.OH + PI_TILE - 1) / PI_TILE;
+    const int area = p.Hin == 2 * p.OH && p.Win == 2 * p.OW;
+    hipLaunchKernelGGL(pose_images_kernel, dim3(unsigned(p.Q) * tiles_x * tiles_y), dim3(256), 0, stream, p.src, p.P, p.Hin, p.Win,
+                       p.rows, p.xstart, p.xcoef, p.ystart, p.ycoef, p.OH, p.OW, tiles_x, tiles_y, p.transposed ? 1 : 0, area, p.out);
     return pope_check_launch();
 }
 

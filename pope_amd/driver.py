@@ -24,6 +24,10 @@ of `locate_pose_from_frames`) names each query's frame, the frames are given onc
 that depends on the frame alone (the generator's proposals, the crops and their intrinsics, their DINOv2 forward) runs once per
 frame; the vote reads the shared CLS rows in place (ops.vote_top3_shared).  `locate_poses_in_frame` asks R references of one
 frame, `share_frames` groups a list of queries by frame ("Shared frames").
+
+The learned pose heads run in the same call: `pose_regressor=` takes the key-point head, the image head or MoCoPE; the image
+pair of the latter two is made on the device from the reference image and the best slot's crop (`preprocess.pose_images`), and
+`regress_pose_from_frames` is the call from the raw frames ("The pose heads inside the query").
 """
 import numpy as np
 import torch
@@ -135,10 +139,16 @@ def _counts(proposals_per_query, Q, N, what):
 class ReferenceSet:
     """R reference images as the batched step needs them (`encode_references`): `cls` [R, 384] DINOv2 CLS tokens, `gray`
     [R, 1, H0, W0] gray / 255, `encoding` the matcher's `ReferenceEncoding` of `gray`.  Built for one (dinov2_model, matcher)
-    pair; the encoding follows later weight changes of the matcher by itself, the CLS tokens are those of the ViT as it was."""
+    pair; the encoding follows later weight changes of the matcher by itself, the CLS tokens are those of the ViT as it was.
 
-    def __init__(self, cls, gray, encoding, index=None):
+    Encoded with an image-conditioned pose head (`encode_references(..., pose_regressor=)`), it also keeps the reference side of
+    that head: `pose_img0` [R, 3, s, s] (`preprocess.pose_images` of the references) and, for a MoCoPE whose `train_type` reads
+    images, `pose_feat0` [R, 1000], the backbone's logits of those images.  `pose_for` = (the regressor, s, its backbone key when
+    logits are kept) names what they were made for; `_pose_side` refuses any other use."""
+
+    def __init__(self, cls, gray, encoding, index=None, pose_img0=None, pose_feat0=None, pose_for=None):
         self.cls, self.gray, self.encoding, self.index = cls, gray, encoding, index
+        self.pose_img0, self.pose_feat0, self.pose_for = pose_img0, pose_feat0, pose_for
 
     @property
     def R(self):
@@ -147,25 +157,75 @@ class ReferenceSet:
     def select(self, ref_index):
         """The same references (nothing is copied) standing for len(ref_index) queries, query q using row ref_index[q]: what
         the `ref_index` keyword says, for the calls that have no such keyword (`locate_pose_from_frames`, `locate_pose_from_frame`)."""
-        return ReferenceSet(self.cls, self.gray, self.encoding, _ref_index(ref_index, self.R, None, "ReferenceSet.select"))
+        return ReferenceSet(self.cls, self.gray, self.encoding, _ref_index(ref_index, self.R, None, "ReferenceSet.select"),
+                            self.pose_img0, self.pose_feat0, self.pose_for)
 
     def __len__(self):
         """The number of queries this stands for: its rows, or the length of its selection."""
         return self.R if self.index is None else len(self.index)
 
 
+def _regressor_kind(pose_regressor, what):
+    """None, "mkpts" (`pose_regressor.Mkpts_Reg_Model`), "mocope" (`mocope.MoCoPE`) or "cnn" (`pose_regressor_cnn.Mkpts_Reg_Model`);
+    TypeError for any other object.  Touches no device."""
+    if pose_regressor is None:
+        return None
+    from . import mocope, pose_regressor as kpts, pose_regressor_cnn as cnn
+    for kind, cls in (("mkpts", kpts.Mkpts_Reg_Model), ("mocope", mocope.MoCoPE), ("cnn", cnn.Mkpts_Reg_Model)):
+        if isinstance(pose_regressor, cls):
+            return kind
+    raise TypeError(f"{what}: pose_regressor must be a pope_amd pose_regressor.Mkpts_Reg_Model, mocope.MoCoPE or "
+                    f"pose_regressor_cnn.Mkpts_Reg_Model, got {type(pose_regressor).__name__}")
+
+
+def _image_size(pose_image_size, what):
+    size = int(pose_image_size)
+    if size <= 0:
+        raise ValueError(f"{what}: pose_image_size must be positive, got {pose_image_size}")
+    return size
+
+
+def _reads_images(kind, pose_regressor):
+    return kind == "cnn" or (kind == "mocope" and pose_regressor.train_type != "mkpts")
+
+
 @torch.no_grad()
-def encode_references(dinov2_model, matcher, refs_bgr):
+def encode_references(dinov2_model, matcher, refs_bgr, pose_regressor=None, pose_image_size=224):
     """`refs_bgr` [R, H0, W0, 3] uint8 BGR (numpy or tensor; H0, W0 multiples of 8, >= 16) -> `ReferenceSet`: the reference side of
-    `locate_and_match_batch_u8`, computed once.  Pass it in place of `refs_bgr`, with `ref_index` naming each query's row."""
-    from .preprocess import gray_batch, set_torch_images
+    `locate_and_match_batch_u8`, computed once.  Pass it in place of `refs_bgr`, with `ref_index` naming each query's row.
+
+    With an image-conditioned `pose_regressor` (`mocope.MoCoPE`, `pose_regressor_cnn.Mkpts_Reg_Model`) the set also keeps the
+    head's reference images at `pose_image_size` and, for a MoCoPE that reads images, their backbone logits, so a query with
+    that regressor and size runs the MoCoPE backbone over its crops only.  The key-point-only head has no reference side."""
+    from .preprocess import gray_batch, pose_images, set_torch_images
+    kind = _regressor_kind(pose_regressor, "encode_references")
+    size = _image_size(pose_image_size, "encode_references")
     dev = next(dinov2_model.parameters()).device
     refs = torch.as_tensor(refs_bgr).to(dev)
     if refs.dim() != 4 or int(refs.shape[0]) == 0:
         raise ValueError("encode_references: refs_bgr is [R >= 1, H0, W0, 3]")
     cls = get_cls_token_torch(dinov2_model, set_torch_images(refs, center_crop=True))
     gray = gray_batch(refs)
-    return ReferenceSet(cls, gray, matcher.encode_reference(gray))
+    img0 = feat0 = pose_for = None
+    if kind in ("mocope", "cnn"):
+        img0 = pose_images(refs, None, size)
+        feat0 = pose_regressor.image_logits(img0) if kind == "mocope" and _reads_images(kind, pose_regressor) else None
+        pose_for = (pose_regressor, size, pose_regressor.backbone_key() if feat0 is not None else None)
+    return ReferenceSet(cls, gray, matcher.encode_reference(gray), None, img0, feat0, pose_for)
+
+
+def _pose_side(refset, rows, pose_regressor, size, what):
+    """(img0, feat0) [Q, ...] of a `ReferenceSet` for an image-conditioned regressor, gathered by `rows` on the device; feat0 is
+    None where the set keeps no logits.  ValueError unless the set was encoded for this regressor object and size, and (with
+    logits) the backbone's tensors are still those the logits were computed with."""
+    made = refset.pose_for
+    if made is None or made[0] is not pose_regressor or made[1] != size:
+        raise ValueError(f"{what}: this ReferenceSet was not encoded for this pose_regressor at pose_image_size {size}: encode it with "
+                         "encode_references(..., pose_regressor=, pose_image_size=)")
+    if made[2] is not None and made[2] != pose_regressor.backbone_key():
+        raise ValueError(f"{what}: the regressor's backbone changed after this ReferenceSet was encoded: encode it again")
+    sel = torch.as_tensor(rows, dtype=torch.int64, device=refset.pose_img0.device)
+    return refset.pose_img0.index_select(0, sel), None if refset.pose_feat0 is None else refset.pose_feat0.index_select(0, sel)
 
 
 def _ref_index(ref_index, R, Q, what):
@@ -394,7 +454,7 @@ def locate_and_match_batch_u8(dinov2_model, matcher, refs_bgr, crops_bgr, propos
 @torch.no_grad()
 def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bboxes_xywh, K0, K1, conf_thr=0.9, ransac_thr=0.5,
                                ransac_conf=0.99, out_size=256, ref_index=None, frame_index=None, pose_regressor=None,
-                               regressor_seed=0):
+                               regressor_seed=0, pose_image_size=224):
     """`locate_match_pose_u8` for Q queries in one call: `refs_bgr` [Q, H0, W0, 3] uint8, `frames_bgr` [Q, H, W, 3] uint8 (an
     array, a tensor or Q frames of one size), `bboxes_xywh` a list of Q arrays [P_q, 4] (P_q = 0 allowed), `K0` / `K1` [3, 3]
     for all queries or [Q, 3, 3].  Returns a list of Q dicts, each what `locate_match_pose_u8` returns for that query alone.
@@ -415,10 +475,23 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     `pose_regressor` (a `pose_regressor.Mkpts_Reg_Model` on the models' device; default None: nothing changes) sends the same
     best-slot matches through `regress_pose_batch` in this call, every query on its own, the device sampler seeded with
     `regressor_seed`: each dict gains `pose_regressed` = (R [3, 3], t [3]) fp32, or None where the best slot has fewer than five
-    matches (the pairs `points_io.save_pair_points` skips) or no slot was filled.  Every other key stays what it was."""
+    matches (the pairs `points_io.save_pair_points` skips) or no slot was filled.  Every other key stays what it was.
+
+    `pose_regressor` may also be one of the image-conditioned heads, `mocope.MoCoPE` or `pose_regressor_cnn.Mkpts_Reg_Model`.  Their
+    image pair is made in this call, on the device: img1 = `preprocess.pose_images` of the best slot's 256 x 256 crop, gathered by
+    the tally's device-side best row, img0 = the same of the query's reference image, both `pose_image_size` square in the
+    layout the fork feeds (linemod.py:129-130, pose/dataset.py:102-106, train0604.py:148-151); nothing is downloaded in between.
+    MoCoPE goes through `regress_pose_fused_batch` on the same compacted matches with `seed=regressor_seed`, every query on its
+    own, and `pose_regressed` is None under the rule above or on a non-zero status.  The CNN head reads no key points
+    (`model(None, None, img0, img1)`): its `pose_regressed` is None only when no slot was filled.  With a `ReferenceSet` encoded
+    for the regressor (`encode_references(..., pose_regressor=, pose_image_size=)`) the reference images, and MoCoPE's backbone
+    logits of them, are gathered by `ref_index` and the backbone runs over the crops only; a set encoded without them, for
+    another regressor object or another size raises ValueError.  Any other object raises TypeError."""
     from .crops import crop_proposals
     from .pose import estimate_pose_batch
     from .pose_regressor import MIN_MATCHES, regress_pose_batch
+    kind = _regressor_kind(pose_regressor, "locate_match_pose_batch_u8")       # before any device work
+    size = _image_size(pose_image_size, "locate_match_pose_batch_u8")
     refs, rows = _select_refs(refs_bgr, ref_index, None, "locate_match_pose_batch_u8")
     Q = len(rows) if rows is not None else int(refs.shape[0])
     if not isinstance(frames_bgr, (torch.Tensor, np.ndarray)):
@@ -455,14 +528,31 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
     else:
         crops = torch.cat([p["crops"] for p in props], 0)
         K_crops = torch.from_numpy(np.ascontiguousarray(np.concatenate([p["K"] for p in props], 0))).to(dev)
-        dv = _batch_u8_on_device(dinov2_model, matcher, refs if rows is not None else refs.to(dev), crops, counts, conf_thr, rows, fidx)
+        if rows is None:
+            refs = refs.to(dev)
+        elif kind in ("mocope", "cnn"):          # refused before the query runs
+            img0, feat0 = _pose_side(refs, rows, pose_regressor, size, "locate_match_pose_batch_u8")
+        dv = _batch_u8_on_device(dinov2_model, matcher, refs, crops, counts, conf_thr, rows, fidx)
         pose = estimate_pose_batch(dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], K0q, K_crops.index_select(0, dv["best_row"]),
                                    ransac_thr, ransac_conf)
-        if pose_regressor is not None:
+        if kind == "mkpts":
             reg = regress_pose_batch(pose_regressor, dv["best_kpts0"], dv["best_kpts1"], dv["best_count"], seed=regressor_seed)
+        elif kind is not None:
+            from .mocope import regress_pose_fused_batch
+            from .preprocess import pose_images
+            img1 = pose_images(crops, dv["best_row"], size)
+            if rows is None:
+                img0, feat0 = pose_images(refs, None, size), None
+            if kind == "mocope":
+                reg = regress_pose_fused_batch(pose_regressor, dv["best_kpts0"], dv["best_kpts1"], dv["best_count"],
+                                               None if feat0 is not None else img0, img1, seed=regressor_seed, feat0=feat0)
+            else:
+                reg_t, reg_R = pose_regressor(None, None, img0, img1)
+                reg = {"R": reg_R, "t": reg_t}
         outs = _download(dv, own)
-        if pose_regressor is not None:
-            reg_R, reg_t, reg_ok = reg["R"].cpu().numpy(), reg["t"].cpu().numpy(), reg["status"].cpu().numpy() == 0
+        if kind is not None:
+            reg_R, reg_t = reg["R"].cpu().numpy(), reg["t"].cpu().numpy()
+            reg_ok = reg["status"].cpu().numpy() == 0 if kind != "cnn" else np.ones(Q, bool)
         R, t, inl, n_inl = (pose[k].cpu().numpy() for k in ("R", "t", "inliers", "n_inliers"))
         off = np.concatenate([[0], np.cumsum(dv["best_count"].cpu().numpy())])
     for q, out in enumerate(outs):
@@ -478,7 +568,7 @@ def locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, frames_bgr, bbox
         out["pre_bbox"], out["pre_K"] = out["boxes"][best], out["K_crops"][best]
         n = int(off[q + 1] - off[q])
         out["pose"] = (R[q], t[q], inl[off[q]:off[q + 1]]) if n >= 5 and int(n_inl[q]) > 0 else None
-        if pose_regressor is not None and n >= MIN_MATCHES and reg_ok[q]:
+        if kind is not None and (n >= MIN_MATCHES or kind == "cnn") and reg_ok[q]:
             out["pose_regressed"] = (reg_R[q], reg_t[q])
     return outs
 
@@ -515,9 +605,22 @@ def locate_pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, fra
                              out_size, max_proposals, None, 0)
 
 
+def regress_pose_from_frames(mask_generator, dinov2_model, matcher, pose_regressor, refs_bgr, frames_bgr, K0, K1, conf_thr=0.9,
+                             ransac_thr=0.5, ransac_conf=0.99, out_size=256, max_proposals=None, regressor_seed=0, pose_image_size=224):
+    """`locate_pose_from_frames` with a learned pose head in the same call: every argument as there, plus `pose_regressor` (any
+    of the three heads `locate_match_pose_batch_u8` accepts), `regressor_seed` and `pose_image_size` as in that call.  Each dict
+    gains `pose_regressed` = (R [3, 3], t [3]) fp32 or None; every other key is that of `locate_pose_from_frames`."""
+    if pose_regressor is None:
+        raise TypeError("regress_pose_from_frames: pose_regressor is required (locate_pose_from_frames is the call without one)")
+    return _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bgr, K0, K1, conf_thr, ransac_thr, ransac_conf,
+                             out_size, max_proposals, pose_regressor, regressor_seed, pose_image_size)
+
+
 def _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bgr, K0, K1, conf_thr, ransac_thr, ransac_conf, out_size,
-                      max_proposals, pose_regressor, regressor_seed):
-    """`locate_pose_from_frames`, with `locate_match_pose_batch_u8`'s `pose_regressor` / `regressor_seed` handed through."""
+                      max_proposals, pose_regressor, regressor_seed, pose_image_size=224):
+    """`locate_pose_from_frames`, with `locate_match_pose_batch_u8`'s `pose_regressor` / `regressor_seed` / `pose_image_size` handed
+    through."""
+    _regressor_kind(pose_regressor, "locate_pose_from_frames")      # checked before any model is touched
     frame_index = None
     if isinstance(frames_bgr, SharedFrames):
         frames_bgr, frame_index = frames_bgr.frames, frames_bgr.index
@@ -549,7 +652,8 @@ def _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, frames_bg
     if max_proposals is not None:
         proposals = [p[:int(max_proposals)] for p in proposals]
     outs = locate_match_pose_batch_u8(dinov2_model, matcher, refs_bgr, stack, proposals, K0, K1, conf_thr, ransac_thr, ransac_conf,
-                                      out_size, frame_index=fidx, pose_regressor=pose_regressor, regressor_seed=regressor_seed)
+                                      out_size, frame_index=fidx, pose_regressor=pose_regressor, regressor_seed=regressor_seed,
+                                      pose_image_size=pose_image_size)
     for q, out in enumerate(outs):
         out["proposals"] = proposals[q] if fidx is None else proposals[fidx[q]].copy()
     return outs
@@ -567,11 +671,13 @@ def locate_pose_from_frame(mask_generator, dinov2_model, matcher, ref_bgr, frame
 
 
 def locate_poses_in_frame(mask_generator, dinov2_model, matcher, refs_bgr, frame_bgr, K0, K1, conf_thr=0.9, ransac_thr=0.5,
-                          ransac_conf=0.99, out_size=256, max_proposals=None, pose_regressor=None, regressor_seed=0):
+                          ransac_conf=0.99, out_size=256, max_proposals=None, pose_regressor=None, regressor_seed=0,
+                          pose_image_size=224):
     """R references asked of ONE frame: `refs_bgr` [R, H0, W0, 3] uint8 or a `ReferenceSet` (its R rows, or its selection),
     `frame_bgr` [H, W, 3], `K0` [3, 3] or [R, 3, 3], `K1` [3, 3].  `locate_pose_from_frames` with `SharedFrames([frame], [0] * R)`:
     the frame passes through the mask generator once and its crops through DINOv2 once.  Returns a list of R dicts.
-    `pose_regressor` / `regressor_seed`: as in `locate_match_pose_batch_u8` (each dict gains `pose_regressed`)."""
+    `pose_regressor` / `regressor_seed` / `pose_image_size`: as in `locate_match_pose_batch_u8` (each dict gains `pose_regressed`;
+    all three heads are accepted)."""
     frame = frame_bgr[None] if on_device(frame_bgr) else np.asarray(frame_bgr.cpu() if torch.is_tensor(frame_bgr) else frame_bgr)[None]
     return _pose_from_frames(mask_generator, dinov2_model, matcher, refs_bgr, SharedFrames(frame, [0] * len(refs_bgr)), K0, K1,
-                             conf_thr, ransac_thr, ransac_conf, out_size, max_proposals, pose_regressor, regressor_seed)
+                             conf_thr, ransac_thr, ransac_conf, out_size, max_proposals, pose_regressor, regressor_seed, pose_image_size)

@@ -10,6 +10,11 @@ SAM's input transform is the same resample of whole frames: `resize_u8_batch` is
 that already sit in HBM, `sam_preprocess_batch` that resize, `Sam.preprocess` and its zero pad as one result (segment_anything
 utils/transforms.py, modeling/sam.py), both bit-identical to the host chain.  `frames_on_device` is how the calls that take
 frames as numpy arrays or tensors (pope_amd/sam_generator.py, pope_amd/driver.py) tell the two apart.
+
+`pose_images` makes the image pair of the fork's image-conditioned pose heads (pose/dataset.py:102-106, train0604.py:148-151:
+`cv2.resize` to 224 x 224, `.float()`, `.permute(0, 3, 2, 1)`) for Q images gathered by a device index, in one launch.  Its resize
+is OpenCV's 8-bit INTER_LINEAR path restated (`resize_linear_cv_tables`, host twin `resize_linear_cv_u8`); cv2 is not installed
+here, so parity with the library is unpinned and the twin is the contract.
 """
 import ctypes as C
 import math
@@ -203,6 +208,104 @@ def crop_normalize(images, crop_hw, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=No
     with on_device_of(images):
         check(_lib.lib().pope_crop_normalize_u8_f32(C.c_void_p(images.data_ptr()), P, H, W, top, left, ch, cw, m, s,
                                                     C.c_void_p(out.data_ptr()), stream_of(images.device)), "pope_crop_normalize_u8_f32")
+    return out
+
+
+# ---- the image pair of the image-conditioned pose heads ---------------------------------------------------------------------------
+CV_COEF_BITS = 11   # OpenCV: INTER_RESIZE_COEF_BITS
+
+
+def resize_linear_cv_tables(n_in, n_out):
+    """One axis of OpenCV's 8-bit `INTER_LINEAR` resize from `n_in` to `n_out` samples: (start[n_out], coef[n_out, 2]) int32 —
+    the first tap of every output sample (the second is min(start + 1, n_in - 1)) and the two coefficients with 11 fractional
+    bits, which sum to 2048.  Restated from OpenCV's public algorithm (cv2 is not in this image: unpinned against the library)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"resize_linear_cv_tables: sizes must be positive, got {n_in} -> {n_out}")
+    scale = 1.0 / (np.float64(n_out) / np.float64(n_in))
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    f = (f - s).astype(np.float32)
+    s = s.astype(np.int64)
+    low, high = s < 0, s >= n_in - 1
+    s = np.where(low, 0, np.where(high, n_in - 1, s))
+    f = np.where(low | high, np.float32(0), f).astype(np.float32)
+    one = np.float32(1 << CV_COEF_BITS)
+    coef = np.stack([np.rint((np.float32(1) - f) * one), np.rint(f * one)], 1).astype(np.int32)   # rint: round half to even
+    return s.astype(np.int32), np.ascontiguousarray(coef)
+
+
+def resize_linear_cv_u8(img_hwc_u8, oh, ow):
+    """`cv2.resize(img, (ow, oh))` of a uint8 [H, W, C] image (default INTER_LINEAR) in numpy, the host twin of
+    `pose_images`: per channel, the horizontal pass `src[sx] * ax0 + src[sx1] * ax1` in int32, then
+    `(((ay0 * (row[sy] >> 4)) >> 16) + ((ay1 * (row[sy1] >> 4)) >> 16) + 2) >> 2`.  Equal sizes are a copy, and an exact 2 x
+    shrink of BOTH axes is the rounded mean of the 2 x 2 block (OpenCV switches to its area path there).  Restated from OpenCV's
+    public algorithm; cv2 is not in this image, so parity with the library is unpinned."""
+    img = np.asarray(img_hwc_u8)
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise TypeError("resize_linear_cv_u8 expects a uint8 [H, W, C] image")
+    H, W = img.shape[:2]
+    oh, ow = int(oh), int(ow)
+    if (H, W) == (oh, ow):
+        return img.copy()
+    src = img.astype(np.int32)
+    if H == 2 * oh and W == 2 * ow:
+        return ((src[0::2, 0::2] + src[0::2, 1::2] + src[1::2, 0::2] + src[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+    ys, yc = resize_linear_cv_tables(H, oh)
+    xs, xc = resize_linear_cv_tables(W, ow)
+    xs1, ys1 = np.minimum(xs + 1, W - 1), np.minimum(ys + 1, H - 1)
+    row = (src[:, xs] * xc[None, :, 0, None] + src[:, xs1] * xc[None, :, 1, None]) >> 4          # [H, ow, C]
+    out = (((yc[:, 0, None, None] * row[ys]) >> 16) + ((yc[:, 1, None, None] * row[ys1]) >> 16) + 2) >> 2
+    return out.astype(np.uint8)
+
+
+_cv_tables = {}
+
+
+def _device_cv_tables(n_in, n_out, device):
+    key = (n_in, n_out, str(device))
+    if key not in _cv_tables:
+        _cv_tables[key] = tuple(torch.from_numpy(a).to(device) for a in resize_linear_cv_tables(n_in, n_out))
+    return _cv_tables[key]
+
+
+@torch.no_grad()
+def pose_images(src_u8, rows=None, size=224, transposed=True):
+    """The images the image-conditioned pose heads read (`pose_regressor_cnn.Mkpts_Reg_Model`, `mocope.MoCoPE`), made on the
+    device in one launch: `src_u8` [P, H, W, 3] uint8 (CUDA, BGR as the drivers hold it) -> fp32 [Q, 3, size, size], image q =
+    `cv2.resize(src_u8[rows[q]], (size, size))` as floats 0..255 in the stored channel order (linemod.py:129-130,
+    pose/dataset.py:102-106).  `transposed` (default, what the fork's train / test loops feed: `.permute(0, 3, 2, 1)`,
+    train0604.py:148-151) gives out[q, c, x, y]; False gives out[q, c, y, x].  `rows`: a CUDA int32 / int64 tensor [Q], or None for
+    every image in order; a row outside [0, P) gives an all-zero image.  Nothing is read back.  Bit-equal to
+    `resize_linear_cv_u8`, the numpy restatement of OpenCV's 8-bit INTER_LINEAR path (unpinned against cv2, which is absent)."""
+    require_cuda(src_u8, "pose_images")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise TypeError("pose_images expects a uint8 [P, H, W, 3] tensor")
+    src = src_u8.contiguous()
+    P, Hin, Win, _ = src.shape
+    OH = OW = int(size)
+    if min(P, Hin, Win, OH) <= 0:
+        raise ValueError(f"pose_images: empty source or size ({P} images of {Hin} x {Win} to {OH} x {OW})")
+    dev = src.device
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 1:
+            raise TypeError("pose_images: rows is a 1-D int32 / int64 tensor on the images' device, or None")
+        if rows.device != dev:
+            raise ValueError(f"pose_images: rows on {rows.device}, images on {dev}")
+        if rows.dtype == torch.int64:           # rows outside [0, P) stay outside after the narrowing
+            rows = rows.clamp(-1, P)
+        rows = rows.to(torch.int32).contiguous()
+    Q = P if rows is None else int(rows.numel())
+    out = torch.empty((Q, 3, OW, OH) if transposed else (Q, 3, OH, OW), dtype=torch.float32, device=dev)
+    if Q == 0:          # an empty tensor has no address to hand over
+        return out
+    xs, xc = _device_cv_tables(Win, OW, dev)
+    ys, yc = _device_cv_tables(Hin, OH, dev)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    with on_device_of(src):
+        check(_lib.lib().pope_pose_images_u8_f32(p(src), P, Hin, Win, p(rows) if rows is not None else None, Q, p(xs), p(xc), p(ys),
+                                                 p(yc), OH, OW, int(bool(transposed)), p(out), stream_of(dev)),
+              "pope_pose_images_u8_f32")
     return out
 
 
