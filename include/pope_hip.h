@@ -921,6 +921,17 @@ int pope_pose_regressor_encoder_f32(const pope_pose_regressor_weights* w, const 
                                     const float* kpts0, const float* kpts1, const int* counts, const int* sample_index,
                                     const unsigned long long* seeds, int B, int S, int G, long long M, float* x_out,
                                     int* index_out, int* status, void* stream);
+/* The launches of the forward one by one (tests).  Each refuses null pointers and sizes <= 0 with POPE_ERR_ARG.
+ * layer: one encoder layer in place on X [B, S, 76], groups as above (1 <= G <= 64, B % G == 0; weights 16-byte aligned).
+ * stream_linear: Y [B, N] = leaky_relu(A [B, K] . W [N, K]^T + bias, 0.01); 16-byte loads when K % 4 == 0 and A and W are
+ * 16-byte aligned, single floats otherwise; a row's summation order depends on K and on that route alone.
+ * tail: mlp.6 .. 18, the heads and convert2matrix over Y2 [B, num_sample]: reads num_sample, mode, mlp_w / mlp_b [2 .. 6]
+ * and the heads of w; a pair whose status is not 0 gets zeros. */
+int pope_pose_regressor_layer_f32(const pope_pose_regressor_layer* w, float* X, int B, int S, int G, void* stream);
+int pope_pose_regressor_stream_linear_f32(const float* A, const float* W, const float* bias, float* Y, int B, long long K, int N,
+                                          void* stream);
+int pope_pose_regressor_tail_f32(const pope_pose_regressor_weights* w, const float* Y2, const int* status, int B, float* trans,
+                                 float* rot, void* stream);
 
 /* ---- ConvNeXtV2 image backbone and the image pose head (pose/convnextv2/convnextv2.py, pose/model_cnn.py) -------- */
 
@@ -1061,6 +1072,20 @@ int pope_mocope_tap_f32(const pope_mocope_weights* w, const float* dense0, const
                         const float* kpts1, const int* counts, const int* sample_index, const unsigned long long* seeds,
                         const float* feat0, const float* feat1, int B, int S, int G, long long M, int train_type, int stage,
                         float* tap_out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The launches of the transformers one by one (tests).  Each refuses null pointers and sizes <= 0 with POPE_ERR_ARG.
+ * linear: Y [R, N] = act(A [R, K] . W [N, K]^T + bias), act 0 (none) or 1 (ReLU); K % 4 == 0, A and W 16-byte aligned.
+ * attention: rows r = b * S + s; row r attends over the G rows (b / G * G + g) * S + s, g < G, softmax(q . k / sqrt(d)) v, one
+ * head; q / k / v rows at pitches ldq / ldk / ldv >= d floats, O [R, d] dense.  d is 76 or 512, 1 <= G <= 64, R % (S G) == 0.
+ * add_ln: X [R, d] = LayerNorm(X + Y; w1, b1), then LayerNorm(.; w2, b2) when w2 / b2 are given (both or neither); eps 1e-5.
+ * ffn76: X [R, 76] = LayerNorm(X + linear2(relu(linear1(X))); nw, nb), then LayerNorm(.; fw, fb) when given; linear1
+ * [2048, 76], linear2 [76, 2048], 16-byte aligned. */
+int pope_mocope_linear_f32(const float* A, const float* W, const float* bias, float* Y, int R, int K, int N, int act, void* stream);
+int pope_mocope_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int R, int S, int G,
+                              int d, void* stream);
+int pope_mocope_add_ln_f32(float* X, const float* Y, const float* w1, const float* b1, const float* w2, const float* b2, int R, int d,
+                           void* stream);
+int pope_mocope_ffn76_f32(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw,
+                          const float* nb, const float* fw, const float* fb, int R, void* stream);
 
 /* ---- host-side helper ------------------------------------------------------------------------ */
 

@@ -266,6 +266,13 @@ PROTOTYPES = {
     "pope_pose_regressor_embedding_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4),
     "pope_pose_regressor_encoder_f32": (C.c_int, [C.POINTER(PoseRegressorWeights)] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_longlong]
                                         + [C.c_void_p] * 4),
+    "pope_pose_regressor_layer_f32": (C.c_int, [C.POINTER(PoseRegressorLayer), C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "pope_pose_regressor_stream_linear_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "pope_pose_regressor_tail_f32": (C.c_int, [C.POINTER(PoseRegressorWeights), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3),
+    "pope_mocope_linear_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "pope_mocope_attention_f32": (C.c_int, [C.c_void_p, C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "pope_mocope_add_ln_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "pope_mocope_ffn76_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_void_p]),
     "pope_mocope_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "pope_mocope_forward_f32": (C.c_int, [C.POINTER(MocopeWeights)] + [C.c_void_p] * 9 + [C.c_int] * 3 + [C.c_longlong, C.c_int]
                                 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),

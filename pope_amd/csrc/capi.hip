@@ -882,6 +882,39 @@ int pope_pose_regressor_forward_f32(const pope_pose_regressor_weights* w, const 
     return pope_launch_posereg_tail(*w, y2, status, B, trans, rot, st);
 }
 
+// the launches of the forward one by one (tests)
+int pope_pose_regressor_layer_f32(const pope_pose_regressor_layer* w, float* X, int B, int S, int G, void* stream) {
+    if (!w || !X || B <= 0 || S <= 0 || G < 1 || G > 64 || B % G) return POPE_ERR_ARG;
+    if (size_t(B) * S * 76 >= (size_t(1) << 31)) return POPE_ERR_ARG;
+    uintptr_t bits = 0;
+    for (const float* p : {w->in_proj_w, w->in_proj_b, w->out_proj_w, w->out_proj_b, w->linear1_w, w->linear1_b, w->linear2_w, w->linear2_b,
+                           w->norm1_w, w->norm1_b, w->norm2_w, w->norm2_b}) {
+        if (!p) return POPE_ERR_ARG;
+        bits |= reinterpret_cast<uintptr_t>(p);
+    }
+    if (bits & 15) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_posereg_layer(*w, X, B, S, G, static_cast<hipStream_t>(stream));
+}
+
+int pope_pose_regressor_stream_linear_f32(const float* A, const float* W, const float* bias, float* Y, int B, long long K, int N,
+                                          void* stream) {
+    if (!A || !W || !bias || !Y || B <= 0 || K <= 0 || N <= 0) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_posereg_stream_linear(A, W, bias, Y, B, K, N, static_cast<hipStream_t>(stream));
+}
+
+int pope_pose_regressor_tail_f32(const pope_pose_regressor_weights* w, const float* Y2, const int* status, int B, float* trans,
+                                 float* rot, void* stream) {
+    if (!w || !Y2 || !status || !trans || !rot || B <= 0 || w->num_sample <= 0) return POPE_ERR_ARG;
+    if (w->mode < POPE_ROT_MATRIX || w->mode > POPE_ROT_6D) return POPE_ERR_ARG;
+    for (int i = 2; i < 7; ++i)
+        if (!w->mlp_w[i] || !w->mlp_b[i]) return POPE_ERR_ARG;
+    if (!w->trans_w || !w->trans_b || !w->rot_w || !w->rot_b) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_posereg_tail(*w, Y2, status, B, trans, rot, static_cast<hipStream_t>(stream));
+}
+
 // ---- ConvNeXtV2 backbone and the image pose head (convnext.hip) ------------------------------------------------------------
 
 size_t pope_convnext_workspace_bytes(const pope_convnext_weights* w, int B, int H, int W) { return pope_convnext_workspace(w, B, H, W); }
@@ -956,4 +989,35 @@ int pope_mocope_tap_f32(const pope_mocope_weights* w, const float* dense0, const
     POPE_TRY(pope_mocope_check(a));
     StreamDevice on_device(stream);
     return pope_launch_mocope(a, static_cast<hipStream_t>(stream));
+}
+
+// the launches of the transformers one by one (tests)
+int pope_mocope_linear_f32(const float* A, const float* W, const float* bias, float* Y, int R, int K, int N, int act, void* stream) {
+    if (!A || !W || !bias || !Y || R <= 0 || K <= 0 || (K & 3) || N <= 0 || act < 0 || act > 1) return POPE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return POPE_ERR_ARG;    // 16-byte loads
+    StreamDevice on_device(stream);
+    return pope_launch_mocope_linear(A, W, bias, Y, R, K, N, act, static_cast<hipStream_t>(stream));
+}
+
+int pope_mocope_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int R, int S, int G,
+                              int d, void* stream) {
+    if (!Q || !K || !V || !O || (d != 76 && d != 512) || G < 1 || G > 64 || R <= 0 || S <= 0) return POPE_ERR_ARG;
+    if (ldq < d || ldk < d || ldv < d || (long long)R % ((long long)S * G)) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_mocope_attention(Q, ldq, K, ldk, V, ldv, O, R, S, G, d, static_cast<hipStream_t>(stream));
+}
+
+int pope_mocope_add_ln_f32(float* X, const float* Y, const float* w1, const float* b1, const float* w2, const float* b2, int R, int d,
+                           void* stream) {
+    if (!X || !Y || !w1 || !b1 || !w2 != !b2 || (d != 76 && d != 512) || R <= 0) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_mocope_add_ln(X, Y, w1, b1, w2, b2, R, d, static_cast<hipStream_t>(stream));
+}
+
+int pope_mocope_ffn76_f32(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw,
+                          const float* nb, const float* fw, const float* fb, int R, void* stream) {
+    if (!X || !l1w || !l1b || !l2w || !l2b || !nw || !nb || !fw != !fb || R <= 0) return POPE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(l1w) | reinterpret_cast<uintptr_t>(l1b) | reinterpret_cast<uintptr_t>(l2w)) & 15) return POPE_ERR_ARG;
+    StreamDevice on_device(stream);
+    return pope_launch_mocope_ffn76(X, l1w, l1b, l2w, l2b, nw, nb, fw, fb, R, static_cast<hipStream_t>(stream));
 }

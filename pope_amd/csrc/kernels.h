@@ -561,6 +561,14 @@ constexpr int MOCOPE_STAGE_FULL = -1;
 size_t pope_mocope_workspace(int B, int S);
 int pope_mocope_check(const MocopeArgs& a);   // no HIP call
 int pope_launch_mocope(const MocopeArgs& a, hipStream_t stream);
+// the launches of mocope.hip one by one (the op-level entries pope_mocope_*_f32; the argument checks are theirs)
+int pope_launch_mocope_linear(const float* A, const float* W, const float* bias, float* Y, int R, int K, int N, int act, hipStream_t stream);
+int pope_launch_mocope_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int R, int S, int G,
+                                 int d, hipStream_t stream);
+int pope_launch_mocope_add_ln(float* X, const float* Y, const float* w1, const float* b1, const float* w2, const float* b2, int R, int d,
+                              hipStream_t stream);
+int pope_launch_mocope_ffn76(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw,
+                             const float* nb, const float* fw, const float* fb, int R, hipStream_t stream);
 
 // ConvNeXtV2 backbone and the image pose head (convnext.hip; pose/convnextv2/convnextv2.py, pose/model_cnn.py): the arguments of
 // pope_convnext_forward_f32 and of the op-level entries.  The *_check functions make no HIP call.

@@ -248,6 +248,12 @@ int launch_add_ln(float* X, const float* Y, const float* w1, const float* b1, co
     return pope_check_launch();
 }
 
+int launch_ffn76(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw, const float* nb,
+                 const float* fw, const float* fb, int R, hipStream_t st) {
+    hipLaunchKernelGGL(mocope_ffn76_kernel, dim3((R + 31) / 32), dim3(256), 0, st, X, l1w, l1b, l2w, l2b, nw, nb, fw, fb, R);
+    return pope_check_launch();
+}
+
 // scratch of a transformer over R rows of width d: qkv [R, 3 d], att [R, d], proj [R, d], hid [min(R, FFN_ROWS), 2048]
 struct Scratch { float *qkv, *att, *proj, *hid; };
 struct Dims { int R, S, G, d; };     // rows r = b * S + s, attention groups of G consecutive b
@@ -276,10 +282,7 @@ int attention_block(float* x, const float* kv, const float* in_w, const float* i
 // x = LayerNorm(x + linear2(relu(linear1(x)))), then the closing norm when given
 int ffn_block(float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* nw, const float* nb,
               const float* fw, const float* fb, const Dims& m, const Scratch& s, hipStream_t st) {
-    if (m.d == D1) {
-        hipLaunchKernelGGL(mocope_ffn76_kernel, dim3((m.R + 31) / 32), dim3(256), 0, st, x, w1, b1, w2, b2, nw, nb, fw, fb, m.R);
-        return pope_check_launch();
-    }
+    if (m.d == D1) return launch_ffn76(x, w1, b1, w2, b2, nw, nb, fw, fb, m.R, st);
     for (int r0 = 0; r0 < m.R; r0 += FFN_ROWS) {
         const int rows = std::min(FFN_ROWS, m.R - r0);
         POPE_TRY(launch_linear(x + size_t(r0) * m.d, w1, b1, s.hid, rows, m.d, HID, ACT_RELU, st));
@@ -369,6 +372,25 @@ bool stage_ok(int stage, int train_type) {
 }
 
 }  // namespace
+
+int pope_launch_mocope_linear(const float* A, const float* W, const float* bias, float* Y, int R, int K, int N, int act, hipStream_t st) {
+    return launch_linear(A, W, bias, Y, R, K, N, act, st);
+}
+
+int pope_launch_mocope_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int R, int S, int G,
+                                 int d, hipStream_t st) {
+    return launch_attention(Q, ldq, K, ldk, V, ldv, O, R, S, G, d, st);
+}
+
+int pope_launch_mocope_add_ln(float* X, const float* Y, const float* w1, const float* b1, const float* w2, const float* b2, int R, int d,
+                              hipStream_t st) {
+    return launch_add_ln(X, Y, w1, b1, w2, b2, R, d, st);
+}
+
+int pope_launch_mocope_ffn76(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw,
+                             const float* nb, const float* fw, const float* fb, int R, hipStream_t st) {
+    return launch_ffn76(X, l1w, l1b, l2w, l2b, nw, nb, fw, fb, R, st);
+}
 
 size_t pope_mocope_workspace(int B, int S) { return B > 0 && S > 0 ? layout(B, S).total : 0; }
 
