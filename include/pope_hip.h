@@ -62,7 +62,7 @@ enum {
  *                      (v_mfma_f32_16x16x32_f16 in the GEMMs, v_mfma_f32_32x32x16_f16 in attention) per product
  *                      block on the matrix cores: same or smaller error than the fp32 chain inside the range
  *                      contract below (measured against fp64), 2.3x faster end to end. */
-enum { POPE_PREC_F32_MFMA = 0, POPE_PREC_F16X3 = 1, POPE_PREC_F16 = 2 /* SAM encoder only: plain f16 operands, see there */ };
+enum { POPE_PREC_F32_MFMA = 0, POPE_PREC_F16X3 = 1, POPE_PREC_F16 = 2 /* opt-in plain f16 operands, one MFMA per product: ViT / SAM encoders, LoFTR ResNet-FPN; see there */ };
 /* bits of a range_flag word: which f16x3 producer saw a value out of range */
 enum { POPE_RANGE_PATCH = 1, POPE_RANGE_LAYERNORM = 2, POPE_RANGE_QKV = 4, POPE_RANGE_GELU = 8, POPE_RANGE_MATCH = 16,
        POPE_RANGE_INPUT = 32 };
@@ -402,7 +402,12 @@ int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L,
  * Outputs are NHWC with a one-pixel border: out_c[n, H/8+2, W/8+2, 256] (x3_out; border zero) and
  * out_f[n, H/2+2, W/2+2, 128] (x1_out; border undefined) — the reference's NCHW maps are the interiors, permuted.
  * precision = POPE_PREC_F16X3, or POPE_PREC_F32_MFMA (the re-run of a range-guard event): w[i] are then the same [Cout, K]
- * matrices as plain fp32 and every convolution runs on the fp32 MFMA (gemm_f32.hip, implicit 3x3 loader). */
+ * matrices as plain fp32 and every convolution runs on the fp32 MFMA (gemm_f32.hip, implicit 3x3 loader).
+ * POPE_PREC_F16 (opt-in): one f16 MFMA per product, fp32 accumulate.  w[i] are plain f16 row-major matrices, value *
+ * POPE_PLANES_W_SCALE, [Cout, K] with the input channels of every tap rounded up to 64 (zero filled; matrix 0: K = 128, the 49
+ * taps then zeros); activations travel between the layers as f16 rows, value * POPE_PLANES_ACT_SCALE, each rounded once in its
+ * producer's epilogue.  Same workspace, same fp32 outputs; POPE_RANGE_INPUT when a scaled activation leaves the f16 range or is
+ * not finite — the caller re-runs with POPE_PREC_F32_MFMA as for POPE_PREC_F16X3. */
 typedef struct pope_resnetfpn_weights {
     const void* w[22];
     const float* b[22];
@@ -465,6 +470,16 @@ typedef struct pope_conv_layer_args {
 } pope_conv_layer_args;
 size_t pope_conv_layer_scratch_bytes(int form, int n, int H, int W, int cch, int taps);
 int pope_conv_layer_f32(const pope_conv_layer_args* args_host, void* stream);
+/* The same struct and the same layer functions for the POPE_PREC_F16 ResNet-FPN (precision must be POPE_PREC_F16), all four
+ * forms.  A chunk is 64 plain f16 columns (value * 8); weights are f16 row-major x 256, tap-major, channels padded to the chunk
+ * (STEM: [N, 128], the 49 taps then zeros; its scratch row holds them the same way).  out_planes and res are F16 ROWS: ldc and
+ * ldres count 4-byte units, i.e. column pairs — ldc = (N rounded up to 64) / 2, the padding columns written as zeros, every value
+ * rounded once as f16(act(acc + bias [+ res]) * 8); 2 ldres >= N and ldres % 32 == 0.  out_f32 (CONV3 only) as in the entry above.
+ * POPE_RANGE_INPUT is ORed into range_flag when a value written as f16 (or a STEM input) does not fit f16 at scale 8 or is not
+ * finite.  Everything else — grids, zero_border, scratch, up_src, the 4 GiB and alignment rules — as above; the whole contract is
+ * checked on the host before any HIP call (POPE_ERR_ARG, a short scratch POPE_ERR_WORKSPACE): res or up_src with the wrong form
+ * (res with CONV1_UP included), out_f32 with another form than CONV3, a misaligned or short buffer. */
+int pope_conv_layer_f16(const pope_conv_layer_args* args_host, void* stream);
 
 /* FinePreprocess.forward — src/matcher/loftr_module/fine_preprocess.py:29-59 (fine_concat_coarse_feat = True), for
  * M > 0 matches: Wn x Wn windows (zero padded by Wn/2) of the 1/2-resolution maps centred on the matched coarse

@@ -212,6 +212,7 @@ PROTOTYPES = {
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_conv_layer_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
     "pope_conv_layer_f32": (C.c_int, [C.POINTER(ConvLayerArgs), C.c_void_p]),
+    "pope_conv_layer_f16": (C.c_int, [C.POINTER(ConvLayerArgs), C.c_void_p]),
     "pope_fine_preprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "pope_fine_preprocess_f32": (C.c_int, [C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 3

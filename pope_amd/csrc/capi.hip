@@ -464,7 +464,14 @@ int pope_conv_layer_f32(const pope_conv_layer_args* args, void* stream) {
     if (!args) return POPE_ERR_ARG;
     if (const int rc = pope_conv_layer_check(*args)) return rc;
     StreamDevice on_device(stream);
-    return pope_launch_conv_layer(*args, static_cast<hipStream_t>(stream));
+    return pope_launch_conv_layer(*args, false, static_cast<hipStream_t>(stream));
+}
+
+int pope_conv_layer_f16(const pope_conv_layer_args* args, void* stream) {
+    if (!args) return POPE_ERR_ARG;
+    if (const int rc = pope_conv_layer_f16_check(*args)) return rc;
+    StreamDevice on_device(stream);
+    return pope_launch_conv_layer(*args, true, static_cast<hipStream_t>(stream));
 }
 
 size_t pope_resnetfpn_workspace_bytes(int n, int H, int W) {

@@ -11,6 +11,9 @@
 // their taps into planes rows first (their outputs are 4x smaller than their inputs), 1x1 convolutions are plain GEMMs
 // over the pixel rows, and the FPN's bilinear x2 (align_corners) + lateral add is the epilogue of the lateral convolution.
 // The GemmParams of every form and the one-layer launch sequences have names (conv_layer.h); pope_launch_conv_layer runs one of them.
+// POPE_PREC_F16 (opt-in, ResNetFPN_8_2.precision = "f16"): the same sequence on plain f16 rows (value * 8, 64-column chunks) and
+// f16 weights (value * 256) — one MFMA per product (gemm_planes.hip PLAIN), every layer output rounded once in its epilogue; same
+// buffers with narrower pitches (kPitchF16), stride-2 layers always gathered, the stem's 49 taps as one chunk plus a zero chunk.
 #include "common.h"
 #include "conv_layer.h"
 #include "kernels.h"
@@ -24,7 +27,10 @@ constexpr float A_SCALE = K_PLANES_ACT_SCALE;
 
 // 7x7 stride-2 pad-3 taps of the gray image as planes rows [n * Hp * Wp, 64] (49 taps, zero-filled to two 32-column
 // chunks), one row per pixel of the zero-bordered H/2 x W/2 output grid (border rows all zero).
-template <bool PLANES>   // false: the fp32 twin (rows of 64 floats, same pitch in bytes)
+// STEM_F16: plain f16 rows, value * 8 — the 49 taps as ONE 64-column chunk; the row keeps the pitch (256 bytes) and its second
+// chunk is written as zeros: the tile kernel's stream wants two K-steps, and the weights' second chunk is zero too
+enum { STEM_F32 = 0, STEM_PLANES = 1, STEM_F16 = 2 };
+template <int FORM>   // STEM_F32: the fp32 twin (rows of 64 floats, same pitch in bytes)
 __global__ __launch_bounds__(256) void stem_gather_kernel(const float* __restrict__ img, _Float16* __restrict__ out,
                                                           int n, int H, int W, unsigned* range_flag) {
     const int Hp = H / 2 + 2, Wp = W / 2 + 2;
@@ -50,7 +56,11 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const float* __restric
             hi[e] = _Float16(s);
             lo[e] = _Float16(s - float(hi[e]));
         }
-        if constexpr (PLANES) {
+        if constexpr (FORM == STEM_F16) {
+            _Float16* o = out + row * 128 + 8 * t;
+            *reinterpret_cast<pope_f16x8*>(o) = hi;
+            *reinterpret_cast<pope_f16x8*>(o + 64) = pope_f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        } else if constexpr (FORM == STEM_PLANES) {
             // its own split and store (the same map as pope_planes_col(8 * t)): through pope_planes_store this kernel measured
             // 3 % slower on its own, see profiles/operand_producers.md
             _Float16* o = out + row * 128 + (t >> 2) * 64 + (t & 3) * 8;
@@ -62,7 +72,7 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const float* __restric
             *reinterpret_cast<f32x4*>(o + 4) = f32x4{raw[4], raw[5], raw[6], raw[7]};
         }
     }
-    if constexpr (PLANES) pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
+    if constexpr (FORM != STEM_F32) pope_range_flag(range_flag, POPE_RANGE_INPUT, !(amax * A_SCALE < POPE_F16_OVERFLOW));
 }
 
 // Stride-2 taps of a zero-bordered planes tensor [n, Hpi, Wpi, cch chunks] as planes rows [n * Hpo * Wpo, taps * cch
@@ -170,6 +180,15 @@ constexpr BufSpec kBufs[NBUF] = {
     {1, 64},  {1, 128}, {1, 128}, {1, 128}, {1, 224}, {1, 224}, {1, 224},
     {2, 1152}, {2, 128}, {2, 224}, {2, 224}, {2, 224}, {2, 256}, {2, 256}, {2, 256}, {2, 224},
     {3, 2016}, {3, 224}, {3, 256}, {3, 256}, {3, 256}};
+// POPE_PREC_F16: the same buffers hold plain f16 rows (value * 8), channels padded to the 64-column chunk (196 -> 256); pitches
+// in column PAIRS, none wider than the planes row it replaces.  The fp32 maps (F1, F2: unused here; X2O) keep theirs.
+constexpr int kPitchF16[NBUF] = {64, 64, 64, 64, 224, 128, 128, 576, 64, 128, 128, 128, 256, 128, 128, 224, 1152, 128, 128, 128, 128};
+constexpr bool f16_rows_fit() {
+    for (int b = 0; b < NBUF; ++b)
+        if (kPitchF16[b] > kBufs[b].pitch) return false;
+    return true;
+}
+static_assert(f16_rows_fit(), "the f16 mode lives in the planes mode's workspace");
 
 // the router of a precision's GEMMs: gemm_f32.hip for POPE_PREC_F32_MFMA, gemm_planes.hip for planes and plain f16
 inline int launch_gemm(int precision, const GemmParams& g, hipStream_t stream) {
@@ -214,9 +233,9 @@ int pope_conv_s2_layer(int precision, const void* x, int x_pitch, const ConvGrid
     return zero_border ? pope_conv_zero_border(out, og, out_pitch, stream) : POPE_OK;
 }
 
-int pope_conv1_up_layer(const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid, const float* up_src,
-                        int up_lds, void* out_pl, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream) {
-    GemmParams g = pope_conv_gemm_params(POPE_PREC_F16X3, a, a_pitch, w, bias, a_pitch, N, grid, false, out_pl, nullptr, out_pitch, slope,
+int pope_conv1_up_layer(int precision, const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid,
+                        const float* up_src, int up_lds, void* out_pl, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream) {
+    GemmParams g = pope_conv_gemm_params(precision, a, a_pitch, w, bias, a_pitch, N, grid, false, out_pl, nullptr, out_pitch, slope,
                                          nullptr, 0, range_flag);
     pope_conv_up_params(g, up_src, up_lds, grid);
     POPE_TRY(pope_launch_gemm_planes(g, stream));
@@ -228,10 +247,13 @@ int pope_conv_stem_layer(int precision, const float* img, int n, int H, int W, v
     const ConvGrid grid = {n, H / 2 + 2, W / 2 + 2};
     const long long total = (long long)grid.rows() * 8;
     if (precision == POPE_PREC_F32_MFMA)
-        hipLaunchKernelGGL(stem_gather_kernel<false>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
+        hipLaunchKernelGGL(stem_gather_kernel<STEM_F32>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
+                           H, W, range_flag);
+    else if (precision == POPE_PREC_F16)
+        hipLaunchKernelGGL(stem_gather_kernel<STEM_F16>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
                            H, W, range_flag);
     else
-        hipLaunchKernelGGL(stem_gather_kernel<true>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
+        hipLaunchKernelGGL(stem_gather_kernel<STEM_PLANES>, dim3(pope_grid_for(total)), dim3(256), 0, stream, img, static_cast<_Float16*>(gathered), n,
                            H, W, range_flag);
     POPE_TRY(pope_check_launch());
     const GemmParams g = pope_conv_gemm_params(precision, gathered, 64, w, bias, 64, N, grid, false, out, nullptr, out_pitch, slope, nullptr, 0,
@@ -250,7 +272,8 @@ size_t pope_resnetfpn_workspace(int n, int H, int W) {
 int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if (!q.img || !q.out_c || !q.out_f || !q.ws || q.n <= 0 || q.H < 16 || q.W < 16 || (q.H & 7) || (q.W & 7)) return POPE_ERR_ARG;
     const bool f32 = q.precision == POPE_PREC_F32_MFMA;
-    if (!f32 && q.precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
+    const bool f16 = q.precision == POPE_PREC_F16;
+    if (!f32 && !f16 && q.precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
     for (int i = 0; i < 22; ++i)
         if (!(f32 ? static_cast<const void*>(q.wf[i]) : q.w[i])) return POPE_ERR_ARG;
     const Plan p = make_plan(q.n, q.H, q.W);
@@ -275,18 +298,19 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     const int prec = q.precision;
     unsigned* const flag = q.range_flag;
     auto wt = [&](int wi) -> const void* { return f32 ? static_cast<const void*>(q.wf[wi]) : q.w[wi]; };
+    auto pitch = [&](int b) -> int { return f16 ? kPitchF16[b] : kBufs[b].pitch; };
     // the layer forms of conv_layer.h on the workspace buffers (one GEMM each, border rows zeroed after a planes output)
     auto conv3 = [&](Buf in, int wi, int N, int level, Buf out, float slope, int res /* Buf or -1 */) -> int {
-        return pope_conv3_layer(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], N, p.grid(level), buf[out], nullptr, kBufs[out].pitch, slope,
-                                res >= 0 ? buf[res] : nullptr, res >= 0 ? kBufs[res].pitch : 0, true, flag, stream);
+        return pope_conv3_layer(prec, buf[in], pitch(in), wt(wi), q.b[wi], N, p.grid(level), buf[out], nullptr, pitch(out), slope,
+                                res >= 0 ? buf[res] : nullptr, res >= 0 ? pitch(res) : 0, true, flag, stream);
     };
     // 3 x 3 or 1 x 1 -> an fp32 map (the FPN's outputs): no border pass
     auto conv3_f32 = [&](Buf in, int wi, int N, int level, float* out, int out_pitch) -> int {
-        return pope_conv3_layer(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], N, p.grid(level), nullptr, out, out_pitch, 1.f, nullptr, 0,
+        return pope_conv3_layer(prec, buf[in], pitch(in), wt(wi), q.b[wi], N, p.grid(level), nullptr, out, out_pitch, 1.f, nullptr, 0,
                                 false, flag, stream);
     };
     auto conv1_f32 = [&](Buf in, int K, int wi, int N, int level, float* out, int out_pitch) -> int {
-        return launch_gemm(prec, pope_conv_gemm_params(prec, buf[in], kBufs[in].pitch, wt(wi), q.b[wi], K, N, p.grid(level), false, nullptr, out,
+        return launch_gemm(prec, pope_conv_gemm_params(prec, buf[in], pitch(in), wt(wi), q.b[wi], K, N, p.grid(level), false, nullptr, out,
                                                        out_pitch, 1.f, nullptr, 0, flag), stream);
     };
     // BasicBlock (resnet_fpn.py:15-40) with stride 1: x -> t -> y; returns with the block output in `y`
@@ -298,10 +322,10 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     // y = relu(conv2(t) + s).  g9 / g1 hold the gathered taps where the implicit route does not serve the call.
     auto block_s2 = [&](Buf x, int level_in, Buf g9, Buf g1, Buf t, Buf s, Buf y, int w0, int N) -> int {
         const int lo = level_in + 1;
-        int r = pope_conv_s2_layer(prec, buf[x], kBufs[x].pitch, p.grid(level_in), 9, wt(w0), q.b[w0], N, buf[g9], buf[t], kBufs[t].pitch, 0.f,
+        int r = pope_conv_s2_layer(prec, buf[x], pitch(x), p.grid(level_in), 9, wt(w0), q.b[w0], N, buf[g9], buf[t], pitch(t), 0.f,
                                    true, flag, stream);
         if (r) return r;
-        r = pope_conv_s2_layer(prec, buf[x], kBufs[x].pitch, p.grid(level_in), 1, wt(w0 + 2), q.b[w0 + 2], N, buf[g1], buf[s], kBufs[s].pitch,
+        r = pope_conv_s2_layer(prec, buf[x], pitch(x), p.grid(level_in), 1, wt(w0 + 2), q.b[w0 + 2], N, buf[g1], buf[s], pitch(s),
                                1.f, false, flag, stream);
         return r ? r : conv3(t, w0 + 1, N, lo, y, 0.f, s);
     };
@@ -316,7 +340,7 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     };
 
     // stem (resnet_fpn.py:60-62,101)
-    if ((rc = pope_conv_stem_layer(prec, q.img, q.n, q.H, q.W, buf[G0], wt(0), q.b[0], 128, buf[P1A], 128, 0.f, flag, stream))) return rc;
+    if ((rc = pope_conv_stem_layer(prec, q.img, q.n, q.H, q.W, buf[G0], wt(0), q.b[0], 128, buf[P1A], pitch(P1A), 0.f, flag, stream))) return rc;
     // layer1 (1/2), layer2 (1/4), layer3 (1/8)
     if ((rc = block_s1(P1A, P1B, P1C, 1, 128, 1))) return rc;
     if ((rc = block_s1(P1C, P1A, P1B, 3, 128, 1))) return rc;             // x1 = P1B
@@ -325,12 +349,14 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if ((rc = block_s2(P2C, 2, G3, D3, P3A, P3C, P3B, 10, 256))) return rc;
     if ((rc = block_s1(P3B, P3A, P3C, 13, 256, 3))) return rc;            // x3 = P3C
     // FPN (resnet_fpn.py:107-117)
-    if ((rc = conv1_f32(P3C, 256, 15, 256, 3, q.out_c, 256))) return rc;                                                   // x3_out
+    if ((rc = conv1_f32(P3C, pitch(P3C), 15, 256, 3, q.out_c, 256))) return rc;                                                   // x3_out
     // f16x3: the lateral 1 x 1 convolution's epilogue adds the bilinear x2 sample of the coarser map and writes the merged planes
     // (round 4: the fp32 lateral map and the upsample_add pass are gone — 1.9 GB of the call's fabric traffic at 48 images); the
-    // fp32 mode keeps the two-step form
+    // fp32 mode keeps the two-step form; the f16 mode runs the plain instantiation of the same epilogue
     if (!f32) {
-        if ((rc = pope_conv1_up_layer(buf[P2C], 224, q.w[16], q.b[16], 256, p.grid(2), q.out_c, 256, buf[T2A], 256, 1.f, flag, stream))) return rc;
+        if ((rc = pope_conv1_up_layer(prec, buf[P2C], pitch(P2C), q.w[16], q.b[16], 256, p.grid(2), q.out_c, 256, buf[T2A], pitch(T2A), 1.f, flag,
+                                      stream)))
+            return rc;
     } else {
         if ((rc = conv1_f32(P2C, 224, 16, 256, 2, reinterpret_cast<float*>(buf[F2]), 256))) return rc;
         if ((rc = upsample_add(F2, q.out_c, 256, T2A, 256, 2))) return rc;
@@ -338,8 +364,8 @@ int pope_launch_resnetfpn(const ResnetFpnParams& q, hipStream_t stream) {
     if ((rc = conv3(T2A, 17, 256, 2, T2B, 0.01f, -1))) return rc;
     if ((rc = conv3_f32(T2B, 18, 196, 2, reinterpret_cast<float*>(buf[X2O]), 224))) return rc;
     if (!f32) {
-        if ((rc = pope_conv1_up_layer(buf[P1B], 128, q.w[19], q.b[19], 196, p.grid(1), reinterpret_cast<const float*>(buf[X2O]), 224, buf[T1A],
-                                      224, 1.f, flag, stream)))
+        if ((rc = pope_conv1_up_layer(prec, buf[P1B], pitch(P1B), q.w[19], q.b[19], 196, p.grid(1), reinterpret_cast<const float*>(buf[X2O]), 224,
+                                      buf[T1A], pitch(T1A), 1.f, flag, stream)))
             return rc;
     } else {
         if ((rc = conv1_f32(P1B, 128, 19, 196, 1, reinterpret_cast<float*>(buf[F1]), 224))) return rc;
@@ -416,8 +442,54 @@ int pope_conv_layer_check(const pope_conv_layer_args& a) {
     return POPE_OK;
 }
 
-int pope_launch_conv_layer(const pope_conv_layer_args& a, hipStream_t stream) {
-    POPE_TRY(pope_conv_layer_check(a));
+// The argument contract of pope_conv_layer_f16 (pope_hip.h has it in words): every form on plain f16 rows.  Pitches (ldc of
+// out_planes, ldres) count column PAIRS, i.e. 4-byte units like every other pitch here; a chunk is 64 columns.
+int pope_conv_layer_f16_check(const pope_conv_layer_args& a) {
+    const int form = a.form;
+    if (form != POPE_CONV3 && form != POPE_CONV_S2 && form != POPE_CONV1_UP && form != POPE_CONV_STEM) return POPE_ERR_ARG;
+    if (a.precision != POPE_PREC_F16) return POPE_ERR_ARG;
+    if (a.n < 1 || a.H < 1 || a.W < 1 || a.N < 4 || (a.N & 3) || a.N > 256) return POPE_ERR_ARG;
+    if (form != POPE_CONV3 && ((a.H | a.W) & 1)) return POPE_ERR_ARG;
+    const bool stem = form == POPE_CONV_STEM, s2 = form == POPE_CONV_S2;
+    if (stem ? a.cch != 0 || a.taps != 0 : a.cch < 1) return POPE_ERR_ARG;
+    if (s2 ? a.taps != 9 && a.taps != 1 : a.taps != 0) return POPE_ERR_ARG;
+    const int taps = form == POPE_CONV3 ? 9 : s2 ? a.taps : 1;
+    if (!stem && taps * a.cch < 2) return POPE_ERR_ARG;                  // the tile kernel's minimum: two K-steps
+    if (!a.a || !a.w || !aligned16(a.a) || !aligned16(a.w) || (a.bias && !aligned16(a.bias))) return POPE_ERR_ARG;
+    const ConvGrid in = {a.n, a.H + 2, a.W + 2};
+    const ConvGrid out = form == POPE_CONV3 || form == POPE_CONV1_UP ? in : in.half();
+    const size_t pitch_in = stem ? 64 : size_t(32) * a.cch;
+    if (!stem && (a.a_rows < in.rows() || !fits32(in.rows(), pitch_in))) return POPE_ERR_ARG;
+    if (stem && size_t(a.n) * a.H * a.W * 4 >= (size_t(1) << 32)) return POPE_ERR_ARG;
+    if (!fits32(256, size_t(taps) * pitch_in)) return POPE_ERR_ARG;      // the weight rows
+    if ((a.out_planes == nullptr) == (a.out_f32 == nullptr)) return POPE_ERR_ARG;
+    if (a.out_planes) {
+        if (a.ldc != ((a.N + 63) & ~63) / 2 || !aligned16(a.out_planes)) return POPE_ERR_ARG;
+    } else {
+        if (form != POPE_CONV3) return POPE_ERR_ARG;                     // the other forms feed the next layer
+        if (a.ldc < a.N || (a.ldc & 3) || !aligned16(a.out_f32)) return POPE_ERR_ARG;
+    }
+    if (!a.zero_border && (stem || (a.out_planes && !s2))) return POPE_ERR_ARG;   // the next layer reads the border as its padding
+    if (!fits32(out.rows(), size_t(a.ldc))) return POPE_ERR_ARG;
+    if (a.res) {
+        if (form != POPE_CONV3 || 2 * a.ldres < a.N || (a.ldres & 31) || !aligned16(a.res)) return POPE_ERR_ARG;
+        if (!fits32(out.rows(), size_t(a.ldres))) return POPE_ERR_ARG;
+    }
+    if (form == POPE_CONV1_UP) {
+        if (!a.up_src || a.up_lds < a.N || (a.up_lds & 3) || !aligned16(a.up_src) || in.Wp < 4) return POPE_ERR_ARG;
+        if (!fits32(in.half().rows(), size_t(a.up_lds))) return POPE_ERR_ARG;
+    } else if (a.up_src) {
+        return POPE_ERR_ARG;
+    }
+    if (s2 || stem) {
+        if (!a.scratch || !aligned16(a.scratch) || !fits32(out.rows(), size_t(taps) * pitch_in)) return POPE_ERR_ARG;
+        if (a.scratch_bytes < pope_conv_layer_scratch(form, a.n, a.H, a.W, a.cch, a.taps)) return POPE_ERR_WORKSPACE;
+    }
+    return POPE_OK;
+}
+
+int pope_launch_conv_layer(const pope_conv_layer_args& a, bool f16_entry, hipStream_t stream) {
+    POPE_TRY(f16_entry ? pope_conv_layer_f16_check(a) : pope_conv_layer_check(a));
     const ConvGrid in = {a.n, a.H + 2, a.W + 2};
     const int pitch = 32 * a.cch;
     switch (a.form) {
@@ -428,7 +500,7 @@ int pope_launch_conv_layer(const pope_conv_layer_args& a, hipStream_t stream) {
             return pope_conv_s2_layer(a.precision, a.a, pitch, in, a.taps, a.w, a.bias, a.N, a.scratch, a.out_planes, a.ldc, a.slope,
                                       a.zero_border != 0, a.range_flag, stream);
         case POPE_CONV1_UP:
-            return pope_conv1_up_layer(a.a, pitch, a.w, a.bias, a.N, in, a.up_src, a.up_lds, a.out_planes, a.ldc, a.slope, a.range_flag, stream);
+            return pope_conv1_up_layer(a.precision, a.a, pitch, a.w, a.bias, a.N, in, a.up_src, a.up_lds, a.out_planes, a.ldc, a.slope, a.range_flag, stream);
         case POPE_CONV_STEM:
             return pope_conv_stem_layer(a.precision, static_cast<const float*>(a.a), a.n, a.H, a.W, a.scratch, a.w, a.bias, a.N,
                                         a.out_planes ? a.out_planes : static_cast<void*>(a.out_f32), a.ldc, a.slope, a.range_flag, stream);

@@ -84,14 +84,15 @@ int pope_conv_zero_border(void* buf, const ConvGrid& grid, int pitch, hipStream_
 int pope_conv3_layer(int precision, const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid, void* out_pl,
                      float* out_f32, int out_pitch, float slope, const void* res, int res_pitch, bool zero_border, unsigned* range_flag,
                      hipStream_t stream);
-// stride 2 (POPE_PREC_F16X3: planes -> planes; POPE_PREC_F32_MFMA: fp32 rows, always gathered): the implicit route where the
-// router serves it, else gather_s2 into `gathered` [in.half(), taps * x_pitch] + a plain GEMM — the same bits; then (zero_border)
-// the border rows.  The implicit route leaves `gathered` untouched and the border rows of `out` undefined.
+// stride 2 (POPE_PREC_F16X3: planes -> planes; POPE_PREC_F32_MFMA: fp32 rows, POPE_PREC_F16: f16 rows, both always gathered):
+// the implicit route where the router serves it, else gather_s2 into `gathered` [in.half(), taps * x_pitch] + a plain GEMM — the
+// same bits; then (zero_border) the border rows.  The implicit route leaves `gathered` untouched and the border rows of `out`
+// undefined.
 int pope_conv_s2_layer(int precision, const void* x, int x_pitch, const ConvGrid& in, int taps, const void* w, const float* bias, int N,
                        void* gathered, void* out, int out_pitch, float slope, bool zero_border, unsigned* range_flag, hipStream_t stream);
-// 1 x 1 lateral convolution with the FPN merge in its epilogue (POPE_PREC_F16X3 only), then the border rows
-int pope_conv1_up_layer(const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid, const float* up_src,
-                        int up_lds, void* out_pl, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream);
+// 1 x 1 lateral convolution with the FPN merge in its epilogue (POPE_PREC_F16X3 or POPE_PREC_F16), then the border rows
+int pope_conv1_up_layer(int precision, const void* a, int a_pitch, const void* w, const float* bias, int N, const ConvGrid& grid,
+                        const float* up_src, int up_lds, void* out_pl, int out_pitch, float slope, unsigned* range_flag, hipStream_t stream);
 // 7 x 7 stride-2 pad-3 stem on the gray image [n, H, W]: stem_gather into `gathered` [grid of H/2 x W/2, 64] + the K = 64 GEMM +
 // the border rows
 int pope_conv_stem_layer(int precision, const float* img, int n, int H, int W, void* gathered, const void* w, const float* bias, int N,
@@ -99,5 +100,7 @@ int pope_conv_stem_layer(int precision, const float* img, int n, int H, int W, v
 
 // The argument contract of pope_conv_layer_f32 (pope_hip.h has it in words; host only: no HIP call) and the call itself
 int pope_conv_layer_check(const pope_conv_layer_args& a);
+// ... and of pope_conv_layer_f16: POPE_PREC_F16 only, all four forms, out_planes / res as f16 rows with pitches in column pairs
+int pope_conv_layer_f16_check(const pope_conv_layer_args& a);
 size_t pope_conv_layer_scratch(int form, int n, int H, int W, int cch, int taps);
-int pope_launch_conv_layer(const pope_conv_layer_args& a, hipStream_t stream);
+int pope_launch_conv_layer(const pope_conv_layer_args& a, bool f16_entry, hipStream_t stream);

@@ -339,7 +339,8 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
         const bool col_ok = col < g.N;
         // EPI_CONV planes rows are wider than N when the channel count is not a multiple of 32 (196 -> 224): the
         // padding columns are the next convolution's K range and must read as zeros
-        const bool col_pad = (EPI == EPI_CONV || EPI == EPI_CONV_UP) && OUT_PLANES && !col_ok && col < g.ldc;
+        // (PLAIN: f16 rows of 2 ldc columns — channels padded to the 64-column chunk, 196 -> 256)
+        const bool col_pad = (EPI == EPI_CONV || EPI == EPI_CONV_UP) && OUT_PLANES && !col_ok && col < (PLAIN ? 2 * g.ldc : g.ldc);
         const int colc = col_ok ? col : 0;
         f32x4 bias = {0.f, 0.f, 0.f, 0.f}, gamma = {0.f, 0.f, 0.f, 0.f};
         if (g.bias) bias = *reinterpret_cast<const f32x4*>(g.bias + colc);
@@ -405,7 +406,15 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 for (int i = 0; i < 8; ++i)
                     sq_dest[i] = __builtin_amdgcn_raw_buffer_load_b32(rmap, (row0 + 4 * i) * 4u, 0, 0) + unsigned(sq_head * g.sam_npad);
             }
-            if constexpr (EPI == EPI_CONV) {   // shortcut rows: (hi + lo) / 8; an empty descriptor (no residual) reads zeros
+            if constexpr (EPI == EPI_CONV && PLAIN) {   // shortcut as f16 rows (value * 8, ldres_pl in column pairs)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned o = (row0 + 4 * i) * unsigned(g.ldres_pl) * 4u + unsigned(col) * 2u;
+                    const f16x4 rh = __builtin_bit_cast(f16x4, __builtin_amdgcn_raw_buffer_load_b64(rresp, col_ok ? o : DROP, 0, 0));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) res[i][e] = float(rh[e]) * (1.0f / A_SCALE);
+                }
+            } else if constexpr (EPI == EPI_CONV) {   // shortcut rows: (hi + lo) / 8; an empty descriptor (no residual) reads zeros
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const unsigned o = (row0 + 4 * i) * unsigned(g.ldres_pl) * 4u + unsigned((col >> 5) * 128 + (col & 31) * 2);
@@ -507,8 +516,13 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_planes16_kernel(const GemmPar
                 if constexpr (OUT_PLANES && PLAIN) {   // f16 row-major, value * 8
                     pope_amax4x2(amax, v);
                     pope_nan_sum4(nsum, v);
-                    const f16x4 h = __builtin_convertvector(v * A_SCALE, f16x4);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), rc, col_ok ? off + unsigned(col) * 2u : DROP, 0, 2);
+                    f16x4 h = __builtin_convertvector(v * A_SCALE, f16x4);   // the one rounding of the value
+                    bool live = col_ok;
+                    if constexpr (EPI == EPI_CONV || EPI == EPI_CONV_UP) {   // the zero channel padding, as the planes rows have it
+                        if (col_pad) h = f16x4{0, 0, 0, 0};
+                        live = col_ok || col_pad;
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), rc, live ? off + unsigned(col) * 2u : DROP, 0, 2);
                 } else if constexpr (OUT_PLANES) {
                     f16x4 hi, lo;
                     pope_amax4x2(amax, v);
@@ -702,12 +716,16 @@ int pope_launch_gemm_planes(const GemmParams& g, hipStream_t stream) {
     if (g.plain && pope_plain256_supported(g)) return pope_launch_plain256(g, stream);   // long-K shapes at large M: gemm_plain.hip
     if (g.epilogue == EPI_SAM_QKV)
         return g.plain ? launch16<EPI_SAM_QKV, true, false, true>(g, stream) : launch16<EPI_SAM_QKV, true, false, false>(g, stream);
-    if (g.plain) {   // single-product f16 (SAM encoder, precision "f16"): the five forms that path uses
+    if (g.plain) {   // single-product f16 (precision "f16" of the encoders): the forms those paths use
         if (g.epilogue == EPI_BIAS && !out_planes) return launch16<EPI_BIAS, false, false, true>(g, stream);
         if (g.epilogue == EPI_BIAS_GELU && out_planes) return launch16<EPI_BIAS_GELU, true, false, true>(g, stream);
         if (g.epilogue == EPI_QKV_F16 && out_planes) return launch16<EPI_QKV_F16, true, false, true>(g, stream);
         if (g.epilogue == EPI_BIAS_LS_RES && !out_planes) return launch16<EPI_BIAS_LS_RES, false, false, true>(g, stream);
-        if (g.epilogue == EPI_CONV && !out_planes && g.conv_cch > 0) return launch16<EPI_CONV, false, true, true>(g, stream);
+        if (g.epilogue == EPI_CONV) {   // the SAM neck's 3 x 3 (fp32 out) and the LoFTR CNN in precision "f16" (conv.hip)
+            if (g.conv_cch > 0) return out_planes ? launch16<EPI_CONV, true, true, true>(g, stream) : launch16<EPI_CONV, false, true, true>(g, stream);
+            if (g.up_src) return launch16<EPI_CONV_UP, true, false, true>(g, stream);
+            return out_planes ? launch16<EPI_CONV, true, false, true>(g, stream) : launch16<EPI_CONV, false, false, true>(g, stream);
+        }
         return POPE_ERR_ARG;
     }
     // large planes -> planes Linears on the LDS-direct mainloops (bit-identical to the tile kernel below): widths that leave a

@@ -60,6 +60,9 @@ def _weights_fit(tensors):
     return amax * _lib.PLANES_W_SCALE < _lib.F16_MAX
 
 
+BACKBONE_PRECISIONS = ("f16x3", "f16")   # ResNetFPN_8_2.precision: the guarded arithmetic of the CNN ("f32" is its re-run only)
+
+
 def _fold_bn(conv_w, bn):
     """Filter and bias of conv -> BatchNorm(eval) as one convolution."""
     g = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
@@ -92,7 +95,13 @@ class BasicBlock(nn.Module):
 
 class ResNetFPN_8_2(nn.Module):
     """resnet_fpn.py:43-118.  [B,1,H,W] -> coarse [B,256,H/8,W/8], fine [B,128,H/2,W/2]: ONE C-ABI call
-    (pope_resnetfpn_forward_f32, conv.hip) — all 22 convolutions as GEMMs over zero-bordered NHWC pixel rows."""
+    (pope_resnetfpn_forward_f32, conv.hip) — all 22 convolutions as GEMMs over zero-bordered NHWC pixel rows.
+
+    `precision` = "f16x3" (default: three f16 MFMAs per product on hi + lo operands) or "f16" (opt-in, also
+    config["precision"]: ONE f16 MFMA per product — activations travel between the layers as f16 at scale 8, weights as f16 at
+    scale 256, fp32 accumulation; every layer rounds its output once, DESIGN.md has the error figures).  Both share the range
+    guard and its policy: a folded filter outside the weight range or a raised range flag re-runs the call on the fp32 MFMA
+    (`on_overflow = "rerun_f32"`) or raises `PopeRangeError` ("raise")."""
 
     def __init__(self, config):
         super().__init__()
@@ -118,6 +127,17 @@ class ResNetFPN_8_2(nn.Module):
         self._hip = None
         self._src = None
         self.on_overflow = None    # None: the module-level ON_OVERFLOW
+        self.precision = config.get("precision") or "f16x3"
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in BACKBONE_PRECISIONS:
+            raise ValueError(f"pope_amd: ResNetFPN_8_2.precision is 'f16x3' or 'f16', got {value!r}")
+        self._precision = value
 
     def invalidate(self):
         self._hip, self._src = None, None
@@ -126,9 +146,10 @@ class ResNetFPN_8_2(nn.Module):
         self._hip, self._src = None, None
         return super()._apply(fn, *a, **k)
 
-    def _matrices(self):
-        """The 22 convolutions in the order of pope_hip.h as fp32 matrices [Cout, taps x Cin rounded up to 32] (tap-major,
-        BatchNorm folded) and their folded biases."""
+    def _matrices(self, chunk=32):
+        """The 22 convolutions in the order of pope_hip.h as fp32 matrices [Cout, taps x Cin rounded up to `chunk`] (tap-major,
+        BatchNorm folded) and their folded biases.  chunk = 64: the plain-f16 mode's K chunk (196 input channels pad to 256 per
+        tap, the stem's 49 taps to 128)."""
         with torch.no_grad():
             convs = [_fold_bn(self.conv1.weight, self.bn1)]
             for layer in (self.layer1, self.layer2, self.layer3):
@@ -142,9 +163,9 @@ class ResNetFPN_8_2(nn.Module):
 
             def mat(w):   # [Cout, Cin, kh, kw] -> [Cout, kh * kw * Cp]
                 co, ci, kh, kw = w.shape
-                if ci == 1:   # the 7x7 stem: 49 taps of one channel, zero-filled to 64 columns
-                    return F.pad(w.reshape(co, kh * kw), (0, 64 - kh * kw))
-                cp = (ci + 31) // 32 * 32
+                if ci == 1:   # the 7x7 stem: 49 taps of one channel, zero-filled to two chunks
+                    return F.pad(w.reshape(co, kh * kw), (0, 2 * chunk - kh * kw))
+                cp = (ci + chunk - 1) // chunk * chunk
                 return F.pad(w.permute(0, 2, 3, 1), (0, cp - ci)).reshape(co, kh * kw * cp)
 
             mats = [mat(w.detach().float()).contiguous() for w, _ in convs]
@@ -152,8 +173,9 @@ class ResNetFPN_8_2(nn.Module):
         return mats, biases
 
     def _weights(self, precision):
-        """ctypes weight struct of one arithmetic mode, cached per parameter version: "f16x3" = weight planes (None when a
-        folded filter leaves the f16x3 weight range), "f32" = the fp32 matrices themselves."""
+        """ctypes weight struct of one arithmetic mode, cached per parameter version: "f16x3" = weight planes, "f16" = plain f16
+        matrices at scale 256 over 64-column chunks (either: None when a folded filter leaves the f16 weight range), "f32" = the
+        fp32 matrices themselves."""
         if self._src is None:
             self._src = _lib.param_slots(self, buffers=True)
         key = _lib.slots_key(self._src)
@@ -162,10 +184,15 @@ class ResNetFPN_8_2(nn.Module):
             self._hip = {"key": key, "mats": mats, "biases": biases, "fit": _weights_fit(mats)}
         ent = self._hip
         if precision not in ent:
-            if precision == "f16x3" and not ent["fit"]:
+            if precision != "f32" and not ent["fit"]:
                 ent[precision] = None
             else:
-                keep = ent["mats"] if precision == "f32" else [_lib.to_planes(m, _lib.PLANES_W_SCALE) for m in ent["mats"]]
+                if precision == "f32":
+                    keep = ent["mats"]
+                elif precision == "f16":
+                    keep = [(m * _lib.PLANES_W_SCALE).half().contiguous() for m in self._matrices(chunk=64)[0]]
+                else:
+                    keep = [_lib.to_planes(m, _lib.PLANES_W_SCALE) for m in ent["mats"]]
                 st = _lib.ResnetFpnWeights()
                 for i in range(22):
                     st.w[i] = keep[i].data_ptr()
@@ -203,11 +230,12 @@ class ResNetFPN_8_2(nn.Module):
     def forward(self, x):
         x = self.checked_input(x)
         policy = self.on_overflow or ON_OVERFLOW
-        if self._weights("f16x3") is None:
+        fast = self.precision
+        if self._weights(fast) is None:
             if policy == "raise":
                 raise PopeRangeError("pope_amd: a folded LoFTR backbone filter is outside the f16x3 weight range (|w| < 255.9)")
             return self._run(x, "f32")[0]
-        out, flag = self._run(x, "f16x3")
+        out, flag = self._run(x, fast)
         bits = _read_flags([flag])
         if bits:
             _overflow("LoFTR backbone", bits, policy)

@@ -255,7 +255,8 @@ class ReferenceEncoding:
     every leading 'self' layer of the coarse transformer ([R, L, 256]); the first 'cross' layer mixes the pair, so nothing
     later can be kept.  The image itself is kept too: the fp32 forms the range guard asks for, and a re-encoding after the
     matcher's weights changed or moved (the encoding carries `_lib.slots_key` of the matcher's parameters and buffers), are built
-    from it on the next use.  Forms are held per arithmetic mode ("f16x3" / "f32") of the backbone and of the transformer, each
+    from it on the next use.  Forms are held per arithmetic mode of the backbone ("f16x3" / "f16" / "f32") and of the
+    transformer ("f16x3" / "f32"), each
     with the range bits it raised; at 256 x 256 a form is ~8.7 MB fine map + 2 x 1 MB coarse map per reference."""
 
     def __init__(self, matcher, image0):
@@ -266,7 +267,7 @@ class ReferenceEncoding:
         if self.image is image0:
             self.image = image0.clone()   # the caller may overwrite theirs
         self.key, self._bb, self._lead = None, {}, {}
-        self.mode = None   # the backbone arithmetic a call reads this encoding in ("f16x3" | "f32"), set when it is built
+        self.mode = None   # the backbone arithmetic a call reads this encoding in (the backbone's `precision` | "f32"), set when it is built
         self._fresh()
 
     R = property(lambda self: int(self.image.shape[0]))
@@ -293,7 +294,7 @@ class ReferenceEncoding:
         whose bits are raised holds nothing usable ('cpos' None)."""
         if precision not in self._bb:
             maps, flag = self._matcher.backbone._run(self.image, precision)
-            self._put_backbone(precision, maps, int(flag.item()) if precision == "f16x3" else 0)
+            self._put_backbone(precision, maps, int(flag.item()) if precision != "f32" else 0)
         return self._bb[precision]
 
     def leading(self, bb_precision, precision):
@@ -364,7 +365,7 @@ class Matcher(nn.Module):
         # in-place version, so a stale graph is simply never looked up again
         if self._gsrc is None:
             self._gsrc = _lib.param_slots(self, buffers=True)
-        key = (tuple(im0.shape), tuple(im1.shape), im0.device.index, _lib.slots_key(self._gsrc))
+        key = (tuple(im0.shape), tuple(im1.shape), im0.device.index, _lib.slots_key(self._gsrc), self.backbone.precision)
         ent = self._graphs.get(key)
         if ent is None:
             if len(self._graphs) >= 16:   # every graph owns its workspaces: keep the set small
@@ -419,16 +420,17 @@ class Matcher(nn.Module):
         return ref
 
     def _reference_backbone(self, ref):
-        """The backbone mode a call reads `ref` in, by `ResNetFPN_8_2.forward`'s rules for the reference images alone (weights
-        outside the f16x3 range, or a raised flag: fp32), and its bits.  The leading 'self' layers are built with it."""
+        """The backbone mode a call reads `ref` in, by `ResNetFPN_8_2.forward`'s rules for the reference images alone (the
+        backbone's `precision`; weights outside the f16 range, or a raised flag: fp32), and its bits.  The leading 'self' layers
+        are built with it."""
         ref._fresh()
         bb = self.backbone
         bits = 0
-        if bb._weights("f16x3") is None:
+        if bb._weights(bb.precision) is None:
             mode = "f32"
         else:
-            bits = ref.backbone("f16x3")["bits"]
-            mode = "f32" if bits else "f16x3"
+            bits = ref.backbone(bb.precision)["bits"]
+            mode = "f32" if bits else bb.precision
         ref.mode = mode
         if all(l._weights("f16x3") is not None for l in self.loftr_coarse.layers):
             if ref.leading(mode, "f16x3")[1]:
@@ -465,7 +467,8 @@ class Matcher(nn.Module):
         bb = self.backbone
         policy = bb.on_overflow or loftr.ON_OVERFLOW
         x1 = bb.checked_input(im1)
-        fits = bb._weights("f16x3") is not None
+        fast = bb.precision   # "f16x3" | "f16": the reference images and the crops of one call are read in one mode
+        fits = bb._weights(fast) is not None
         if not fits and policy == "raise":
             raise PopeRangeError("pope_amd: a folded LoFTR backbone filter is outside the f16x3 weight range (|w| < 255.9)")
         crops = None
@@ -473,7 +476,7 @@ class Matcher(nn.Module):
             ref = ReferenceEncoding(self, data["image0"])
             if ref.hw_i == x1.shape[2:]:   # the encoding is built inside the call: one launch sequence for R + n images
                 both = torch.cat([ref.image, x1], 0)
-                mode = "f16x3" if fits else "f32"
+                mode = fast if fits else "f32"
                 maps, flag = bb._run(both, mode)
                 if fits:
                     bits = loftr._read_flags([flag])
@@ -487,8 +490,8 @@ class Matcher(nn.Module):
         same = ref.hw_i == x1.shape[2:]
         if crops is None:
             mode, rbits = self._reference_backbone(ref)
-            if same and mode == "f16x3":
-                crops, flag = bb._run(x1, "f16x3")
+            if same and mode == fast:
+                crops, flag = bb._run(x1, fast)
                 cbits = loftr._read_flags([flag])
                 if cbits:
                     loftr._overflow("LoFTR backbone", cbits, policy)
