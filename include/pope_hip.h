@@ -1102,6 +1102,71 @@ int pope_mocope_add_ln_f32(float* X, const float* Y, const float* w1, const floa
 int pope_mocope_ffn76_f32(float* X, const float* l1w, const float* l1b, const float* l2w, const float* l2b, const float* nw,
                           const float* nb, const float* fw, const float* fb, int R, void* stream);
 
+/* ---- Vision Mamba backbone (pose/vim/models_mamba.py:VisionMamba; mixer after the Mamba and Vim papers) -------- */
+
+/* One direction of a bidirectional ("v2") mixer, device pointers, fp32: conv_w [E, 4] (Conv1d(E, E, 4, groups = E) weight
+ * [E, 1, 4] as it lies), conv_b [E], x_proj_w [R + 32, E] (rows dt | B | C), dt_w [E, R], dt_b [E], A_log [E, 16], D [E]. */
+typedef struct pope_vim_dir_weights {
+    const float *conv_w, *conv_b, *x_proj_w, *dt_w, *dt_b, *A_log, *D;
+} pope_vim_dir_weights;
+
+/* One Block: norm_w [D] (RMSNorm, no bias), in_proj_w [2E, D], out_proj_w [D, E] (nn.Linear layout, no bias); in_proj_wp /
+ * out_proj_wp the same matrices as weight planes (POPE_PREC_F16X3 only); dir[0] the forward, dir[1] the backward (`_b`) set. */
+typedef struct pope_vim_layer_weights {
+    const float *norm_w, *in_proj_w, *out_proj_w;
+    const void *in_proj_wp, *out_proj_wp;
+    pope_vim_dir_weights dir[2];
+} pope_vim_layer_weights;
+
+/* img: side of the square image (a multiple of 8); patch 16; stride 8 or 16; dim D (a multiple of 64, <= 512); E = 2 D,
+ * d_state 16, d_conv 4, dt_rank R = ceil(D / 16).  patch_w [D, 768] (the Conv2d weight as it lies), patch_wp its weight planes
+ * (POPE_PREC_F16X3), patch_b [D], cls [D], pos [L, D] with L = g g + 1, g = (img - 16) / stride + 1: the class token sits at
+ * row (g g) / 2.  layers_host: HOST array of `depth` layers.  norm_f_w [D]; head_w [num_classes, D], head_b: read when logits
+ * are asked for (num_classes % 4 == 0). */
+typedef struct pope_vim_weights {
+    int img, stride, dim, depth, num_classes;
+    float eps;
+    const float *patch_w, *patch_b, *cls, *pos;
+    const void* patch_wp;
+    const pope_vim_layer_weights* layers_host;
+    const float *norm_f_w, *head_w, *head_b;
+} pope_vim_weights;
+
+/* VisionMamba.forward_features / forward (eval mode) for image [B, 3, img, img] fp32.  precision POPE_PREC_F32_MFMA, or
+ * POPE_PREC_F16X3: patch embedding, in_proj and out_proj on f16x3 planes (operands written as planes by the gather, the
+ * add + RMSNorm and the scan), x_proj and the head split their fp32 operands in the K loop where the shape allows it and run
+ * on the fp32 MFMA where not; conv1d, dt_proj, the scan and the norms are fp32 in both.  range_flag (device word, may be NULL)
+ * collects POPE_RANGE_PATCH, POPE_RANGE_LAYERNORM (norm output), POPE_RANGE_GELU (scan output) and POPE_RANGE_INPUT; the
+ * caller re-runs with POPE_PREC_F32_MFMA when it is set.  Nothing in the call depends on B: an image's result is the same
+ * bits alone or in a batch.  features [B, D] and logits [B, num_classes] are each optional; taps: NULL or a HOST array of 4
+ * device pointers (each may be NULL), [B, L, D] each: the token matrix, and hidden + residual after layers 0,
+ * depth / 2 - 1 and depth - 1.  Workspace >= pope_vim_workspace_bytes(w, B) (0: bad arguments), 256-byte aligned.  Every bad
+ * argument is POPE_ERR_ARG (a short workspace POPE_ERR_WORKSPACE), returned before the device is touched. */
+size_t pope_vim_workspace_bytes(const pope_vim_weights* w, int B);
+int pope_vim_forward_f32(const pope_vim_weights* w, const float* image, int B, int precision, void* workspace,
+                         size_t workspace_bytes, float* features, float* logits, float* const* taps, unsigned* range_flag,
+                         void* stream);
+/* The launches one by one (tests).  Null pointers and sizes <= 0 are POPE_ERR_ARG, a short workspace POPE_ERR_WORKSPACE.
+ * scan: both directions of one layer.  xc [2, B L, E] (the conv1d outputs of the two directions), z [B L] rows of pitch ldz,
+ * xdbl [2, B L, R + 32] (x_proj outputs), dirs: HOST array of 2 (dt_w, dt_b, A_log, D are read); exactly one of out_f32
+ * [B L, E] and out_planes (activation planes, POPE_RANGE_GELU): (o_fwd + o_bwd) / 2.  E % 16 == 0, R % 4 == 0, R <= 32.
+ * The sequence is cut into chunks of pope_vim_scan_chunk() steps whose states are carried in chunk order. */
+int pope_vim_scan_chunk(void);
+size_t pope_vim_scan_workspace_bytes(int B, int L, int E);
+int pope_vim_scan_f32(const float* xc, const float* z, int ldz, const float* xdbl, const pope_vim_dir_weights* dirs, int B, int L,
+                      int E, int R, float* out_f32, void* out_planes, void* workspace, size_t workspace_bytes,
+                      unsigned* range_flag, void* stream);
+/* xc [2, B L, E]: xc[0] = silu(causal conv1d of x; dirs[0]), xc[1] = silu(anti-causal conv1d; dirs[1]): the backward
+ * direction's convolution in un-reversed time.  x [B L] rows of pitch ldx (the first E columns of xz).  Any L >= 1. */
+int pope_vim_conv1d_silu_f32(const float* x, int ldx, const pope_vim_dir_weights* dirs, int B, int L, int E, float* xc,
+                             void* stream);
+/* r = hidden [+ res_in]; res_out = r (optional); y = r * rsqrt(mean(r^2) + eps) * w as fp32 rows or activation planes (exactly
+ * one; planes: D % 32 == 0, POPE_RANGE_LAYERNORM).  Input row i is row i * row_stride + row_offset of hidden / res_in /
+ * res_out, output row i is row i of y.  D % 4 == 0, D <= 2048. */
+int pope_vim_add_rmsnorm_f32(const float* hidden, const float* res_in, float* res_out, const float* w, float* y_f32,
+                             void* y_planes, long long rows, int D, float eps, long long row_stride, long long row_offset,
+                             unsigned* range_flag, void* stream);
+
 /* ---- host-side helper ------------------------------------------------------------------------ */
 
 /* Streaming top-3 proposal vote — eval_linemod_json.py:71,95-101 (HOST pointers): slots start at

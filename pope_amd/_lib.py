@@ -125,6 +125,20 @@ class ConvNextWeights(C.Structure):
         ("blocks_host", C.POINTER(ConvNextBlockWeights))] + [(n, C.c_void_p) for n in ("norm_w", "norm_b", "head_w", "head_b", "ones")]
 
 
+class VimDirWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("conv_w", "conv_b", "x_proj_w", "dt_w", "dt_b", "A_log", "D")]
+
+
+class VimLayerWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("norm_w", "in_proj_w", "out_proj_w", "in_proj_wp", "out_proj_wp")] + [("dir", VimDirWeights * 2)]
+
+
+class VimWeights(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("img", "stride", "dim", "depth", "num_classes")] + [("eps", C.c_float)] + [
+        (n, C.c_void_p) for n in ("patch_w", "patch_b", "cls", "pos", "patch_wp")] + [("layers_host", C.POINTER(VimLayerWeights))] + [
+        (n, C.c_void_p) for n in ("norm_f_w", "head_w", "head_b")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pope_hip.h
 PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
@@ -287,6 +301,16 @@ PROTOTYPES = {
     "pope_convnext_grn_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_convnext_grn_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_convnext_pose_heads_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "pope_vim_workspace_bytes": (C.c_size_t, [C.POINTER(VimWeights), C.c_int]),
+    "pope_vim_forward_f32": (C.c_int, [C.POINTER(VimWeights), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "pope_vim_scan_chunk": (C.c_int, []),
+    "pope_vim_scan_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "pope_vim_scan_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(VimDirWeights)] + [C.c_int] * 4
+                          + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_vim_conv1d_silu_f32": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VimDirWeights), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_vim_add_rmsnorm_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_int, C.c_float, C.c_longlong, C.c_longlong, C.c_void_p,
+                                                              C.c_void_p]),
     "pope_five_point_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_streaming_top3_host": (C.c_int, [c_float_p, C.c_int, c_float_p, c_ll_p]),
     "pope_vote_top3_batch_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5 + [C.c_void_p]),

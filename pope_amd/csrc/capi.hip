@@ -967,6 +967,47 @@ int pope_five_point_f64(const double* x0, const double* x1, int S, double* E_out
     return pope_launch_five_point(x0, x1, S, E_out, n_out, static_cast<hipStream_t>(stream));
 }
 
+// ---- Vision Mamba backbone (vim.hip) ------------------------------------------------------------------------------------------
+
+size_t pope_vim_workspace_bytes(const pope_vim_weights* w, int B) { return pope_vim_workspace(w, B); }
+
+int pope_vim_forward_f32(const pope_vim_weights* w, const float* image, int B, int precision, void* workspace, size_t workspace_bytes,
+                         float* features, float* logits, float* const* taps, unsigned* range_flag, void* stream) {
+    VimArgs a = {};
+    a.w = w; a.image = image; a.B = B; a.precision = precision; a.features = features; a.logits = logits; a.taps = taps;
+    a.ws = workspace; a.ws_bytes = workspace_bytes; a.range_flag = range_flag;
+    POPE_TRY(pope_vim_check(a));
+    StreamDevice on_device(stream);
+    return pope_launch_vim(a, static_cast<hipStream_t>(stream));
+}
+
+int pope_vim_scan_chunk(void) { return pope_vim_scan_chunk_len(); }
+
+size_t pope_vim_scan_workspace_bytes(int B, int L, int E) { return pope_vim_scan_workspace(B, L, E); }
+
+int pope_vim_scan_f32(const float* xc, const float* z, int ldz, const float* xdbl, const pope_vim_dir_weights* dirs, int B, int L, int E,
+                      int R, float* out_f32, void* out_planes, void* workspace, size_t workspace_bytes, unsigned* range_flag,
+                      void* stream) {
+    POPE_TRY(pope_vim_scan_check(xc, z, ldz, xdbl, dirs, B, L, E, R, out_f32, out_planes, workspace, workspace_bytes));
+    StreamDevice on_device(stream);
+    return pope_launch_vim_scan(xc, z, ldz, xdbl, dirs, B, L, E, R, out_f32, out_planes, workspace, range_flag, static_cast<hipStream_t>(stream));
+}
+
+int pope_vim_conv1d_silu_f32(const float* x, int ldx, const pope_vim_dir_weights* dirs, int B, int L, int E, float* xc, void* stream) {
+    POPE_TRY(pope_vim_conv1d_check(x, ldx, dirs, B, L, E, xc));
+    StreamDevice on_device(stream);
+    return pope_launch_vim_conv1d(x, ldx, dirs, B, L, E, xc, static_cast<hipStream_t>(stream));
+}
+
+int pope_vim_add_rmsnorm_f32(const float* hidden, const float* res_in, float* res_out, const float* w, float* y_f32, void* y_planes,
+                             long long rows, int D, float eps, long long row_stride, long long row_offset, unsigned* range_flag,
+                             void* stream) {
+    POPE_TRY(pope_vim_add_rmsnorm_check(hidden, w, y_f32, y_planes, rows, D, eps, row_stride, row_offset));
+    StreamDevice on_device(stream);
+    return pope_launch_vim_add_rmsnorm(hidden, res_in, res_out, w, y_f32, y_planes, rows, D, eps, row_stride, row_offset, range_flag,
+                                       static_cast<hipStream_t>(stream));
+}
+
 // ---- MoCoPE fusion pose model (mocope.hip) ------------------------------------------------------------------------------------
 
 size_t pope_mocope_workspace_bytes(int B, int S) { return pope_mocope_workspace(B, S); }

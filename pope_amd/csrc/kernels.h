@@ -593,3 +593,31 @@ int pope_launch_convnext_grn(const float* x, const float* gamma, const float* be
                              void* ws, unsigned* range_flag, hipStream_t stream);
 int pope_launch_convnext_pose_heads(const float* feat, const float* trans_w, const float* trans_b, const float* rot_w,
                                     const float* rot_b, int mode, int B, int inner, float* trans, float* rot, hipStream_t stream);
+
+// Vision Mamba backbone (vim.hip; pose/vim/models_mamba.py:VisionMamba): the arguments of pope_vim_forward_f32 and of the
+// op-level entries.  The *_check functions make no HIP call.
+struct VimArgs {
+    const pope_vim_weights* w;
+    const float* image;
+    int B, precision;
+    float *features, *logits;
+    float* const* taps;
+    void* ws; size_t ws_bytes;
+    unsigned* range_flag;
+};
+size_t pope_vim_workspace(const pope_vim_weights* w, int B);   // 0: bad weights or geometry
+int pope_vim_check(const VimArgs& a);
+int pope_launch_vim(const VimArgs& a, hipStream_t stream);
+int pope_vim_scan_chunk_len();
+size_t pope_vim_scan_workspace(int B, int L, int E);
+int pope_vim_scan_check(const float* xc, const float* z, int ldz, const float* xdbl, const pope_vim_dir_weights* dirs, int B, int L, int E,
+                        int R, const float* out_f32, const void* out_planes, const void* ws, size_t ws_bytes);
+int pope_launch_vim_scan(const float* xc, const float* z, int ldz, const float* xdbl, const pope_vim_dir_weights* dirs, int B, int L, int E,
+                         int R, float* out_f32, void* out_planes, void* ws, unsigned* range_flag, hipStream_t stream);
+int pope_vim_conv1d_check(const float* x, int ldx, const pope_vim_dir_weights* dirs, int B, int L, int E, const float* xc);
+int pope_launch_vim_conv1d(const float* x, int ldx, const pope_vim_dir_weights* dirs, int B, int L, int E, float* xc, hipStream_t stream);
+int pope_vim_add_rmsnorm_check(const float* hidden, const float* w, const float* y_f32, const void* y_planes, long long rows, int D, float eps,
+                               long long row_stride, long long row_offset);
+int pope_launch_vim_add_rmsnorm(const float* hidden, const float* res_in, float* res_out, const float* w, float* y_f32, void* y_planes,
+                                long long rows, int D, float eps, long long row_stride, long long row_offset, unsigned* range_flag,
+                                hipStream_t stream);

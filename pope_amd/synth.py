@@ -998,3 +998,100 @@ def mocope_case(num_sample, n_pairs):
     g = torch.Generator().manual_seed(11000 + 100 * int(num_sample) + int(n_pairs))
     shape = (int(n_pairs), 3, MOCOPE_IMAGE, MOCOPE_IMAGE)
     return d0, d1, torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+
+
+# ---- Vision Mamba (pope_amd/vim.py; tests/golden/vim.npz) ------------------------------------------------------------------------
+VIM_TINY = dict(embed_dim=192, depth=24)
+VIM_SMALL = dict(embed_dim=384, depth=24)
+# name -> (width settings, stride, img_size, num_classes, B, seed).  small_s8 is the fork's default
+# (vim_small_patch16_stride8_224_..., L = 730); small_s8_64: 7 x 7 patches, L = 50, shorter than one scan chunk
+VIM_CASES = {"tiny_s16": (VIM_TINY, 16, 224, 100, 2, 0), "small_s8": (VIM_SMALL, 8, 224, 1000, 2, 1),
+             "small_s16": (VIM_SMALL, 16, 224, 100, 1, 2), "small_s8_64": (VIM_SMALL, 8, 64, 100, 3, 3)}
+VIM_TAPS = ("tokens", "layer0", "layer11", "layer23", "features", "logits")
+VIM_TAP_SAMPLES = 1024          # entries kept of a tap wider than that, at seeded flat positions
+VIM_D_STATE, VIM_D_CONV = 16, 4
+
+
+def vim_geometry(img_size, stride):
+    """(g, L, class-token row) of a square image: g = (img - 16) // stride + 1 patches per side, L = g g + 1 tokens."""
+    g = (img_size - 16) // stride + 1
+    return g, g * g + 1, (g * g) // 2
+
+
+def vim_keys(embed_dim, depth, num_classes, img_size=224, stride=16):
+    """State-dict keys of the four registered `VisionMamba` factories' configuration with their shapes, in the reference's order:
+    a module's own parameters come before its children's, so a mixer lists A_log, D, A_b_log, D_b first."""
+    d, e, n = embed_dim, 2 * embed_dim, VIM_D_STATE
+    r = -(-d // 16)
+    _, L, _ = vim_geometry(img_size, stride)
+    keys = [("cls_token", (1, 1, d)), ("pos_embed", (1, L, d)), ("patch_embed.proj.weight", (d, 3, 16, 16)), ("patch_embed.proj.bias", (d,)),
+            ("head.weight", (num_classes, d)), ("head.bias", (num_classes,))]
+    for i in range(depth):
+        p = f"layers.{i}.mixer."
+        keys += [(p + "A_log", (e, n)), (p + "D", (e,)), (p + "A_b_log", (e, n)), (p + "D_b", (e,)), (p + "in_proj.weight", (2 * e, d)),
+                 (p + "conv1d.weight", (e, 1, VIM_D_CONV)), (p + "conv1d.bias", (e,)), (p + "x_proj.weight", (r + 2 * n, e)),
+                 (p + "dt_proj.weight", (e, r)), (p + "dt_proj.bias", (e,)), (p + "conv1d_b.weight", (e, 1, VIM_D_CONV)),
+                 (p + "conv1d_b.bias", (e,)), (p + "x_proj_b.weight", (r + 2 * n, e)), (p + "dt_proj_b.weight", (e, r)),
+                 (p + "dt_proj_b.bias", (e,)), (p + "out_proj.weight", (d, e)), (f"layers.{i}.norm.weight", (d,))]
+    keys += [("norm_f.weight", (d,))]
+    return keys
+
+
+def _vim_tensor(k, shape, gen):
+    leaf = k.split(".")[-1] if k.split(".")[-1] not in ("weight", "bias") else ".".join(k.split(".")[-2:])
+    if leaf in ("A_log", "A_b_log"):        # A = -(1 .. 16) f, f per channel in [0.5, 2] (log-uniform)
+        f = torch.exp(torch.rand(shape[0], 1, generator=gen) * math.log(4.0) + math.log(0.5))
+        return torch.log(torch.arange(1, shape[1] + 1, dtype=torch.float32)[None, :] * f)
+    if leaf in ("D", "D_b"):
+        return 1.0 + 0.3 * torch.randn(shape, generator=gen)
+    if leaf in ("dt_proj.bias", "dt_proj_b.bias"):   # softplus^-1 of log-uniform [1e-3, 1e-1]
+        dt = torch.exp(torch.rand(shape, generator=gen) * (math.log(0.1) - math.log(1e-3)) + math.log(1e-3))
+        return dt + torch.log(-torch.expm1(-dt))
+    if leaf in ("conv1d.weight", "conv1d_b.weight"):
+        return 0.5 * torch.randn(shape, generator=gen)
+    if leaf in ("cls_token", "pos_embed"):
+        return torch.randn(shape, generator=gen)
+    if leaf in ("dt_proj.weight", "dt_proj_b.weight"):
+        return torch.randn(shape, generator=gen) * (2.0 / shape[1] ** 0.5)
+    if leaf == "out_proj.weight":           # the gated scan output has an rms of about 8 (long memories: delta |A| is small)
+        return torch.randn(shape, generator=gen) * (0.12 / shape[1] ** 0.5)
+    if len(shape) >= 2:                     # in_proj, x_proj, patch kernel, head: 1.5 / sqrt(fan_in)
+        return torch.randn(shape, generator=gen) * (1.5 / math.prod(shape[1:]) ** 0.5)
+    if leaf.endswith("bias"):
+        return 0.2 * torch.randn(shape, generator=gen)
+    return 1.0 + 0.3 * torch.randn(shape, generator=gen)    # RMSNorm gains
+
+
+def vim_state_dict(embed_dim, depth, num_classes, img_size=224, stride=16, seed=0):
+    """Seeded weights with every term of the mixer alive (the reference's init leaves out_proj at 1 / sqrt(depth) of a 0.02
+    branch): A = -(1 .. 16) f with f in [0.5, 2] per channel, dt_proj.bias the inverse softplus of log-uniform [1e-3, 1e-1],
+    D = 1 + 0.3 N, conv taps 0.5 N, pos_embed / cls_token N, the `_b` tensors drawn after and independently of the forward
+    ones, matrices scaled so that a block's mixer output is of order 1 against an order-1 residual."""
+    g = torch.Generator().manual_seed(9000 + seed)
+    return {k: _vim_tensor(k, s, g) for k, s in vim_keys(embed_dim, depth, num_classes, img_size, stride)}
+
+
+def vim_case(name):
+    """One case of tests/golden/vim.npz: dict(cfg (VisionMamba keyword arguments), state_dict, x [B, 3, S, S])."""
+    width, stride, img, ncls, B, seed = VIM_CASES[name]
+    g = torch.Generator().manual_seed(9500 + seed)
+    cfg = dict(width, stride=stride, img_size=img, num_classes=ncls)
+    return {"cfg": cfg, "state_dict": vim_state_dict(width["embed_dim"], width["depth"], ncls, img, stride, seed=seed),
+            "x": torch.randn(B, 3, img, img, generator=g)}
+
+
+def vim_tap_index(name, tap, numel):
+    """Flat positions of a tap the fixture keeps: all of it up to VIM_TAP_SAMPLES entries, else that many seeded positions."""
+    if numel <= VIM_TAP_SAMPLES:
+        return torch.arange(numel)
+    g = torch.Generator().manual_seed(9800 + sum(map(ord, name + tap)))
+    return torch.randperm(numel, generator=g)[:VIM_TAP_SAMPLES].sort().values
+
+
+def vim_pos_embed_checkpoint(embed_dim=384, orig_size=14, num_classes=1000, seed=0):
+    """A seeded stand-in for a released Vim checkpoint as the `Vim` loader sees it: {'model': {pos_embed of a 14 x 14 grid + class
+    token, head.* of `num_classes`}}; the other keys are left to the model's own values (the loader is strict=False)."""
+    g = torch.Generator().manual_seed(9900 + seed)
+    return {"model": {"pos_embed": torch.randn(1, orig_size * orig_size + 1, embed_dim, generator=g),
+                      "head.weight": torch.randn(num_classes, embed_dim, generator=g) * 0.05,
+                      "head.bias": torch.randn(num_classes, generator=g) * 0.05}}
