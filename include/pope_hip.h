@@ -389,6 +389,22 @@ int pope_loftr_encoder_layer_full_f32(const pope_loftr_layer_weights* w_host, fl
 int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L, int S, int C, int nhead, int precision,
                                   float* out, unsigned* range_flag, void* stream);
 
+/* The LINEAR attention core of pope_loftr_encoder_layer_f32 / _masked_f32 alone, by the layer's own launches: q[n L, C],
+ * kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32; x_mask[n,L] / source_mask[n,S] as in the masked layer, each may be
+ * NULL.  Exactly one output: out_f32[n L, C] fp32 rows (what the layer computes under POPE_PREC_F32_MFMA), or out_planes
+ * [n L, C] activation planes (scale 8; what it computes under POPE_PREC_F16X3), which ORs POPE_RANGE_INPUT into range_flag
+ * (may be NULL) when a scaled value leaves the f16 range.  The per-head state is summed over the source rows in chunks of
+ * `chunk_rows` rows, the partial sums in chunk order; a workgroup of the message kernel serves `rows_per_block` query rows
+ * (pope_loftr_linear_attention_seams).  workspace: 256-byte aligned, pope_loftr_linear_attention_workspace_bytes (0 for
+ * non-positive sizes, C not 128 / 256 or nhead != 8).  POPE_ERR_ARG before any HIP call: null q / kv / workspace,
+ * non-positive sizes, C not 128 / 256, nhead != 8, both outputs or none, a misaligned workspace, n L or n S beyond the
+ * layer's index range (2^31 / 2C rows); POPE_ERR_WORKSPACE for a short workspace. */
+size_t pope_loftr_linear_attention_workspace_bytes(int n, int S, int C, int nhead);
+void pope_loftr_linear_attention_seams(int* chunk_rows, int* rows_per_block);
+int pope_loftr_linear_attention_f32(const float* q, const float* kv, const float* x_mask, const float* source_mask,
+                                    int n, int L, int S, int C, int nhead, float* out_f32, void* out_planes,
+                                    void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
+
 /* ResNetFPN_8_2.forward — src/matcher/backbone/resnet_fpn.py:100-118 (BasicBlock :15-40), eval mode: the LoFTR
  * matcher's local-feature CNN.  gray[n,1,H,W] in [0,1], H and W multiples of 8.  Every convolution is an f16x3 planes
  * GEMM over zero-bordered NHWC activations (3x3 stride 1: implicit, no im2col; pope_amd/csrc/conv.hip); eval-mode

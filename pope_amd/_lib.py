@@ -221,6 +221,9 @@ PROTOTYPES = {
     "pope_loftr_encoder_layer_full_f32": (C.c_int, [C.POINTER(LoftrLayerWeights), C.c_void_p, C.c_void_p] + [C.c_int] * 5
                                           + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_loftr_full_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pope_loftr_linear_attention_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "pope_loftr_linear_attention_seams": (None, [c_int_p, c_int_p]),
+    "pope_loftr_linear_attention_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_resnetfpn_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_resnetfpn_forward_f32": (C.c_int, [C.POINTER(ResnetFpnWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

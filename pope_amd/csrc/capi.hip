@@ -454,6 +454,22 @@ int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L,
     return pope_launch_loftr_full_attention(q, kv, n, L, S, C, nhead, false, out, range_flag, static_cast<hipStream_t>(stream));
 }
 
+size_t pope_loftr_linear_attention_workspace_bytes(int n, int S, int C, int nhead) {
+    return pope_loftr_linear_attention_workspace(n, S, C, nhead);
+}
+
+void pope_loftr_linear_attention_seams(int* chunk_rows, int* rows_per_block) { pope_loftr_linattn_seams(chunk_rows, rows_per_block); }
+
+int pope_loftr_linear_attention_f32(const float* q, const float* kv, const float* x_mask, const float* source_mask, int n, int L, int S,
+                                    int C, int nhead, float* out_f32, void* out_planes, void* workspace, size_t workspace_bytes,
+                                    unsigned* range_flag, void* stream) {
+    // checked before the stream's device is touched: a refused call makes no HIP call
+    POPE_TRY(pope_loftr_linear_attention_check(q, kv, n, L, S, C, nhead, out_f32, out_planes, workspace, workspace_bytes));
+    StreamDevice on_device(stream);
+    return pope_launch_loftr_linear_attention(q, kv, x_mask, source_mask, n, L, S, C, nhead, out_f32, out_planes, workspace, workspace_bytes,
+                                              range_flag, static_cast<hipStream_t>(stream));
+}
+
 // one layer of the ResNet-FPN forward (or the SAM neck's 3 x 3) through the layer functions the models call (conv_layer.h);
 // checked before the stream's device is touched
 size_t pope_conv_layer_scratch_bytes(int form, int n, int H, int W, int cch, int taps) {

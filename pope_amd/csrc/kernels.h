@@ -382,6 +382,16 @@ int pope_launch_fine_match_scaled(const float* win0, const float* win1, int M, i
                                   const float* scale1, const long long* b_ids, float* expec, float* mkpts1_f, hipStream_t stream);
 size_t pope_loftr_layer_workspace(int n, int L, int S, int C, int H);
 int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream);
+// The layer's linear attention alone (the same launches): q [n L, C], kv [n S, 2C] (k | v) fp32 -> the message as fp32 rows
+// (out_f32) or as activation planes (out_planes; POPE_RANGE_INPUT on a value outside the f16 range); exactly one of the two.
+// ws: 256-byte aligned, pope_loftr_linear_attention_workspace bytes (0 for bad sizes).  The check makes no HIP call.
+void pope_loftr_linattn_seams(int* chunk_rows, int* rows_per_block);
+size_t pope_loftr_linear_attention_workspace(int n, int S, int C, int H);
+int pope_loftr_linear_attention_check(const void* q, const void* kv, int n, int L, int S, int C, int H, const void* out_f32,
+                                      const void* out_planes, const void* ws, size_t ws_bytes);
+int pope_launch_loftr_linear_attention(const float* q, const float* kv, const float* x_mask, const float* source_mask, int n, int L, int S,
+                                       int C, int H, float* out_f32, void* out_planes, void* ws, size_t ws_bytes, unsigned* range_flag,
+                                       hipStream_t stream);
 
 // SAM image encoder (sam.hip; segment_anything/segment_anything/modeling/image_encoder.py:17-118): the arguments of
 // pope_sam_encoder_forward_f32.  The weights are read from the ABI's struct as it is (pope_hip.h: what every `*_wp` holds per precision).

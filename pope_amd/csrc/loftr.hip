@@ -21,6 +21,7 @@
 namespace {
 
 constexpr int LA_CHUNK = 64;   // source rows per workgroup of the KV reduction
+constexpr int LA_ROWS_PER_BLOCK = 16;   // query rows per workgroup of the apply kernel
 
 // elu(x) + 1 as torch evaluates it in fp32: x > 0 ? x : exp(x) - 1, then + 1 (two roundings on the negative side)
 __device__ __forceinline__ float elu1(float x) { return (x > 0.f ? x : expf(x) - 1.0f) + 1.0f; }
@@ -219,6 +220,67 @@ __global__ __launch_bounds__(256) void ln_add_kernel(float* __restrict__ x, cons
 
 }  // namespace
 
+// The linear attention of one layer update (steps 3 and 4 of pope_launch_loftr_layer) and of the op-level entry: the chunk
+// partials of KV / Ksum, their sum in chunk order, then the message row by row.  part: [n H, chunks, D D + D], kvf: [n H, D D + D].
+// planes: the message leaves as activation planes (and range_flag is raised on a value outside the f16 range), else as fp32 rows.
+static void linattn_launch(const float* q, const float* kv, const float* x_mask, const float* source_mask, int n, int L, int S, int C, int H,
+                           bool planes, float* dst, float* part, float* kvf, unsigned* range_flag, hipStream_t stream) {
+    const int D = C / H, chunks = (S + LA_CHUNK - 1) / LA_CHUNK, per = D * D + D;
+    // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
+#define LA_REDUCE(DD, MK) hipLaunchKernelGGL((linattn_reduce_kernel<DD, MK>), dim3(n * H, chunks), dim3(256), 0, stream, kv, S, C, H, 0.f, \
+                                             part, chunks, source_mask)
+    if (source_mask) { if (D == 32) LA_REDUCE(32, true); else LA_REDUCE(16, true); }
+    else { if (D == 32) LA_REDUCE(32, false); else LA_REDUCE(16, false); }
+#undef LA_REDUCE
+    hipLaunchKernelGGL(linattn_finish_kernel, dim3(n * H, (per + 255) / 256), dim3(256), 0, stream, part, chunks, per, kvf);
+    const int rpb = LA_ROWS_PER_BLOCK;
+#define LA_APPLY(DD, PL, MK, DST) hipLaunchKernelGGL((linattn_apply_kernel<DD, PL, MK>), dim3(n, (L + rpb - 1) / rpb), dim3(256), 0, stream, q, \
+                                                     kvf, L, C, H, S, 1e-6f, DST, rpb, range_flag, x_mask)
+#define LA_APPLY_D(PL, MK, DST) do { if (D == 32) LA_APPLY(32, PL, MK, DST); else LA_APPLY(16, PL, MK, DST); } while (0)
+    if (!planes) {
+        if (x_mask) LA_APPLY_D(false, true, dst); else LA_APPLY_D(false, false, dst);
+    } else {
+        if (x_mask) LA_APPLY_D(true, true, dst); else LA_APPLY_D(true, false, dst);
+    }
+#undef LA_APPLY_D
+#undef LA_APPLY
+}
+
+void pope_loftr_linattn_seams(int* chunk_rows, int* rows_per_block) {
+    if (chunk_rows) *chunk_rows = LA_CHUNK;
+    if (rows_per_block) *rows_per_block = LA_ROWS_PER_BLOCK;
+}
+
+size_t pope_loftr_linear_attention_workspace(int n, int S, int C, int H) {
+    if (n <= 0 || S <= 0 || (C != 256 && C != 128) || H != 8) return 0;
+    const size_t D = C / H, chunks = (S + LA_CHUNK - 1) / LA_CHUNK;
+    return pope_align256(size_t(n) * H * chunks * (D * D + D) * 4) + pope_align256(size_t(n) * H * (D * D + D) * 4);
+}
+
+int pope_loftr_linear_attention_check(const void* q, const void* kv, int n, int L, int S, int C, int H, const void* out_f32,
+                                      const void* out_planes, const void* ws, size_t ws_bytes) {
+    if (!q || !kv || !ws || n <= 0 || L <= 0 || S <= 0 || (C != 256 && C != 128) || H != 8) return POPE_ERR_ARG;
+    if ((out_f32 != nullptr) == (out_planes != nullptr)) return POPE_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return POPE_ERR_ARG;
+    const size_t rx = size_t(n) * L, rs = size_t(n) * S;
+    if (rx > 0x7fffffffull / (2 * C) || rs > 0x7fffffffull / (2 * C)) return POPE_ERR_ARG;   // the layer's index range
+    if (ws_bytes < pope_loftr_linear_attention_workspace(n, S, C, H)) return POPE_ERR_WORKSPACE;
+    return POPE_OK;
+}
+
+int pope_launch_loftr_linear_attention(const float* q, const float* kv, const float* x_mask, const float* source_mask, int n, int L, int S,
+                                       int C, int H, float* out_f32, void* out_planes, void* ws, size_t ws_bytes, unsigned* range_flag,
+                                       hipStream_t stream) {
+    POPE_TRY(pope_loftr_linear_attention_check(q, kv, n, L, S, C, H, out_f32, out_planes, ws, ws_bytes));
+    const int D = C / H, chunks = (S + LA_CHUNK - 1) / LA_CHUNK, per = D * D + D;
+    pope_carver carve{static_cast<char*>(ws)};
+    float* part = carve.take<float>(size_t(n) * H * chunks * per * 4);
+    float* kvf = carve.take<float>(size_t(n) * H * per * 4);
+    linattn_launch(q, kv, x_mask, source_mask, n, L, S, C, H, out_planes != nullptr, out_planes ? static_cast<float*>(out_planes) : out_f32, part,
+                   kvf, range_flag, stream);
+    return pope_check_launch();
+}
+
 size_t pope_loftr_layer_workspace(int n, int L, int S, int C, int H) {
     const size_t rx = size_t(n) * L, rs = size_t(n) * S, D = C / H, chunks = (S + LA_CHUNK - 1) / LA_CHUNK;
     return pope_align256(rx * C * 4) /*xp*/ + pope_align256(rs * C * 4) /*sp*/ + pope_align256(rx * C * 4) /*q, later merge out*/ + pope_align256(rs * 2 * C * 4) /*kv*/ +
@@ -288,27 +350,9 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
         if (f32) msgp = msg;
         POPE_TRY(pope_launch_loftr_full_attention(q, kv, p.n, p.L, p.S, C, H, !f32, static_cast<float*>(msgp), p.range_flag, stream));
     } else {
-        // 3. per-head state, 4. message
-        // (padding masks, LoFTREncoderLayer's x_mask / source_mask: separate instantiations, the unmasked ones are unchanged)
-#define LA_REDUCE(DD, MK) hipLaunchKernelGGL((linattn_reduce_kernel<DD, MK>), dim3(p.n * H, chunks), dim3(256), 0, stream, kv, p.S, C, H, 0.f, \
-                                             part, chunks, p.source_mask)
-        if (p.source_mask) { if (D == 32) LA_REDUCE(32, true); else LA_REDUCE(16, true); }
-        else { if (D == 32) LA_REDUCE(32, false); else LA_REDUCE(16, false); }
-#undef LA_REDUCE
-        hipLaunchKernelGGL(linattn_finish_kernel, dim3(p.n * H, (per + 255) / 256), dim3(256), 0, stream, part, chunks, per, kvf);
-        const int rpb = 16;
-        // (f16x3: the message is written as planes straight away; fp32 mode: plain rows)
-#define LA_APPLY(DD, PL, MK, DST) hipLaunchKernelGGL((linattn_apply_kernel<DD, PL, MK>), dim3(p.n, (p.L + rpb - 1) / rpb), dim3(256), 0, stream, q, \
-                                                     kvf, p.L, C, H, p.S, 1e-6f, DST, rpb, p.range_flag, p.x_mask)
-#define LA_APPLY_D(PL, MK, DST) do { if (D == 32) LA_APPLY(32, PL, MK, DST); else LA_APPLY(16, PL, MK, DST); } while (0)
-        if (f32) {
-            if (p.x_mask) LA_APPLY_D(false, true, msg); else LA_APPLY_D(false, false, msg);
-            msgp = msg;
-        } else {
-            if (p.x_mask) LA_APPLY_D(true, true, static_cast<float*>(msgp)); else LA_APPLY_D(true, false, static_cast<float*>(msgp));
-        }
-#undef LA_APPLY_D
-#undef LA_APPLY
+        // 3. per-head state, 4. message (f16x3: the message is written as planes straight away; fp32 mode: plain rows)
+        if (f32) msgp = msg;
+        linattn_launch(q, kv, p.x_mask, p.source_mask, p.n, p.L, p.S, C, H, !f32, static_cast<float*>(msgp), part, kvf, p.range_flag, stream);
     }
     // 5. merge (-> q buffer), 6. cat[x, LN1(merge)] as planes
     POPE_TRY(gemm(msgp, Wm, q, nullptr, int(rx), C, C, EPI_BIAS));
