@@ -664,6 +664,43 @@ int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w_host, 
                                         int n_sparse, const float* dense, long long dense_stride, int multimask, float* masks,
                                         float* iou, void* workspace, size_t workspace_bytes, unsigned* range_flag,
                                         void* stream);
+/* The decoder's kernels one at a time, as the decoder launches them (for tests that compare one kernel with a reference).  All
+ * pointers are DEVICE pointers except slot_host (HOST [P]: entry p selects which block of a strided buffer prompt p reads; every
+ * entry >= 0).  T = tokens per prompt, 1 .. max_tokens; P = prompts of the launch, 1 .. chunk (self-attention, linear: no such
+ * limit).  The image side is always 4 096 tokens.  Each entry returns POPE_ERR_ARG before any launch for a NULL pointer, a size
+ * out of range, a buffer read as float4 that is not 16-byte aligned or a stride that is no multiple of 4 floats.
+ *   seams: chunk = prompts per pass over the image side, lin_rows = rows per workgroup of the token linear, max_tokens,
+ *     base_tokens = iou token + mask tokens (T = base_tokens + n_sparse).
+ *   token_linear: Y[m, n] = act(sum_k X'[m, k] W[n, k] + bias[n]) (+ res[m, n]); X' = X + add for the columns n < add_cols (add
+ *     may be NULL), X otherwise; rows of X and add have pitch ldx >= K, rows of Y and res pitch ldy >= N; K % 4 == 0, W 16-byte
+ *     aligned; the staged rows (lin_rows x K floats, twice with add) must fit 64 KiB of LDS.
+ *   self_attention: qkv[P T, 768] = q | k | v (8 heads of 32) -> out[P T, 256].
+ *   t2i_attention: q[P T, 128] against the 4 096 keys K + slot[p] * kps (rows of pitch ldk >= 128) and values V + slot[p] * vps
+ *     (rows of 128), 8 heads of 16 -> out[P T, 128].
+ *   i2t_attention: the 4 096 queries Q + slot[p] * qps (rows of 256, the first 128 columns read) against kv[P T, 256] = k | v ->
+ *     [P 4096, 128] as fp32 rows or activation planes (exactly one; planes: POPE_RANGE_QKV).
+ *   residual_norm: keys[p, n] = LayerNorm(res[slot[p] * rps + n] + y[p, n]) * w + b over 256 columns; f32 != 0: opB = fp32
+ *     keys + pe_t[n]; else opA = planes(keys), opB = planes(keys + pe_t[n]) (POPE_RANGE_LAYERNORM).
+ *   prepare_keys: keys[z] = (image + z * image_stride + dense + z * dense_stride)^T for z < nz <= chunk ([256, 4096] ->
+ *     [4096, 256]), pe_t = image_pe^T, and the operands as above.
+ *   upscale_tail: y[P 4096, 256] (the first ConvTranspose's output, column tap * 64 + channel) -> LayerNorm2d(eps), GELU, second
+ *     ConvTranspose w2[128, 64] + b2[32], GELU, dot with hyper[P, 4, 32] -> masks[P, 3 or 1, 256, 256] (multimask: masks 1..3). */
+void pope_sam_decoder_seams(int* chunk, int* lin_rows, int* max_tokens, int* base_tokens);
+int pope_sam_decoder_token_linear_f32(const float* X, int ldx, const float* add, int add_cols, const float* W, const float* bias,
+                                      const float* res, float* Y, int ldy, int M, int N, int K, int relu, void* stream);
+int pope_sam_decoder_self_attention_f32(const float* qkv, float* out, int P, int T, void* stream);
+int pope_sam_decoder_t2i_attention_f32(const float* q, const float* K, int ldk, long long kps, const float* V, long long vps,
+                                       const int* slot_host, float* out, int T, int P, void* stream);
+int pope_sam_decoder_i2t_attention_f32(const float* Q, long long qps, const int* slot_host, const float* kv, int T, int P,
+                                       float* out_f32, void* out_planes, unsigned* range_flag, void* stream);
+int pope_sam_decoder_residual_norm_f32(const float* res, long long rps, const int* slot_host, const float* y, const float* w,
+                                       const float* b, float eps, const float* pe_t, float* keys, void* opA, void* opB, int f32,
+                                       int P, unsigned* range_flag, void* stream);
+int pope_sam_decoder_prepare_keys_f32(const float* image, long long image_stride, const float* image_pe, const float* dense,
+                                      long long dense_stride, int nz, float* keys, void* opA, void* opB, int f32, float* pe_t,
+                                      unsigned* range_flag, void* stream);
+int pope_sam_decoder_upscale_tail_f32(const float* y, const float* ln_w, const float* ln_b, float eps, const float* w2,
+                                      const float* b2, const float* hyper, int multimask, int P, float* masks, void* stream);
 
 /* ---- SAM prompt encoder: mask prompts --------------------------------------------------------------------------- */
 

@@ -254,6 +254,20 @@ PROTOTYPES = {
     "pope_sam_decoder_forward_images_f32": (C.c_int, [C.POINTER(SamDecoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                       c_int_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int]
                                             + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_sam_decoder_seams": (None, [c_int_p] * 4),
+    "pope_sam_decoder_token_linear_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 5
+                                          + [C.c_void_p]),
+    "pope_sam_decoder_self_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pope_sam_decoder_t2i_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, c_int_p,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pope_sam_decoder_i2t_attention_f32": (C.c_int, [C.c_void_p, C.c_longlong, c_int_p, C.c_void_p, C.c_int, C.c_int]
+                                           + [C.c_void_p] * 4),
+    "pope_sam_decoder_residual_norm_f32": (C.c_int, [C.c_void_p, C.c_longlong, c_int_p] + [C.c_void_p] * 3 + [C.c_float]
+                                           + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_sam_decoder_prepare_keys_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int]
+                                          + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
+    "pope_sam_decoder_upscale_tail_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p,
+                                                                                                         C.c_void_p]),
     "pope_sam_mask_embed_f32": (C.c_int, [C.POINTER(SamMaskEmbedWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_sam_postprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pope_sam_postprocess_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_double]

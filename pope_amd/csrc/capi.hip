@@ -615,6 +615,57 @@ int pope_sam_decoder_forward_images_f32(const pope_sam_decoder_weights* w, const
     return pope_launch_sam_decoder(a, static_cast<hipStream_t>(stream));
 }
 
+// the decoder's kernels one at a time: the launchers check every argument before their launch
+void pope_sam_decoder_seams(int* chunk, int* lin_rows, int* max_tokens, int* base_tokens) {
+    pope_sam_decoder_seam_values(chunk, lin_rows, max_tokens, base_tokens);
+}
+
+int pope_sam_decoder_token_linear_f32(const float* X, int ldx, const float* add, int add_cols, const float* W, const float* bias,
+                                      const float* res, float* Y, int ldy, int M, int N, int K, int relu, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_token_linear(X, ldx, add, add_cols, W, bias, res, Y, ldy, M, N, K, relu, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_self_attention_f32(const float* qkv, float* out, int P, int T, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_self_attention(qkv, out, P, T, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_t2i_attention_f32(const float* q, const float* K, int ldk, long long kps, const float* V, long long vps,
+                                       const int* slot_host, float* out, int T, int P, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_t2i_attention(q, K, ldk, kps, V, vps, slot_host, out, T, P, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_i2t_attention_f32(const float* Q, long long qps, const int* slot_host, const float* kv, int T, int P,
+                                       float* out_f32, void* out_planes, unsigned* range_flag, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_i2t_attention(Q, qps, slot_host, kv, T, P, out_f32, out_planes, range_flag,
+                                                 static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_residual_norm_f32(const float* res, long long rps, const int* slot_host, const float* y, const float* w,
+                                       const float* b, float eps, const float* pe_t, float* keys, void* opA, void* opB, int f32, int P,
+                                       unsigned* range_flag, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_residual_norm(res, rps, slot_host, y, w, b, eps, pe_t, keys, opA, opB, f32, P, range_flag,
+                                                 static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_prepare_keys_f32(const float* image, long long image_stride, const float* image_pe, const float* dense,
+                                      long long dense_stride, int nz, float* keys, void* opA, void* opB, int f32, float* pe_t,
+                                      unsigned* range_flag, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_prepare_keys(image, image_stride, image_pe, dense, dense_stride, nz, keys, opA, opB, f32, pe_t,
+                                                range_flag, static_cast<hipStream_t>(stream));
+}
+
+int pope_sam_decoder_upscale_tail_f32(const float* y, const float* ln_w, const float* ln_b, float eps, const float* w2, const float* b2,
+                                      const float* hyper, int multimask, int P, float* masks, void* stream) {
+    StreamDevice on_device(stream);
+    return pope_launch_sam_decoder_upscale_tail(y, ln_w, ln_b, eps, w2, b2, hyper, multimask, P, masks, static_cast<hipStream_t>(stream));
+}
+
 int pope_sam_mask_embed_f32(const pope_sam_mask_embed_weights* w, const float* masks, int P, float* dense, void* stream) {
     if (const int rc = pope_sam_mask_embed_check(w, masks, P, dense)) return rc;   // before any HIP call
     StreamDevice on_device(stream);

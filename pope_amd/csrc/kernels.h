@@ -487,6 +487,23 @@ size_t pope_sam_decoder_workspace(const pope_sam_decoder_weights* w, int P, int 
 size_t pope_sam_decoder_images_workspace(const pope_sam_decoder_weights* w, int n_images, const int* prompt_image, int P, int n_sparse,
                                          long long dense_stride);
 int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream);
+// its kernels one at a time (pope_sam_decoder_*_f32): POPE_ERR_ARG on the host before the launch; slot_host: HOST [P]
+void pope_sam_decoder_seam_values(int* chunk, int* lin_rows, int* max_tokens, int* base_tokens);
+int pope_launch_sam_decoder_token_linear(const float* X, int ldx, const float* add, int add_cols, const float* W, const float* bias,
+                                         const float* res, float* Y, int ldy, int M, int N, int K, int relu, hipStream_t stream);
+int pope_launch_sam_decoder_self_attention(const float* qkv, float* out, int P, int T, hipStream_t stream);
+int pope_launch_sam_decoder_t2i_attention(const float* q, const float* K, int ldk, long long kps, const float* V, long long vps,
+                                          const int* slot_host, float* out, int T, int P, hipStream_t stream);
+int pope_launch_sam_decoder_i2t_attention(const float* Q, long long qps, const int* slot_host, const float* kv, int T, int P,
+                                          float* out_f32, void* out_planes, unsigned* range_flag, hipStream_t stream);
+int pope_launch_sam_decoder_residual_norm(const float* res, long long rps, const int* slot_host, const float* y, const float* w,
+                                          const float* b, float eps, const float* pe_t, float* keys, void* opA, void* opB, int f32,
+                                          int P, unsigned* range_flag, hipStream_t stream);
+int pope_launch_sam_decoder_prepare_keys(const float* image, long long image_stride, const float* image_pe, const float* dense,
+                                         long long dense_stride, int nz, float* keys, void* opA, void* opB, int f32, float* pe_t,
+                                         unsigned* range_flag, hipStream_t stream);
+int pope_launch_sam_decoder_upscale_tail(const float* y, const float* ln_w, const float* ln_b, float eps, const float* w2,
+                                         const float* b2, const float* hyper, int multimask, int P, float* masks, hipStream_t stream);
 
 // SAM prompt encoder, mask prompts (sam_prompt.hip): pope_sam_mask_embed_f32
 int pope_sam_mask_embed_check(const pope_sam_mask_embed_weights* w, const float* masks, int P, const float* dense);   // no HIP call

@@ -490,10 +490,7 @@ int gemm(const Ctx& c, const void* A, const void* W, const float* bias, float* C
 
 int lin(const Ctx& c, const float* X, int ldx, const float* add, int add_cols, const float* W, const float* b, const float* res,
         float* Y, int ldy, int M, int N, int K, bool relu) {
-    const size_t lds = size_t(LIN_ROWS) * K * (add ? 2 : 1) * sizeof(float);
-    hipLaunchKernelGGL(sd_lin_kernel, dim3((N + 255) / 256, (M + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, c.s, X, ldx, add, ldx,
-                       add_cols, W, b, res, ldy, Y, ldy, M, N, K, relu ? 1 : 0);
-    return pope_check_launch();
+    return pope_launch_sam_decoder_token_linear(X, ldx, add, add_cols, W, b, res, Y, ldy, M, N, K, relu ? 1 : 0, c.s);
 }
 
 int ln_tok(const Ctx& c, const float* x, float* out, const float* w, const float* b, float eps, int rows) {
@@ -504,6 +501,39 @@ int ln_tok(const Ctx& c, const float* x, float* out, const float* w, const float
 int t2i(const Ctx& c, const float* q, const float* K, int ldk, long long kps, const float* V, long long vps, const SdImageOf& im,
         float* out, int T, int np) {
     hipLaunchKernelGGL(sd_t2i_attn_kernel, dim3(HEADS, np), dim3(256), 0, c.s, q, K, ldk, kps, V, vps, im, out, T);
+    return pope_check_launch();
+}
+
+int self_attn(const Ctx& c, const float* qkv, float* out, int T, int np) {
+    hipLaunchKernelGGL(sd_self_attn_kernel, dim3(HEADS, np), dim3(64), 0, c.s, qkv, out, T, __builtin_sqrtf(float(HDS)));
+    return pope_check_launch();
+}
+
+// out: planes [np * 4096, 128], or fp32 (c.f32)
+int i2t(const Ctx& c, const float* Q, long long qps, const SdImageOf& im, const float* kv, int T, void* out, int np) {
+    hipLaunchKernelGGL(sd_i2t_attn_kernel, dim3(NPIX / 32, np), dim3(256), 0, c.s, Q, qps, im, kv, T, out, c.f32 ? 1 : 0, c.flag);
+    return pope_check_launch();
+}
+
+int res_ln(const Ctx& c, const float* res, long long rps, const SdImageOf& im, const float* y, const float* w, const float* b, float eps,
+           const float* pe_t, float* keys, void* opA, void* opB, int np) {
+    const int rows = np * NPIX;
+    hipLaunchKernelGGL(sd_res_ln_kernel, dim3(rows / 4), dim3(256), 0, c.s, res, rps, im, y, w, b, eps, pe_t, keys, opA, opB,
+                       c.f32 ? 1 : 0, rows, c.flag);
+    return pope_check_launch();
+}
+
+int prep(const Ctx& c, const float* img, long long is, const float* pe, const float* dense, long long ds, float* keys, void* opA,
+         void* opB, float* pe_t, int nz) {
+    hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, nz), dim3(256), 0, c.s, img, is, pe, dense, ds, keys, opA, opB,
+                       c.f32 ? 1 : 0, pe_t, c.flag);
+    return pope_check_launch();
+}
+
+int tail(const Ctx& c, const float* y, const float* lnw, const float* lnb, float eps, const float* w2, const float* b2,
+         const float* hyper, bool multimask, int np, float* masks) {
+    const int C = multimask ? NMASK - 1 : 1, m0 = multimask ? 1 : 0;
+    hipLaunchKernelGGL(sd_tail_kernel, dim3(NPIX * 4 / 256, np), dim3(256), 0, c.s, y, lnw, lnb, eps, w2, b2, hyper, m0, C, masks);
     return pope_check_launch();
 }
 
@@ -572,7 +602,6 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
     const Buffers B = carve(static_cast<char*>(a.ws), cp_max, T, shared ? NI : 0, &need);
     if (a.ws_bytes < need) return POPE_ERR_WORKSPACE;
     const Ctx c{w->precision == POPE_PREC_F32_MFMA, a.range_flag, stream};
-    const int f32 = c.f32 ? 1 : 0;
     const float teps = w->token_eps, ueps = w->up_eps;
     const int C = a.multimask ? NMASK - 1 : 1, m0 = a.multimask ? 1 : 0;
     const size_t img = size_t(NPIX) * D;
@@ -587,9 +616,7 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
         float* keys0 = B.keys0 + o;
         void* opA0 = static_cast<float*>(B.opA0) + o;   // planes of [rows, 256]: 4 bytes per element, like fp32
         void* opB0 = static_cast<float*>(B.opB0) + o;
-        hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, ni), dim3(256), 0, stream, a.image + o, (long long)img, a.image_pe,
-                           a.dense, 0LL, keys0, opA0, opB0, f32, B.pe_t, a.range_flag);
-        POPE_TRY(pope_check_launch());
+        POPE_TRY(prep(c, a.image + o, (long long)img, a.image_pe, a.dense, 0LL, keys0, opA0, opB0, B.pe_t, ni));
         const void* A0 = c.f32 ? static_cast<const void*>(keys0) : opA0;
         POPE_TRY(gemm(c, opB0, w->layers_host[0].img_qk_wp, w->layers_host[0].img_qk_b, B.qk0 + o, ni * NPIX, D, D));
         POPE_TRY(gemm(c, A0, w->layers_host[0].img_v_wp, w->layers_host[0].img_v_b, B.v0 + ov, ni * NPIX, DI, D));
@@ -602,11 +629,8 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(sd_tokens_kernel, dim3((R * D + 255) / 256), dim3(256), 0, stream, w->tokens,
                            a.n_sparse ? a.sparse + size_t(pg0) * a.n_sparse * D : nullptr, a.n_sparse, T, R, B.qry, B.tpe);
         POPE_TRY(pope_check_launch());
-        if (!shared) {
-            hipLaunchKernelGGL(sd_prep_kernel, dim3(NPIX / 32, D / 32, cp), dim3(256), 0, stream, a.image, 0LL, a.image_pe,
-                               a.dense + pg0 * a.dense_stride, a.dense_stride, B.keys, B.opA, B.opB, f32, B.pe_t, a.range_flag);
-            POPE_TRY(pope_check_launch());
-        }
+        if (!shared)
+            POPE_TRY(prep(c, a.image, 0LL, a.image_pe, a.dense + pg0 * a.dense_stride, a.dense_stride, B.keys, B.opA, B.opB, B.pe_t, cp));
         for (int l = 0; l < 2; ++l) {
             const pope_sam_decoder_layer_weights& L = w->layers_host[l];
             const float *qk = B.qk, *v = B.v, *res = B.keys;
@@ -621,8 +645,7 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
             }
             // self-attention; layer 0 (skip_first_layer_pe): no pe, and its output replaces the queries
             POPE_TRY(lin(c, B.qry, D, l ? B.tpe : nullptr, 2 * D, L.sa_qkv_w, L.sa_qkv_b, nullptr, B.tqkv, 3 * D, R, 3 * D, D, false));
-            hipLaunchKernelGGL(sd_self_attn_kernel, dim3(HEADS, cp), dim3(64), 0, stream, B.tqkv, B.tatt, T, __builtin_sqrtf(float(HDS)));
-            POPE_TRY(pope_check_launch());
+            POPE_TRY(self_attn(c, B.tqkv, B.tatt, T, cp));
             POPE_TRY(lin(c, B.tatt, D, nullptr, 0, L.sa_o_w, L.sa_o_b, l ? B.qry : nullptr, B.tmp, D, R, D, D, false));
             POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm1_w, L.norm1_b, teps, R));
             // tokens -> image
@@ -636,13 +659,9 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
             POPE_TRY(ln_tok(c, B.tmp, B.qry, L.norm3_w, L.norm3_b, teps, R));
             // image -> tokens: k from tokens + pe, v from tokens
             POPE_TRY(lin(c, B.qry, D, B.tpe, DI, L.i2t_kv_w, L.i2t_kv_b, nullptr, B.tkv, D, R, D, D, false));
-            hipLaunchKernelGGL(sd_i2t_attn_kernel, dim3(NPIX / 32, cp), dim3(256), 0, stream, qk + DI, qps, im, B.tkv, T,
-                               static_cast<void*>(B.att), f32, a.range_flag);
-            POPE_TRY(pope_check_launch());
+            POPE_TRY(i2t(c, qk + DI, qps, im, B.tkv, T, B.att, cp));
             POPE_TRY(gemm(c, B.att, L.i2t_o_wp, L.i2t_o_b, B.y, rows, D, DI));
-            hipLaunchKernelGGL(sd_res_ln_kernel, dim3(rows / 4), dim3(256), 0, stream, res, rps, im, B.y, L.norm4_w, L.norm4_b, teps, B.pe_t,
-                               B.keys, B.opA, B.opB, f32, rows, a.range_flag);
-            POPE_TRY(pope_check_launch());
+            POPE_TRY(res_ln(c, res, rps, im, B.y, L.norm4_w, L.norm4_b, teps, B.pe_t, B.keys, B.opA, B.opB, cp));
         }
         // final token -> image attention: k into qk (ld 128), v into v
         POPE_TRY(gemm(c, B.opB, w->fin_k_wp, w->fin_k_b, B.qk, rows, DI, D));
@@ -670,9 +689,98 @@ int pope_launch_sam_decoder(const SamDecArgs& a, hipStream_t stream) {
                    D, false));
         // upscaling: first ConvTranspose as a GEMM (N = 4 taps x 64), then the fused tail
         POPE_TRY(gemm(c, opA, w->up1_wp, w->up1_b, B.y, rows, D, D));
-        hipLaunchKernelGGL(sd_tail_kernel, dim3(NPIX * 4 / 256, cp), dim3(256), 0, stream, B.y, w->up_ln_w, w->up_ln_b, ueps, w->up2_w,
-                           w->up2_b, B.hyper, m0, C, a.masks + size_t(pg0) * C * (16 * NPIX));
-        POPE_TRY(pope_check_launch());
+        POPE_TRY(tail(c, B.y, w->up_ln_w, w->up_ln_b, ueps, w->up2_w, w->up2_b, B.hyper, a.multimask != 0, cp,
+                      a.masks + size_t(pg0) * C * (16 * NPIX)));
     }
     return POPE_OK;
+}
+
+// ---- the kernels one at a time (pope_sam_decoder_*_f32): every argument is checked on the host before the launch ----------
+namespace {
+
+bool al16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool stride_ok(long long s) { return s >= 0 && s % 4 == 0; }   // rows read as f32x4
+bool tokens_ok(int T, int P) { return T >= 1 && T <= MAX_T && P >= 1 && P <= CHUNK; }
+
+// slot_host [P] -> the kernel argument; false: null or a negative slot
+bool slots(const int* slot_host, int P, SdImageOf* im) {
+    if (!slot_host) return false;
+    *im = SdImageOf{};
+    for (int p = 0; p < P; ++p) {
+        if (slot_host[p] < 0) return false;
+        im->i[p] = slot_host[p];
+    }
+    return true;
+}
+
+constexpr size_t LIN_LDS_LIMIT = 64 * 1024;   // dynamic LDS of a launch without an opt-in attribute
+
+}  // namespace
+
+void pope_sam_decoder_seam_values(int* chunk, int* lin_rows, int* max_tokens, int* base_tokens) {
+    if (chunk) *chunk = CHUNK;
+    if (lin_rows) *lin_rows = LIN_ROWS;
+    if (max_tokens) *max_tokens = MAX_T;
+    if (base_tokens) *base_tokens = NBASE;
+}
+
+// lin()'s convention: ADD rows have the pitch of X, residual rows the pitch of Y
+int pope_launch_sam_decoder_token_linear(const float* X, int ldx, const float* add, int add_cols, const float* W, const float* bias,
+                                         const float* res, float* Y, int ldy, int M, int N, int K, int relu, hipStream_t stream) {
+    if (!X || !al16(W) || !bias || !Y || M <= 0 || N <= 0 || K <= 0 || K % 4 != 0 || ldx < K || ldy < N || add_cols < 0)
+        return POPE_ERR_ARG;
+    if ((M + LIN_ROWS - 1) / LIN_ROWS > 65535) return POPE_ERR_ARG;
+    const size_t lds = size_t(LIN_ROWS) * K * (add ? 2 : 1) * sizeof(float);
+    if (lds > LIN_LDS_LIMIT) return POPE_ERR_ARG;
+    hipLaunchKernelGGL(sd_lin_kernel, dim3((N + 255) / 256, (M + LIN_ROWS - 1) / LIN_ROWS), dim3(256), lds, stream, X, ldx, add, ldx,
+                       add_cols, W, bias, res, ldy, Y, ldy, M, N, K, relu ? 1 : 0);
+    return pope_check_launch();
+}
+
+int pope_launch_sam_decoder_self_attention(const float* qkv, float* out, int P, int T, hipStream_t stream) {
+    if (!qkv || !out || T < 1 || T > MAX_T || P < 1 || P > 65535) return POPE_ERR_ARG;
+    return self_attn(Ctx{true, nullptr, stream}, qkv, out, T, P);
+}
+
+int pope_launch_sam_decoder_t2i_attention(const float* q, const float* K, int ldk, long long kps, const float* V, long long vps,
+                                          const int* slot_host, float* out, int T, int P, hipStream_t stream) {
+    SdImageOf im;
+    if (!q || !al16(K) || !al16(V) || !out || !tokens_ok(T, P) || ldk < DI || ldk % 4 != 0 || !stride_ok(kps) || !stride_ok(vps) ||
+        !slots(slot_host, P, &im))
+        return POPE_ERR_ARG;
+    return t2i(Ctx{true, nullptr, stream}, q, K, ldk, kps, V, vps, im, out, T, P);
+}
+
+int pope_launch_sam_decoder_i2t_attention(const float* Q, long long qps, const int* slot_host, const float* kv, int T, int P,
+                                          float* out_f32, void* out_planes, unsigned* range_flag, hipStream_t stream) {
+    SdImageOf im;
+    if (!al16(Q) || !kv || !tokens_ok(T, P) || !stride_ok(qps) || (out_f32 != nullptr) == (out_planes != nullptr) ||
+        !slots(slot_host, P, &im))
+        return POPE_ERR_ARG;
+    return i2t(Ctx{out_f32 != nullptr, range_flag, stream}, Q, qps, im, kv, T, out_f32 ? static_cast<void*>(out_f32) : out_planes, P);
+}
+
+int pope_launch_sam_decoder_residual_norm(const float* res, long long rps, const int* slot_host, const float* y, const float* w,
+                                          const float* b, float eps, const float* pe_t, float* keys, void* opA, void* opB, int f32,
+                                          int P, unsigned* range_flag, hipStream_t stream) {
+    SdImageOf im;
+    if (!al16(res) || !al16(y) || !al16(w) || !al16(b) || !al16(pe_t) || !al16(keys) || !opB || (!f32 && !opA) || !(eps >= 0.f) ||
+        !stride_ok(rps) || P < 1 || P > CHUNK || !slots(slot_host, P, &im))
+        return POPE_ERR_ARG;
+    return res_ln(Ctx{f32 != 0, range_flag, stream}, res, rps, im, y, w, b, eps, pe_t, keys, opA, opB, P);
+}
+
+int pope_launch_sam_decoder_prepare_keys(const float* image, long long image_stride, const float* image_pe, const float* dense,
+                                         long long dense_stride, int nz, float* keys, void* opA, void* opB, int f32, float* pe_t,
+                                         unsigned* range_flag, hipStream_t stream) {
+    if (!image || !image_pe || !dense || !keys || !pe_t || !opB || (!f32 && !opA) || image_stride < 0 || dense_stride < 0 || nz < 1 ||
+        nz > CHUNK)
+        return POPE_ERR_ARG;
+    return prep(Ctx{f32 != 0, range_flag, stream}, image, image_stride, image_pe, dense, dense_stride, keys, opA, opB, pe_t, nz);
+}
+
+int pope_launch_sam_decoder_upscale_tail(const float* y, const float* ln_w, const float* ln_b, float eps, const float* w2,
+                                         const float* b2, const float* hyper, int multimask, int P, float* masks, hipStream_t stream) {
+    if (!al16(y) || !ln_w || !ln_b || !al16(w2) || !b2 || !hyper || !masks || !(eps >= 0.f) || P < 1 || P > CHUNK) return POPE_ERR_ARG;
+    return tail(Ctx{true, nullptr, stream}, y, ln_w, ln_b, eps, w2, b2, hyper, multimask != 0, P, masks);
 }
