@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define POPE_ABI_VERSION 9
+#define POPE_ABI_VERSION 10
 
 enum {
     POPE_EPI_BIAS = 0,        /* C = A.W^T + bias                         nn.Linear                     */
@@ -47,7 +47,7 @@ enum {
      * columns, rows 64t .. 64t+31 are w12 rows 32t .. 32t+31 (gates), rows 64t+32 .. 64t+63 are w12 rows
      * hidden+32t .. hidden+32t+31 (values).  N % 64 == 0.  silu(x) = x / (1 + exp(-x)) in fp32 (exp as exp2 of the pre-scaled
      * argument), finite for every finite gate.  pope_linear_planes_f32 (planes or fp32 out, range bit POPE_RANGE_GELU: it marks the
-     * FC1 producer) and pope_linear_prec_f32 with POPE_PREC_F32_MFMA take it; gamma and res are ignored. */
+     * FC1 producer) and pope_linear_f32 with POPE_PREC_F32_MFMA take it; gamma and res are ignored. */
     POPE_EPI_BIAS_SWIGLU = 11,
     /* pope_linear_f16 only — the QKV projection of the POPE_PREC_F16 ViT blocks, whose output is the operand of
      * pope_attention_f16: C = (A.W^T + bias) * (col < N/3 ? 0.125 * log2 e : 1), rounded ONCE to f16 rows with no activation
@@ -77,14 +77,11 @@ int pope_layernorm_f32(const float* x, const float* weight, const float* bias, f
                        int rows, int dim, float eps, void* stream);
 
 /* nn.Linear (+ fused epilogue) — attention.py:51,60; mlp.py:35-44.  A[M,K], W[N,K], C[M,N];
- * gamma[N] and res[M,N] only for POPE_EPI_BIAS_LS_RES (res may alias C). */
+ * gamma[N] and res[M,N] only for POPE_EPI_BIAS_LS_RES (res may alias C).  precision: POPE_PREC_F32_MFMA or POPE_PREC_F16X3,
+ * which splits A and W inside the kernel; with range_flag both operands are scanned first (POPE_RANGE_INPUT). */
 int pope_linear_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
-                    int epilogue, const float* gamma, const float* res, void* stream);
-/* Same with an explicit POPE_PREC_* (pope_linear_f32 == POPE_PREC_F32_MFMA).  POPE_PREC_F16X3 splits A and W inside
- * the kernel; with range_flag both operands are scanned first (POPE_RANGE_INPUT). */
-int pope_linear_prec_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
-                         int epilogue, const float* gamma, const float* res, int precision,
-                         unsigned* range_flag, void* stream);
+                    int epilogue, const float* gamma, const float* res, int precision,
+                    unsigned* range_flag, void* stream);
 
 /* f16x3 "planes": a tensor X[rows, cols] (cols % 32 == 0) kept as f16 halves with X * scale = hi + lo
  * (scale a power of two: POPE_PLANES_ACT_SCALE for activations, POPE_PLANES_W_SCALE for weights), laid
@@ -167,12 +164,10 @@ int pope_patch_embed_planes_f32(const float* img, const void* proj_w_planes, con
                                 size_t scratch_bytes, unsigned* range_flag, void* stream);
 
 /* Attention.forward core — attention.py:51-59: qkv[B,N,3,heads,64] -> out[B,N,heads*64],
- * softmax((q*0.125) k^T) v. */
-int pope_attention_f32(const float* qkv, float* out, int B, int N, int heads, void* stream);
-/* Same with an explicit POPE_PREC_* (pope_attention_f32 == POPE_PREC_F32_MFMA); with range_flag a POPE_PREC_F16X3
+ * softmax((q*0.125) k^T) v.  precision: POPE_PREC_F32_MFMA or POPE_PREC_F16X3; with range_flag a POPE_PREC_F16X3
  * call scans qkv first (POPE_RANGE_INPUT). */
-int pope_attention_prec_f32(const float* qkv, float* out, int B, int N, int heads, int precision,
-                            unsigned* range_flag, void* stream);
+int pope_attention_f32(const float* qkv, float* out, int B, int N, int heads, int precision,
+                       unsigned* range_flag, void* stream);
 /* f16x3 attention on planes (layout and scale: POPE_PLANES_* above; the producer of the planes guards the range:
  * the output is a convex combination of v rows, so it fits whenever v did): qkv_planes [B*N, 3*heads*64] as written by
  * pope_linear_planes_f32(..., c_planes), out_planes [B*N, heads*64] as read by the proj GEMM.  heads*64 % 32 == 0. */
@@ -235,18 +230,13 @@ enum { POPE_FFN_MLP = 0, POPE_FFN_SWIGLU = 1 };
  * Outputs: x_prenorm[B,ntok,dim] (also the residual stream, required) and x_norm[B,ntok,dim]
  * (final LayerNorm; row 0 = x_norm_clstoken, rows 1.. = x_norm_patchtokens; may be NULL).
  * n_taps/tap_blocks_host/tap_out_host: optional copies of the residual stream after the listed
- * blocks (get_intermediate_layers, vision_transformer.py:238-288). */
-int pope_vit_forward_f32(const pope_vit_weights* w_host, const float* img, int B, int H, int W,
+ * blocks (get_intermediate_layers, vision_transformer.py:238-288).
+ * ffn: POPE_FFN_* of the blocks.  An unknown kind, POPE_FFN_SWIGLU with POPE_PREC_F16, with hidden % 32 != 0 or with a NULL
+ * fc1_w / fc1_b / fc2_w return POPE_ERR_ARG before any HIP call. */
+int pope_vit_forward_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
                          const float* posb, float* x_prenorm, float* x_norm,
                          int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
                          void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
-
-/* Same with an explicit POPE_FFN_* (pope_vit_forward_f32 == POPE_FFN_MLP).  An unknown kind, POPE_FFN_SWIGLU with
- * POPE_PREC_F16, with hidden % 32 != 0 or with a NULL fc1_w / fc1_b / fc2_w return POPE_ERR_ARG before any HIP call. */
-int pope_vit_forward_ffn_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
-                             const float* posb, float* x_prenorm, float* x_norm,
-                             int n_taps, const int* tap_blocks_host, float* const* tap_out_host,
-                             void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
 
 /* In-situ kernel timing of the product path (bench.py's roofline leg): identical launches, plus
  * events_host[i] (hipEvent_t made by pope_event_create) recorded on `stream` immediately before
@@ -259,138 +249,115 @@ int pope_vit_launch_count(int depth);
  * all): timing one kernel kind leaves every other launch of the sequence back to back, as in the untimed path.  events_host[i] / kinds_host[i] then hold the recorded events in order; kinds_host[i] is the kind
  * of the launch that STARTS at event i, or -1 for an event that only closes the previous bracket;
  * *n_launches_host = number of recorded events - 1. */
-int pope_vit_forward_profiled_mask_f32(const pope_vit_weights* w_host, const float* img, int B, int H, int W,
-                                       const float* posb, float* x_prenorm, float* x_norm,
-                                       void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                       void* const* events_host, int n_events, int* kinds_host,
-                                       int* n_launches_host, unsigned kind_mask);
-/* Same with an explicit POPE_FFN_* (see pope_vit_forward_ffn_f32). */
-int pope_vit_forward_ffn_profiled_mask_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
-                                           const float* posb, float* x_prenorm, float* x_norm,
-                                           void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                           void* const* events_host, int n_events, int* kinds_host,
-                                           int* n_launches_host, unsigned kind_mask);
+int pope_vit_forward_profiled_f32(const pope_vit_weights* w_host, int ffn, const float* img, int B, int H, int W,
+                                  const float* posb, float* x_prenorm, float* x_norm,
+                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream,
+                                  void* const* events_host, int n_events, int* kinds_host,
+                                  int* n_launches_host, unsigned kind_mask);
 int pope_event_create(void** event_host);
 int pope_event_destroy(void* event);
 int pope_event_elapsed_ms(void* start, void* stop, float* ms_host);  /* both events must have completed */
 
 /* ---- dense matcher --------------------------------------------------------------------------- */
 
-/* CoarseMatching.forward + get_coarse_match (eval, dual-softmax) —
- * src/matcher/utils/coarse_matching.py:106-119,151-261.
- * feat0[n,L,C], feat1[n,S,C] with `stride0`/`stride1` elements between consecutive pairs (L*C / S*C
- * when dense; larger when the features are the patch rows of an x_norm[B,1+L,C] buffer);
- * grids (h0,w0),(h1,w1); scale = hw0_i[0]/hw0_c[0].
- * conf_matrix[n,L,S]: the published confidence matrix (the drop-in CoarseMatching publishes it,
- * coarse_matching.py:145), or NULL for callers that only consume the match lists: the matrix then lives in the
- * workspace as sim only and is never written a second time.
- * Outputs have capacity n*L: b_ids,i_ids,j_ids (int64), mconf, mkpts0_c/mkpts1_c [.,2] (x,y);
- * counts[n+1] (int32): matches per pair, then the total M (read it after synchronising).
- * precision = POPE_PREC_* of the L x S x C contraction; POPE_PREC_F16X3 needs C % 32 == 0 (feat / sqrt(C) kept as
- * hi/lo planes, range-guarded: POPE_RANGE_MATCH); everything after the contraction is identical.
- * Workspace: pope_dense_match_workspace_bytes_prec(n, L, S, C, precision, conf_matrix != NULL). */
-size_t pope_dense_match_workspace_bytes_prec(int n, int L, int S, int C, int precision, int publish_conf);
-int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
-                              int n, int L, int S, int C, int h0, int w0, int h1, int w1,
-                              float thr, int border_rm, float temperature, float scale,
-                              float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids,
-                              float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
-                              void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
-                              void* stream);
-/* Padded batches and rescaling (coarse_matching.py:115-118,178-184,242-250): pope_dense_match_prec_f32 plus six optional
- * inputs (NULL = absent; masks hold 0 / 1 as fp32):
- *   fill_mask0[n,L], fill_mask1[n,S]: sim = -1e9 (finite, the reference's -INF) where fill_mask0[i] * fill_mask1[j] == 0,
- *     before both softmaxes (a missing one counts as ones);
- *   border_mask0[n,h0,w0], border_mask1[n,h1,w1]: when either is given, the bottom / right border of each pair lies at its
- *     valid extent (h = max column sum, w = max row sum, per image) instead of the grid's (mask_border_with_padding);
- *   scale0[n,2], scale1[n,2]: (x, y) factors, mkpts*_c = (idx % w, idx / w) * (scale * scale*[b]).
- * With all six NULL this is exactly pope_dense_match_prec_f32 (which forwards here).
- * Workspace: pope_dense_match_masked_workspace_bytes(..., has_border_masks). */
-size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks);
-int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
-                                int n, int L, int S, int C, int h0, int w0, int h1, int w1,
-                                float thr, int border_rm, float temperature, float scale,
-                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0,
-                                const float* border_mask1, const float* scale0, const float* scale1,
-                                float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids,
-                                float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
-                                void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
-                                void* stream);
-/* match_type='sinkhorn' (coarse_matching.py:121-143): pope_dense_match_masked_f32 with the dual softmax replaced by log-domain
- * optimal transport.  sim carries no temperature; Z [L+1, S+1] is sim (after the -1e9 fill) bordered by a dustbin row, column
- * and corner that all hold *bin_score; norm = -log(L+S), log_mu = [norm]*L + [log(S)+norm], log_nu = [norm]*S + [log(L)+norm];
- * from u = v = 0, skh_iters (>= 1) times u_i = log_mu_i - logsumexp_j(Z_ij + v_j), v_j = log_nu_j - logsumexp_i(Z_ij + u_i);
- * conf = exp(Z + u + v - norm)[:L, :S].  skh_prefilter != 0 zeroes the rows of conf whose largest assignment over the S+1
- * columns is the dustbin (strictly: a tie goes to the real cell) and the columns likewise (:136-140).  Threshold, border,
- * mutual nearest neighbour, ordering and scaling then apply to conf exactly as in the dual-softmax entries.
- *   bin_score: DEVICE pointer to one float, read by the kernels at run time (the learned parameter's own storage; the host
- *     never reads it, an in-place update is seen by the next call).
- *   The masks and scales are optional as above (NULL = none).  conf_matrix may be NULL: conf then lives in the workspace.
- * Workspace: pope_dense_match_sinkhorn_workspace_bytes(...). */
-size_t pope_dense_match_sinkhorn_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks);
-int pope_dense_match_sinkhorn_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
-                                  int n, int L, int S, int C, int h0, int w0, int h1, int w1,
-                                  float thr, int border_rm, const float* bin_score, int skh_iters, int skh_prefilter, float scale,
-                                  const float* fill_mask0, const float* fill_mask1, const float* border_mask0,
-                                  const float* border_mask1, const float* scale0, const float* scale1,
-                                  float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids,
-                                  float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
-                                  void* workspace, size_t workspace_bytes, int precision, unsigned* range_flag,
-                                  void* stream);
-/* Shorthands: POPE_PREC_F32_MFMA, conf_matrix published, no range flag. */
-size_t pope_dense_match_workspace_bytes(int n, int L, int S);
-int pope_dense_match_f32(const float* feat0, long long stride0, const float* feat1, long long stride1,
-                         int n, int L, int S, int C,
-                         int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature,
-                         float scale, float* conf_matrix, long long* b_ids, long long* i_ids,
-                         long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts,
-                         void* workspace, size_t workspace_bytes, void* stream);
+/* CoarseMatching.forward + get_coarse_match (eval) — src/matcher/utils/coarse_matching.py:106-148,151-261, for both of
+ * its matchers.  The caller fills one pope_dense_match_args, asks pope_dense_match_workspace_bytes for the size, sets
+ * `workspace` / `workspace_bytes` and calls pope_dense_match_f32.
+ * POPE_MATCH_DUAL_SOFTMAX (:106-119): conf = softmax_rows(sim) * softmax_cols(sim), sim = (feat0 / sqrt C) . (feat1 / sqrt C)^T /
+ *   temperature.
+ * POPE_MATCH_SINKHORN (:121-143): the dual softmax replaced by log-domain optimal transport.  sim carries no temperature
+ *   (`temperature` is ignored: 1); Z [L+1, S+1] is sim (after the -1e9 fill) bordered by a dustbin row, column and corner that
+ *   all hold *bin_score; norm = -log(L+S), log_mu = [norm]*L + [log(S)+norm], log_nu = [norm]*S + [log(L)+norm]; from u = v = 0,
+ *   skh_iters times u_i = log_mu_i - logsumexp_j(Z_ij + v_j), v_j = log_nu_j - logsumexp_i(Z_ij + u_i);
+ *   conf = exp(Z + u + v - norm)[:L, :S].
+ * Threshold, border, mutual nearest neighbour, ordering and scaling then apply to conf in the same way for both.
+ * POPE_ERR_ARG (null feat / output / workspace pointers, non-positive or inconsistent sizes, an unknown precision or match_type,
+ * POPE_MATCH_SINKHORN without bin_score or with skh_iters < 1) and POPE_ERR_WORKSPACE are returned before any HIP call. */
+enum { POPE_MATCH_DUAL_SOFTMAX = 0, POPE_MATCH_SINKHORN = 1 };
+typedef struct pope_dense_match_args {
+    /* feat0[n,L,C], feat1[n,S,C], 16-byte aligned, with `stride0` / `stride1` elements (multiples of 4) between consecutive
+     * pairs: L*C / S*C when dense; larger when the features are the patch rows of an x_norm[B,1+L,C] buffer */
+    const float* feat0; long long stride0;
+    const float* feat1; long long stride1;
+    int n, L, S, C;                /* C % 4 == 0, n <= 65535 */
+    int h0, w0, h1, w1;            /* the grids: L == h0 * w0, S == h1 * w1 */
+    float thr; int border_rm;
+    float temperature;             /* POPE_MATCH_DUAL_SOFTMAX only */
+    float scale;                   /* hw0_i[0] / hw0_c[0] */
+    int match_type;                /* POPE_MATCH_* */
+    /* POPE_MATCH_SINKHORN only.  bin_score: DEVICE pointer to one float, read by the kernels at run time (the learned parameter's
+     * own storage; the host never reads it, an in-place update is seen by the next call).  skh_iters >= 1.  skh_prefilter != 0
+     * zeroes the rows of conf whose largest assignment over the S+1 columns is the dustbin (strictly: a tie goes to the real
+     * cell) and the columns likewise (:136-140). */
+    const float* bin_score; int skh_iters, skh_prefilter;
+    /* Padded batches and rescaling (coarse_matching.py:115-118,178-184,242-250): six optional inputs (NULL = absent; masks hold
+     * 0 / 1 as fp32):
+     *   fill_mask0[n,L], fill_mask1[n,S]: sim = -1e9 (finite, the reference's -INF) where fill_mask0[i] * fill_mask1[j] == 0,
+     *     before both softmaxes (a missing one counts as ones);
+     *   border_mask0[n,h0,w0], border_mask1[n,h1,w1]: when either is given, the bottom / right border of each pair lies at its
+     *     valid extent (h = max column sum, w = max row sum, per image) instead of the grid's (mask_border_with_padding);
+     *   scale0[n,2], scale1[n,2]: (x, y) factors, mkpts*_c = (idx % w, idx / w) * (scale * scale*[b]). */
+    const float *fill_mask0, *fill_mask1, *border_mask0, *border_mask1, *scale0, *scale1;
+    /* conf_matrix[n,L,S]: the published confidence matrix (the drop-in CoarseMatching publishes it, coarse_matching.py:145), or
+     * NULL for callers that only consume the match lists: the matrix then lives in the workspace only. */
+    float* conf_matrix;
+    /* Outputs of capacity n*L: b_ids, i_ids, j_ids (int64), mconf, mkpts0_c / mkpts1_c [.,2] (x,y); counts[n+1] (int32): matches
+     * per pair, then the total M (read it after synchronising). */
+    long long *b_ids, *i_ids, *j_ids;
+    float *mconf, *mkpts0_c, *mkpts1_c;
+    int* counts;
+    void* workspace; size_t workspace_bytes;
+    /* POPE_PREC_* of the L x S x C contraction; POPE_PREC_F16X3 needs C % 32 == 0 (feat / sqrt(C) kept as hi/lo planes,
+     * range-guarded: POPE_RANGE_MATCH); everything after the contraction is identical. */
+    int precision;
+    unsigned* range_flag;
+} pope_dense_match_args;
+/* Reads n, L, S, C, precision, match_type, and whether conf_matrix and either border mask are non-NULL; 0 for a NULL struct or
+ * non-positive sizes. */
+size_t pope_dense_match_workspace_bytes(const pope_dense_match_args* args_host);
+int pope_dense_match_f32(const pope_dense_match_args* args_host, void* stream);
 
 /* ---- LoFTR encoder layer (first slice) ---------------------------------------------------- */
 
-/* LoFTREncoderLayer.forward with LinearAttention — src/matcher/loftr_module/transformer.py:35-58,
- * linear_attention.py:20-47 (no masks): x[n,L,C] <- x + norm2(mlp(cat[x, norm1(merge(attention(q(x), k(source),
- * v(source))))])), in place; source[n,S,C] may be x itself ('self' layers).  C = 256 (coarse) or 128 (fine), nhead = 8.
+/* LoFTREncoderLayer.forward — src/matcher/loftr_module/transformer.py:35-58: x[n,L,C] <- x + norm2(mlp(cat[x, norm1(merge(
+ * attention(q(x), k(source), v(source))))])), in place; source[n,S,C] may be x itself ('self' layers).  C = 256 (coarse) or 128
+ * (fine), nhead = 8.
  * The five bias-free Linears are given as f16x3 WEIGHT planes (layout above): q_wp [C,C], kv_wp [2C,C] (k_proj rows,
  * then v_proj rows), merge_wp [C,C], mlp0_wp [2C,2C], mlp1_wp [C,2C]; LayerNorm eps = ln_eps (nn.LayerNorm default
  * 1e-5).  LocalFeatureTransformer.forward (:85-106) is a sequence of these calls: 'self' = (f0,f0),(f1,f1); 'cross' =
  * (f0,f1) then (f1, NEW f0).
  * precision = POPE_PREC_F16X3, or POPE_PREC_F32_MFMA: the re-run of a range-guard event — the five `*_wp` are then plain fp32
- * [out, in] matrices and every contraction runs on the fp32 MFMA (no range contract; range_flag is not touched). */
+ * [out, in] matrices and every contraction runs on the fp32 MFMA (no range contract; range_flag is not touched).
+ * attention = POPE_LOFTR_ATTN_LINEAR: LinearAttention (linear_attention.py:20-47) with optional padding masks (:35-41; NULL = no
+ * mask), 0 / 1 as fp32: x_mask[n,L] zeroes Q of padded query rows (their message is 0), source_mask[n,S] zeroes K and V of
+ * padded source rows (V / S keeps the full length S).
+ * attention = POPE_LOFTR_ATTN_FULL: FullAttention (linear_attention.py:50-81, the config's attention = 'full'): message =
+ * softmax(Q K^T / sqrt(D), over the S source rows) V per head, D = C / nhead; everything around it, the weights struct and the
+ * workspace are the same.  No masks (a padded query row is NaN in the reference): a non-NULL mask is POPE_ERR_ARG.  The softmax
+ * runs in fp32 under both precisions (S > 64: flash-style on the fp32 MFMA, online softmax, nothing of size L x S is stored;
+ * S <= 64: fp32 FMAs, one workgroup per 32 queries of a sequence); POPE_PREC_F16X3 writes the message as the merge GEMM's operand
+ * planes and ORs POPE_RANGE_QKV into range_flag when a scaled value leaves the f16 range.  Every output row is bit-identical
+ * whatever n.  POPE_ERR_ARG before any launch: null pointers, C not 128 / 256, nhead != 8, non-positive sizes, an unknown
+ * precision.
+ * An unknown `attention` is POPE_ERR_ARG. */
 typedef struct pope_loftr_layer_weights {
     const void *q_wp, *kv_wp, *merge_wp, *mlp0_wp, *mlp1_wp;
     const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
 } pope_loftr_layer_weights;
+enum { POPE_LOFTR_ATTN_LINEAR = 0, POPE_LOFTR_ATTN_FULL = 1 };
 size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead);
 int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
-                                 int n, int L, int S, int C, int nhead, float ln_eps, int precision,
+                                 const float* x_mask, const float* source_mask,
+                                 int n, int L, int S, int C, int nhead, float ln_eps, int attention, int precision,
                                  void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
-/* The same layer with padding masks (linear_attention.py:35-41), each optional (NULL = no mask), 0 / 1 as fp32:
- * x_mask[n,L] zeroes Q of padded query rows (their message is 0), source_mask[n,S] zeroes K and V of padded source rows
- * (V / S keeps the full length S).  Same workspace; with both NULL this is pope_loftr_encoder_layer_f32. */
-int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
-                                        const float* x_mask, const float* source_mask,
-                                        int n, int L, int S, int C, int nhead, float ln_eps, int precision,
-                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
-/* The same layer with FullAttention (linear_attention.py:50-81, the config's attention = 'full') in place of the linear body:
- * message = softmax(Q K^T / sqrt(D), over the S source rows) V per head, D = C / nhead; everything around it, the weights
- * struct and the workspace are those of pope_loftr_encoder_layer_f32.  No masks: a padded query row is NaN in the reference.
- * The softmax runs in fp32 under both precisions (S > 64: flash-style on the fp32 MFMA, online softmax, nothing of size
- * L x S is stored; S <= 64: fp32 FMAs, one workgroup per 32 queries of a sequence); POPE_PREC_F16X3 writes the message as
- * the merge GEMM's operand planes and ORs POPE_RANGE_QKV into range_flag when a scaled value leaves the f16 range.  Every
- * output row is bit-identical whatever n.  POPE_ERR_ARG before any launch: null pointers, C not 128 / 256, nhead != 8,
- * non-positive sizes, an unknown precision. */
-int pope_loftr_encoder_layer_full_f32(const pope_loftr_layer_weights* w_host, float* x, const float* source,
-                                      int n, int L, int S, int C, int nhead, float ln_eps, int precision,
-                                      void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream);
-/* The attention core of that layer alone: q[n L, C], kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32, 16-byte aligned
+/* The FULL attention core of that layer alone: q[n L, C], kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32, 16-byte aligned
  * -> out[n L, C] fp32 rows.  precision is validated (F32_MFMA or F16X3; both run the fp32 kernels); range_flag is not
  * touched.  Same argument checks. */
 int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L, int S, int C, int nhead, int precision,
                                   float* out, unsigned* range_flag, void* stream);
 
-/* The LINEAR attention core of pope_loftr_encoder_layer_f32 / _masked_f32 alone, by the layer's own launches: q[n L, C],
- * kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32; x_mask[n,L] / source_mask[n,S] as in the masked layer, each may be
+/* The LINEAR attention core of pope_loftr_encoder_layer_f32 alone, by the layer's own launches: q[n L, C],
+ * kv[n S, 2C] (k in columns 0..C-1, v in C..2C-1) fp32; x_mask[n,L] / source_mask[n,S] as in the layer, each may be
  * NULL.  Exactly one output: out_f32[n L, C] fp32 rows (what the layer computes under POPE_PREC_F32_MFMA), or out_planes
  * [n L, C] activation planes (scale 8; what it computes under POPE_PREC_F16X3), which ORs POPE_RANGE_INPUT into range_flag
  * (may be NULL) when a scaled value leaves the f16 range.  The per-head state is summed over the source rows in chunks of
@@ -505,7 +472,13 @@ int pope_conv_layer_f16(const pope_conv_layer_args* args_host, void* stream);
  * (n, c, h, w), so NCHW tensors and NHWC views both work; feat_c0[n,L,Cc], feat_c1[n,S,Cc]; b/i/j_ids: int64[M];
  * down_wp[Cf,Cc], merge_wp[Cf,2*Cf]: weight planes (scale 256) — plain fp32 matrices for precision = POPE_PREC_F32_MFMA, the
  * re-run of a range-guard event —, biases fp32; out[2*M, Wn*Wn, Cf] = windows of stream 0 then stream 1 (the reference's
- * torch.chunk(…, 2)). */
+ * torch.chunk(…, 2)).
+ * ref0_of_pair = NULL: feat_f0 has one row per pair (n, n0 unused).  Otherwise SHARED map-0 rows (one reference image matched
+ * against many crops): feat_f0 has n0 rows, and the windows of match m in map 0 are read at row ref0_of_pair[b_ids[m]].
+ * ref0_of_pair: int64[n] (DEVICE), n = the number of pairs, n, n0 >= 1; feat_c0 stays [n, L, Cc] and indexed by b_ids[m] (it is
+ * the per-pair transformer output), and so does everything of stream 1.  A pair outside [0, n) and a row outside [0, n0) are
+ * clamped on the device (a wrong window, never a read outside the map).
+ * n < 0, n0 < 0 and null feature / id / weight / out / workspace pointers return POPE_ERR_ARG before any HIP call. */
 size_t pope_fine_preprocess_workspace_bytes(int M, int Wn, int Cc, int Cf);
 int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0_host, int H0, int W0, int wc0,
                              const float* feat_f1, const long long* strides1_host, int H1, int W1, int wc1,
@@ -513,33 +486,16 @@ int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0_hos
                              const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
                              int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
                              const float* merge_b, int precision, float* out, void* workspace, size_t workspace_bytes,
-                             unsigned* range_flag, void* stream);
-/* The same with SHARED map-0 rows (one reference image matched against many crops): feat_f0 has n0 rows instead of one per
- * pair, and the windows of match m in map 0 are read at row ref0_of_pair[b_ids[m]].  ref0_of_pair: int64[n] (DEVICE), n =
- * the number of pairs; feat_c0 stays [n, L, Cc] and indexed by b_ids[m] (it is the per-pair transformer output), and so
- * does everything of stream 1.  A pair outside [0, n) and a row outside [0, n0) are clamped on the device (a wrong window,
- * never a read outside the map).  ref0_of_pair = NULL: pope_fine_preprocess_f32 (n, n0 unused); otherwise n, n0 >= 1.
- * n < 0, n0 < 0 and null feature / id / weight / out / workspace pointers return POPE_ERR_ARG before any HIP call.  Same
- * workspace query. */
-int pope_fine_preprocess_indexed_f32(const float* feat_f0, const long long* strides0_host, int H0, int W0, int wc0,
-                                     const float* feat_f1, const long long* strides1_host, int H1, int W1, int wc1,
-                                     const float* feat_c0, const float* feat_c1, int L, int S, int Cc, int Cf,
-                                     const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
-                                     int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
-                                     const float* merge_b, int precision, float* out, void* workspace,
-                                     size_t workspace_bytes, unsigned* range_flag, const long long* ref0_of_pair, int n,
-                                     int n0, void* stream);
+                             unsigned* range_flag, const long long* ref0_of_pair, int n, int n0, void* stream);
 /* FineMatching.forward + get_fine_match — src/matcher/utils/fine_matching.py:15-74 for M > 0: correlation of the
  * centre of window 0 with window 1 (temperature 1/sqrt(C)), softmax, expectation over linspace(-1,1,Wn)^2 as (x, y)
  * and the summed standard deviation -> expec_f[M,3]; mkpts1_f[M,2] = mkpts1_c + expec_xy * (Wn/2) * scale_px
- * (scale_px = hw0_i[0] / hw0_f[0]).  win0, win1: [M, Wn*Wn, C] fp32 (the fine transformer's outputs). */
+ * (scale_px = hw0_i[0] / hw0_f[0]).  win0, win1: [M, Wn*Wn, C] fp32 (the fine transformer's outputs).
+ * Optional per-pair rescaling (fine_matching.py:68): scale1[n,2] (x, y) with b_ids int64[M] (the matches' pairs):
+ * mkpts1_f[m] = mkpts1_c[m] + expec_xy * (Wn/2) * (scale_px * scale1[b_ids[m]]).  scale1 = NULL: none (b_ids unused). */
 int pope_fine_match_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c,
-                        float scale_px, float* expec_f, float* mkpts1_f, void* stream);
-/* The same with per-pair rescaling (fine_matching.py:68): scale1[n,2] (x, y) and b_ids int64[M] (the matches' pairs);
- * mkpts1_f[m] = mkpts1_c[m] + expec_xy * (Wn/2) * (scale_px * scale1[b_ids[m]]).  scale1 = NULL: pope_fine_match_f32. */
-int pope_fine_match_scaled_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c,
-                               float scale_px, const float* scale1, const long long* b_ids, float* expec_f,
-                               float* mkpts1_f, void* stream);
+                        float scale_px, const float* scale1, const long long* b_ids, float* expec_f,
+                        float* mkpts1_f, void* stream);
 
 /* ---- SAM image encoder (BASELINE config 5) --------------------------------------------------- */
 

@@ -47,6 +47,17 @@ class ConvLayerArgs(C.Structure):
                 ("scratch_bytes", C.c_size_t), ("range_flag", C.c_void_p)]
 
 
+class DenseMatchArgs(C.Structure):
+    """pope_dense_match_args: everything one dense-matcher call takes (pope_dense_match_workspace_bytes, pope_dense_match_f32)."""
+    _fields_ = [("feat0", C.c_void_p), ("stride0", C.c_longlong), ("feat1", C.c_void_p), ("stride1", C.c_longlong)] + [
+        (n, C.c_int) for n in ("n", "L", "S", "C", "h0", "w0", "h1", "w1")] + [
+        ("thr", C.c_float), ("border_rm", C.c_int), ("temperature", C.c_float), ("scale", C.c_float), ("match_type", C.c_int),
+        ("bin_score", C.c_void_p), ("skh_iters", C.c_int), ("skh_prefilter", C.c_int)] + [
+        (n, C.c_void_p) for n in ("fill_mask0", "fill_mask1", "border_mask0", "border_mask1", "scale0", "scale1", "conf_matrix",
+                                  "b_ids", "i_ids", "j_ids", "mconf", "mkpts0_c", "mkpts1_c", "counts", "workspace")] + [
+        ("workspace_bytes", C.c_size_t), ("precision", C.c_int), ("range_flag", C.c_void_p)]
+
+
 class SamBlockWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "norm1_b", "qkv_wp", "qkv_b", "proj_wp", "proj_b", "rel_h", "rel_w",
                                            "norm2_w", "norm2_b", "fc1_wp", "fc1_b", "fc2_wp", "fc2_b")] + [("global_attn", C.c_int)]
@@ -144,6 +155,8 @@ PREC_F32_MFMA, PREC_F16X3, PREC_F16 = 0, 1, 2
 PLANES_ACT_SCALE, PLANES_W_SCALE = 8.0, 256.0
 PRECISIONS = {"f32": PREC_F32_MFMA, "f16x3": PREC_F16X3, "f16": PREC_F16}
 FFN_KINDS = {"mlp": 0, "swiglu": 1}    # POPE_FFN_*
+MATCH_TYPES = {"dual_softmax": 0, "sinkhorn": 1}   # POPE_MATCH_*
+LOFTR_ATTENTIONS = {"linear": 0, "full": 1}        # POPE_LOFTR_ATTN_*
 EPI_BIAS_SWIGLU = 11                   # POPE_EPI_BIAS_SWIGLU
 EPI_QKV_F16 = 8                        # POPE_EPI_QKV_F16 (pope_linear_f16 only)
 CONV3, CONV_S2, CONV1_UP, CONV_STEM = 0, 1, 2, 3   # POPE_CONV_* forms of pope_conv_layer_f32
@@ -157,8 +170,7 @@ PROTOTYPES = {
     "pope_abi_version": (C.c_int, []),
     "pope_error_string": (C.c_char_p, [C.c_int]),
     "pope_layernorm_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
-    "pope_linear_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 3),
-    "pope_linear_prec_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_linear_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]),
     "pope_split_planes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "pope_linear_planes_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 4),
     "pope_layernorm_planes_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
@@ -171,55 +183,29 @@ PROTOTYPES = {
     "pope_div_planes_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                       C.c_void_p, C.c_void_p]),
     "pope_patch_embed_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
-    "pope_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "pope_attention_prec_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pope_patch_embed_planes_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_attention_planes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pope_attention_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pope_attention_planes_diag_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_ll_p, C.c_void_p]),
     "pope_cls_cosine_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "pope_vit_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "pope_vit_forward_f32": (C.c_int, [C.POINTER(VitWeights), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+    "pope_vit_forward_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_void_p),
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "pope_vit_forward_ffn_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_void_p),
-                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "pope_vit_forward_ffn_profiled_mask_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_int_p,
-                                                         c_int_p, C.c_uint]),
+    "pope_vit_forward_profiled_f32": (C.c_int, [C.POINTER(VitWeights), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_int_p,
+                                                c_int_p, C.c_uint]),
     "pope_vit_launch_count": (C.c_int, [C.c_int]),
-    "pope_vit_forward_profiled_mask_f32": (C.c_int, [C.POINTER(VitWeights), C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, c_int_p,
-                                                     c_int_p, C.c_uint]),
     "pope_event_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "pope_event_destroy": (C.c_int, [C.c_void_p]),
     "pope_event_elapsed_ms": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p]),
-    "pope_dense_match_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
-    "pope_dense_match_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_float,
-                                                                                  C.c_float] + [C.c_void_p] * 8
-                             + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pope_dense_match_workspace_bytes_prec": (C.c_size_t, [C.c_int] * 6),
-    "pope_dense_match_prec_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
-                                  + [C.c_float, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 8
-                                  + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
-    "pope_dense_match_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
-    "pope_dense_match_masked_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
-                                    + [C.c_float, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.c_void_p] * 8
-                                    + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
-    "pope_dense_match_sinkhorn_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
-    "pope_dense_match_sinkhorn_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 8
-                                      + [C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 6
-                                      + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "pope_dense_match_workspace_bytes": (C.c_size_t, [C.POINTER(DenseMatchArgs)]),
+    "pope_dense_match_f32": (C.c_int, [C.POINTER(DenseMatchArgs), C.c_void_p]),
     "pope_loftr_layer_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "pope_loftr_encoder_layer_f32": (C.c_int, [C.POINTER(LoftrLayerWeights), C.c_void_p, C.c_void_p] + [C.c_int] * 5
-                                     + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "pope_loftr_encoder_layer_masked_f32": (C.c_int, [C.POINTER(LoftrLayerWeights)] + [C.c_void_p] * 4 + [C.c_int] * 5
-                                            + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "pope_loftr_encoder_layer_full_f32": (C.c_int, [C.POINTER(LoftrLayerWeights), C.c_void_p, C.c_void_p] + [C.c_int] * 5
-                                          + [C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pope_loftr_encoder_layer_f32": (C.c_int, [C.POINTER(LoftrLayerWeights)] + [C.c_void_p] * 4 + [C.c_int] * 5
+                                     + [C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pope_loftr_full_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_loftr_linear_attention_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "pope_loftr_linear_attention_seams": (None, [c_int_p, c_int_p]),
@@ -231,17 +217,12 @@ PROTOTYPES = {
     "pope_conv_layer_f32": (C.c_int, [C.POINTER(ConvLayerArgs), C.c_void_p]),
     "pope_conv_layer_f16": (C.c_int, [C.POINTER(ConvLayerArgs), C.c_void_p]),
     "pope_fine_preprocess_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "pope_fine_preprocess_f32": (C.c_int, [C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 3
-                                 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "pope_fine_preprocess_indexed_f32": (C.c_int, [C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_ll_p, C.c_int, C.c_int,
-                                                   C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 3
-                                         + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]
-                                         + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pope_fine_preprocess_f32": (C.c_int, [C.c_void_p, c_ll_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_ll_p, C.c_int, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 3
+                                 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]
+                                 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pope_fine_match_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]),
-    "pope_fine_match_scaled_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pope_sam_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(SamEncoderWeights), C.c_int]),
     "pope_sam_encoder_forward_f32": (C.c_int, [C.POINTER(SamEncoderWeights), C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_int_p,
                                                C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -375,7 +356,7 @@ def lib():
             fn = getattr(handle, name)  # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args
-        if handle.pope_abi_version() != 9:
+        if handle.pope_abi_version() != 10:
             raise RuntimeError("libpope_hip.so ABI version mismatch")
         _lib = handle
     return _lib

@@ -54,13 +54,8 @@ int pope_layernorm_f32(const float* x, const float* weight, const float* bias, f
 }
 
 int pope_linear_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
-                    int epilogue, const float* gamma, const float* res, void* stream) {
-    return pope_linear_prec_f32(A, W, bias, C, M, N, K, epilogue, gamma, res, POPE_PREC_F32_MFMA, nullptr, stream);
-}
-
-int pope_linear_prec_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
-                         int epilogue, const float* gamma, const float* res, int precision, unsigned* range_flag,
-                         void* stream) {
+                    int epilogue, const float* gamma, const float* res, int precision, unsigned* range_flag,
+                    void* stream) {
     const bool swiglu = epilogue == POPE_EPI_BIAS_SWIGLU;
     if (!A || !W || !C || epilogue < 0 || (epilogue > POPE_EPI_BIAS_LS_RES && !swiglu)) return POPE_ERR_ARG;
     if (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
@@ -187,12 +182,8 @@ int pope_attention_planes_diag_f32(const void* qkv_planes, void* out_planes, int
     return pope_launch_attention_f16x3_planes_io_diag(qkv_planes, out_planes, B, N, heads, exact_passes_host, static_cast<hipStream_t>(stream));
 }
 
-int pope_attention_f32(const float* qkv, float* out, int B, int N, int heads, void* stream) {
-    return pope_attention_prec_f32(qkv, out, B, N, heads, POPE_PREC_F32_MFMA, nullptr, stream);
-}
-
-int pope_attention_prec_f32(const float* qkv, float* out, int B, int N, int heads, int precision, unsigned* range_flag,
-                            void* stream) {
+int pope_attention_f32(const float* qkv, float* out, int B, int N, int heads, int precision, unsigned* range_flag,
+                       void* stream) {
     StreamDevice on_device(stream);
     if (!qkv || !out) return POPE_ERR_ARG;
     if (precision == POPE_PREC_F16X3 && range_flag) {  // q, k, v are split inside the kernel: check them in a scan
@@ -231,102 +222,64 @@ int pope_event_elapsed_ms(void* start, void* stop, float* ms_host) {
 }
 
 namespace {
-// workspace carving of the dense matcher, shared by the size query and the launcher
+// workspace carving of the dense matcher, shared by the size query and the entry: the dual-softmax pieces, the pair extents of
+// the padded border rule, then the Sinkhorn scratch (u [n, L + 1], v [n, S + 1], the last column step's maxima [n, S])
 struct MatchLayout {
-    size_t nl, ns, part, rowp, colp, pl0, pl1, simb, total;
+    size_t nl, ns, part, rowp, colp, pl0, pl1, simb, extent, skh_u, skh_v, skh_cmax, total;
     int ncb, nrb, nrb2, ldp;
-    MatchLayout(int n, int L, int S, int C, int precision, bool publish_conf) {
-        nl = pope_align256(size_t(n) * L * 4);
-        ns = pope_align256(size_t(n) * S * 4);
+    explicit MatchLayout(const pope_dense_match_args& a) {
+        const size_t n = size_t(a.n);
+        const int L = a.L, S = a.S;
+        nl = pope_align256(n * L * 4);
+        ns = pope_align256(n * S * 4);
         ncb = 2 * ((S + 127) / 128);
         nrb = 4 * ((L + 127) / 128);
         nrb2 = pope_match_nrb2(L);
         ldp = (S + 3) & ~3;
-        part = pope_align256(size_t(n) * nrb2 * ldp * 4);
-        const bool x3 = precision == POPE_PREC_F16X3;
-        rowp = x3 ? pope_align256(size_t(n) * L * ncb * 8) : 0;
-        colp = x3 ? pope_align256(size_t(n) * nrb * ldp * 4) : 0;
-        pl0 = x3 ? pope_align256(size_t(n) * L * C * 4) : 0;
-        pl1 = x3 ? pope_align256(size_t(n) * S * C * 4) : 0;
-        simb = publish_conf ? 0 : pope_align256(size_t(n) * L * S * 4);
-        total = 7 * nl + 3 * ns + part + rowp + 2 * colp + pl0 + pl1 + simb;
+        part = pope_align256(n * nrb2 * ldp * 4);
+        const bool x3 = a.precision == POPE_PREC_F16X3;
+        rowp = x3 ? pope_align256(n * L * ncb * 8) : 0;
+        colp = x3 ? pope_align256(n * nrb * ldp * 4) : 0;
+        pl0 = x3 ? pope_align256(n * L * a.C * 4) : 0;
+        pl1 = x3 ? pope_align256(n * S * a.C * 4) : 0;
+        // (Sinkhorn: the matrix holds conf after the confidence pass even when it is not published; it lives here then)
+        simb = a.conf_matrix ? 0 : pope_align256(n * L * S * 4);
+        extent = a.border_mask0 || a.border_mask1 ? pope_align256(n * 4 * 4) : 0;
+        const bool skh = a.match_type == POPE_MATCH_SINKHORN;
+        skh_u = skh ? pope_align256(n * (L + 1) * 4) : 0;
+        skh_v = skh ? pope_align256(n * (S + 1) * 4) : 0;
+        skh_cmax = skh ? ns : 0;
+        total = 7 * nl + 3 * ns + part + rowp + 2 * colp + pl0 + pl1 + simb + extent + skh_u + skh_v + skh_cmax;
     }
 };
 }  // namespace
 
-size_t pope_dense_match_workspace_bytes(int n, int L, int S) {
-    if (n <= 0 || L <= 0 || S <= 0) return 0;
-    return MatchLayout(n, L, S, 4, POPE_PREC_F32_MFMA, true).total;
+size_t pope_dense_match_workspace_bytes(const pope_dense_match_args* a) {
+    if (!a || a->n <= 0 || a->L <= 0 || a->S <= 0 || a->C <= 0) return 0;
+    return MatchLayout(*a).total;
 }
 
-size_t pope_dense_match_workspace_bytes_prec(int n, int L, int S, int C, int precision, int publish_conf) {
-    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
-    return MatchLayout(n, L, S, C, precision, publish_conf != 0).total;
-}
-
-int pope_dense_match_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                         int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale, float* conf_matrix,
-                         long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0_c,
-                         float* mkpts1_c, int* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    return pope_dense_match_prec_f32(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, temperature, scale,
-                                     conf_matrix, b_ids, i_ids, j_ids, mconf, mkpts0_c, mkpts1_c, counts, workspace,
-                                     workspace_bytes, POPE_PREC_F32_MFMA, nullptr, stream);
-}
-
-int pope_dense_match_prec_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                              int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale, float* conf_matrix,
-                              long long* b_ids, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0_c,
-                              float* mkpts1_c, int* counts, void* workspace, size_t workspace_bytes, int precision,
-                              unsigned* range_flag, void* stream) {
-    return pope_dense_match_masked_f32(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, temperature, scale,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, conf_matrix, b_ids, i_ids, j_ids, mconf,
-                                       mkpts0_c, mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream);
-}
-
-size_t pope_dense_match_masked_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks) {
-    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
-    return MatchLayout(n, L, S, C, precision, publish_conf != 0).total + (has_border_masks ? pope_align256(size_t(n) * 4 * 4) : 0);
-}
-
-namespace {
-// Sinkhorn scratch behind the dual-softmax layout: u [n, L + 1], v [n, S + 1], the last column step's maxima [n, S]
-struct SinkhornLayout {
-    size_t u, v, cmax, total;
-    SinkhornLayout(int n, int L, int S) {
-        u = pope_align256(size_t(n) * (L + 1) * 4);
-        v = pope_align256(size_t(n) * (S + 1) * 4);
-        cmax = pope_align256(size_t(n) * S * 4);
-        total = u + v + cmax;
-    }
-};
-
-// One body for both matchers: bin_score == nullptr is the dual softmax with `temperature`
-int dense_match_entry(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                      int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
-                      const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
-                      const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
-                      long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
-                      size_t workspace_bytes, int precision, unsigned* range_flag, void* stream, const float* bin_score,
-                      int skh_iters, int skh_prefilter) {
-    if (!feat0 || !feat1 || !b_ids || !i_ids || !j_ids || !mconf || !mkpts0_c || !mkpts1_c || !counts || !workspace)
+// One body for both matchers; every check comes before the stream's device is touched: a refused call makes no HIP call
+int pope_dense_match_f32(const pope_dense_match_args* args, void* stream) {
+    if (!args) return POPE_ERR_ARG;
+    const pope_dense_match_args& a = *args;
+    if (!a.feat0 || !a.feat1 || !a.b_ids || !a.i_ids || !a.j_ids || !a.mconf || !a.mkpts0_c || !a.mkpts1_c || !a.counts || !a.workspace)
         return POPE_ERR_ARG;
-    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return POPE_ERR_ARG;
-    if (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
-    StreamDevice on_device(stream);
-    const bool publish = conf_matrix != nullptr;
-    const bool padded = border_mask0 || border_mask1;
-    const MatchLayout lay(n, L, S, C, precision, publish);
-    const size_t ext_bytes = padded ? pope_align256(size_t(n) * 4 * 4) : 0;
-    const SinkhornLayout skh(n, L, S);
-    if (workspace_bytes < lay.total + ext_bytes + (bin_score ? skh.total : 0)) return POPE_ERR_WORKSPACE;
-    pope_carver ws{static_cast<char*>(workspace)};   // (every piece of the layout is a multiple of 256 bytes)
+    if (a.n <= 0 || a.L <= 0 || a.S <= 0 || a.C <= 0) return POPE_ERR_ARG;
+    if (a.precision != POPE_PREC_F32_MFMA && a.precision != POPE_PREC_F16X3) return POPE_ERR_ARG;
+    const bool sinkhorn = a.match_type == POPE_MATCH_SINKHORN;
+    if (!sinkhorn && a.match_type != POPE_MATCH_DUAL_SOFTMAX) return POPE_ERR_ARG;
+    if (sinkhorn && (!a.bin_score || a.skh_iters < 1)) return POPE_ERR_ARG;
+    const MatchLayout lay(a);
+    if (a.workspace_bytes < lay.total) return POPE_ERR_WORKSPACE;
+    pope_carver ws{static_cast<char*>(a.workspace)};   // (every piece of the layout is a multiple of 256 bytes)
     MatchParams p = {};
-    p.feat0 = feat0; p.feat1 = feat1;
-    p.n = n; p.L = L; p.S = S; p.C = C;
-    p.bs0 = stride0; p.bs1 = stride1;
-    p.h0 = h0; p.w0 = w0; p.h1 = h1; p.w1 = w1;
-    p.thr = thr; p.temperature = temperature; p.border = border_rm; p.scale = scale;
-    p.publish_conf = publish;
+    p.feat0 = a.feat0; p.feat1 = a.feat1;
+    p.n = a.n; p.L = a.L; p.S = a.S; p.C = a.C;
+    p.bs0 = a.stride0; p.bs1 = a.stride1;
+    p.h0 = a.h0; p.w0 = a.w0; p.h1 = a.h1; p.w1 = a.w1;
+    p.thr = a.thr; p.temperature = sinkhorn ? 1.0f : a.temperature; p.border = a.border_rm; p.scale = a.scale;
+    p.publish_conf = a.conf_matrix != nullptr;
     p.ncb = lay.ncb; p.nrb = lay.nrb; p.nrb2 = lay.nrb2; p.ldp = lay.ldp;
     p.row_max = ws.take<float>(lay.nl);
     p.row_sum = ws.take<float>(lay.nl);
@@ -339,61 +292,32 @@ int dense_match_entry(const float* feat0, long long stride0, const float* feat1,
     p.col_sum = ws.take<float>(lay.ns);
     p.conf_colmax = ws.take<float>(lay.ns);
     p.colmax_part = ws.take<float>(lay.part);
-    if (precision == POPE_PREC_F16X3) {
+    if (a.precision == POPE_PREC_F16X3) {
         p.row_part = ws.take<float>(lay.rowp);
         p.col_pmax = ws.take<float>(lay.colp);
         p.col_psum = ws.take<float>(lay.colp);
         p.planes0 = ws.take(lay.pl0);
         p.planes1 = ws.take(lay.pl1);
     }
-    p.sim = publish ? conf_matrix : ws.take<float>(lay.simb);
-    p.counts = counts;
-    p.range_flag = range_flag;
-    p.b_ids = b_ids; p.i_ids = i_ids; p.j_ids = j_ids;
-    p.mconf = mconf; p.mkpts0 = mkpts0_c; p.mkpts1 = mkpts1_c;
-    p.fill0 = fill_mask0; p.fill1 = fill_mask1;
-    p.border0 = border_mask0; p.border1 = border_mask1;
-    if (padded) p.extent = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.total);
-    p.scale0 = scale0; p.scale1 = scale1;
-    if (!bin_score) return pope_launch_dense_match_f32(p, static_cast<hipStream_t>(stream));
-    pope_carver tail{static_cast<char*>(workspace) + lay.total + ext_bytes};
-    p.bin_score = bin_score; p.skh_iters = skh_iters; p.skh_prefilter = skh_prefilter;
-    p.skh_u = tail.take<float>(skh.u);
-    p.skh_v = tail.take<float>(skh.v);
-    p.skh_cmax = tail.take<float>(skh.cmax);
-    return pope_launch_dense_match_sinkhorn_f32(p, static_cast<hipStream_t>(stream));
-}
-}  // namespace
-
-int pope_dense_match_masked_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                                int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, float temperature, float scale,
-                                const float* fill_mask0, const float* fill_mask1, const float* border_mask0, const float* border_mask1,
-                                const float* scale0, const float* scale1, float* conf_matrix, long long* b_ids, long long* i_ids,
-                                long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace,
-                                size_t workspace_bytes, int precision, unsigned* range_flag, void* stream) {
-    return dense_match_entry(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, temperature, scale, fill_mask0,
-                             fill_mask1, border_mask0, border_mask1, scale0, scale1, conf_matrix, b_ids, i_ids, j_ids, mconf, mkpts0_c,
-                             mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream, nullptr, 0, 0);
-}
-
-size_t pope_dense_match_sinkhorn_workspace_bytes(int n, int L, int S, int C, int precision, int publish_conf, int has_border_masks) {
-    if (n <= 0 || L <= 0 || S <= 0 || C <= 0) return 0;
-    // the matrix holds conf after the confidence pass even when it is not published: it lives in the workspace then
-    return pope_dense_match_masked_workspace_bytes(n, L, S, C, precision, publish_conf, has_border_masks) + SinkhornLayout(n, L, S).total;
-}
-
-int pope_dense_match_sinkhorn_f32(const float* feat0, long long stride0, const float* feat1, long long stride1, int n, int L,
-                                  int S, int C, int h0, int w0, int h1, int w1, float thr, int border_rm, const float* bin_score,
-                                  int skh_iters, int skh_prefilter, float scale, const float* fill_mask0, const float* fill_mask1,
-                                  const float* border_mask0, const float* border_mask1, const float* scale0, const float* scale1,
-                                  float* conf_matrix, long long* b_ids, long long* i_ids, long long* j_ids, float* mconf,
-                                  float* mkpts0_c, float* mkpts1_c, int* counts, void* workspace, size_t workspace_bytes,
-                                  int precision, unsigned* range_flag, void* stream) {
-    if (!bin_score || skh_iters < 1) return POPE_ERR_ARG;
-    return dense_match_entry(feat0, stride0, feat1, stride1, n, L, S, C, h0, w0, h1, w1, thr, border_rm, 1.0f, scale, fill_mask0,
-                             fill_mask1, border_mask0, border_mask1, scale0, scale1, conf_matrix, b_ids, i_ids, j_ids, mconf, mkpts0_c,
-                             mkpts1_c, counts, workspace, workspace_bytes, precision, range_flag, stream, bin_score, skh_iters,
-                             skh_prefilter);
+    p.sim = a.conf_matrix ? a.conf_matrix : ws.take<float>(lay.simb);
+    if (lay.extent) p.extent = ws.take<int>(lay.extent);
+    if (sinkhorn) {
+        p.bin_score = a.bin_score; p.skh_iters = a.skh_iters; p.skh_prefilter = a.skh_prefilter;
+        p.skh_u = ws.take<float>(lay.skh_u);
+        p.skh_v = ws.take<float>(lay.skh_v);
+        p.skh_cmax = ws.take<float>(lay.skh_cmax);
+    }
+    p.counts = a.counts;
+    p.range_flag = a.range_flag;
+    p.b_ids = a.b_ids; p.i_ids = a.i_ids; p.j_ids = a.j_ids;
+    p.mconf = a.mconf; p.mkpts0 = a.mkpts0_c; p.mkpts1 = a.mkpts1_c;
+    p.fill0 = a.fill_mask0; p.fill1 = a.fill_mask1;
+    p.border0 = a.border_mask0; p.border1 = a.border_mask1;
+    p.scale0 = a.scale0; p.scale1 = a.scale1;
+    POPE_TRY(pope_match_params_check(p));
+    StreamDevice on_device(stream);
+    if (sinkhorn) return pope_launch_dense_match_sinkhorn_f32(p, static_cast<hipStream_t>(stream));
+    return pope_launch_dense_match_f32(p, static_cast<hipStream_t>(stream));
 }
 
 size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead) {
@@ -401,10 +325,13 @@ size_t pope_loftr_layer_workspace_bytes(int n, int L, int S, int C, int nhead) {
     return pope_loftr_layer_workspace(n, L, S, C, nhead);
 }
 
-// the three layer entries: one parameter block, the attention body chosen by `attention` (LOFTR_ATTN_*)
-static int loftr_layer_call(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
-                            const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
-                            void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream, int attention) {
+int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
+                                 const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int attention,
+                                 int precision, void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
+    if (attention != POPE_LOFTR_ATTN_LINEAR && attention != POPE_LOFTR_ATTN_FULL) return POPE_ERR_ARG;
+    if (attention == POPE_LOFTR_ATTN_FULL &&
+        (x_mask || source_mask || (C != 256 && C != 128) || nhead != 8 || (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3)))
+        return POPE_ERR_ARG;
     if (!w || !x || !source || !workspace || n <= 0 || L <= 0 || S <= 0) return POPE_ERR_ARG;
     StreamDevice on_device(stream);
     LoftrLayerParams p = {};
@@ -421,28 +348,6 @@ static int loftr_layer_call(const pope_loftr_layer_weights* w, float* x, const f
     p.x_mask = x_mask; p.source_mask = source_mask;
     p.attention = attention;
     return pope_launch_loftr_layer(p, static_cast<hipStream_t>(stream));
-}
-
-int pope_loftr_encoder_layer_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
-                                 int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
-                                 unsigned* range_flag, void* stream) {
-    return pope_loftr_encoder_layer_masked_f32(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace,
-                                               workspace_bytes, range_flag, stream);
-}
-
-int pope_loftr_encoder_layer_masked_f32(const pope_loftr_layer_weights* w, float* x, const float* source, const float* x_mask,
-                                        const float* source_mask, int n, int L, int S, int C, int nhead, float ln_eps, int precision,
-                                        void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
-    return loftr_layer_call(w, x, source, x_mask, source_mask, n, L, S, C, nhead, ln_eps, precision, workspace, workspace_bytes,
-                            range_flag, stream, LOFTR_ATTN_LINEAR);
-}
-
-int pope_loftr_encoder_layer_full_f32(const pope_loftr_layer_weights* w, float* x, const float* source, int n, int L, int S, int C,
-                                      int nhead, float ln_eps, int precision, void* workspace, size_t workspace_bytes,
-                                      unsigned* range_flag, void* stream) {
-    if ((C != 256 && C != 128) || nhead != 8 || (precision != POPE_PREC_F32_MFMA && precision != POPE_PREC_F16X3)) return POPE_ERR_ARG;
-    return loftr_layer_call(w, x, source, nullptr, nullptr, n, L, S, C, nhead, ln_eps, precision, workspace, workspace_bytes, range_flag,
-                            stream, LOFTR_ATTN_FULL);
 }
 
 int pope_loftr_full_attention_f32(const float* q, const float* kv, int n, int L, int S, int C, int nhead, int precision, float* out,
@@ -514,20 +419,10 @@ size_t pope_fine_preprocess_workspace_bytes(int M, int Wn, int Cc, int Cf) {
 
 int pope_fine_preprocess_f32(const float* feat_f0, const long long* strides0, int H0, int W0, int wc0, const float* feat_f1,
                              const long long* strides1, int H1, int W1, int wc1, const float* feat_c0, const float* feat_c1, int L,
-                             int S, int Cc, int Cf, const long long* b_ids, const long long* i_ids, const long long* j_ids, int M, int Wn,
-                             int stride, const void* down_wp, const float* down_b, const void* merge_wp, const float* merge_b,
-                             int precision, float* out, void* workspace, size_t workspace_bytes, unsigned* range_flag, void* stream) {
-    return pope_fine_preprocess_indexed_f32(feat_f0, strides0, H0, W0, wc0, feat_f1, strides1, H1, W1, wc1, feat_c0, feat_c1, L, S, Cc, Cf,
-                                            b_ids, i_ids, j_ids, M, Wn, stride, down_wp, down_b, merge_wp, merge_b, precision, out,
-                                            workspace, workspace_bytes, range_flag, nullptr, 0, 0, stream);
-}
-
-int pope_fine_preprocess_indexed_f32(const float* feat_f0, const long long* strides0, int H0, int W0, int wc0, const float* feat_f1,
-                                     const long long* strides1, int H1, int W1, int wc1, const float* feat_c0, const float* feat_c1, int L,
-                                     int S, int Cc, int Cf, const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
-                                     int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
-                                     const float* merge_b, int precision, float* out, void* workspace, size_t workspace_bytes,
-                                     unsigned* range_flag, const long long* ref0_of_pair, int n, int n0, void* stream) {
+                             int S, int Cc, int Cf, const long long* b_ids, const long long* i_ids, const long long* j_ids, int M,
+                             int Wn, int stride, const void* down_wp, const float* down_b, const void* merge_wp,
+                             const float* merge_b, int precision, float* out, void* workspace, size_t workspace_bytes,
+                             unsigned* range_flag, const long long* ref0_of_pair, int n, int n0, void* stream) {
     // the checks that need no device come first: a bad call returns before any HIP call
     if (n < 0 || n0 < 0 || (ref0_of_pair && (n == 0 || n0 == 0))) return POPE_ERR_ARG;
     if (!feat_f0 || !feat_f1 || !feat_c0 || !feat_c1 || !b_ids || !i_ids || !j_ids || !down_wp || !merge_wp || !out || !workspace)
@@ -549,13 +444,7 @@ int pope_fine_preprocess_indexed_f32(const float* feat_f0, const long long* stri
 }
 
 int pope_fine_match_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
-                        float* expec_f, float* mkpts1_f, void* stream) {
-    StreamDevice on_device(stream);
-    return pope_launch_fine_match(win0, win1, M, Wn, C, mkpts1_c, scale_px, expec_f, mkpts1_f, static_cast<hipStream_t>(stream));
-}
-
-int pope_fine_match_scaled_f32(const float* win0, const float* win1, int M, int Wn, int C, const float* mkpts1_c, float scale_px,
-                               const float* scale1, const long long* b_ids, float* expec_f, float* mkpts1_f, void* stream) {
+                        const float* scale1, const long long* b_ids, float* expec_f, float* mkpts1_f, void* stream) {
     if (!win0 || !win1 || !mkpts1_c || !expec_f || !mkpts1_f || (scale1 && !b_ids) || M <= 0 || Wn <= 0 || Wn * Wn > 64 || C <= 0)
         return POPE_ERR_ARG;
     StreamDevice on_device(stream);

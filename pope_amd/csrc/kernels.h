@@ -238,6 +238,7 @@ struct MatchParams {
     float skh_norm, skh_log_mu_bin, skh_log_nu_bin;   // -log(L + S), log(S) + norm, log(L) + norm (fp32, set by the launcher)
 };
 int pope_match_nrb2(int L);
+int pope_match_params_check(const MatchParams& p);   // host only (no HIP call); both launchers run it first
 int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream);
 // match_type='sinkhorn': same contraction (temperature 1), then the passes of sinkhorn.hip in place of the dual softmax, then
 // the same selection / compaction kernels.  The matrix always ends up holding conf (in the workspace when not published).
@@ -330,9 +331,8 @@ struct LoftrLayerParams {
     // source_mask [n, S] padded source rows' K and V; null = no mask (the unmasked kernels)
     const float* x_mask;
     const float* source_mask;
-    int attention;         // LOFTR_ATTN_LINEAR (0: a zeroed struct is the linear layer) | LOFTR_ATTN_FULL (softmax; no masks)
+    int attention;         // POPE_LOFTR_ATTN_LINEAR (0: a zeroed struct is the linear layer) | POPE_LOFTR_ATTN_FULL (softmax; no masks)
 };
-enum { LOFTR_ATTN_LINEAR = 0, LOFTR_ATTN_FULL = 1 };
 // Full softmax attention of the layer (loftr_attention.hip): q [n L, C], kv [n S, 2C] (k | v) fp32 -> the message [n L, C] as fp32
 // rows, or (planes) as activation planes with POPE_RANGE_QKV on a value outside the f16 range.  C = 256 / 128, H = 8.
 int pope_loftr_full_attention_check(const void* q, const void* kv, int n, int L, int S, int C, int H, const void* out);   // no HIP call

@@ -7,7 +7,7 @@
 //     msg = (Q . KV) * 1 / (Q . Ksum + 1e-6) * S
 //     msg = LayerNorm(msg Wm^T)  (eps 1e-5)
 //     x  <- x + LayerNorm(relu(cat[x, msg] W0^T) W1^T)
-// With LoftrLayerParams::attention = LOFTR_ATTN_FULL the second and third line are the softmax attention of
+// With LoftrLayerParams::attention = POPE_LOFTR_ATTN_FULL the second and third line are the softmax attention of
 // linear_attention.py:50-81 instead, msg = softmax(q k^T / sqrt(D)) v per head: one launch (loftr_attention.hip), no masks.
 // The five projections run on the f16x3 planes GEMM (gemm_planes.hip: fp32-equivalent arithmetic, bias-free, the MLP's
 // ReLU in the epilogue, its output straight to planes); everything around them is small and HBM / launch bound:
@@ -296,8 +296,8 @@ int pope_launch_loftr_layer(const LoftrLayerParams& p, hipStream_t stream) {
     if (!p.norm1_w || !p.norm1_b || !p.norm2_w || !p.norm2_b) return POPE_ERR_ARG;
     if (f32 ? (!p.q_w || !p.kv_w || !p.merge_w || !p.mlp0_w || !p.mlp1_w) : (!p.q_wp || !p.kv_wp || !p.merge_wp || !p.mlp0_wp || !p.mlp1_wp))
         return POPE_ERR_ARG;
-    const bool full = p.attention == LOFTR_ATTN_FULL;
-    if (!full && p.attention != LOFTR_ATTN_LINEAR) return POPE_ERR_ARG;
+    const bool full = p.attention == POPE_LOFTR_ATTN_FULL;
+    if (!full && p.attention != POPE_LOFTR_ATTN_LINEAR) return POPE_ERR_ARG;
     if (full && (p.x_mask || p.source_mask)) return POPE_ERR_ARG;   // a padded query row is NaN in the reference's FullAttention
     if (p.ws_bytes < pope_loftr_layer_workspace(p.n, p.L, p.S, C, H)) return POPE_ERR_WORKSPACE;
     const size_t rx = size_t(p.n) * p.L, rs = size_t(p.n) * p.S;

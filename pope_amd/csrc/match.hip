@@ -565,9 +565,7 @@ void launch_conf_and_select(const MatchParams& p, hipStream_t stream) {
 
 int pope_match_nrb2(int L) { return (L + CP_ROWS - 1) / CP_ROWS; }
 
-namespace {
-
-int check_match_params(const MatchParams& p) {
+int pope_match_params_check(const MatchParams& p) {
     if (p.n <= 0 || p.L <= 0 || p.S <= 0 || p.C <= 0 || (p.C & 3) || p.n > 65535) return POPE_ERR_ARG;
     if (p.L != p.h0 * p.w0 || p.S != p.h1 * p.w1) return POPE_ERR_ARG;
     if (p.bs0 < (long long)p.L * p.C || p.bs1 < (long long)p.S * p.C || (p.bs0 & 3) || (p.bs1 & 3)) return POPE_ERR_ARG;
@@ -576,6 +574,8 @@ int check_match_params(const MatchParams& p) {
     if ((p.border0 || p.border1) && !p.extent) return POPE_ERR_ARG;
     return POPE_OK;
 }
+
+namespace {
 
 // sim = (f0 / sqrt(C)) . (f1 / sqrt(C))^T / temperature with the padding fill, and its softmax statistics: row_max / row_sum
 // always, col_max / col_sum when `col_stats` (the Sinkhorn matcher's column steps run on u, not on sim alone)
@@ -627,7 +627,7 @@ void launch_compaction(const MatchParams& p, hipStream_t stream) {
 }  // namespace
 
 int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
-    POPE_TRY(check_match_params(p));
+    POPE_TRY(pope_match_params_check(p));
     POPE_TRY(launch_contraction(p, true, stream));
     if (p.extent) hipLaunchKernelGGL(border_extent_kernel, dim3(p.n, 2), dim3(256), 0, stream, p);
     if (p.publish_conf) launch_conf_and_select<true>(p, stream);
@@ -637,7 +637,7 @@ int pope_launch_dense_match_f32(const MatchParams& p, hipStream_t stream) {
 }
 
 int pope_launch_dense_match_sinkhorn_f32(MatchParams p, hipStream_t stream) {
-    POPE_TRY(check_match_params(p));
+    POPE_TRY(pope_match_params_check(p));
     if (!p.bin_score || p.skh_iters < 1 || !p.skh_u || !p.skh_v || !p.skh_cmax) return POPE_ERR_ARG;
     p.temperature = 1.0f;   // coarse_matching.py:122: the similarity of the transport problem has no temperature
     p.skh_norm = -logf(float(p.L + p.S));

@@ -231,37 +231,20 @@ size_t pope_vit_workspace_bytes(int B, int ntok, int dim, int hidden) {
     return pope_align256(rows * dim * sizeof(float)) + pope_align256(rows * big * sizeof(float));
 }
 
-int pope_vit_forward_f32(const pope_vit_weights* w, const float* img, int B, int H, int W, const float* posb,
+int pope_vit_forward_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
                          float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
                          float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
                          void* stream) {
-    return pope_vit_forward_ffn_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host,
-                                    workspace, workspace_bytes, range_flag, stream);
-}
-
-int pope_vit_forward_ffn_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W, const float* posb,
-                             float* x_prenorm, float* x_norm, int n_taps, const int* tap_blocks_host,
-                             float* const* tap_out_host, void* workspace, size_t workspace_bytes, unsigned* range_flag,
-                             void* stream) {
     Recorder rec{nullptr, 0, nullptr, 0};
     return vit_forward_impl(w, ffn, img, B, H, W, posb, x_prenorm, x_norm, n_taps, tap_blocks_host, tap_out_host, workspace,
                             workspace_bytes, range_flag, stream, rec);
 }
 
-int pope_vit_forward_profiled_mask_f32(const pope_vit_weights* w, const float* img, int B, int H, int W,
-                                       const float* posb, float* x_prenorm, float* x_norm, void* workspace,
-                                       size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                       void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
-                                       unsigned kind_mask) {
-    return pope_vit_forward_ffn_profiled_mask_f32(w, POPE_FFN_MLP, img, B, H, W, posb, x_prenorm, x_norm, workspace, workspace_bytes,
-                                                  range_flag, stream, events_host, n_events, kinds_host, n_launches_host, kind_mask);
-}
-
-int pope_vit_forward_ffn_profiled_mask_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W,
-                                           const float* posb, float* x_prenorm, float* x_norm, void* workspace,
-                                           size_t workspace_bytes, unsigned* range_flag, void* stream,
-                                           void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
-                                           unsigned kind_mask) {
+int pope_vit_forward_profiled_f32(const pope_vit_weights* w, int ffn, const float* img, int B, int H, int W,
+                                  const float* posb, float* x_prenorm, float* x_norm, void* workspace,
+                                  size_t workspace_bytes, unsigned* range_flag, void* stream,
+                                  void* const* events_host, int n_events, int* kinds_host, int* n_launches_host,
+                                  unsigned kind_mask) {
     if (!events_host || n_events < 2 || !kinds_host || !n_launches_host) return POPE_ERR_ARG;
     Recorder rec{events_host, n_events, kinds_host, 0};
     rec.mask = kind_mask;

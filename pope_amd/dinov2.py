@@ -372,16 +372,16 @@ class DinoVisionTransformer(nn.Module):
             if slot is not None:
                 off, ev, cap, kinds = slot
                 n_launch = C.c_int()
-                check(L.pope_vit_forward_ffn_profiled_mask_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
-                                                               C.c_void_p(ws.data_ptr()), ws.numel(), flag_ptr,
-                                                               stream_of(x.device), ev, cap, kinds, C.byref(n_launch),
-                                                               self.profiler.mask),
-                      "pope_vit_forward_ffn_profiled_mask_f32")
+                check(L.pope_vit_forward_profiled_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
+                                                      C.c_void_p(ws.data_ptr()), ws.numel(), flag_ptr,
+                                                      stream_of(x.device), ev, cap, kinds, C.byref(n_launch),
+                                                      self.profiler.mask),
+                      "pope_vit_forward_profiled_f32")
                 self.profiler.commit(off, n_launch.value)
             else:
-                check(L.pope_vit_forward_ffn_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
-                                                 len(taps), tap_blocks, tap_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                 flag_ptr, stream_of(x.device)), "pope_vit_forward_ffn_f32")
+                check(L.pope_vit_forward_f32(C.byref(w), ffn, ptr(x), B, H, W, ptr(posb), ptr(x_pre), ptr(x_norm),
+                                             len(taps), tap_blocks, tap_ptrs, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                             flag_ptr, stream_of(x.device)), "pope_vit_forward_f32")
         if own_flag is not None:
             bits = int(own_flag.item())  # the direct call's synchronisation point
             if bits:

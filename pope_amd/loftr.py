@@ -297,7 +297,7 @@ def _refuse_full_masks(attention, *masks):
 class LoFTREncoderLayer(nn.Module):
     """loftr_module/transformer.py:7-58 with the linear attention of linear_attention.py:20-47 (attention='linear') or the
     softmax attention of :50-81 ('full'; same parameters, no padding masks).  The layer update is ONE call into the HIP
-    library (pope_loftr_encoder_layer_f32 / pope_loftr_encoder_layer_full_f32: five GEMMs + the attention kernels + both
+    library (pope_loftr_encoder_layer_f32: five GEMMs + the attention kernels + both
     LayerNorms); this module holds the parameters."""
 
     def __init__(self, d_model, nhead, attention="linear"):
@@ -354,19 +354,12 @@ class LoFTREncoderLayer(nn.Module):
         n, L, Cd = x.shape
         S = source.shape[1]
         flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        if x_mask is not None or source_mask is not None:
-            with _lib.on_device_of(x):
-                _lib.check(_lib.lib().pope_loftr_encoder_layer_masked_f32(
-                    C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), _lib.ptr(x_mask), _lib.ptr(source_mask),
-                    n, L, S, Cd, self.nhead, float(self.norm1.eps), _lib.PRECISIONS[precision], C.c_void_p(workspace.data_ptr()),
-                    workspace.numel(), C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), "pope_loftr_encoder_layer_masked_f32")
-            return flag
-        name = "pope_loftr_encoder_layer_full_f32" if self.attention == "full" else "pope_loftr_encoder_layer_f32"
         with _lib.on_device_of(x):
-            _lib.check(getattr(_lib.lib(), name)(
-                C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), n, L, S, Cd, self.nhead,
-                float(self.norm1.eps), _lib.PRECISIONS[precision], C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)), name)
+            _lib.check(_lib.lib().pope_loftr_encoder_layer_f32(
+                C.byref(w), C.c_void_p(x.data_ptr()), C.c_void_p(source.data_ptr()), _lib.ptr(x_mask), _lib.ptr(source_mask),
+                n, L, S, Cd, self.nhead, float(self.norm1.eps), _lib.LOFTR_ATTENTIONS[self.attention], _lib.PRECISIONS[precision],
+                C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(flag.data_ptr()), _lib.stream_of(x.device)),
+                "pope_loftr_encoder_layer_f32")
         return flag
 
     @torch.no_grad()
@@ -610,18 +603,6 @@ class FinePreprocess(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         s0, s1 = (C.c_longlong * 4)(*f0.stride()), (C.c_longlong * 4)(*f1.stride())
-        if ref0_of_pair is not None:   # shared references: f0 has one row per reference, pair b reads row ref0_of_pair[b]
-            with _lib.on_device_of(f0):
-                _lib.check(lib.pope_fine_preprocess_indexed_f32(
-                    C.c_void_p(f0.data_ptr()), s0, f0.shape[2], f0.shape[3], int(data["hw0_c"][1]),
-                    C.c_void_p(f1.data_ptr()), s1, f1.shape[2], f1.shape[3], int(data["hw1_c"][1]),
-                    C.c_void_p(fc0.data_ptr()), C.c_void_p(fc1.data_ptr()), fc0.shape[1], fc1.shape[1], fc0.shape[2], Cf,
-                    C.c_void_p(b.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(j.data_ptr()), M, W, int(stride),
-                    C.c_void_p(dwp.data_ptr()), C.c_void_p(db.data_ptr()), C.c_void_p(mwp.data_ptr()), C.c_void_p(mb.data_ptr()),
-                    _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
-                    C.c_void_p(flag.data_ptr()), C.c_void_p(ref0_of_pair.data_ptr()), int(ref0_of_pair.shape[0]), int(f0.shape[0]),
-                    _lib.stream_of(dev)), "pope_fine_preprocess_indexed_f32")
-            return (out[:M], out[M:]), flag
         with _lib.on_device_of(f0):
             _lib.check(lib.pope_fine_preprocess_f32(
                 C.c_void_p(f0.data_ptr()), s0, f0.shape[2], f0.shape[3], int(data["hw0_c"][1]),
@@ -629,8 +610,10 @@ class FinePreprocess(nn.Module):
                 C.c_void_p(fc0.data_ptr()), C.c_void_p(fc1.data_ptr()), fc0.shape[1], fc1.shape[1], fc0.shape[2], Cf,
                 C.c_void_p(b.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(j.data_ptr()), M, W, int(stride),
                 C.c_void_p(dwp.data_ptr()), C.c_void_p(db.data_ptr()), C.c_void_p(mwp.data_ptr()), C.c_void_p(mb.data_ptr()),
-                _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(flag.data_ptr()),
-                _lib.stream_of(dev)), "pope_fine_preprocess_f32")
+                _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
+                C.c_void_p(flag.data_ptr()),
+                # shared references: f0 has one row per reference, pair b reads row ref0_of_pair[b] (None: one row per pair)
+                _lib.ptr(ref0_of_pair), int(fc0.shape[0]), int(f0.shape[0]), _lib.stream_of(dev)), "pope_fine_preprocess_f32")
         return (out[:M], out[M:]), flag
 
     @torch.no_grad()
@@ -668,7 +651,7 @@ class FineMatching(nn.Module):
     """utils/fine_matching.py:9-74: correlate the centre of window 0 with window 1, softmax(1/sqrt(C)),
     expectation over the normalised [-1,1]^2 grid (x,y) (kornia dsnt.spatial_expectation2d / create_meshgrid
     in the reference; both are closed-form, see SURVEY.md §8c 'unpinned'): one kernel, fp32 throughout
-    (pope_fine_match_f32; pope_fine_match_scaled_f32 with per-pair `scale1` rescaling)."""
+    (pope_fine_match_f32, with optional per-pair `scale1` rescaling)."""
 
     @torch.no_grad()
     def forward(self, feat_f0, feat_f1, data):
@@ -688,21 +671,15 @@ class FineMatching(nn.Module):
         expec = torch.empty(M, 3, dtype=torch.float32, device=w0.device)
         mk1f = torch.empty(M, 2, dtype=torch.float32, device=w0.device)
         # fine_matching.py:68: the offset is rescaled by data['scale1'] — keyed on 'scale0' being present, as in the reference
-        scale1 = None
+        scale1 = b_ids = None
         if "scale0" in data:
             n = int(data["bs"]) if "bs" in data else data["scale1"].shape[0]
             scale1 = _lib.pair_scale(data["scale1"], n, w0.device, "FineMatching scale1")
+            b_ids = data["b_ids"].contiguous()
         with _lib.on_device_of(w0):
-            if scale1 is None:
-                _lib.check(_lib.lib().pope_fine_match_f32(
-                    C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
-                    float(scale), C.c_void_p(expec.data_ptr()), C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)),
-                    "pope_fine_match_f32")
-            else:
-                b_ids = data["b_ids"].contiguous()
-                _lib.check(_lib.lib().pope_fine_match_scaled_f32(
-                    C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
-                    float(scale), C.c_void_p(scale1.data_ptr()), C.c_void_p(b_ids.data_ptr()), C.c_void_p(expec.data_ptr()),
-                    C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)), "pope_fine_match_scaled_f32")
+            _lib.check(_lib.lib().pope_fine_match_f32(
+                C.c_void_p(w0.data_ptr()), C.c_void_p(w1.data_ptr()), M, W, Cd, C.c_void_p(mk1c.data_ptr()),
+                float(scale), _lib.ptr(scale1), _lib.ptr(b_ids), C.c_void_p(expec.data_ptr()),
+                C.c_void_p(mk1f.data_ptr()), _lib.stream_of(w0.device)), "pope_fine_match_f32")
         # get_fine_match (:61-74): image 0 keeps its coarse cell centre, image 1 moves inside the window
         data.update({"expec_f": expec, "mkpts0_f": data["mkpts0_c"], "mkpts1_f": mk1f})

@@ -98,7 +98,6 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     sc0 = _lib.pair_scale(scale0, n, dev, "dense_match scale0")
     sc1 = _lib.pair_scale(scale1, n, dev, "dense_match scale1")
     extra = (fill0, fill1, bord0, bord1, sc0, sc1)
-    masked = any(t is not None for t in extra)
     if n == 0:   # an empty batch: what torch.where gives the reference on a [0, L, S] mask
         el, ef = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
         out = {"b_ids": el, "i_ids": el.clone(), "j_ids": el.clone(), "gt_mask": torch.empty(0, dtype=torch.bool, device=dev),
@@ -110,19 +109,10 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     precision = precision or DEFAULT_PRECISION
     if Cc % 32 or Cc < 64:
         precision = "f32"   # the planes layout needs whole 32-column chunks
-    prec = _lib.PRECISIONS[precision]
     if sinkhorn:
         bin_score = bin_score.detach()
         if bin_score.device != dev:
             bin_score = bin_score.to(dev)
-        ws_bytes = lib.pope_dense_match_sinkhorn_workspace_bytes(n, L, S, Cc, prec, 1 if want_conf else 0,
-                                                                 int(bord0 is not None or bord1 is not None))
-    elif masked:
-        ws_bytes = lib.pope_dense_match_masked_workspace_bytes(n, L, S, Cc, prec, 1 if want_conf else 0,
-                                                               int(bord0 is not None or bord1 is not None))
-    else:
-        ws_bytes = lib.pope_dense_match_workspace_bytes_prec(n, L, S, Cc, prec, 1 if want_conf else 0)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     conf = torch.empty(n, L, S, dtype=torch.float32, device=dev) if want_conf else None
     cap = n * L
     b_ids = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -132,33 +122,23 @@ def dense_match(feat0, feat1, hw0_c, hw1_c, hw0_i, thr=0.2, border_rm=2, tempera
     mk0 = torch.empty(cap, 2, dtype=torch.float32, device=dev)
     mk1 = torch.empty(cap, 2, dtype=torch.float32, device=dev)
     counts = torch.zeros(n + 2, dtype=torch.int32, device=dev)   # per-pair counts | total | f16x3 range-guard word
-    flag_ptr = C.c_void_p(counts.data_ptr() + 4 * (n + 1)) if precision == "f16x3" else None
-    scale = hw0_i[0] / hw0_c[0]  # coarse_matching.py:242 (heights only)
-    # (the stride of a size-1 dimension is arbitrary in torch: a batch of one has no batch stride to speak of)
-    bs0 = feat0.stride(0) if n > 1 else L * Cc
-    bs1 = feat1.stride(0) if n > 1 else S * Cc
+    args = _lib.DenseMatchArgs(
+        feat0=feat0.data_ptr(), feat1=feat1.data_ptr(),
+        # (the stride of a size-1 dimension is arbitrary in torch: a batch of one has no batch stride to speak of)
+        stride0=feat0.stride(0) if n > 1 else L * Cc, stride1=feat1.stride(0) if n > 1 else S * Cc,
+        n=n, L=L, S=S, C=Cc, h0=h0, w0=w0, h1=h1, w1=w1, thr=float(thr), border_rm=int(border_rm), temperature=float(temperature),
+        scale=float(hw0_i[0] / hw0_c[0]),  # coarse_matching.py:242 (heights only)
+        match_type=_lib.MATCH_TYPES[match_type], bin_score=ptr(bin_score) if sinkhorn else None,
+        skh_iters=int(skh_iters), skh_prefilter=int(bool(skh_prefilter)),
+        fill_mask0=ptr(fill0), fill_mask1=ptr(fill1), border_mask0=ptr(bord0), border_mask1=ptr(bord1), scale0=ptr(sc0),
+        scale1=ptr(sc1), conf_matrix=ptr(conf), b_ids=ptr(b_ids), i_ids=ptr(i_ids), j_ids=ptr(j_ids), mconf=ptr(mconf),
+        mkpts0_c=ptr(mk0), mkpts1_c=ptr(mk1), counts=ptr(counts), precision=_lib.PRECISIONS[precision],
+        range_flag=counts.data_ptr() + 4 * (n + 1) if precision == "f16x3" else None)
+    args.workspace_bytes = lib.pope_dense_match_workspace_bytes(C.byref(args))
+    ws = torch.empty(args.workspace_bytes, dtype=torch.uint8, device=dev)
+    args.workspace = ws.data_ptr()
     with on_device_of(feat0):
-        if sinkhorn:
-            check(lib.pope_dense_match_sinkhorn_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
-                                                    bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
-                                                    C.c_void_p(bin_score.data_ptr()), int(skh_iters), int(bool(skh_prefilter)),
-                                                    float(scale), *[ptr(t) for t in extra], ptr(conf), ptr(b_ids),
-                                                    ptr(i_ids), ptr(j_ids), ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts),
-                                                    C.c_void_p(ws.data_ptr()), ws_bytes, prec, flag_ptr, stream_of(dev)),
-                  "pope_dense_match_sinkhorn_f32")
-        elif masked:
-            check(lib.pope_dense_match_masked_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
-                                                  bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
-                                                  float(temperature), float(scale), *[ptr(t) for t in extra], ptr(conf), ptr(b_ids),
-                                                  ptr(i_ids), ptr(j_ids), ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts),
-                                                  C.c_void_p(ws.data_ptr()), ws_bytes, prec, flag_ptr, stream_of(dev)),
-                  "pope_dense_match_masked_f32")
-        else:
-            check(lib.pope_dense_match_prec_f32(C.c_void_p(feat0.data_ptr()), bs0, C.c_void_p(feat1.data_ptr()),
-                                                bs1, n, L, S, Cc, h0, w0, h1, w1, float(thr), int(border_rm),
-                                                float(temperature), float(scale), ptr(conf), ptr(b_ids), ptr(i_ids), ptr(j_ids),
-                                                ptr(mconf), ptr(mk0), ptr(mk1), ptr(counts), C.c_void_p(ws.data_ptr()), ws_bytes,
-                                                prec, flag_ptr, stream_of(dev)), "pope_dense_match_prec_f32")
+        check(lib.pope_dense_match_f32(C.byref(args), stream_of(dev)), "pope_dense_match_f32")
     counts_h = counts.cpu()  # sync point
     if int(counts_h[n + 1]):   # features outside the f16x3 range: nothing of this call is valid
         msg = (f"pope_amd: f16x3 range contract breached in dense_match ({_lib.describe_range_bits(int(counts_h[n + 1]))}: "

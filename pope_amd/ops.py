@@ -48,9 +48,9 @@ def linear(a, weight, bias=None, epilogue=EPI_BIAS, gamma=None, res=None, out=No
     if out is None:
         out = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
     with on_device_of(a):
-        check(_lib.lib().pope_linear_prec_f32(ptr(a), ptr(weight), ptr(bias), ptr(out), m, n, k, epilogue, ptr(gamma),
-                                              ptr(res), _lib.PRECISIONS[precision], _flag_ptr(range_flag), stream_of(a.device)),
-                  "pope_linear_prec_f32")
+        check(_lib.lib().pope_linear_f32(ptr(a), ptr(weight), ptr(bias), ptr(out), m, n, k, epilogue, ptr(gamma),
+                                         ptr(res), _lib.PRECISIONS[precision], _flag_ptr(range_flag), stream_of(a.device)),
+              "pope_linear_f32")
     return out
 
 
@@ -90,8 +90,8 @@ def attention(qkv, heads, precision="f32", range_flag=None):
     assert d3 == 3 * heads * 64
     out = torch.empty(b, n, heads * 64, device=qkv.device, dtype=torch.float32)
     with on_device_of(qkv):
-        check(_lib.lib().pope_attention_prec_f32(ptr(qkv), ptr(out), b, n, heads, _lib.PRECISIONS[precision],
-                                                 _flag_ptr(range_flag), stream_of(qkv.device)), "pope_attention_prec_f32")
+        check(_lib.lib().pope_attention_f32(ptr(qkv), ptr(out), b, n, heads, _lib.PRECISIONS[precision],
+                                            _flag_ptr(range_flag), stream_of(qkv.device)), "pope_attention_f32")
     return out
 
 

@@ -1,7 +1,7 @@
 """In-situ per-kernel timing of the product path with HIP events (used by bench.py's roofline leg).
 
 `KernelProfiler` owns a pool of hipEvents; while `model.profiler` is set, every forward goes through
-`pope_vit_forward_profiled_mask_f32`, which brackets the kernel launches of the selected kinds with events
+`pope_vit_forward_profiled_f32`, which brackets the kernel launches of the selected kinds with events
 on the launch stream (all kinds by default; `kinds=("attention",)` times one kernel and leaves every other
 launch back to back as in the untimed path).  After a synchronise, `summary()` turns the event pairs into
 per-kernel-kind durations.

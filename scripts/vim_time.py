@@ -68,7 +68,7 @@ def layer_ops(model, B, precision):
         return lambda: _lib.check(lib.pope_linear_planes_f32(P(a), wp, None, P(c), None, m, n, kk, 0, None, None, fp, None), "linear")
 
     def linear_prec(a, wf, c, m, n, kk):
-        return lambda: _lib.check(lib.pope_linear_prec_f32(P(a), wf, None, P(c), m, n, kk, 0, None, None, prec, fp, None), "linear")
+        return lambda: _lib.check(lib.pope_linear_f32(P(a), wf, None, P(c), m, n, kk, 0, None, None, prec, fp, None), "linear")
 
     ops = {"add_rmsnorm": lambda: _lib.check(lib.pope_vim_add_rmsnorm_f32(P(hid), P(res), P(res), k.norm_w, None if x3 else P(op),
                                                                           P(op) if x3 else None, M, d, 1e-5, 1, 0, fp, None), "norm"),

@@ -8,9 +8,9 @@ The kernels, through their entries:
               linattn_apply_kernel): the per-head D x D state is summed over the source rows in chunks of c rows, the chunk
               partials in chunk order, and a workgroup of the message kernel serves r query rows, 256 / C of them per pass;
               c and r are read from pope_loftr_linear_attention_seams, never written here as literals
-  layer       pope_loftr_encoder_layer_f32 / _masked_f32 through LoFTREncoderLayer.update_: the same attention between five
+  layer       pope_loftr_encoder_layer_f32 (with and without masks) through LoFTREncoderLayer.update_: the same attention between five
               GEMMs, ln_cat_planes_kernel and ln_add_kernel
-  fine match  pope_fine_match_f32 / pope_fine_match_scaled_f32 (csrc/fine.hip: fine_match_kernel, four matches per workgroup)
+  fine match  pope_fine_match_f32 without and with scale1 (csrc/fine.hip: fine_match_kernel, four matches per workgroup)
   fine pre    pope_fine_preprocess_f32 (fine_gather_coarse_kernel, fine_gather_windows_kernel, two GEMMs)
 
 Comparison of one GROUP of outputs (the project's convention, MARGIN = 4, plus a floor):

@@ -39,7 +39,7 @@ def test_code_object_is_gfx950():
 
 
 def test_abi_version_and_errors(hip_lib):
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
     assert hip_lib.pope_error_string(0) == b"ok"
     assert b"workspace" in hip_lib.pope_error_string(-3)
 
@@ -49,14 +49,17 @@ def test_workspace_queries(hip_lib):
     n = hip_lib.pope_vit_workspace_bytes(64, 1531, 384, 1536)
     assert n >= 64 * 1531 * 5 * 384 * 4 and n < 64 * 1531 * 5 * 384 * 4 + 1024
     assert hip_lib.pope_vit_workspace_bytes(0, 1, 1, 1) == 0
-    assert hip_lib.pope_dense_match_workspace_bytes(2, 1530, 1530) >= 8 * 2 * 1530 * 4
+    import ctypes
+    args = _lib.DenseMatchArgs(n=2, L=1530, S=1530, C=4, precision=_lib.PREC_F32_MFMA, conf_matrix=64)   # conf published
+    assert hip_lib.pope_dense_match_workspace_bytes(ctypes.byref(args)) >= 8 * 2 * 1530 * 4
+    assert hip_lib.pope_dense_match_workspace_bytes(None) == 0
 
 
 def test_argument_validation_without_gpu(hip_lib):
     # invalid arguments are rejected before any HIP call is made
     assert hip_lib.pope_layernorm_f32(None, None, None, None, 4, 384, 1e-6, None) == -1
-    assert hip_lib.pope_linear_f32(None, None, None, None, 1, 1, 4, 0, None, None, None) == -1
-    assert hip_lib.pope_attention_f32(None, None, 1, 1, 6, None) == -1
+    assert hip_lib.pope_linear_f32(None, None, None, None, 1, 1, 4, 0, None, None, _lib.PREC_F32_MFMA, None, None) == -1
+    assert hip_lib.pope_attention_f32(None, None, 1, 1, 6, _lib.PREC_F32_MFMA, None, None) == -1
     # every attention entry shares one argument check; nothing below gets as far as a launch (a null range flag: no scan).
     # The accepting side of a bound cannot be shown here: a call that passes the check launches.
     import ctypes
@@ -64,9 +67,8 @@ def test_argument_validation_without_gpu(hip_lib):
     ok = (ctypes.addressof(buf) + 15) & ~15          # 16-byte aligned, never dereferenced
     count = ctypes.c_longlong(0)
     entries = {
-        "f32": lambda q, o, B, N, H: hip_lib.pope_attention_f32(q, o, B, N, H, None),
-        "prec f32": lambda q, o, B, N, H: hip_lib.pope_attention_prec_f32(q, o, B, N, H, _lib.PREC_F32_MFMA, None, None),
-        "prec f16x3": lambda q, o, B, N, H: hip_lib.pope_attention_prec_f32(q, o, B, N, H, _lib.PREC_F16X3, None, None),
+        "f32": lambda q, o, B, N, H: hip_lib.pope_attention_f32(q, o, B, N, H, _lib.PREC_F32_MFMA, None, None),
+        "f16x3": lambda q, o, B, N, H: hip_lib.pope_attention_f32(q, o, B, N, H, _lib.PREC_F16X3, None, None),
         "planes": lambda q, o, B, N, H: hip_lib.pope_attention_planes_f32(q, o, B, N, H, None),
         "planes diag": lambda q, o, B, N, H: hip_lib.pope_attention_planes_diag_f32(q, o, B, N, H, ctypes.byref(count), None),
         "f16": lambda q, o, B, N, H: hip_lib.pope_attention_f16(q, o, B, N, H, None),
@@ -81,6 +83,71 @@ def test_argument_validation_without_gpu(hip_lib):
         # (N + 64) * 6144 >= 2^32 - 512 from N = 698987
         assert call(ok, ok, 1, 698987 if name == "f16" else 349526, 16) == -1, name
     assert hip_lib.pope_attention_planes_diag_f32(ok, ok, 1, 64, 6, None, None) == -1    # the diagnostic entry needs its counter
+
+
+def _header_struct_fields(name):
+    """Field names of `typedef struct <name> { ... }` in pope_hip.h, in declaration order."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pope_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
+    return [re.search(r"(\w+)\s*$", d).group(1) for stmt in body.split(";") for d in stmt.split(",") if d.strip()]
+
+
+def test_dense_match_args_layout(tmp_path):
+    """The ctypes mirror of pope_dense_match_args has the C struct's size, field names, field order and offsets (the check the
+    positional signatures never had)."""
+    import ctypes
+    names = _header_struct_fields("pope_dense_match_args")
+    assert names == [n for n, _ in _lib.DenseMatchArgs._fields_]
+    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"pope_hip.h\"\nint main(void){\n"
+    src += "printf(\"%zu\\n\", sizeof(pope_dense_match_args));\n"
+    src += "".join("printf(\"%%zu\\n\", offsetof(pope_dense_match_args, %s));\n" % n for n in names) + "return 0;}\n"
+    exe = str(tmp_path / "layout")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
+                       input=src, text=True, capture_output=True)
+    assert r.returncode == 0, r.stderr
+    out = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    assert len(out) == 1 + len(names)
+    assert out[0] == ctypes.sizeof(_lib.DenseMatchArgs)
+    for n, off in zip(names, out[1:]):
+        assert getattr(_lib.DenseMatchArgs, n).offset == off, n
+
+
+def test_dense_match_refuses_before_any_hip_call(hip_lib):
+    """Every refusal of pope_dense_match_f32 is decided on the host: fake aligned pointers that are never dereferenced, no GPU.
+    (The accepting side launches; the GPU suites cover it.)"""
+    import ctypes
+    import itertools
+    buf = ctypes.create_string_buffer(64)
+    ok = (ctypes.addressof(buf) + 15) & ~15
+    ERR_ARG, ERR_WORKSPACE = -1, -3
+    required = ("feat0", "feat1", "b_ids", "i_ids", "j_ids", "mconf", "mkpts0_c", "mkpts1_c", "counts", "workspace")
+    n, L, S, Cd = 2, 192, 140, 256
+    for sinkhorn, border, publish in itertools.product((False, True), repeat=3):
+        def make(**over):
+            a = _lib.DenseMatchArgs(
+                feat0=ok, stride0=L * Cd, feat1=ok, stride1=S * Cd, n=n, L=L, S=S, C=Cd, h0=12, w0=16, h1=10, w1=14, thr=0.2,
+                border_rm=2, temperature=0.1, scale=8.0, match_type=_lib.MATCH_TYPES["sinkhorn" if sinkhorn else "dual_softmax"],
+                bin_score=ok if sinkhorn else None, skh_iters=3, skh_prefilter=1, border_mask0=ok if border else None,
+                border_mask1=ok if border else None, conf_matrix=ok if publish else None, b_ids=ok, i_ids=ok, j_ids=ok,
+                mconf=ok, mkpts0_c=ok, mkpts1_c=ok, counts=ok, workspace=ok, precision=_lib.PREC_F16X3)
+            a.workspace_bytes = hip_lib.pope_dense_match_workspace_bytes(ctypes.byref(a))
+            for k, v in over.items():
+                setattr(a, k, v)
+            return a
+        call = lambda a: hip_lib.pope_dense_match_f32(ctypes.byref(a), None)   # noqa: E731
+        case = (sinkhorn, border, publish)
+        need = make().workspace_bytes
+        assert need > 0, case
+        assert call(make(workspace_bytes=need - 1)) == ERR_WORKSPACE, case
+        for name in required:
+            assert call(make(**{name: None})) == ERR_ARG, (case, name)
+        assert call(make(n=0)) == ERR_ARG, case
+        assert call(make(match_type=2)) == ERR_ARG, case
+        assert call(make(match_type=-1)) == ERR_ARG, case
+        if sinkhorn:
+            assert call(make(bin_score=None)) == ERR_ARG, case
+            assert call(make(skh_iters=0)) == ERR_ARG, case
+    assert hip_lib.pope_dense_match_f32(None, None) == ERR_ARG
 
 
 def test_streaming_top3_host_matches_oracle(golden_dir):

@@ -100,7 +100,7 @@ def _fake_weights(ok, depths=(1, 1, 1, 1), dims=(64, 80, 160, 320)):
 
 
 def test_c_entries_refuse_bad_arguments_without_a_gpu(hip_lib):
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
     buf = ctypes.create_string_buffer(1024)
     ok = (ctypes.addressof(buf) + 255) & ~255
     w, keep = _fake_weights(ok)

@@ -65,7 +65,7 @@ def test_new_symbols_declared_bound_and_reexported(hip_lib):
     for name in NEW_SYMBOLS:
         assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in pope_hip.h"
         assert name in _lib.PROTOTYPES and hasattr(hip_lib, name)
-    assert hip_lib.pope_abi_version() == 9          # additive change
+    assert hip_lib.pope_abi_version() == 10
     from pope_amd import pope_model_api as api
     for name in ("locate_and_match_batch", "locate_and_match_batch_u8", "locate_match_pose_batch_u8"):
         assert callable(getattr(api, name))

@@ -175,16 +175,14 @@ def test_encoder_layer_matches_fp64(dev, hip_lib, seams, msd, precision):
 def _fine_match(lib, dev, case, x):
     w0, w1, mk, b_ids, scale1 = x
     M = w0.shape[0]
-    w0d, w1d, mkd, bd = w0.to(dev).contiguous(), w1.to(dev).contiguous(), mk.to(dev).contiguous(), b_ids.to(dev).contiguous()
+    w0d, w1d, mkd = w0.to(dev).contiguous(), w1.to(dev).contiguous(), mk.to(dev).contiguous()
     expec = torch.full((M + 1, 3), lc.SENTINEL, dtype=torch.float32, device=dev)
     mk1f = torch.full((M + 1, 2), lc.SENTINEL, dtype=torch.float32, device=dev)
-    if case["entry"] == "plain":
-        _ok(lib.pope_fine_match_f32(_p(w0d), _p(w1d), M, case["W"], case["C"], _p(mkd), lc.SCALE_PX, _p(expec), _p(mk1f),
-                                    _lib.stream_of(dev)), case["id"])
-    else:
-        s1 = scale1.to(dev).contiguous()
-        _ok(lib.pope_fine_match_scaled_f32(_p(w0d), _p(w1d), M, case["W"], case["C"], _p(mkd), lc.SCALE_PX, _p(s1), _p(bd), _p(expec),
-                                           _p(mk1f), _lib.stream_of(dev)), case["id"])
+    s1 = bd = None                                                           # plain: no scale1, no b_ids
+    if case["entry"] == "scaled":
+        s1, bd = scale1.to(dev).contiguous(), b_ids.to(dev).contiguous()
+    _ok(lib.pope_fine_match_f32(_p(w0d), _p(w1d), M, case["W"], case["C"], _p(mkd), lc.SCALE_PX, _p(s1), _p(bd), _p(expec), _p(mk1f),
+                                _lib.stream_of(dev)), case["id"])
     _sync(case["id"])
     out = torch.cat([expec.cpu(), mk1f.cpu()], 1)
     assert bool((out[M:] == lc.SENTINEL).all()), f"{case['id']}: the guard row was written"

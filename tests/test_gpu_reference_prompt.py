@@ -1,5 +1,5 @@
 """GPU: encode the reference once, match many crops (Matcher.encode_reference, data['reference'] / data['image0_index'],
-pope_fine_preprocess_indexed_f32, driver.encode_references / ReferenceSet / ref_index).
+the ref0_of_pair index of pope_fine_preprocess_f32, driver.encode_references / ReferenceSet / ref_index).
 
 The contract is equality: every published output of an indexed call is, bit for bit, that of the plain call on
 image0 = refs.index_select(0, image0_index) — no tolerance appears below.  Each test first shows on the PLAIN call that matches
@@ -241,8 +241,8 @@ def test_range_guard_of_a_reference_makes_its_encoding_fp32(dev, peaked_sd):
     assert_same_outputs(b, want, "flagged reference / kept encoding")
 
 
-# ---- 7. pope_fine_preprocess_indexed_f32 at op level -------------------------------------------------------------------------
-def _fine_entry(name, fp, f0, f1, c0, c1, b, i, j, wc, stride, precision, ref0=None, indexed_args=False):
+# ---- 7. the ref0_of_pair index of pope_fine_preprocess_f32 at op level -------------------------------------------------------------------------
+def _fine_entry(fp, f0, f1, c0, c1, b, i, j, wc, stride, precision, ref0=None):
     from pope_amd import _lib
     lib = _lib.lib()
     dwp, mwp = fp._weights(precision)
@@ -257,11 +257,10 @@ def _fine_entry(name, fp, f0, f1, c0, c1, b, i, j, wc, stride, precision, ref0=N
             C.c_void_p(c0.data_ptr()), C.c_void_p(c1.data_ptr()), c0.shape[1], c1.shape[1], c0.shape[2], Cf,
             C.c_void_p(b.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(j.data_ptr()), M, W, stride,
             C.c_void_p(dwp.data_ptr()), C.c_void_p(db.data_ptr()), C.c_void_p(mwp.data_ptr()), C.c_void_p(mb.data_ptr()),
-            _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(flag.data_ptr())]
-    if indexed_args:
-        args += [None if ref0 is None else C.c_void_p(ref0.data_ptr()), int(c0.shape[0]), int(f0.shape[0])]
+            _lib.PRECISIONS[precision], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(flag.data_ptr()),
+            None if ref0 is None else C.c_void_p(ref0.data_ptr()), int(c0.shape[0]), int(f0.shape[0])]
     with torch.cuda.device(f0.device):
-        _lib.check(getattr(lib, name)(*args, _lib.stream_of(f0.device)), name)
+        _lib.check(lib.pope_fine_preprocess_f32(*args, _lib.stream_of(f0.device)), "pope_fine_preprocess_f32")
     assert int(flag.item()) == 0
     return out
 
@@ -290,19 +289,19 @@ def test_indexed_fine_preprocess_equals_the_entry_on_the_expanded_map(dev, peake
     expanded = f0.index_select(0, ref0)
     assert not torch.equal(f0[0], f0[1]) and set(b.tolist()) == set(range(n))
     tail = (b, i, j, wc, s, precision)
-    want = _fine_entry("pope_fine_preprocess_f32", fp, expanded, f1, c0, c1, *tail)
+    want = _fine_entry(fp, expanded, f1, c0, c1, *tail)          # no index: one map-0 row per pair
     assert bool(torch.isfinite(want).all())
-    got = _fine_entry("pope_fine_preprocess_indexed_f32", fp, f0, f1, c0, c1, *tail, ref0=ref0, indexed_args=True)
+    got = _fine_entry(fp, f0, f1, c0, c1, *tail, ref0=ref0)
     assert torch.equal(got, want)
-    # a NULL index: the existing entry on the same inputs
-    null = _fine_entry("pope_fine_preprocess_indexed_f32", fp, expanded, f1, c0, c1, *tail, ref0=None, indexed_args=True)
-    assert torch.equal(null, want)
+    # a NULL index is the identity index on the expanded map
+    ident = _fine_entry(fp, expanded, f1, c0, c1, *tail, ref0=torch.arange(n, dtype=torch.int64, device=dev))
+    assert torch.equal(ident, want)
     # and through the module, which is how the Matcher reaches it
     data = {"hw0_f": (hf, wf), "hw0_c": (hc, wc), "hw1_c": (hc, wc), "b_ids": b, "i_ids": i, "j_ids": j}
     (w0, w1), _ = fp._run(f0, f1, c0, c1, data, s, precision, ref0)
     assert torch.equal(torch.cat([w0, w1]), want)
     # the index matters: the wrong rows give other windows
-    swapped = _fine_entry("pope_fine_preprocess_indexed_f32", fp, f0, f1, c0, c1, *tail, ref0=1 - ref0, indexed_args=True)
+    swapped = _fine_entry(fp, f0, f1, c0, c1, *tail, ref0=1 - ref0)
     assert not torch.equal(swapped[:M], want[:M]) and torch.equal(swapped[M:], want[M:])
 
 

@@ -103,8 +103,8 @@ class SwigluOp:
         M = M or self.M
         out = torch.full((M, self.h), float("nan"), device=self.a.device)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.pope_linear_prec_f32(_ptr(self.a), _ptr(self.wq), _ptr(self.bq), _ptr(out), M, self.N, self.K, EPI_SWIGLU, None, None,
-                                      0, None, st)
+        rc = lib.pope_linear_f32(_ptr(self.a), _ptr(self.wq), _ptr(self.bq), _ptr(out), M, self.N, self.K, EPI_SWIGLU, None, None,
+                                 0, None, st)
         assert rc == 0, rc
         torch.cuda.synchronize()
         return out

@@ -81,7 +81,7 @@ def test_f16_entry_argument_validation_without_gpu(hip_lib):
         a, _ = _args(**kw)
         assert hip_lib.pope_conv_layer_f16(ctypes.byref(a), None) == -3, what      # POPE_ERR_WORKSPACE
     assert hip_lib.pope_conv_layer_f16(None, None) == -1
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
 
 
 def test_precision_attribute_and_config():

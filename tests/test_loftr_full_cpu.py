@@ -102,13 +102,17 @@ def test_new_entry_points_reject_invalid_arguments(hip_lib):
     w = _lib.LoftrLayerWeights()
     p = ctypes.c_void_p(16)       # non-null, 16-byte aligned, never dereferenced
     odd = ctypes.c_void_p(20)     # not 16-byte aligned
-    layer = hip_lib.pope_loftr_encoder_layer_full_f32
+    layer = hip_lib.pope_loftr_encoder_layer_f32
+    FULL = _lib.LOFTR_ATTENTIONS["full"]
 
-    def lay(w_=w, x=p, src=p, n=1, L=4, S=4, C=256, H=8, prec=1, ws=p):
-        return layer(w_, x, src, n, L, S, C, H, 1e-5, prec, ws, 1 << 20, None, None)
+    def lay(w_=w, x=p, src=p, n=1, L=4, S=4, C=256, H=8, prec=1, ws=p, xm=None, sm=None, attn=FULL):
+        return layer(w_, x, src, xm, sm, n, L, S, C, H, 1e-5, attn, prec, ws, 1 << 20, None, None)
 
     for bad in (dict(w_=None), dict(x=None), dict(src=None), dict(ws=None), dict(n=0), dict(L=0), dict(S=-1), dict(C=64), dict(C=192),
                 dict(H=4), dict(prec=2), dict(prec=-1)):
+        assert lay(**bad) == ERR_ARG, bad
+    # full attention takes no padding masks (the Python layer raises NotImplementedError for them); an unknown attention kind
+    for bad in (dict(xm=p), dict(sm=p), dict(xm=p, sm=p), dict(attn=2), dict(attn=-1)):
         assert lay(**bad) == ERR_ARG, bad
     core = hip_lib.pope_loftr_full_attention_f32
 
@@ -118,4 +122,4 @@ def test_new_entry_points_reject_invalid_arguments(hip_lib):
     for bad in (dict(q=None), dict(kv=None), dict(out=None), dict(q=odd), dict(n=0), dict(L=-3), dict(S=0), dict(C=512), dict(H=16),
                 dict(prec=2), dict(prec=7)):
         assert att(**bad) == ERR_ARG, bad
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10

@@ -21,7 +21,7 @@ def _model(S, mode="6d", **kw):
 
 
 def test_library_exports_the_entries(hip_lib):
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
     for name in ("pope_mocope_workspace_bytes", "pope_mocope_forward_f32", "pope_mocope_tap_f32"):
         fn = getattr(hip_lib, name)
         res, args = _lib.PROTOTYPES[name]

@@ -119,7 +119,7 @@ def test_permuted_layout_is_the_forks():
 
 def test_symbol_and_abi(hip_lib):
     from pope_amd import _lib
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
     assert "pope_pose_images_u8_f32" in _lib.PROTOTYPES and hasattr(hip_lib, "pope_pose_images_u8_f32")
     import os
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pope_hip.h")).read()

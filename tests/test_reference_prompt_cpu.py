@@ -1,5 +1,5 @@
 """CPU: the public surface of "encode the reference once, match many crops" — the argument checks of the Matcher's
-`reference` / `image0_index` keys, the new C entry `pope_fine_preprocess_indexed_f32`, and the driver's `ReferenceSet` /
+`reference` / `image0_index` keys, the `ref0_of_pair` index of `pope_fine_preprocess_f32`, and the driver's `ReferenceSet` /
 `ref_index` — everything that is decided before a launch.  What the calls compute is pinned on the card by
 tests/test_gpu_reference_prompt.py."""
 import ctypes
@@ -105,11 +105,11 @@ def test_leading_self_layers():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------
 def test_indexed_fine_entry_is_exported_and_validates_without_gpu(hip_lib):
-    assert hip_lib.pope_abi_version() == 9                   # an added entry: the ABI number stays
-    fn = hip_lib.pope_fine_preprocess_indexed_f32
-    plain = _lib.PROTOTYPES["pope_fine_preprocess_f32"][1]
-    assert _lib.PROTOTYPES["pope_fine_preprocess_indexed_f32"][1] == plain[:-1] + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                                                   ctypes.c_void_p]
+    assert hip_lib.pope_abi_version() == 10
+    fn = hip_lib.pope_fine_preprocess_f32
+    # the index, the pair count and the row count sit between the range flag and the stream
+    assert _lib.PROTOTYPES["pope_fine_preprocess_f32"][1][-5:] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                                   ctypes.c_void_p]
     buf = ctypes.create_string_buffer(256)
     ok = (ctypes.addressof(buf) + 15) & ~15                  # never dereferenced: every call below stops at the checks
     st = (ctypes.c_longlong * 4)(1, 1, 1, 1)

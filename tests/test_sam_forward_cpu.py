@@ -22,7 +22,7 @@ def golden(golden_dir):
 def test_prototypes_and_abi_version(hip_lib):
     assert "pope_sam_decoder_forward_images_f32" in _lib.PROTOTYPES
     assert "pope_sam_decoder_images_workspace_bytes" in _lib.PROTOTYPES
-    assert hip_lib.pope_abi_version() == 9
+    assert hip_lib.pope_abi_version() == 10
 
 
 def test_images_entry_rejects_bad_arguments_without_a_gpu(hip_lib):

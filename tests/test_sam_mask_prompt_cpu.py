@@ -45,7 +45,7 @@ def restate_embed(sd, masks, dtype=torch.float32, eps=1e-6):
 # ---- the C entry -------------------------------------------------------------------------------------------------------
 def test_prototype_and_abi_version(hip_lib):
     assert "pope_sam_mask_embed_f32" in _lib.PROTOTYPES
-    assert hip_lib.pope_abi_version() == 9   # an additive change
+    assert hip_lib.pope_abi_version() == 10
 
 
 def test_entry_rejects_bad_arguments_without_a_gpu(hip_lib):

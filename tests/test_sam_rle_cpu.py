@@ -73,7 +73,7 @@ def test_header_declares_the_entries_and_the_binding_covers_them(hip_lib):
         assert f"int {name}(" in header
         assert name in _lib.PROTOTYPES and hasattr(hip_lib, name)
     assert len(_lib.PROTOTYPES["pope_sam_rle_u32"][1]) == 9 and len(_lib.PROTOTYPES["pope_sam_nms_segments_f32"][1]) == 9
-    assert hip_lib.pope_abi_version() == 9                                  # an additive change
+    assert hip_lib.pope_abi_version() == 10
 
 
 def test_argument_validation_without_gpu(hip_lib):

@@ -12,7 +12,7 @@ ERR_ARG = -1
 def test_symbols_are_bound(hip_lib):
     for name in ("pope_sam_small_regions_workspace_bytes", "pope_sam_small_regions_u32"):
         assert name in _lib.PROTOTYPES and hasattr(hip_lib, name)
-    assert hip_lib.pope_abi_version() == 9                      # an additive change
+    assert hip_lib.pope_abi_version() == 10
     assert list(inspect.signature(sg.clean_masks_packed).parameters) == ["packed", "W", "min_area"]
     assert list(inspect.signature(sg.postprocess_small_regions_segments).parameters) == ["data", "seg", "W", "min_area", "nms_thresh"]
 

@@ -137,7 +137,7 @@ def test_new_symbol_declared_bound_and_reexported(hip_lib):
     res, args = _lib.PROTOTYPES[name]
     p, i = ctypes.c_void_p, ctypes.c_int
     assert res is i and args == [p, p, p, i, p, p, i, i, i, ctypes.c_float, p, p, p, p, p, p]
-    assert hip_lib.pope_abi_version() == 9          # additive change
+    assert hip_lib.pope_abi_version() == 10
     from pope_amd import pope_model_api as api
     for exported in ("locate_poses_in_frame", "share_frames", "vote_top3_shared", "SharedFrames"):
         assert callable(getattr(api, exported))

@@ -89,15 +89,20 @@ def test_host_side_argument_checks(hip_lib):
         dense_match(*args, match_type="other")
     # the C entry: a null dustbin pointer and skh_iters < 1 are argument errors; the workspace holds u, v and the column maxima
     import ctypes
+    from pope_amd import _lib
     buf = ctypes.create_string_buffer(64)
     ok = (ctypes.addressof(buf) + 15) & ~15   # never dereferenced
 
+    def args(bin_score, iters, n=1, L=4, S=4, match_type=_lib.MATCH_TYPES["sinkhorn"]):
+        return _lib.DenseMatchArgs(
+            feat0=ok, stride0=1024, feat1=ok, stride1=1024, n=n, L=L, S=S, C=256, h0=2, w0=2, h1=2, w1=2, thr=0.2, border_rm=2,
+            match_type=match_type, bin_score=bin_score, skh_iters=iters, skh_prefilter=1, scale=8.0, b_ids=ok, i_ids=ok, j_ids=ok,
+            mconf=ok, mkpts0_c=ok, mkpts1_c=ok, counts=ok, conf_matrix=ok, workspace=ok, workspace_bytes=1 << 20, precision=1)
+
     def call(bin_score, iters):
-        return hip_lib.pope_dense_match_sinkhorn_f32(ok, 1024, ok, 1024, 1, 4, 4, 256, 2, 2, 2, 2, 0.2, 2, bin_score, iters, 1, 8.0,
-                                                     None, None, None, None, None, None, None, ok, ok, ok, ok, ok, ok, ok, ok, 1 << 20,
-                                                     1, None, None)
+        return hip_lib.pope_dense_match_f32(ctypes.byref(args(bin_score, iters)), None)
     assert call(None, 3) == -1 and call(ok, 0) == -1
-    extra = hip_lib.pope_dense_match_sinkhorn_workspace_bytes(2, 192, 140, 256, 1, 1, 0) \
-        - hip_lib.pope_dense_match_masked_workspace_bytes(2, 192, 140, 256, 1, 1, 0)
+    query = lambda a: hip_lib.pope_dense_match_workspace_bytes(ctypes.byref(a))   # noqa: E731
+    extra = query(args(ok, 3, 2, 192, 140)) - query(args(ok, 3, 2, 192, 140, match_type=_lib.MATCH_TYPES["dual_softmax"]))
     assert extra >= 4 * 2 * (193 + 141 + 140)
-    assert hip_lib.pope_dense_match_sinkhorn_workspace_bytes(0, 4, 4, 256, 1, 1, 0) == 0
+    assert query(args(ok, 3, n=0)) == 0

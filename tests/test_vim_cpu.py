@@ -119,7 +119,7 @@ def test_synth_vim_state_dict():
 
 
 def test_workspace_query_refuses_bad_arguments(hip_lib):
-    assert hip_lib.pope_abi_version() == 9            # added entries: the ABI number stays
+    assert hip_lib.pope_abi_version() == 10
     w = _lib.VimWeights()
     w.img, w.stride, w.dim, w.depth, w.num_classes, w.eps = 224, 8, 384, 24, 1000, 1e-5
     layers = (_lib.VimLayerWeights * 24)()

@@ -185,9 +185,9 @@ def test_new_entry_points_reject_bad_arguments_without_a_gpu(hip_lib):
     assert hip_lib.pope_linear_planes_f32(one, one, None, one, one, 128, 2048, 384, 11, None, None, None, None) == -1
     assert hip_lib.pope_linear_planes_f32(one, one, None, None, None, 128, 2048, 384, 11, None, None, None, None) == -1
     assert hip_lib.pope_linear_planes_f32(one, one, None, None, one, 128, 2048, 384, 12, None, None, None, None) == -1
-    assert hip_lib.pope_linear_prec_f32(None, None, None, None, 128, 2048, 384, 11, None, None, 0, None, None) == -1
-    assert hip_lib.pope_linear_prec_f32(one, one, None, one, 128, 2080, 384, 11, None, None, 0, None, None) == -1
-    assert hip_lib.pope_linear_prec_f32(one, one, None, one, 128, 2048, 384, 11, None, None, 1, None, None) == -1
+    assert hip_lib.pope_linear_f32(None, None, None, None, 128, 2048, 384, 11, None, None, 0, None, None) == -1
+    assert hip_lib.pope_linear_f32(one, one, None, one, 128, 2080, 384, 11, None, None, 0, None, None) == -1
+    assert hip_lib.pope_linear_f32(one, one, None, one, 128, 2048, 384, 11, None, None, 1, None, None) == -1
     # whole model
     blocks = (_lib.VitBlockWeights * 1)()
     for n, _ in _lib.VitBlockWeights._fields_:
@@ -197,8 +197,8 @@ def test_new_entry_points_reject_bad_arguments_without_a_gpu(hip_lib):
         return _lib.VitWeights(384, 1, 6, 14, hidden, one, one, one, blocks, precision, one)
 
     def call(w, ffn, img=one, ws=one):
-        return hip_lib.pope_vit_forward_ffn_f32(C.byref(w) if w is not None else None, ffn, img, 1, 224, 224, one, one, one, 0,
-                                                None, None, ws, 1 << 30, None, None)
+        return hip_lib.pope_vit_forward_f32(C.byref(w) if w is not None else None, ffn, img, 1, 224, 224, one, one, one, 0,
+                                            None, None, ws, 1 << 30, None, None)
     assert call(None, 1) == -1 and call(weights(), 1, img=None) == -1 and call(weights(), 1, ws=None) == -1
     assert call(weights(), 2) == -1 and call(weights(), -1) == -1                  # unknown FFN kind
     assert call(weights(precision=_lib.PREC_F16), 1) == -1                         # no plain-f16 SwiGLU
@@ -208,7 +208,7 @@ def test_new_entry_points_reject_bad_arguments_without_a_gpu(hip_lib):
     blocks[0].fc1_b = 256
     ev = (C.c_void_p * 4)()
     kinds, n = (C.c_int * 4)(), C.c_int()
-    assert hip_lib.pope_vit_forward_ffn_profiled_mask_f32(C.byref(weights()), 1, one, 1, 224, 224, one, one, one, one, 1 << 30, None,
-                                                          None, None, 4, kinds, C.byref(n), 0xffffffff) == -1   # no events
-    assert hip_lib.pope_vit_forward_ffn_profiled_mask_f32(C.byref(weights()), 3, one, 1, 224, 224, one, one, one, one, 1 << 30, None,
-                                                          None, ev, 4, kinds, C.byref(n), 0xffffffff) == -1
+    assert hip_lib.pope_vit_forward_profiled_f32(C.byref(weights()), 1, one, 1, 224, 224, one, one, one, one, 1 << 30, None,
+                                                 None, None, 4, kinds, C.byref(n), 0xffffffff) == -1   # no events
+    assert hip_lib.pope_vit_forward_profiled_f32(C.byref(weights()), 3, one, 1, 224, 224, one, one, one, one, 1 << 30, None,
+                                                 None, ev, 4, kinds, C.byref(n), 0xffffffff) == -1
